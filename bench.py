@@ -6,7 +6,11 @@ A "step" is one turn of the DE loop (best scan + stop tests + one generation of
 mutation/crossover/evaluation/selection over the whole population) on synthetic
 input: x0_i = 4.096, CR=0.9, F=0.8, strategy random, early stops disabled.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up (2000 untimed steps, re-initialisation, W steps), times exactly K
+steps and prints the line; --dump-outputs DIR writes what the last step left a caller as .npy
+files. --full adds everything else the benchmark measures (kernel roofline, accepting regime,
+north_star sizes, CPU baselines, other_configs, time_to_solution).
 N > 1: one rank per GPU, weak scaling (every GPU owns 65536 agents). Either an external launcher
 (torch.distributed.run) has set RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*, or — WORLD_SIZE unset —
 this process starts the N ranks itself as fresh child processes before anything touches a GPU
@@ -79,8 +83,8 @@ def launch_ranks(args):
     of this one (which has not imported torch, let alone touched a GPU — never an exec), wait for
     them, forward rank 0's JSON line, exit non-zero if any rank failed.
 
-    The headline (DE) job at its default size is followed by a second N-rank job of the same
-    script, BASELINE configs[4] as it is worded — the PSO swarm sharded over the N GPUs, 131 072
+    Under --full, the headline (DE) job at its default size is followed by a second N-rank job of
+    the same script, BASELINE configs[4] as it is worded — the PSO swarm sharded over the N GPUs, 131 072
     particles x 256 each, one all-gather of the best record per iteration — whose summary rides in
     the headline line as `other_configs`; it can only add to the line, never cost it."""
     rcs, lines = spawn_ranks(args.gpus, sys.argv[1:])
@@ -89,8 +93,8 @@ def launch_ranks(args):
     if any(rcs) or not lines:
         raise SystemExit(f"bench.py --gpus {args.gpus}: rank exit codes {rcs}")
     line = lines[-1]
-    if (args.workload == "de" and args.pop_per_gpu == POP_PER_GPU and not args.no_other_configs
-            and line.startswith("{")):
+    if (args.workload == "de" and args.full and args.pop_per_gpu == POP_PER_GPU
+            and not args.no_other_configs and line.startswith("{")):
         entry = {"config": f"configs[4] PSO Accelerated, swarm sharded over {args.gpus} GPUs, "
                            "131072 x 256 per GPU"}
         try:
@@ -259,18 +263,19 @@ def check_kernel_within_step(kernel_ms, ms_per_step, what):
     return ok
 
 
-def timed_steps(ranks, stepper, steps):
+def timed_steps(ranks, stepper, steps, min_s=MIN_TIMED_S):
     """The contract's timed region — barrier + synchronize on both sides, max over ranks — around
-    `steps` steps, REPEATED until the region covers MIN_TIMED_S (a 20-step run of 47 us turns is
+    `steps` steps, REPEATED until the region covers min_s (a 20-step run of 47 us turns is
     0.9 ms: one clock ramp away from noise). Every rank repeats the same number of times (agreed
-    on the slowest rank's first repetition). Returns (seconds, steps actually timed)."""
+    on the slowest rank's first repetition). min_s = 0 times exactly `steps` steps.
+    Returns (seconds, steps actually timed)."""
     ranks.barrier()
     t0 = time.perf_counter()
     stepper(steps)
     ranks.barrier()
     dt = ranks.max_over_ranks(time.perf_counter() - t0)
     total, done = dt, steps
-    extra = int(np.ceil(MIN_TIMED_S / max(dt, 1e-9))) - 1
+    extra = int(np.ceil(min_s / max(dt, 1e-9))) - 1
     if extra > 0:
         ranks.barrier()
         t0 = time.perf_counter()
@@ -279,6 +284,36 @@ def timed_steps(ranks, stepper, steps):
         total += ranks.max_over_ranks(time.perf_counter() - t0)
         done += steps * extra
     return total, done
+
+
+DUMP_POP_ROWS = 16384        # population rows --dump-outputs writes: 16 MiB at D = 128
+DUMP_SCORES_MAX = 1 << 22    # scores of every agent up to 32 MiB, the same row sample past it
+
+
+def dump_rows(n):
+    """The population rows --dump-outputs writes: all n, or a fixed seeded sample of DUMP_POP_ROWS
+    of them in ascending order."""
+    if n <= DUMP_POP_ROWS:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(20240917).choice(n, DUMP_POP_ROWS, replace=False))
+
+
+def dump_de_outputs(dirname, eng, st, population, scores):
+    """--dump-outputs: what the timed path left a caller after its last step, as float64 .npy files
+    (at most 16 + 32 MiB in all): the scores of every agent, the best agent, a status vector
+    (best f, best index, iteration, function calls, std_err) and the population rows dump_rows
+    picks. The same run arguments give the same inputs, so two builds can be compared file for
+    file."""
+    os.makedirs(dirname, exist_ok=True)
+    n = len(scores)
+    rows = dump_rows(n)
+    best_x, best_f, best_index = eng.best()
+    arrays = {"population_sample": population[rows],
+              "scores": scores if n <= DUMP_SCORES_MAX else scores[rows],
+              "best_x": best_x,
+              "status": [best_f, best_index, st.iteration, st.function_calls_used, st.std_err]}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def ref_baseline(cmd, key, unit, sample):
@@ -1282,11 +1317,19 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--pop-per-gpu", type=int, default=POP_PER_GPU)
+    ap.add_argument("--full", action="store_true",
+                    help="de workload: everything beside the headline figure as well — the accepting "
+                         "regime, the generation kernel timed alone (roofline), the north_star sizes, "
+                         "the CPU baselines, other_configs and time_to_solution; without it the run "
+                         "sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="de workload: after the timed steps write what the last step left a caller "
+                         "(scores, best agent, status, a fixed sample of population rows) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-north-star", action="store_true",
-                    help="de workload: skip the pop = 2^20 pass after the configs[1] pass")
+                    help="de workload, --full: skip the pop = 2^20 pass after the configs[1] pass")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="de workload: skip the configs[2..4] passes (child processes) whose "
+                    help="de workload, --full: skip the configs[2..4] passes (child processes) whose "
                          "summaries ride in the headline line as `other_configs`")
     ap.add_argument("--lm-solver", choices=["cholesky", "qr"], default="cholesky",
                     help="lm workload: damped-system solver whose rate is the line's value (cholesky "
@@ -1310,6 +1353,8 @@ def main():
     ap.add_argument("--tts-grid", action="store_true",
                     help="tts workload: the full pop x D grid instead of the six DE cases")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "de":
+        raise SystemExit("--dump-outputs: only the de workload (the headline) writes its outputs")
     if args.workload == "tts":
         return main_tts(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1364,19 +1409,26 @@ def main():
     # (measured: the first 200 turns after the download took 36 ms instead of 9.8 ms). So the
     # reference scores are read first, then the device is kept busy (untimed) until it is timed.
     eng.init(x0)
-    scores_before = eng.download()[1]
+    scores_before = eng.download()[1] if args.full else None
     stepper(2000)
     eng.init(x0)
     stepper(args.warmup)
-    dt, steps_timed = timed_steps(ranks, stepper, args.steps)
+    # exactly --steps steps: the outputs of the last step depend on warmup + steps alone
+    dt, steps_timed = timed_steps(ranks, stepper, args.steps, min_s=0.0)
     st = eng.status()
     assert st.iteration == args.warmup + steps_timed, (st.iteration, args.warmup + steps_timed)
-    improved = float(np.mean(eng.download()[1] < scores_before))
+    improved = None
+    if args.full or (args.dump_outputs and rank == 0):
+        population, scores = eng.download()
+        if args.dump_outputs and rank == 0:
+            dump_de_outputs(args.dump_outputs, eng, st, population, scores)
+        if args.full:
+            improved = float(np.mean(scores < scores_before))
 
     # the same pass in a regime where selection does accept (~10 % per generation: CR = 0.2,
     # F = 0.5, x0 = 0.6): evidence that throughput does not hinge on the acceptance rate
     accepting = None
-    if not distributed:
+    if args.full and not distributed:
         torch = ranks.torch
         with nlsolver_amd.DEEngine("rosenbrock", pop, D, **dict(common, CR=0.2, F=0.5)) as e2:
             e2.init(np.full(D, 0.6))
@@ -1393,10 +1445,28 @@ def main():
                          "agents_improved_frac": float(np.mean(e2.download()[1] < s0))}
 
     out = None
-    # untimed, every rank (a sharded turn is collective): clocks back up after the host-side
-    # pauses (status, downloads) before rank 0 times the dominant kernel
-    stepper(1000)
     if rank == 0:
+        out = {
+            "metric": "candidate-evals/sec (pop x iters/s) Rosenbrock-128D DE",
+            "value": pop * steps_timed / dt,
+            "unit": "candidate-evals/s",
+            "n_gpus": world, "steps": args.steps, "steps_timed": steps_timed, "warmup": args.warmup,
+            "ms_per_step": dt / steps_timed * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic",
+            "config": {"workload": f"Rosenbrock-{D}D DE strategy=random CR=0.9 F=0.8, "
+                                   f"pop={pop_local} per GPU (BASELINE configs[1]), "
+                                   "one step = best scan + std_err + stop tests + one generation",
+                       "global_pop": pop, "dim": D,
+                       "parallelism": f"population-sharded x{world} (island donors, "
+                                      "one all-gather of the best record per generation)",
+                       "turn_driver": turn_driver(drv), "rccl_ranks": rccl_ranks(drv)},
+        }
+    if args.full:
+        # untimed, every rank (a sharded turn is collective): clocks back up after the host-side
+        # pauses (status, downloads) before rank 0 times the dominant kernel
+        stepper(1000)
+    if args.full and rank == 0:
         # dominant kernel: de_generation_kernel, timed alone with hipEvents on its stream
         launches = max(args.steps, 20)
         kern_ms = eng.time_generation_kernel(launches) / launches
@@ -1411,40 +1481,22 @@ def main():
             except Exception as exc:  # never lose the line to the second attempt
                 print(f"bench.py: second kernel timing failed: {exc}", file=sys.stderr)
         achieved = BYTES_PER_CANDIDATE * pop_local / (kern_ms * 1e-3) / 1e9
-        within = check_kernel_within_step(kern_ms, dt / steps_timed * 1e3, "de")
-        out = {
-            "metric": "candidate-evals/sec (pop x iters/s) Rosenbrock-128D DE",
-            "value": pop * steps_timed / dt,
-            "unit": "candidate-evals/s",
-            # `steps` as requested; the timed region repeated that loop until it covered 50 ms
-            "n_gpus": world, "steps": args.steps, "steps_timed": steps_timed, "warmup": args.warmup,
-            "kernel_within_step": within,
-            "ms_per_step": dt / steps_timed * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"Rosenbrock-{D}D DE strategy=random CR=0.9 F=0.8, "
-                                   f"pop={pop_local} per GPU (BASELINE configs[1]), "
-                                   "one step = best scan + std_err + stop tests + one generation",
-                       "global_pop": pop, "dim": D,
-                       # share of rank 0's agents that accepted at least one trial during the
-                       # warm-up + timed steps (selection is data dependent; the kernel does
-                       # the same loads, evaluation and row store either way)
-                       "agents_improved_frac": improved,
-                       "accepting_regime": accepting,
-                       "parallelism": f"population-sharded x{world} (island donors, "
-                                      "one all-gather of the best record per generation)",
-                       "turn_driver": turn_driver(drv), "rccl_ranks": rccl_ranks(drv)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         **pmc_traffic(pop_local),
-                         "kernel": "de_generation_kernel",
-                         "kernel_ms": kern_ms,
-                         "algorithmic_bytes_per_launch": BYTES_PER_CANDIDATE * pop_local},
-        }
+        out["kernel_within_step"] = check_kernel_within_step(kern_ms, dt / steps_timed * 1e3, "de")
+        # share of rank 0's agents that accepted at least one trial during the
+        # warm-up + timed steps (selection is data dependent; the kernel does
+        # the same loads, evaluation and row store either way)
+        out["config"]["agents_improved_frac"] = improved
+        out["config"]["accepting_regime"] = accepting
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                           **pmc_traffic(pop_local),
+                           "kernel": "de_generation_kernel",
+                           "kernel_ms": kern_ms,
+                           "algorithmic_bytes_per_launch": BYTES_PER_CANDIDATE * pop_local}
     if distributed:
         dist.barrier()  # no rank tears its communicator down while another is still measuring
     eng.close()
-    if rank == 0:
+    if args.full and rank == 0:
         if world == 1 and not args.no_north_star and pop_local == POP_PER_GPU:
             try:
                 out["north_star"] = north_star_pass(args.steps)

@@ -28,8 +28,8 @@ run() {  # tag, bench args...
     find "$out/${tag}_$ctr" -type f ! -name '*counter_collection.csv' -delete
   done
 }
-run de_c2 --steps 1000 --warmup 50 --no-other-configs --no-north-star &&
-run de_ns --pop-per-gpu 1048576 --steps 100 --warmup 5 --no-cpu-baseline &&
+run de_c2 --full --steps 1000 --warmup 50 --no-other-configs --no-north-star &&
+run de_ns --full --pop-per-gpu 1048576 --steps 100 --warmup 5 --no-cpu-baseline &&
 run pso_accel --workload pso-accel --steps 100 --warmup 10 &&
 run pso_vanilla --workload pso-vanilla --steps 100 --warmup 10 --no-cpu-baseline &&
 run bfgs --workload bfgs &&

@@ -95,3 +95,46 @@ def test_timed_region_is_repeated_until_it_covers_the_minimum():
     calls.clear()
     dt, done = bench.timed_steps(Ranks(), stepper, 200)  # already 100 ms
     assert calls == [200] and done == 200
+    calls.clear()
+    dt, done = bench.timed_steps(Ranks(), stepper, 20, min_s=0.0)  # the headline: exactly 20 steps
+    assert calls == [20] and done == 20
+
+
+def test_dump_outputs_writes_float64_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs writes what the timed path leaves a caller as float64 .npy files: every
+    score, the best agent, the status and a fixed, seeded sample of population rows, which is the
+    same on every call and keeps the files under 64 MB at any population size."""
+    import numpy as np
+    bench = load_bench()
+
+    class Eng:
+        def best(self):
+            return np.arange(4.0), -1.5, 7
+
+    st = types.SimpleNamespace(iteration=12, function_calls_used=13 * 20000, std_err=0.25)
+    n = 20000
+    population = np.arange(n * 4, dtype=np.float64).reshape(n, 4)
+    scores = np.arange(n, dtype=np.float64)
+    bench.dump_de_outputs(str(tmp_path / "a"), Eng(), st, population, scores)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["best_x", "population_sample", "scores", "status"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    rows = bench.dump_rows(n)
+    assert len(rows) == bench.DUMP_POP_ROWS and np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert np.array_equal(rows, bench.dump_rows(n))
+    assert np.array_equal(got["population_sample"], population[rows])
+    assert np.array_equal(got["scores"], scores) and np.array_equal(got["best_x"], np.arange(4.0))
+    assert got["status"].tolist() == [-1.5, 7, 12, 13 * 20000, 0.25]
+    assert np.array_equal(bench.dump_rows(100), np.arange(100))
+    assert bench.DUMP_POP_ROWS * bench.D * 8 + bench.DUMP_SCORES_MAX * 8 <= 64e6
+    # past DUMP_SCORES_MAX agents the scores are cut to the same row sample
+    monkeypatch.setattr(bench, "DUMP_SCORES_MAX", n - 1)
+    bench.dump_de_outputs(str(tmp_path / "b"), Eng(), st, population, scores)
+    assert np.array_equal(np.load(tmp_path / "b" / "scores.npy"), scores[rows])
+
+
+def test_dump_outputs_is_refused_for_other_workloads():
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "bfgs",
+                        "--dump-outputs", "unused"], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and "only the de workload" in r.stderr

@@ -454,3 +454,44 @@ def test_packing_does_not_change_the_history(eng_mod, monkeypatch, D, pop, strat
     (pa, sa, ta), (pb, sb, tb) = out[0][0], out[1][0]
     assert np.array_equal(pa, pb) and np.array_equal(sa, sb) and np.array_equal(ta, tb)
     assert out[0][1] == out[1][1]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(oracle, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: a lean line over exactly K timed
+    steps (none of the --full passes), and the arrays it writes are the oracle's after W + K
+    generations of the same seeded run."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7",
+           "--warmup", "3", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["steps"] == out["steps_timed"] == 7 and out["warmup"] == 3
+    assert out["ms_per_step"] > 0 and out["value"] > 0 and out["dtype"] == "f64"
+    assert out["higher_is_better"] is True and out["unit"] == "candidate-evals/s"
+    for k in ("roofline", "north_star", "cpu_baseline", "other_configs", "time_to_solution"):
+        assert k not in out, k
+    pop, D = 65536, 128
+    ref = O.DESyncRun(oracle, "rosenbrock", pop, D, np.full(D, 4.096), eps=1e-300,
+                      max_iter=10**12, best_val_no_change=10**12)
+    ref.step(3 + 7, threads=8)
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    got = {f.stem: np.load(f) for f in tmp_path.iterdir()}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["scores"], ref.scores)
+    assert np.array_equal(got["population_sample"], ref.population[bench.dump_rows(pop)])
+    best_f, best_index, iteration, fcalls, std_err = got["status"].tolist()
+    assert (best_index, iteration, fcalls, std_err) == (ref.s.best_id, ref.s.iter, ref.s.fcalls,
+                                                        ref.s.std_err)
+    assert got["best_x"].shape == (D,)

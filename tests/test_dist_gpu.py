@@ -111,7 +111,7 @@ def test_sharded_turn_world1_matches_unsharded_engine(mode, port):
 
 
 @pytest.mark.parametrize("workload,extra", [
-    ("de", ["--pop-per-gpu", "8192"]), ("pso-accel", ["--pop-per-gpu", "8192"]),
+    ("de", ["--pop-per-gpu", "8192", "--full"]), ("pso-accel", ["--pop-per-gpu", "8192"]),
     ("bfgs", ["--pop-per-gpu", "16"]), ("lm", ["--pop-per-gpu", "64"]), ("nm", ["--pop-per-gpu", "64"])])
 def test_bench_two_rank_flow_rehearsal(workload, extra):
     """`python3 bench.py --gpus 2` exactly as the driver spells it — no external launcher:
@@ -162,13 +162,13 @@ def test_bench_four_rank_flow_rehearsal(workload):
 
 
 def test_bench_two_rank_default_line_carries_the_sharded_pso_run():
-    """`python3 bench.py --gpus 2 --steps K --warmup W` at the default size, as the driver runs the
-    scaling series: after the DE job a second two-rank job runs BASELINE configs[4] (the PSO swarm
-    sharded over the ranks) and its summary rides in the one JSON line as `other_configs`."""
+    """`python3 bench.py --gpus 2 --steps K --warmup W --full` at the default size: after the DE
+    job a second two-rank job runs BASELINE configs[4] (the PSO swarm sharded over the ranks) and
+    its summary rides in the one JSON line as `other_configs`."""
     env = dict(os.environ, NLSG_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "5"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "5", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

@@ -15,6 +15,7 @@ typedef unsigned long long uint64_t;
 typedef long long int64_t;
 typedef unsigned int uint32_t;
 typedef int int32_t;
+typedef unsigned char uint8_t;
 #else
 #include <hip/hip_runtime.h>
 #include <stdint.h>

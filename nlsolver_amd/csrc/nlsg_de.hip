@@ -405,6 +405,8 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.buf[1]), rows);
   if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.scores[0]), n * sizeof(double));
   if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.scores[1]), n * sizeof(double));
+  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.home[0]), n);
+  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.home[1]), n);
   if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.best_x), D * sizeof(double));
   if (he == hipSuccess && cfg->trace)
     he = alloc(reinterpret_cast<void **>(&p.trace), n * kTraceWords * sizeof(uint64_t));
@@ -491,15 +493,17 @@ int nlsg_de_destroy(nlsg_de *e) {
   if (!e) return NLSG_OK;
   PhaseClock clk;
   hipSetDevice(e->cfg.device);
+  // every stream the engine queues work on is drained before its blocks go back to the pool
+  // (pool_free does not synchronise the device the way hipFree does)
   if (e->stream) hipStreamSynchronize(e->stream);
+  if (e->side) hipStreamSynchronize(e->side);
   pool_free(e->p.buf[0]);
   pool_free(e->p.buf[1]);
   pool_free(e->p.scores[0]);
   pool_free(e->p.scores[1]);
-  if (e->side) {
-    hipStreamSynchronize(e->side);
-    pool_stream_put(e->cfg.device, e->side);
-  }
+  pool_free(e->p.home[0]);
+  pool_free(e->p.home[1]);
+  if (e->side) pool_stream_put(e->cfg.device, e->side);
   for (int i = 0; i < 4; i++) {
     if (e->ev_gen[i]) hipEventDestroy(e->ev_gen[i]);
     if (e->ev_head[i]) hipEventDestroy(e->ev_head[i]);
@@ -588,9 +592,22 @@ int nlsg_de_download(nlsg_de *e, double *pop_host, double *scores_host, uint64_t
   int rc = read_state(e, &s);
   if (rc) return rc;
   const uint64_t n = e->p.shard_n, D = e->p.D;
-  if (pop_host)
-    NLSG_HIP(hipMemcpy(pop_host, e->p.buf[s.parity], n * D * sizeof(double),
-                       hipMemcpyDeviceToHost));
+  if (pop_host) {  // rows are spread over both buffers (DeParams.home): gathered, then one copy
+    double *stage = nullptr;
+    NLSG_HIP(pool_malloc(reinterpret_cast<void **>(&stage), n * D * sizeof(double)));
+    const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(n, 65536));
+    hipLaunchKernelGGL(de_gather_kernel, dim3(grid), dim3(256), 0, e->stream, e->p, s.parity, stage);
+    hipError_t he = hipMemcpyAsync(pop_host, stage, n * D * sizeof(double), hipMemcpyDeviceToHost,
+                                   e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he == hipSuccess) he = launches_status();
+    if (he != hipSuccess) {  // the copy may still be queued: the block is released, not parked
+      hipStreamSynchronize(e->stream);
+      pool_free(stage);
+      return fail(NLSG_ERR_HIP, "population download failed: %s", hipGetErrorString(he));
+    }
+    pool_free(stage);
+  }
   if (scores_host)
     NLSG_HIP(hipMemcpy(scores_host, e->p.scores[s.parity], n * sizeof(double),
                        hipMemcpyDeviceToHost));
@@ -611,6 +628,8 @@ int nlsg_de_upload(nlsg_de *e, const double *pop_host, const double *scores_host
   if (rc) return rc;
   const uint64_t n = e->p.shard_n, D = e->p.D;
   NLSG_HIP(hipMemcpy(e->p.buf[s.parity], pop_host, n * D * sizeof(double), hipMemcpyHostToDevice));
+  NLSG_HIP(hipMemsetAsync(e->p.home[s.parity], s.parity, n, e->stream));  // every row in buf[parity]
+  NLSG_HIP(hipStreamSynchronize(e->stream));
   NLSG_HIP(hipMemcpy(e->p.scores[s.parity], scores_host, n * sizeof(double),
                      hipMemcpyHostToDevice));
   return NLSG_OK;

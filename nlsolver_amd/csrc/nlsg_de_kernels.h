@@ -10,9 +10,9 @@
 //                         per wave, one per group of lanes
 //   de_finalize_kernel    the head's decisions from the records of all shards
 //
-// Data layout in HBM: population row-major [shard_n][D] fp64, two buffers
-// (synchronous generation: donors are read from `cur`, survivors written to
-// `nxt`); scores [shard_n] fp64 updated in place by the owning wave.
+// Data layout in HBM: population row-major [shard_n][D] fp64, two buffers; a per-agent
+// selector (DeParams.home) says which one holds the row of the generation being read, and
+// only accepted trials are stored (into the other one). Scores [shard_n] fp64, double-buffered.
 // Mapping (D > 64): one wave64 per agent; lane l holds elements c*128 + 2l, +1 of each
 // 128-element chunk c, so every wave-level load/store is one contiguous 1 KiB
 // burst (global_load_dwordx4 / global_store_dwordx4) when D is even. One agent
@@ -41,11 +41,23 @@ struct DeState {
   int32_t pad[2];
 };
 
+// Where a row lives. A synchronous generation reads generation k and writes k + 1, but a row is
+// only stored when its trial is accepted: home[par][j] (0 or 1) says which of buf[0] / buf[1]
+// holds agent j's row in the generation read from parity par. A generation that reads parity
+// par stores an accepted trial of agent a into buf[home[par][a] ^ 1] and sets
+// home[par ^ 1][a] = home[par][a] ^ 1; a rejected one stores nothing and carries the selector
+// over (home[par ^ 1][a] = home[par][a]). Like `scores`, the selectors are double-buffered by
+// parity. Why the slot written is free: during generation k + 1 and head k, every reader
+// (donor gathers, the own / non-crossed row, the head's best row) goes through home_k, so
+// nobody reads buf[1 - home_k[a]] row a; and a speculative generation that a stop test
+// discards leaves home_k, scores_k and the rows they point to untouched: it is never adopted,
+// exactly as when every row was copied into the other buffer.
 struct DeParams {
-  double *buf[2];      // population ping-pong
+  double *buf[2];      // population ping-pong, rows addressed through `home`
   double *scores[2];   // [shard_n] each, ping-pong with the population: a generation reads
                        // scores[src] and writes scores[src^1], so it never destroys the
                        // state it started from (it may run speculatively, see nlsg_de.hip)
+  uint8_t *home[2];    // [shard_n] each: the buffer holding each agent's row (see above)
   double *best_x;      // [D] row of the incumbent best (valid after a scan)
   uint64_t *trace;     // [shard_n*5] or nullptr
   DeState *state;
@@ -68,6 +80,12 @@ struct DeParams {
   int32_t pad2;
 };
 
+// agent `local`'s row in buffer h (a home selector value; the select keeps DeParams out of
+// scratch and any stray byte inside the two buffers)
+__device__ inline double *de_row(const DeParams &p, uint32_t h, uint64_t local) {
+  return ((h & 1u) ? p.buf[1] : p.buf[0]) + local * p.D;
+}
+
 // ---- generation 0 ----------------------------------------------------------
 template <int OBJ, int CHUNKS, bool VEC>
 __global__ __launch_bounds__(256) void de_init_kernel(DeParams p, const double *__restrict__ x0) {
@@ -89,7 +107,10 @@ __global__ __launch_bounds__(256) void de_init_kernel(DeParams p, const double *
   }
   store_row<CHUNKS, VEC>(p.buf[0] + a * p.D, p.D, xv);
   const double f = p.fmul * wave_objective<OBJ, CHUNKS>(xv, p.D);  // :2423-2425
-  if (lane == 0) p.scores[0][a] = f;
+  if (lane == 0) {
+    p.scores[0][a] = f;
+    p.home[0][a] = 0;
+  }
 }
 
 __global__ void de_reset_state_kernel(DeParams p) {
@@ -106,21 +127,43 @@ __global__ void de_reset_state_kernel(DeParams p) {
 
 // ---- one generation ----------------------------------------------------------
 // Everything a wave needs about one agent before it can build the trial: donor indices
-// (wave-uniform), the rows and the old score. All loads of a fetch are issued back to back.
+// (wave-uniform), the crossover mask, the rows and the old score. All row loads of a fetch are
+// issued back to back.
 template <int CHUNKS>
 struct DeAgent {
   uint64_t a, ka, r0, r1, r2, jrand;
-  double own[CHUNKS][2], keep[CHUNKS][2], d1[CHUNKS][2], d2[CHUNKS][2], d3[CHUNKS][2];
+  uint32_t home;          // home[par][a]: the buffer holding the agent's row
+  bool cross[CHUNKS][2];  // the trial takes the mutant here (crossover draw or jrand)
+  double keep[CHUNKS][2], d1[CHUNKS][2], d2[CHUNKS][2], d3[CHUNKS][2];
   double old_score;
 };
 
+// load_row where the trial keeps the old coordinate only: a lane whose coordinates all take the
+// mutant (`skip`) reads the zero pad instead (at CR 0.9 about 4 lanes in 5)
 template <int CHUNKS, bool VEC>
-__device__ inline void de_fetch_agent(const DeParams &p, const double *__restrict__ cur, int par,
-                                      uint64_t kg, uint64_t best_id, uint64_t a, bool valid,
-                                      DeAgent<CHUNKS> &c) {
-  // !valid (second agent of a wave past the end of the shard): the loads are still issued but
-  // every lane reads the 16 zero bytes, and the agent is not processed
-  const uint64_t D = valid ? p.D : 0;
+__device__ inline void load_row_kept(const double *__restrict__ row, uint64_t D,
+                                     const double *__restrict__ zero, const bool (&skip)[CHUNKS][2],
+                                     double (&v)[CHUNKS][2]) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int c = 0; c < CHUNKS; c++) {
+    const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+    if (VEC) {
+      const double *src = (e0 < D && !(skip[c][0] && skip[c][1])) ? row + e0 : zero;
+      const double2 t = *reinterpret_cast<const double2 *>(src);
+      v[c][0] = t.x;
+      v[c][1] = t.y;
+    } else {
+      v[c][0] = *((e0 < D && !skip[c][0]) ? row + e0 : zero);
+      v[c][1] = *((e0 + 1 < D && !skip[c][1]) ? row + e0 + 1 : zero);
+    }
+  }
+}
+
+template <int CHUNKS, bool VEC>
+__device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, uint64_t best_id,
+                                      uint64_t a, DeAgent<CHUNKS> &c) {
+  const uint64_t D = p.D;
   const uint64_t ga = p.shard_lo + a;  // the global agent id keys the RNG
   // the agent's key and its wave-uniform draws are computed on the vector unit (see on_valu):
   // lane L takes draw D + L of the agent's stream — lane 0 the crossover's jrand (:2364), lane
@@ -134,6 +177,28 @@ __device__ inline void de_fetch_agent(const DeParams &p, const double *__restric
   const uint32_t idx = static_cast<uint32_t>(u01(ctr_key(ka, p.D + static_cast<uint64_t>(lane))) *
                                              static_cast<double>(lim));
   const uint64_t drawn = idx >= lim ? lim - 1 : idx;  // the u == 1.0 corner clamped (B10)
+  // Home selectors, loaded here so that their latency hides behind the donor picks: lane 0 the
+  // agent's own, lanes 1..7 those of donor candidates 0..6 (a pick past candidate 6 -- tiny
+  // shards -- takes a scalar load below). The other lanes repeat lane 0's address: one load of
+  // every candidate would touch 64 cache lines per wave, more than the rows themselves.
+  const uint8_t *__restrict__ hp = p.home[par];
+  const uint32_t hsel = hp[(lane >= 1 && lane < 8) ? drawn : a];
+  c.jrand = readlane64(drawn, 0);  // :2364
+  // the crossover mask of propose_new_agent (nlsolver.h:2357-2375), before any row load: the
+  // non-crossed source is read only where the trial keeps it.
+  // ctr_key(ka, e) = mix64(ka + G (e + 1)), e + 1 = (2 lane + 1) + (128 ch + k): one 64-bit
+  // multiply per lane, the rest are compile-time constants; u01(z) < CR is decided on the
+  // draw's bits (cr_thresh: the smallest z whose uniform is >= CR)
+  const uint64_t ka_lane = ka + kGolden * (2 * static_cast<uint64_t>(lane) + 1);
+#pragma unroll
+  for (int ch = 0; ch < CHUNKS; ch++) {
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      const uint64_t e = static_cast<uint64_t>(ch) * 128 + 2 * static_cast<uint64_t>(lane) + k;
+      const uint64_t z = mix64(ka_lane + kGolden * static_cast<uint64_t>(128 * ch + k));
+      c.cross[ch][k] = z < p.cr_thresh || p.cr_all || e == c.jrand;
+    }
+  }
   // generate_indices (nlsolver.h:2331-2355): three distinct donors != fixed,
   // by rejection, drawn inside this engine's shard. Wave-uniform (scalar) code.
   const uint64_t fixed = (p.strategy == NLSG_DE_RANDOM) ? ga : best_id;  // :2451-2457
@@ -153,8 +218,8 @@ __device__ inline void de_fetch_agent(const DeParams &p, const double *__restric
   const uint64_t m2 = m1 & __ballot(cand_v != r1) & ((~0ull << i1) << 1);
   const int i2 = __builtin_ctzll(m2 | top);
   uint64_t r2 = readlane64(cand_v, i2);
-  if (m0 == 0 || m1 == 0 || m2 == 0) {  // fewer than three among 63 candidates (tiny shards):
-                                         // the literal loop, from the start
+  const bool slow = m0 == 0 || m1 == 0 || m2 == 0;
+  if (slow) {  // fewer than three among 63 candidates (tiny shards): the literal loop, from the start
     r0 = r1 = r2 = ~0ull;
     int have = 0;
     for (int k = 0; k < kDeMaxTries && have < 3; k++) {
@@ -180,65 +245,61 @@ __device__ inline void de_fetch_agent(const DeParams &p, const double *__restric
       }
     }
   }
+  // candidate i - 1 sits in lane i
+  auto home_of = [&](int i, uint64_t r) -> uint32_t {
+    return (!slow && i < 8) ? static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hsel), i))
+                            : hp[r - p.shard_lo];
+  };
+  const uint32_t h0 = home_of(i0, r0), h1 = home_of(i1, r1), h2 = home_of(i2, r2);
   c.a = a;
   c.ka = ka;
   c.r0 = r0;
   c.r1 = r1;
   c.r2 = r2;
-  c.jrand = readlane64(drawn, 0);  // :2364
-  // rows: own (selection survivor; non-crossed coordinates for strategy random), 3 donors,
-  // and for strategy best the row of best_id (L2-resident; strategy random reads the zero
-  // pad instead so that the instruction stream does not depend on the strategy)
+  c.home = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hsel), 0));
+  // rows: 3 donors and the non-crossed source -- the agent's own row for strategy random, the
+  // row of best_id (L2-resident) for strategy best -- where the trial keeps it
   // (shard-local indices and D fit 32 bits: one scalar multiply pair per row offset)
   const uint32_t d32 = static_cast<uint32_t>(p.D);
-  auto row = [&](uint64_t local) { return cur + static_cast<uint64_t>(static_cast<uint32_t>(local)) * d32; };
-  load_row<CHUNKS, VEC>(row(a), D, p.zero, c.own);
-  load_row<CHUNKS, VEC>(row(r0 - p.shard_lo), D, p.zero, c.d1);
-  load_row<CHUNKS, VEC>(row(r1 - p.shard_lo), D, p.zero, c.d2);
-  load_row<CHUNKS, VEC>(row(r2 - p.shard_lo), D, p.zero, c.d3);
-  load_row<CHUNKS, VEC>(p.best_x, p.strategy == NLSG_DE_RANDOM ? 0 : D, p.zero, c.keep);
-  c.old_score = *(valid ? p.scores[par] + a : p.zero);
+  auto row = [&](uint32_t h, uint64_t local) {
+    return ((h & 1u) ? p.buf[1] : p.buf[0]) + static_cast<uint64_t>(static_cast<uint32_t>(local)) * d32;
+  };
+  load_row<CHUNKS, VEC>(row(h0, r0 - p.shard_lo), D, p.zero, c.d1);
+  load_row<CHUNKS, VEC>(row(h1, r1 - p.shard_lo), D, p.zero, c.d2);
+  load_row<CHUNKS, VEC>(row(h2, r2 - p.shard_lo), D, p.zero, c.d3);
+  load_row_kept<CHUNKS, VEC>(p.strategy == NLSG_DE_RANDOM ? row(c.home, a) : p.best_x, D, p.zero,
+                             c.cross, c.keep);
+  c.old_score = p.scores[par][a];
 }
 
 template <int OBJ, int CHUNKS, bool VEC>
-__device__ inline void de_process_agent(const DeParams &p, double *__restrict__ nxt, int par,
-                                        const DeAgent<CHUNKS> &c) {
+__device__ inline void de_process_agent(const DeParams &p, int par, const DeAgent<CHUNKS> &c) {
   const int lane = lane_id();
   const uint64_t D = p.D;
-  const bool rnd = p.strategy == NLSG_DE_RANDOM;
   // propose_new_agent (nlsolver.h:2357-2375)
   double trial[CHUNKS][2];
-  // ctr_key(ka, e) = mix64(ka + G (e + 1)), e + 1 = (2 lane + 1) + (128 ch + k): one 64-bit
-  // multiply per lane, the rest are compile-time constants
-  const uint64_t ka_lane = c.ka + kGolden * (2 * static_cast<uint64_t>(lane) + 1);
 #pragma unroll
   for (int ch = 0; ch < CHUNKS; ch++) {
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-      const uint64_t e = static_cast<uint64_t>(ch) * 128 + 2 * static_cast<uint64_t>(lane) + k;
-      // u01(z) < CR decided on the draw's bits (cr_thresh: the smallest z whose uniform is >= CR)
-      const uint64_t z = mix64(ka_lane + kGolden * static_cast<uint64_t>(128 * ch + k));
-      const bool cross = z < p.cr_thresh || p.cr_all;
       const double mut = c.d1[ch][k] + p.F * (c.d2[ch][k] - c.d3[ch][k]);
-      trial[ch][k] = (cross || e == c.jrand) ? mut : (rnd ? c.own[ch][k] : c.keep[ch][k]);
+      trial[ch][k] = c.cross[ch][k] ? mut : c.keep[ch][k];
     }
   }
   // (elements >= D are 0 in every loaded row, hence 0 in the trial as well)
   const double score = p.fmul * wave_objective<OBJ, CHUNKS>(trial, D);  // :2463
   const bool accept = score < c.old_score;                               // :2466 (NaN -> keep)
-  double *out = nxt + c.a * D;
-  if (p.stream) {  // wave-uniform
-    if (accept) {
+  if (accept) {  // a rejected trial stores nothing: the row stays where home says it is
+    double *out = de_row(p, c.home ^ 1u, c.a);
+    if (p.stream)  // wave-uniform
       store_row_stream<CHUNKS, VEC>(out, D, trial);
-    } else {
-      store_row_stream<CHUNKS, VEC>(out, D, c.own);
-    }
-  } else if (accept) {
-    store_row<CHUNKS, VEC>(out, D, trial);
-  } else {
-    store_row<CHUNKS, VEC>(out, D, c.own);
+    else
+      store_row<CHUNKS, VEC>(out, D, trial);
   }
-  if (lane == 0) p.scores[par ^ 1][c.a] = accept ? score : c.old_score;
+  if (lane == 0) {
+    p.scores[par ^ 1][c.a] = accept ? score : c.old_score;
+    p.home[par ^ 1][c.a] = static_cast<uint8_t>(accept ? c.home ^ 1u : c.home);
+  }
   if (p.trace != nullptr && lane == 0) {
     uint64_t *t = p.trace + c.a * kTraceWords;
     t[0] = c.r0;
@@ -269,8 +330,8 @@ __device__ inline void de_generation_groups_block(const DeParams &p, int par, ui
   const bool live = wave * P + gi < p.shard_n;
   const uint64_t a = live ? wave * P + gi : wave * P;  // idle groups shadow a live agent
   const uint64_t D = p.D;
-  const double *__restrict__ cur = p.buf[par];
-  double *__restrict__ nxt = p.buf[par ^ 1];
+  const uint8_t *__restrict__ hp = p.home[par];
+  const uint32_t ha = hp[a];  // issued ahead of the donor picks
   const bool rnd = p.strategy == NLSG_DE_RANDOM;
   const uint64_t kg = first64(ctr_key(on_valu(p.seed), generation));
   const uint64_t ga = p.shard_lo + a;
@@ -305,42 +366,53 @@ __device__ inline void de_generation_groups_block(const DeParams &p, int par, ui
     r2 = (take && have == 2) ? cand : r2;
     have += take ? 1 : 0;
   }
-  // rows: own, three donors, and for strategy best the row of best_id
+  // the crossover mask of propose_new_agent (nlsolver.h:2357-2375); u01(zc) < CR on the draw's
+  // bits (DeParams.cr_thresh)
   const uint32_t j0 = 2 * g, j1 = 2 * g + 1;
   const bool in0 = j0 < D, in1 = j1 < D;
+  const uint64_t ka_lane = ka + kGolden * (2 * static_cast<uint64_t>(g) + 1);
+  bool cross[2];
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const uint64_t zc = mix64(ka_lane + kGolden * static_cast<uint64_t>(k));
+    cross[k] = zc < p.cr_thresh || p.cr_all || 2 * static_cast<uint64_t>(g) + k == jrand;
+  }
+  // rows through the home selectors: three donors, and where the trial keeps the old coordinate
+  // the agent's own row (strategy random) or the row of best_id (strategy best)
   const uint32_t d32 = static_cast<uint32_t>(D);
-  auto row = [&](uint64_t local) { return cur + static_cast<uint64_t>(static_cast<uint32_t>(local)) * d32; };
+  auto row = [&](uint32_t h, uint64_t local) {
+    return ((h & 1u) ? p.buf[1] : p.buf[0]) + static_cast<uint64_t>(static_cast<uint32_t>(local)) * d32;
+  };
   auto load2 = [&](const double *rp, double (&v)[2]) {
     v[0] = in0 ? rp[j0] : 0.0;
     v[1] = in1 ? rp[j1] : 0.0;
   };
-  double own[2], d1[2], d2[2], d3[2], keep[2] = {0.0, 0.0};
-  load2(row(a), own);
-  load2(row(r0 - p.shard_lo), d1);
-  load2(row(r1 - p.shard_lo), d2);
-  load2(row(r2 - p.shard_lo), d3);
-  if (!rnd) load2(p.best_x, keep);
+  double d1[2], d2[2], d3[2], keep[2];
+  load2(row(hp[r0 - p.shard_lo], r0 - p.shard_lo), d1);
+  load2(row(hp[r1 - p.shard_lo], r1 - p.shard_lo), d2);
+  load2(row(hp[r2 - p.shard_lo], r2 - p.shard_lo), d3);
+  const double *ks = rnd ? row(ha, a) : p.best_x;
+  keep[0] = (in0 && !cross[0]) ? ks[j0] : 0.0;
+  keep[1] = (in1 && !cross[1]) ? ks[j1] : 0.0;
   const double old_score = p.scores[par][a];
-  // propose_new_agent (nlsolver.h:2357-2375)
   double trial[2];
-  const uint64_t ka_lane = ka + kGolden * (2 * static_cast<uint64_t>(g) + 1);
 #pragma unroll
   for (int k = 0; k < 2; k++) {
-    const uint64_t e = 2 * static_cast<uint64_t>(g) + k;
-    const uint64_t zc = mix64(ka_lane + kGolden * static_cast<uint64_t>(k));
     const double mut = d1[k] + p.F * (d2[k] - d3[k]);
-    // u01(zc) < CR on the draw's bits (DeParams.cr_thresh)
-    const double t = (zc < p.cr_thresh || p.cr_all || e == jrand) ? mut : (rnd ? own[k] : keep[k]);
+    const double t = cross[k] ? mut : keep[k];
     trial[k] = (k ? in1 : in0) ? t : 0.0;
   }
   const double score = p.fmul * group_objective<OBJ, G>(trial[0], trial[1], D);  // :2463
   const bool accept = score < old_score;                                         // :2466
   if (live) {
-    double *out = nxt + static_cast<uint64_t>(static_cast<uint32_t>(a)) * d32;
-    if (in0) out[j0] = accept ? trial[0] : own[0];
-    if (in1) out[j1] = accept ? trial[1] : own[1];
+    if (accept) {  // a rejected trial stores nothing (DeParams.home)
+      double *out = row(ha ^ 1u, a);
+      if (in0) out[j0] = trial[0];
+      if (in1) out[j1] = trial[1];
+    }
     if (g == 0) {
       p.scores[par ^ 1][a] = accept ? score : old_score;
+      p.home[par ^ 1][a] = static_cast<uint8_t>(accept ? ha ^ 1u : ha);
       if (p.trace != nullptr) {
         uint64_t *t = p.trace + a * kTraceWords;
         t[0] = r0;
@@ -373,19 +445,25 @@ __device__ inline void de_generation_block(const DeParams &p, int par, uint64_t 
   if (!ignore_done && st->done) return;  // a stop test fired: the turn is a no-op
   const uint64_t a0 = block * 4 + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
   if (a0 >= p.shard_n) return;
-  const double *__restrict__ cur = p.buf[par];
-  double *__restrict__ nxt = p.buf[par ^ 1];
   const uint64_t kg = p.gen_key;  // = ctr_key(p.seed, generation), from the host
   const uint64_t best_id = st->best_id;
   DeAgent<CHUNKS> A;
-  de_fetch_agent<CHUNKS, VEC>(p, cur, par, kg, best_id, a0, true, A);
-  de_process_agent<OBJ, CHUNKS, VEC>(p, nxt, par, A);
+  de_fetch_agent<CHUNKS, VEC>(p, par, kg, best_id, a0, A);
+  de_process_agent<OBJ, CHUNKS, VEC>(p, par, A);
 }
 
 template <int OBJ, int CHUNKS, bool VEC>
 __global__ __launch_bounds__(256) void de_generation_kernel(DeParams p, int par, uint64_t generation,
                                                           int ignore_done) {
   de_generation_block<OBJ, CHUNKS, VEC>(p, par, generation, ignore_done, blockIdx.x);
+}
+
+// Gather of the population `par` into one contiguous [shard_n][D] block (host download)
+__global__ __launch_bounds__(256) void de_gather_kernel(DeParams p, int par, double *__restrict__ out) {
+  for (uint64_t r = blockIdx.x; r < p.shard_n; r += gridDim.x) {
+    const double *__restrict__ src = de_row(p, p.home[par][r], r);
+    for (uint64_t d = threadIdx.x; d < p.D; d += 256) out[r * p.D + d] = src[d];
+  }
 }
 
 // ---- best scan + stop tests -------------------------------------------------
@@ -542,7 +620,8 @@ __device__ inline void de_scan_head_block(const DeParams &p, uint64_t k, uint32_
   }
   __syncthreads();
   const bool have = s_have != 0;
-  const double *row = p.buf[par] + (have ? s_row : 0) * p.D;  // x = agents[best_id], :2444
+  const uint64_t r = have ? s_row : 0;
+  const double *row = de_row(p, p.home[par][r], r);  // x = agents[best_id], :2444
   if (rec != nullptr) {
     for (uint64_t d = threadIdx.x; d < p.D; d += 256) rec[kRecHeader + d] = have ? row[d] : 0.0;
   } else if (have) {
@@ -637,9 +716,10 @@ __global__ __launch_bounds__(256) void de_finalize_kernel(DeParams p, const doub
 
 // ---- rows longer than a wave's registers hold (D > 1024; the reference has no limit) -----------
 // One wave per agent, the rows taken in segments of 1024 coordinates. A generation makes two
-// passes: the first builds the trial segment by segment, scores it (objective_accumulate: the
-// whole-row summation order) and stores it; the second, only for a rejected trial, copies the
-// survivor's row over it. Same draws (the element's index keys them), same arithmetic, same bits
+// pass: it builds the trial segment by segment, scores it (objective_accumulate: the whole-row
+// summation order) and stores it into the buffer the agent's row is not in (DeParams.home: that
+// slot is nobody's until the generation is adopted); the selector then says whether the trial
+// or the old row is the survivor, so a rejected trial costs no copy. Same draws (the element's index keys them), same arithmetic, same bits
 // as the register-resident kernels would give — the oracle restates neither layout.
 template <int OBJ, bool VEC>
 __global__ __launch_bounds__(256) void de_init_long_kernel(DeParams p, const double *__restrict__ x0) {
@@ -664,7 +744,10 @@ __global__ __launch_bounds__(256) void de_init_long_kernel(DeParams p, const dou
     objective_accumulate<OBJ, kSeg>(acc, xv, e_base, D, element(e_base + 128 * kSeg));
   }
   const double f = p.fmul * objective_finish<OBJ>(acc, D);  // :2423-2425
-  if (lane == 0) p.scores[0][a] = f;
+  if (lane == 0) {
+    p.scores[0][a] = f;
+    p.home[0][a] = 0;
+  }
 }
 
 template <int OBJ, bool VEC>
@@ -677,8 +760,7 @@ __global__ __launch_bounds__(256) void de_generation_long_kernel(DeParams p, int
   if (a >= p.shard_n) return;
   const int lane = lane_id();
   const uint64_t D = p.D;
-  const double *__restrict__ cur = p.buf[par];
-  double *__restrict__ nxt = p.buf[par ^ 1];
+  const uint8_t *__restrict__ hp = p.home[par];
   const uint64_t kg = first64(ctr_key(on_valu(p.seed), generation));
   // donors and the forced dimension exactly as de_fetch_agent draws them
   const uint64_t ga = p.shard_lo + a;
@@ -711,8 +793,10 @@ __global__ __launch_bounds__(256) void de_generation_long_kernel(DeParams p, int
     }
   }
   const uint64_t jrand = readlane64(drawn, 0);
-  const double *own = cur + a * D, *d1 = cur + (r0 - p.shard_lo) * D, *d2 = cur + (r1 - p.shard_lo) * D,
-               *d3 = cur + (r2 - p.shard_lo) * D;
+  const uint32_t ha = hp[a];
+  const double *own = de_row(p, ha, a), *d1 = de_row(p, hp[r0 - p.shard_lo], r0 - p.shard_lo),
+               *d2 = de_row(p, hp[r1 - p.shard_lo], r1 - p.shard_lo),
+               *d3 = de_row(p, hp[r2 - p.shard_lo], r2 - p.shard_lo);
   const double *keep = rnd ? own : p.best_x;  // non-crossed coordinates (:2369-2372)
   auto trial_at = [&](uint64_t e) {  // one coordinate of the trial, the same in every lane
     if (e >= D) return 0.0;
@@ -720,7 +804,7 @@ __global__ __launch_bounds__(256) void de_generation_long_kernel(DeParams p, int
     const double mut = d1[e] + p.F * (d2[e] - d3[e]);
     return (zc < p.cr_thresh || p.cr_all || e == jrand) ? mut : keep[e];
   };
-  double *out = nxt + a * D;
+  double *out = de_row(p, ha ^ 1u, a);
   double acc = 0.0;
   const uint64_t ka_lane = ka + kGolden * (2 * static_cast<uint64_t>(lane) + 1);
   for (uint64_t e_base = 0; e_base < D; e_base += 128 * kSeg) {
@@ -745,13 +829,10 @@ __global__ __launch_bounds__(256) void de_generation_long_kernel(DeParams p, int
   const double score = p.fmul * objective_finish<OBJ>(acc, D);  // :2463
   const double old_score = p.scores[par][a];
   const bool accept = score < old_score;  // :2466 (NaN -> keep)
-  if (!accept)
-    for (uint64_t e_base = 0; e_base < D; e_base += 128 * kSeg) {
-      double vo[kSeg][2];
-      load_segment<VEC>(own, e_base, D, p.zero, vo);
-      store_segment<VEC, true>(out, e_base, D, vo);
-    }
-  if (lane == 0) p.scores[par ^ 1][a] = accept ? score : old_score;
+  if (lane == 0) {
+    p.scores[par ^ 1][a] = accept ? score : old_score;
+    p.home[par ^ 1][a] = static_cast<uint8_t>(accept ? ha ^ 1u : ha);
+  }
   if (p.trace != nullptr && lane == 0) {
     uint64_t *t = p.trace + a * kTraceWords;
     t[0] = r0;

@@ -590,6 +590,66 @@ int nlsg_nmpso_minimize(nlsg_nmpso *e, double *x_inout_host, const double *lower
 int nlsg_nmpso_time_solve(nlsg_nmpso *e, const double *x0_host, uint32_t repeats, float *ms_total);
 
 /* ========================================================================== */
+/* Reference-order Differential Evolution — DE::solve (nlsolver.h:2414-2476)   */
+/* with the reference's own generation (in place, asynchronous: agent i's      */
+/* donors may be rows agents < i replaced moments earlier) and every draw from */
+/* the caller's xorshift stream (rng::xorshift, :1344-1361), for `batch`       */
+/* independent solves. Each solve b returns the reference's x, solver_status   */
+/* and final generator state bit for bit (the keyed engine nlsg_de_* runs a    */
+/* synchronous generation on a counter generator: the same algorithm as a      */
+/* distribution only). Objectives given by their terms (not Rastrigin, not a  */
+/* whole-vector custom body); the objective's terms and std_err's two sums are */
+/* added in index order. One wave per solve; see DESIGN.md §3.                 */
+/* ========================================================================== */
+typedef struct nlsg_de_ref nlsg_de_ref;
+
+typedef struct {
+  uint32_t struct_size; /* sizeof(nlsg_de_ref_config)                             */
+  int32_t device;
+  void *stream;
+  int32_t objective;    /* nlsg_objective (not Rastrigin)                         */
+  int32_t minimize;     /* 1 = minimize(), 0 = maximize() (f_multiplier, :2418)   */
+  int32_t strategy;     /* nlsg_de_strategy                                       */
+  int32_t reserved;
+  uint64_t batch;       /* independent solves, one workgroup each                 */
+  uint64_t pop;         /* >= 4 (generate_indices never terminates below)         */
+  uint64_t dim;         /* >= 1                                                   */
+  double CR, F, eps;    /* ctor args, :2392-2395                                  */
+  uint64_t max_iter, best_val_no_change;
+  uint64_t log_capacity; /* evaluations logged per solve (tests); 0 = none        */
+} nlsg_de_ref_config;
+
+/* pop < 4, Rastrigin and a whole-vector custom body are refused before the device is touched */
+int nlsg_de_ref_create(const nlsg_de_ref_config *cfg, nlsg_de_ref **out);
+/* cfg->objective == NLSG_OBJ_CUSTOM (NLSG_CUSTOM_TERMS or NLSG_CUSTOM_CHAIN), as nlsg_de_create_custom */
+int nlsg_de_ref_create_custom(const nlsg_de_ref_config *cfg, const nlsg_custom_objective *obj,
+                              nlsg_de_ref **out);
+int nlsg_de_ref_destroy(nlsg_de_ref *e);
+/* Solves all; syncs. x_inout_host [batch][dim]: x0 in, the best agent out; rng_state_inout_host
+ * [batch][2]: the xorshift state (x[0], x[1]) in, the state the reference leaves behind out;
+ * status_host [batch] (may be NULL): done = 1, reserved = 0 for a finished solve. A solve whose
+ * donor pick met a draw of exactly 1.0 (generate_index would return pop: the reference reads out
+ * of bounds) or drew 2^20 times without three distinct donors (a degenerate state: the reference
+ * spins) ends there with done = 0, reserved = 1 / 2; the call then returns NLSG_ERR_UNSUPPORTED
+ * naming the first such solve, after filling every output. */
+int nlsg_de_ref_minimize(nlsg_de_ref *e, double *x_inout_host, uint64_t *rng_state_inout_host,
+                         nlsg_status *status_host);
+/* Evaluation log of solve b from the last minimize, in the reference's call order (the pop initial
+ * agents, then every trial): xs_host [min(count, log_capacity)][dim], fs_host the objective values
+ * (before f_multiplier); either may be NULL. *count = evaluations made (may exceed the capacity). */
+int nlsg_de_ref_log(nlsg_de_ref *e, uint64_t b, double *xs_host, double *fs_host, uint64_t *count);
+/* `repeats` whole solves from x0 / rng_state0 bracketed by hipEvents (the host's polls included). */
+int nlsg_de_ref_time_solve(nlsg_de_ref *e, const double *x0_host, const uint64_t *rng_state0_host,
+                           uint32_t repeats, float *ms_total);
+/* Host helpers behind the engine, exposed for tests: the nibble table of M^64 (xorshift128+
+ * advanced 64 steps; table_host [32][16][2]: entry (j, v) = M^64 of the state whose nibble j is v,
+ * nibbles 0-15 of x[0] then 0-15 of x[1]); and the donor pick on given draws (ids_host[4],
+ * *used = draws consumed, *flag = 0 / 1 (an index >= pop) / 2 (2^20 draws)). */
+int nlsg_de_ref_jump_table(uint64_t *table_host);
+int nlsg_de_ref_pick_donors(const double *draws_host, uint64_t n, uint64_t fixed, uint64_t pop,
+                            uint64_t *ids_host, uint64_t *used, int32_t *flag);
+
+/* ========================================================================== */
 /* Batched linear least squares by Givens QR — replaces tinyqr::lm             */
 /* (tinyqr.h:461-470: qr_decomposition :291-310 -> qr_impl :253-283 with        */
 /* givens_rotation :86-97 and rotate_matrix :126-139, then back_solve :437-459) */

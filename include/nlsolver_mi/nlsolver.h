@@ -22,6 +22,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -92,6 +93,8 @@ struct xorshift {
   std::vector<scalar_t> get_state() const {
     return {static_cast<scalar_t>(x_[0]), static_cast<scalar_t>(x_[1])};
   }
+  // the raw state x[0], x[1] (get_state() casts it to scalar_t); set it back with set_state
+  std::array<uint64_t, 2> raw_state() const { return {x_[0], x_[1]}; }
 
  private:
   uint64_t x_[2]{};
@@ -328,6 +331,12 @@ class api {
   decltype(&nlsg_sann_create_custom) sann_create_custom;
   decltype(&nlsg_sann_destroy) sann_destroy;
   decltype(&nlsg_sann_minimize) sann_minimize;
+  // optional: null when the library was built without reference-order DE
+  decltype(&nlsg_de_ref_create) de_ref_create = nullptr;
+  decltype(&nlsg_de_ref_create_custom) de_ref_create_custom = nullptr;
+  decltype(&nlsg_de_ref_destroy) de_ref_destroy = nullptr;
+  decltype(&nlsg_de_ref_minimize) de_ref_minimize = nullptr;
+  bool has_de_ref() const { return de_ref_create && de_ref_create_custom && de_ref_destroy && de_ref_minimize; }
 
   void check(int rc) const {
     if (rc != NLSG_OK)
@@ -374,6 +383,10 @@ class api {
     bind(h, "nlsg_sann_create_custom", sann_create_custom);
     bind(h, "nlsg_sann_destroy", sann_destroy);
     bind(h, "nlsg_sann_minimize", sann_minimize);
+    bind_optional(h, "nlsg_de_ref_create", de_ref_create);
+    bind_optional(h, "nlsg_de_ref_create_custom", de_ref_create_custom);
+    bind_optional(h, "nlsg_de_ref_destroy", de_ref_destroy);
+    bind_optional(h, "nlsg_de_ref_minimize", de_ref_minimize);
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
   }
@@ -381,6 +394,10 @@ class api {
   static void bind(void *h, const char *sym, F &fn) {
     fn = reinterpret_cast<F>(dlsym(h, sym));
     if (!fn) throw device_error(std::string("missing symbol ") + sym);
+  }
+  template <typename F>
+  static void bind_optional(void *h, const char *sym, F &fn) {
+    fn = reinterpret_cast<F>(dlsym(h, sym));
   }
 };
 
@@ -431,6 +448,32 @@ inline sum_order &summation() {
   return order;
 }
 inline bool reference_order() { return summation() == sum_order::reference; }
+
+// The generation DE runs on a device objective:
+//   keyed      (default) the device's own: a synchronous generation whose draws come from a counter
+//              generator keyed by two draws of the caller's generator — the reference's algorithm as
+//              a distribution.
+//   reference  the reference's own in-place, asynchronous generation on the caller's
+//              rng::xorshift<double> itself (nlsg_de_ref_*): x, the status and the generator's final
+//              state are the reference's bit for bit. Needs an RNG of that type and an objective whose
+//              arithmetic the device shares with the reference (not Rastrigin, not a whole-vector
+//              Custom); anything else throws device_error. Slower: the commit of a generation is
+//              serial.
+// Set before the solves it should govern: `nlsolver::device::de_generation_mode() =
+// de_generation::reference`, or the environment variable NLSG_DE_GENERATION = keyed | reference
+// (read at first use).
+enum class de_generation { keyed, reference };
+inline de_generation &de_generation_mode() {
+  static de_generation mode = [] {
+    const char *e = std::getenv("NLSG_DE_GENERATION");
+    const std::string v = e ? e : "";
+    if (v == "reference") return de_generation::reference;
+    if (!v.empty() && v != "keyed")
+      throw device_error("NLSG_DE_GENERATION must be keyed or reference, not '" + v + "'");
+    return de_generation::keyed;
+  }();
+  return mode;
+}
 }  // namespace device
 
 // ---------------------------------------------------------------------------
@@ -477,6 +520,7 @@ class DE {
   // GPU path: the whole while(true) loop of nlsolver.h:2429-2475 runs device-resident.
   template <bool minimize>
   solver_status<scalar_t> solve_device(std::vector<scalar_t> &x) {
+    if (device::de_generation_mode() == device::de_generation::reference) return solve_reference<minimize>(x);
     const device::api &api = device::api::get();
     nlsg_de_config cfg{};
     cfg.struct_size = sizeof(cfg);
@@ -507,6 +551,57 @@ class DE {
     api.de_destroy(eng);
     if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
     return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
+  }
+
+  // device::de_generation::reference: the reference's own generation on the caller's xorshift
+  // (nlsg_de_ref_*, one solve), which is left in the state the reference would leave it in
+  template <bool minimize>
+  solver_status<scalar_t> solve_reference(std::vector<scalar_t> &x) {
+    if constexpr (!std::is_same_v<RNG, rng::xorshift<double>>) {
+      throw device_error(
+          "NLSG_DE_GENERATION=reference draws from the caller's generator itself: it needs "
+          "rng::xorshift<double>");
+    } else {
+      if (Callable::nlsg_objective == NLSG_OBJ_RASTRIGIN)
+        throw device_error("NLSG_DE_GENERATION=reference: Rastrigin's cosine is the device's own, not the "
+                           "reference's");
+      if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM)
+        if (f.chain == NLSG_CUSTOM_VECTOR)
+          throw device_error("NLSG_DE_GENERATION=reference: a whole-vector Custom body sums in the device's "
+                             "lane-tree order, not the reference's");
+      const device::api &api = device::api::get();
+      if (!api.has_de_ref()) throw device_error("library has no reference-order DE");
+      nlsg_de_ref_config cfg{};
+      cfg.struct_size = sizeof(cfg);
+      if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+      cfg.objective = Callable::nlsg_objective;
+      cfg.minimize = minimize ? 1 : 0;
+      cfg.strategy = RecombinationType == best ? NLSG_DE_BEST : NLSG_DE_RANDOM;
+      cfg.batch = 1;
+      cfg.pop = pop_size;
+      cfg.dim = x.size();
+      cfg.CR = crossover_prob;
+      cfg.F = differential_weight;
+      cfg.eps = eps;
+      cfg.max_iter = max_iter;
+      cfg.best_val_no_change = best_value_no_change;
+      nlsg_de_ref *eng = nullptr;
+      if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
+        api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
+        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+        api.check(api.de_ref_create_custom(&cfg, &obj, &eng));
+      } else {
+        api.check(api.de_ref_create(&cfg, &eng));
+      }
+      std::array<uint64_t, 2> state = generator.raw_state();
+      nlsg_status st{};
+      const int rc = api.de_ref_minimize(eng, x.data(), state.data(), &st);
+      const std::string msg = rc ? api.last_error() : "";
+      api.de_ref_destroy(eng);
+      if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
+      generator.set_state(state[0], state[1]);
+      return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
+    }
   }
 
   // Host path for arbitrary callables (config C1): the reference's serial,

@@ -5,6 +5,7 @@ Layout:
     libnlsolver_hip.so    built in-tree by `make -C nlsolver_amd/csrc`
     _capi.py              ctypes binding of include/nlsg_c_api.h
     de.py                 DE / DESolver: mirror of nlsolver::DE (nlsolver.h:2379-2477)
+    rng.py                XorShift: pure-Python rng::xorshift<double> (nlsolver.h:1344-1378)
     pso.py                PSO / PSOSolver: mirror of nlsolver::PSO (nlsolver.h:2498-2742)
     bfgs.py               BFGS (batched starts): mirror of nlsolver::BFGS (nlsolver.h:3169-3286)
     lm.py                 LevenbergMarquardt (batched NLLS): mirror of nlsolver.h:3428-3545
@@ -15,7 +16,8 @@ Layout:
     dist.py               population sharding across ranks (torch.distributed / RCCL)
 """
 from ._capi import DE_BEST, DE_RANDOM, PSO_ACCELERATED, PSO_VANILLA, NlsgError, pinned_empty  # noqa: F401
-from .de import DE, CustomObjective, DEEngine, DESolver  # noqa: F401
+from .de import DE, CustomObjective, DEEngine, DERefEngine, DESolver  # noqa: F401
+from .rng import XorShift  # noqa: F401
 from .pso import PSO, PSOEngine, PSOSolver  # noqa: F401
 from .bfgs import BFGS, BFGSEngine, QuadDiagRank1  # noqa: F401
 from .lm import LevenbergMarquardt, LMEngine, TanhRegression  # noqa: F401

@@ -49,6 +49,14 @@ class DEConfig(C.Structure):
 OBJ_CUSTOM = 64
 
 
+class DERefConfig(C.Structure):  # nlsg_de_ref_config
+    _fields_ = [("struct_size", C.c_uint32), ("device", i32), ("stream", C.c_void_p),
+                ("objective", i32), ("minimize", i32), ("strategy", i32), ("reserved", i32),
+                ("batch", u64), ("pop", u64), ("dim", u64),
+                ("CR", f64), ("F", f64), ("eps", f64),
+                ("max_iter", u64), ("best_val_no_change", u64), ("log_capacity", u64)]
+
+
 class CustomObjectiveC(C.Structure):  # nlsg_custom_objective
     _fields_ = [("term_body", C.c_char_p), ("finish_body", C.c_char_p), ("chain", i32),
                 ("reserved", i32)]
@@ -216,6 +224,22 @@ SYMBOLS = {
     "nlsg_sann_time_solve": (C.c_int, [_H, pd, C.c_uint32, C.POINTER(C.c_float)]),
 }
 
+# Bound when the library has them: a library built without reference-order DE still loads for
+# everything else and fails only when that is asked for (require()).
+OPTIONAL_SYMBOLS = {
+    "nlsg_de_ref_create": (C.c_int, [C.POINTER(DERefConfig), C.POINTER(_H)]),
+    "nlsg_de_ref_create_custom": (C.c_int, [C.POINTER(DERefConfig), C.POINTER(CustomObjectiveC),
+                                            C.POINTER(_H)]),
+    "nlsg_de_ref_destroy": (C.c_int, [_H]),
+    "nlsg_de_ref_minimize": (C.c_int, [_H, pd, pu, C.POINTER(Status)]),
+    "nlsg_de_ref_log": (C.c_int, [_H, u64, pd, pd, pu]),
+    "nlsg_de_ref_time_solve": (C.c_int, [_H, pd, pu, C.c_uint32, C.POINTER(C.c_float)]),
+    "nlsg_de_ref_jump_table": (C.c_int, [pu]),
+    "nlsg_de_ref_pick_donors": (C.c_int, [pd, u64, u64, u64, pu, pu, C.POINTER(i32)]),
+}
+SYMBOLS.update(OPTIONAL_SYMBOLS)
+_MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE"}
+
 _lib = None
 
 
@@ -228,10 +252,23 @@ def lib():
                                 "`make -C nlsolver_amd/csrc` (no CPU fallback exists)")
         l = C.CDLL(LIB_PATH)
         for name, (res, args) in SYMBOLS.items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = res, args
+            fn = getattr(l, name, None) if name in OPTIONAL_SYMBOLS else getattr(l, name)
+            if fn is not None:
+                fn.restype, fn.argtypes = res, args
         _lib = l
     return _lib
+
+
+def require(name):
+    """The optional entry point `name`; NlsgError if this build of the library lacks it."""
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        msg = next((m for p, m in _MISSING_MESSAGE.items() if name.startswith(p)), f"library has no {name}")
+        raise NlsgError(NLSG_ERR_UNSUPPORTED, msg)
+    return fn
+
+
+NLSG_ERR_INVALID_ARG, NLSG_ERR_UNSUPPORTED = 1, 2
 
 
 def check(rc):

@@ -34,6 +34,12 @@ struct NmRtcKernels {
 };
 int rtc_build_nm(const nlsg_custom_objective *obj, int chunks, bool reference_order, NmRtcKernels *out);
 void rtc_release(NmRtcKernels *k);
+struct DeRefRtcKernels {  // reference-order DE (nlsg_de_ref_kernels.h)
+  hipModule_t mod = nullptr;
+  hipFunction_t solve = nullptr;
+};
+int rtc_build_de_ref(const nlsg_custom_objective *obj, DeRefRtcKernels *out);
+void rtc_release(DeRefRtcKernels *k);
 struct LmRtcKernels {  // finite-difference model (default functors) around the user's objective
   hipModule_t mod = nullptr;
   hipFunction_t iter = nullptr;

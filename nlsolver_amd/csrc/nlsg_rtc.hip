@@ -285,6 +285,22 @@ void rtc_release(NmRtcKernels *k) {
   if (k) *k = NmRtcKernels();
 }
 
+int rtc_build_de_ref(const nlsg_custom_objective *obj, DeRefRtcKernels *out) {
+  std::vector<hipFunction_t> f;
+  DeRefRtcKernels k;
+  const int rc = rtc_compile(obj, "nlsg_de_ref_kernels.h",
+                             {"nlsg::de_ref_kernel<" + std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) + ">"},
+                             &k.mod, &f);
+  if (rc) return rc;
+  k.solve = f[0];
+  *out = k;
+  return NLSG_OK;
+}
+void rtc_release(DeRefRtcKernels *k) {
+  if (k && k->mod) hipModuleUnload(k->mod);
+  if (k) *k = DeRefRtcKernels();
+}
+
 int rtc_build_nmpso(const nlsg_custom_objective *obj, int wide_chunks, HybRtcKernels *out) {
   std::vector<hipFunction_t> f;
   HybRtcKernels k;

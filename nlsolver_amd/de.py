@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import DE_BEST, DE_RANDOM, DEConfig, Status, check, lib
+from ._capi import DE_BEST, DE_RANDOM, DEConfig, DERefConfig, Status, check, lib, require
+from .rng import XorShift
 
 DEFAULT_SEED = 12374563468  # rng::splitmix seed, nlsolver.h:1265
 
@@ -197,13 +198,122 @@ class DEEngine:
         return w.value, r.value
 
 
+class DERefEngine:
+    """Reference-order DE (nlsg_de_ref_*): `batch` independent solves of the reference's own DE
+    (nlsolver.h:2414-2476) — in-place asynchronous generation, every draw from the solve's own
+    xorshift state — each returning the reference's x, status and final generator state bit for bit.
+    `objective`: "rosenbrock", "sphere", "styblinski_tang" or a CustomObjective given by its terms."""
+
+    def __init__(self, objective, batch, pop, dim, *, minimize=True, strategy=DE_RANDOM, CR=0.9,
+                 F=0.8, eps=10e-4, max_iter=1000, best_val_no_change=50, log_capacity=0, device=0,
+                 stream=None):
+        cfg = DERefConfig()
+        cfg.struct_size = C.sizeof(DERefConfig)
+        cfg.device = device
+        cfg.stream = None if stream is None else (stream or 1)
+        custom = objective if isinstance(objective, CustomObjective) else None
+        cfg.objective = (_capi.OBJ_CUSTOM if custom else
+                         _capi.OBJECTIVES[objective] if isinstance(objective, str) else objective)
+        cfg.minimize, cfg.strategy = int(bool(minimize)), strategy
+        cfg.batch, cfg.pop, cfg.dim = batch, pop, dim
+        cfg.CR, cfg.F, cfg.eps = CR, F, eps
+        cfg.max_iter, cfg.best_val_no_change, cfg.log_capacity = max_iter, best_val_no_change, log_capacity
+        self.cfg = cfg
+        self._h = C.c_void_p()
+        if custom:
+            create = require("nlsg_de_ref_create_custom")
+            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
+            obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
+                                         int(custom.chain), 0)
+            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+        else:
+            check(require("nlsg_de_ref_create")(C.byref(cfg), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().nlsg_de_ref_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _inputs(self, x, states):
+        B, D = self.cfg.batch, self.cfg.dim
+        x = np.array(x, dtype=np.float64).reshape(B, D)
+        states = np.array(states, dtype=np.uint64).reshape(B, 2)
+        return x, states
+
+    def minimize(self, x, states):
+        """x [batch, dim] (x0), states [batch, 2] (xorshift x[0], x[1]) ->
+        (x [batch, dim], [Status] * batch, states [batch, 2]) — new arrays, the inputs are kept"""
+        x, states = self._inputs(x, states)
+        st = (Status * self.cfg.batch)()
+        check(lib().nlsg_de_ref_minimize(self._h, x.ctypes.data_as(_capi.pd),
+                                         states.ctypes.data_as(_capi.pu), st))
+        return x, list(st), states
+
+    def log(self, b):
+        """(xs [n, dim], fs [n], count) of solve b's last minimize: the evaluations in the
+        reference's call order, n = min(count, log_capacity)"""
+        n = C.c_uint64()
+        check(lib().nlsg_de_ref_log(self._h, b, None, None, C.byref(n)))
+        m = min(n.value, self.cfg.log_capacity)
+        xs, fs = np.empty((m, self.cfg.dim)), np.empty(m)
+        if m:
+            check(lib().nlsg_de_ref_log(self._h, b, xs.ctypes.data_as(_capi.pd),
+                                        fs.ctypes.data_as(_capi.pd), C.byref(n)))
+        return xs, fs, n.value
+
+    def time_solve(self, x0, states, repeats=1):
+        """milliseconds of `repeats` whole solves from x0 / states (hipEvents)"""
+        x0, states = self._inputs(x0, states)
+        ms = C.c_float()
+        check(lib().nlsg_de_ref_time_solve(self._h, x0.ctypes.data_as(_capi.pd),
+                                           states.ctypes.data_as(_capi.pu), repeats, C.byref(ms)))
+        return ms.value
+
+
+def jump_table():
+    """The nibble table of M^64 the reference-order engine advances its lanes with:
+    uint64 [32, 16, 2] (entry (j, v) = xorshift128+ advanced 64 steps from the state whose nibble
+    j is v; nibbles 0-15 of x[0], then 0-15 of x[1])."""
+    t = np.empty((32, 16, 2), dtype=np.uint64)
+    check(require("nlsg_de_ref_jump_table")(t.ctypes.data_as(_capi.pu)))
+    return t
+
+
+def pick_donors(draws, fixed, pop):
+    """The engine's generate_indices on given draws: (ids[4], draws used, flag) with flag 0,
+    1 (an index >= pop: a draw of 1.0) or 2 (the 2^20-draw cap)."""
+    d = np.ascontiguousarray(draws, dtype=np.float64)
+    ids, used, flag = np.zeros(4, dtype=np.uint64), C.c_uint64(), C.c_int32()
+    check(require("nlsg_de_ref_pick_donors")(d.ctypes.data_as(_capi.pd), d.size, fixed, pop,
+                                             ids.ctypes.data_as(_capi.pu), C.byref(used), C.byref(flag)))
+    return [int(v) for v in ids], used.value, flag.value
+
+
 class DE:
-    """Drop-in for nlsolver::DE on a device objective (same ctor args/defaults)."""
+    """Drop-in for nlsolver::DE on a device objective (same ctor args/defaults).
+
+    generation="reference": the reference's own generation on the caller's generator, which must
+    then be an XorShift; it is advanced in place exactly as the reference advances it, and x and the
+    status are the reference's bit for bit (DERefEngine, batch 1). Default: the keyed engine
+    (synchronous generation, counter generator keyed by two draws of `generator`)."""
 
     def __init__(self, f, generator=None, crossover_prob=0.9, differential_weight=0.8, eps=10e-4,
                  pop_size=50, max_iter=1000, best_val_no_change=50, *, strategy=DE_RANDOM,
-                 device=0):
-        self.f, self.generator = f, generator
+                 device=0, generation="keyed"):
+        if generation not in ("keyed", "reference"):
+            raise ValueError(f"generation must be 'keyed' or 'reference', not {generation!r}")
+        if generation == "reference" and not isinstance(generator, XorShift):
+            raise TypeError("generation='reference' draws from the caller's stream: generator must be an "
+                            "nlsolver_amd.XorShift")
+        self.f, self.generator, self.generation = f, generator, generation
         self.args = dict(CR=crossover_prob, F=differential_weight, eps=eps, max_iter=max_iter,
                          best_val_no_change=best_val_no_change, strategy=strategy, device=device)
         self.pop_size = pop_size
@@ -212,6 +322,12 @@ class DE:
         if not isinstance(x, np.ndarray) or x.dtype != np.float64 or x.ndim != 1:
             raise TypeError("x must be a 1-D float64 numpy array (it is updated in place, "
                             "like std::vector<T>& in nlsolver.h:2404)")
+        if self.generation == "reference":
+            with DERefEngine(self.f, 1, self.pop_size, x.size, minimize=minimize, **self.args) as eng:
+                xo, st, states = eng.minimize(x[None, :], [self.generator.state])
+            x[:] = xo[0]
+            self.generator.state = tuple(int(v) for v in states[0])
+            return st[0]
         seed = seed_from_generator(self.generator)
         with DEEngine(self.f, self.pop_size, x.size, minimize=minimize, seed=seed,
                       **self.args) as eng:

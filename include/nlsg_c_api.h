@@ -111,8 +111,9 @@ uint64_t nlsg_cached_bytes(void);
 /* The device's deterministic math primitives (the log / cos of rnorm nlsolver.h:2479-2485, the
  * exp / tanh of the NLLS model, the cosine of Rastrigin test_functions.h:74-76) evaluated on n
  * caller-chosen arguments: in / out are the IEEE-754 bit patterns of the doubles (for
- * NLSG_PROBE_U01 and NLSG_PROBE_RNORM the input is the 64-bit draw itself). Exists so that the
- * bit-for-bit agreement with the CPU restatement can be tested on the primitives directly. */
+ * NLSG_PROBE_U01, NLSG_PROBE_RNORM and NLSG_PROBE_RNORM_COS the input is the 64-bit draw itself).
+ * Exists so that the bit-for-bit agreement with the CPU restatement, and each primitive's accuracy,
+ * can be tested on the primitives directly. */
 typedef enum {
   NLSG_PROBE_LOG = 0,
   NLSG_PROBE_COS = 1,
@@ -120,7 +121,11 @@ typedef enum {
   NLSG_PROBE_TANH = 3,
   NLSG_PROBE_COS_2PI = 4,
   NLSG_PROBE_U01 = 5,   /* draw -> uniform in [0, 1] (xorshift::yield's conversion, :1358) */
-  NLSG_PROBE_RNORM = 6  /* draw -> normal variate (both uniforms from the one draw)       */
+  NLSG_PROBE_RNORM = 6, /* draw -> normal variate (both uniforms from the one draw)       */
+  NLSG_PROBE_LOG_UNIT = 7,  /* the table logarithm of rnorm, x in [2^-64, 1]               */
+  NLSG_PROBE_RNORM_COS = 8, /* draw -> rnorm's signed cosine factor cos(2 pi_ u2)          */
+  NLSG_PROBE_GIVENS_T = 9,  /* r -> 1 / sqrt(r^2 + 1), the Givens rotation of tinyqr / LM   */
+  NLSG_PROBE_SQRT = 10      /* x -> sqrt(x), x = 0, +inf or x >= 2^-767                     */
 } nlsg_probe_fn;
 int nlsg_probe_math(int32_t fn, const uint64_t *in_host, uint64_t *out_host, uint64_t n,
                     int32_t device);

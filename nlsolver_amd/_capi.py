@@ -310,13 +310,14 @@ def pinned_empty(shape, dtype="float64"):
     return np.frombuffer(buf, dtype=dt, count=count).reshape(shape)
 
 
-PROBE_FUNCTIONS = {"log": 0, "cos": 1, "exp": 2, "tanh": 3, "cos_2pi": 4, "u01": 5, "rnorm": 6}
+PROBE_FUNCTIONS = {"log": 0, "cos": 1, "exp": 2, "tanh": 3, "cos_2pi": 4, "u01": 5, "rnorm": 6,
+                   "log_unit": 7, "rnorm_cos": 8, "givens_t": 9, "sqrt": 10}
 
 
 def probe_math(fn, bits, device=0):
     """nlsg_probe_math: the device's deterministic primitive `fn` ("log", "cos", "exp", "tanh",
-    "cos_2pi": argument = a double's bit pattern; "u01", "rnorm": argument = a 64-bit draw) on
-    a uint64 array; returns the results' bit patterns."""
+    "cos_2pi", "log_unit", "givens_t", "sqrt": argument = a double's bit pattern; "u01", "rnorm",
+    "rnorm_cos": argument = a 64-bit draw) on a uint64 array; returns the results' bit patterns."""
     import numpy as np
     bits = np.ascontiguousarray(bits, dtype=np.uint64)
     out = np.empty_like(bits)

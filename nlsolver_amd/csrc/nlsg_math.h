@@ -7,9 +7,11 @@
 // v_fma_f64 instead of a multiply and an add — the kernels that draw normal variates are bound
 // by exactly these instructions) and integer ops only, in a fixed operation order (the TU is
 // compiled with -ffp-contract=off, so nothing else is ever fused), so the CPU restatement, which
-// carries its own copy of the same algorithms with C's fma(), agrees bit for bit; vs libm they
-// are within 1 ulp
-// (tests/test_oracle_pso_golden.py). Algorithms: argument reduction + the
+// carries its own copy of the same algorithms with C's fma(), agrees bit for bit. Accuracy against
+// 256-bit references, as tests/test_math_accuracy_*.py enforce it: log <= 1 ulp; the table log of
+// rnorm <= 0.62 ulp; exp <= 1 ulp (subnormal results: <= 2^-1074 absolute); tanh <= 2.5 ulp; cos
+// <= 1.5 2^-53 absolute, <= 1.5 ulp where |cos| >= 2^-5, the relative error unbounded next to the
+// zeros of cos; rnorm's cosine <= 2.3e-16 absolute. Algorithms: argument reduction + the
 // classic minimax kernels (Sun fdlibm coefficient sets).
 #pragma once
 
@@ -84,7 +86,11 @@ __device__ inline double det_kernel_sin(double x) {  // |x| <= pi/4
   return __builtin_fma(v, fma_k(z, r, S1), x);
 }
 
-// cosine for |y| <= 64 (two-term Cody-Waite reduction by pi/2); NaN outside
+// cosine for |y| <= 64 (two-term Cody-Waite reduction by pi/2); NaN outside. Absolute error
+// <= 1.5 2^-53, <= 1.5 ulp where |cos y| >= 2^-5; next to the odd multiples of pi/2 the relative
+// error is unbounded (no third reduction term: r carries the 2^-86-sized error of pi/2's two parts).
+// Even bit for bit except within a few ulps of |y| = (n + 1/2) pi/2, where y and -y can fall into
+// quadrants that are not mirror images: 1 ulp apart there
 __device__ inline double det_cos(double y) {
   constexpr double invpio2 = 6.36619772367581382433e-01, pio2_1 = 1.57079632673412561417e+00,
                    pio2_1t = 6.07710050650619224932e-11;
@@ -302,36 +308,17 @@ __device__ inline double det_log_unit(double x, const double *tab) {  // x in [2
   return hi + (err + __builtin_fma(dk, ln2_lo, lo + logc_lo));
 }
 
-// One normal variate from one 64-bit draw z (rnorm, nlsolver.h:2479-2485):
-// sqrt(-2 log u1) * cos(2 * 3.141593 * u2) with u1 = z 2^-64 and u2 = (z mod 2^32) 2^-32, written
-// for the arguments that occur here: u1 is 0 or a normal number in [2^-64, 1] — the table-driven
-// logarithm above, u1 = 0 -> -inf as a final select; the cosine's argument lies in [0, 6.3] —
-// one sine polynomial on [-pi/2, pi/2] (below).
-// oracle_math.c's orc_rnorm is the CPU mirror. The kernels that draw normal variates are bound
-// by the vector unit's instruction count: 265 -> ~120 vector instructions per variate since
-// round 1.
-// SPECIAL = false leaves out the two selects that only the draws z = 0 (u1 = 0: the logarithm is
-// -inf) and z >= 2^64 - 2^10 (u1 rounds to 1: the square root of -0) need — det_rnorm below takes
-// that path when no lane of the wave holds such a draw (all but 2^-53 of the time), six vector
-// instructions per variate fewer; same bits either way.
-template <bool SPECIAL>
-__device__ inline double det_rnorm_impl(uint64_t zbits, const double *tab) {  // tab: the LDS table
-  constexpr double pio2_1 = 1.57079632673412561417e+00, pio2_1t = 6.07710050650619224932e-11;
-  // u1 = (double)z 2^-64 rounded once, as the conversion rounds: hi 2^-32 + lo 2^-64 in one fma
-  // (both terms exact); the angle y = 2 pi_ u2 = lo (2 pi_ 2^-32) — scaling by 2^-32 is exact, so
-  // the one rounding is that of 2 pi_ u2
-  const double hi_d = static_cast<double>(static_cast<uint32_t>(zbits >> 32));
-  const double lo_d = static_cast<double>(static_cast<uint32_t>(zbits));
-  const double u1 = __builtin_fma(hi_d, 0x1p-32, lo_d * 0x1p-64);
-  double lg = det_log_unit(u1, tab);  // (u1 = 0: garbage, replaced below)
-  if constexpr (SPECIAL) lg = u1 == 0.0 ? -__builtin_inf() : lg;
-  // cos(2 pi_ u2), y in [0, 6.3]: cos y = -(-1)^g sin(r) with g = rint(y / pi - 1/2) in {0, 1, 2}
+// The signed cosine factor of det_rnorm, cos(2 pi_ u2) for u2 = lo_d 2^-32, lo_d the draw's low 32
+// bits as a double (NLSG_PROBE_RNORM_COS evaluates it alone).
+__device__ inline double det_rnorm_cos(double lo_d) {
+  // y in [0, 6.3]: cos y = -(-1)^g sin(r) with g = rint(y / pi - 1/2) in {0, 1, 2}
   // and r = y - (g + 1/2) pi in [-pi/2, pi/2] (two-term Cody-Waite, (2g + 1) pio2_1 exact), and
   // ONE odd polynomial for the sine there, sin r = r + r^3 Q(r^2) (degree 8: Chebyshev fit of
   // (sin x - x) / x^3, truncation 5e-22) — fdlibm's pair of kernels on [-pi/4, pi/4] costs a
-  // lane both although it needs one. Within 2.3e-16 (absolute) of libm's cos; oracle_math.c's
-  // orc_cos_unit is the same arithmetic.
-  constexpr double invpi = 3.18309886183790671538e-01,
+  // lane both although it needs one. Absolute error <= 2.3e-16 against cos of the rounded y;
+  // oracle_math.c's orc_cos_unit is the same arithmetic.
+  constexpr double pio2_1 = 1.57079632673412561417e+00, pio2_1t = 6.07710050650619224932e-11,
+                   invpi = 3.18309886183790671538e-01,
                    Q8 = -0x1.275ecac266a3ap-57, Q7 = 0x1.9507fb692a94ap-49,
                    Q6 = -0x1.ae7ee39a09ceap-41, Q5 = 0x1.612460b690375p-33,
                    Q4 = -0x1.ae64567e73021p-26, Q3 = 0x1.71de3a556b9b2p-19,
@@ -352,6 +339,32 @@ __device__ inline double det_rnorm_impl(uint64_t zbits, const double *tab) {  //
   const uint64_t flip = (hbits << 12) & 0x8000000000000000ull;
   const double cs = __longlong_as_double(static_cast<long long>(
       static_cast<uint64_t>(__double_as_longlong(nsn)) ^ flip));
+  return cs;
+}
+
+// One normal variate from one 64-bit draw z (rnorm, nlsolver.h:2479-2485):
+// sqrt(-2 log u1) * cos(2 * 3.141593 * u2) with u1 = z 2^-64 and u2 = (z mod 2^32) 2^-32, written
+// for the arguments that occur here: u1 is 0 or a normal number in [2^-64, 1] — the table-driven
+// logarithm above, u1 = 0 -> -inf as a final select; the cosine's argument lies in [0, 6.3] —
+// one sine polynomial on [-pi/2, pi/2] (det_rnorm_cos above).
+// oracle_math.c's orc_rnorm is the CPU mirror. The kernels that draw normal variates are bound
+// by the vector unit's instruction count: 265 -> ~120 vector instructions per variate since
+// round 1.
+// SPECIAL = false leaves out the two selects that only the draws z = 0 (u1 = 0: the logarithm is
+// -inf) and z >= 2^64 - 2^10 (u1 rounds to 1: the square root of -0) need — det_rnorm below takes
+// that path when no lane of the wave holds such a draw (all but 2^-53 of the time), six vector
+// instructions per variate fewer; same bits either way.
+template <bool SPECIAL>
+__device__ inline double det_rnorm_impl(uint64_t zbits, const double *tab) {  // tab: the LDS table
+  // u1 = (double)z 2^-64 rounded once, as the conversion rounds: hi 2^-32 + lo 2^-64 in one fma
+  // (both terms exact); the angle y = 2 pi_ u2 = lo (2 pi_ 2^-32) — scaling by 2^-32 is exact, so
+  // the one rounding is that of 2 pi_ u2
+  const double hi_d = static_cast<double>(static_cast<uint32_t>(zbits >> 32));
+  const double lo_d = static_cast<double>(static_cast<uint32_t>(zbits));
+  const double u1 = __builtin_fma(hi_d, 0x1p-32, lo_d * 0x1p-64);
+  double lg = det_log_unit(u1, tab);  // (u1 = 0: garbage, replaced below)
+  if constexpr (SPECIAL) lg = u1 == 0.0 ? -__builtin_inf() : lg;
+  const double cs = det_rnorm_cos(lo_d);
   return sqrt_unscaled<SPECIAL>(-2 * lg) * cs;  // -2 lg is 0, +inf or at least 2^-53
 }
 __device__ inline double det_rnorm(uint64_t zbits, const double *tab) {
@@ -372,21 +385,29 @@ __device__ inline double det_cos_2pi(double x) {
   return det_cos(t);
 }
 
-// exp / tanh for the NLLS residual models (same algorithms as oracle_lm.c orc_exp/orc_tanh)
+// exp / tanh for the NLLS residual models (same algorithms as oracle_lm.c orc_exp/orc_tanh).
+// exp: fdlibm's thresholds — +inf above 709.782712893383973096, 0 below -745.133219101941108420 —
+// <= 1 ulp for normal results; a subnormal result is y 2^(k+1000) (exact) times 2^-1000, one
+// rounding, <= 2^-1074 absolute; k = 1024 is scaled as 2 y 2^1023.
 __device__ inline double det_exp(double x) {
   constexpr double ln2HI = 6.93147180369123816490e-01, ln2LO = 1.90821492927058770002e-10,
                    invln2 = 1.44269504088896338700e+00, P1 = 1.66666666666666019037e-01,
                    P2 = -2.77777777770155933842e-03, P3 = 6.61375632143793436117e-05,
                    P4 = -1.65339022054652515390e-06, P5 = 4.13813679705723846039e-08;
+  constexpr double o_threshold = 7.09782712893383973096e+02, u_threshold = -7.45133219101941108420e+02;
   if (x != x) return x;
-  if (x > 709.0) return __builtin_inf();
-  if (x < -708.0) return 0.0;
+  if (x > o_threshold) return __builtin_inf();
+  if (x < u_threshold) return 0.0;
   const int k = static_cast<int>(__builtin_fma(invln2, x, x < 0 ? -0.5 : 0.5));
   const double hi = __builtin_fma(-static_cast<double>(k), ln2HI, x), lo = static_cast<double>(k) * ln2LO;
   const double r = hi - lo;
   const double t = r * r;
   const double c = __builtin_fma(-t, fma_k(t, fma_k(t, fma_k(t, __builtin_fma(t, P5, P4), P3), P2), P1), r);
   const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
+  if (k > 1023) return (2.0 * y) * 0x1p1023;  // k = 1024: x in [709.44, 709.79]
+  if (k < -1021)  // x <= -708.05: the result is subnormal or close to it, round once
+    return (y * __longlong_as_double(static_cast<long long>(static_cast<uint64_t>(1023 + 1000 + k) << 52))) *
+           0x1p-1000;
   return y * __longlong_as_double(static_cast<long long>(static_cast<uint64_t>(1023 + k) << 52));
 }
 // tanh from the rational form of the exponential: with 2|x| = k ln2 + r and fdlibm's
@@ -394,7 +415,9 @@ __device__ inline double det_exp(double x) {
 //   tanh|x| = (e - 1) / (e + 1) = ((s - 1) B + 2 s r) / ((s + 1) B + 2 s r)
 // — ONE division (1 - 2 / (exp(2|x|) + 1) takes two: the NLLS evaluation pays for every fp64
 // vector instruction of this chain), no cancellation for small |x| (k = 0:
-// r / (B + r)), 1 exactly from |x| = 22 on; within 2.3e-16 (absolute) of libm's tanh.
+// r / (B + r)), 1 exactly from |x| = 22 on; <= 2.5 ulp (numerator and denominator <= 1 ulp each,
+// plus the division); the absolute error reaches 2.6e-16 near |x| = 3.2. Not monotone from one
+// double to the next: neighbouring arguments' results can step back by a few ulps (2 seen).
 // oracle_lm.c's orc_tanh is the same arithmetic.
 __device__ inline double det_tanh(double x) {
   constexpr double ln2HI = 6.93147180369123816490e-01, ln2LO = 1.90821492927058770002e-10,

@@ -26,7 +26,12 @@ __global__ __launch_bounds__(256) void probe_kernel(int fn, const uint64_t *in, 
     case NLSG_PROBE_TANH: r = det_tanh(x); break;
     case NLSG_PROBE_COS_2PI: r = det_cos_2pi(x); break;
     case NLSG_PROBE_U01: r = u01(b); break;
-    default: r = det_rnorm(b, rn_tab); break;  // NLSG_PROBE_RNORM: the input is the 64-bit draw
+    case NLSG_PROBE_RNORM: r = det_rnorm(b, rn_tab); break;  // the input is the 64-bit draw
+    case NLSG_PROBE_LOG_UNIT: r = det_log_unit(x, rn_tab); break;
+    case NLSG_PROBE_RNORM_COS: r = det_rnorm_cos(static_cast<double>(static_cast<uint32_t>(b))); break;
+    // the expression of nlsg_tinyqr_kernels.h's and nlsg_lm_kernels.h's Givens rotations
+    case NLSG_PROBE_GIVENS_T: r = div_unscaled(1.0, sqrt_unscaled(x * x + 1.0)); break;
+    default: r = sqrt_unscaled<true>(x); break;  // NLSG_PROBE_SQRT
   }
   out[i] = static_cast<uint64_t>(__double_as_longlong(r));
 }
@@ -36,7 +41,7 @@ __global__ __launch_bounds__(256) void probe_kernel(int fn, const uint64_t *in, 
 extern "C" int nlsg_probe_math(int32_t fn, const uint64_t *in_host, uint64_t *out_host, uint64_t n,
                                int32_t device) {
   if (!in_host || !out_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (fn < NLSG_PROBE_LOG || fn > NLSG_PROBE_RNORM)
+  if (fn < NLSG_PROBE_LOG || fn > NLSG_PROBE_SQRT)
     return fail(NLSG_ERR_INVALID_ARG, "unknown probe function %d", fn);
   if (n == 0) return NLSG_OK;
   if (n > (1ull << 31)) return fail(NLSG_ERR_UNSUPPORTED, "more than 2^31 arguments per call");

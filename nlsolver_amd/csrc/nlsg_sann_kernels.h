@@ -37,9 +37,12 @@ struct SannParams {
 };
 
 // The acceptance test of a worse point (:2805), u < exp(-difference / t). A difference beyond
-// 710 t puts the exponential's argument below -708, where det_exp returns 0 and no uniform is below
-// it: the draw, the division and the exponential are then skipped — the same decision, and the
-// usual case once a chain is cold (draws are keyed, so skipping one changes nothing else).
+// 710 t puts the exponential's argument below -710, where det_exp is below 2.3e-308 (and 0 below
+// -745.13): no non-zero uniform (>= 2^-64) is below it, so the draw, the division and the
+// exponential are then skipped — the same decision for every draw but z = 0 (u = 0), which the
+// full test would accept while exp(-difference / t) is still a subnormal number, as the
+// reference's std::exp is, and which this shortcut rejects (a 2^-64 event per test); the usual
+// case once a chain is cold (draws are keyed, so skipping one changes nothing else).
 // `sure_reject` must be wave-uniform where it is branched on.
 __device__ inline bool sann_sure_reject(double difference, double t) {
   return t > 0.0 && difference > 710.0 * t;

@@ -30,15 +30,21 @@ double orc_exp(double x) {
                       invln2 = 1.44269504088896338700e+00, P1 = 1.66666666666666019037e-01,
                       P2 = -2.77777777770155933842e-03, P3 = 6.61375632143793436117e-05,
                       P4 = -1.65339022054652515390e-06, P5 = 4.13813679705723846039e-08;
+  /* fdlibm's thresholds: +inf above o_threshold, 0 below u_threshold, gradual underflow between */
+  static const double o_threshold = 7.09782712893383973096e+02,
+                      u_threshold = -7.45133219101941108420e+02;
   if (x != x) return x;
-  if (x > 709.0) return INFINITY;
-  if (x < -708.0) return 0.0; /* results below the normal range are flushed */
+  if (x > o_threshold) return INFINITY;
+  if (x < u_threshold) return 0.0;
   const int k = (int)fma(invln2, x, x < 0 ? -0.5 : 0.5);
   const double hi = fma(-(double)k, ln2HI, x), lo = (double)k * ln2LO;
   const double r = hi - lo;
   const double t = r * r;
   const double c = fma(-t, fma(t, fma(t, fma(t, fma(t, P5, P4), P3), P2), P1), r);
   const double y = 1.0 - ((lo - (r * c) / (2.0 - c)) - hi);
+  if (k > 1023) return (2.0 * y) * 0x1p1023; /* k = 1024: x in [709.44, 709.79] */
+  if (k < -1021) /* x <= -708.05: y 2^(k+1000) is exact, the multiply by 2^-1000 rounds once */
+    return (y * bits2d((uint64_t)(1023 + 1000 + k) << 52)) * 0x1p-1000;
   return y * bits2d((uint64_t)(1023 + k) << 52); /* y * 2^k, k in [-1021, 1023] */
 }
 /* tanh from the rational form of the exponential: with 2|x| = k ln2 + r and fdlibm's

@@ -508,7 +508,8 @@ class OraclePSOShardEngine:
         self.lib.orc_pso_commit(C.byref(s))
 
 
-PROBE = {"log": 0, "cos": 1, "exp": 2, "tanh": 3, "cos_2pi": 4, "u01": 5, "rnorm": 6}
+PROBE = {"log": 0, "cos": 1, "exp": 2, "tanh": 3, "cos_2pi": 4, "u01": 5, "rnorm": 6,
+         "log_unit": 7, "rnorm_cos": 8, "givens_t": 9, "sqrt": 10}
 
 
 def probe_math(lib, fn, bits):

@@ -585,7 +585,10 @@ __device__ inline void de_scan_head_block(const DeParams &p, uint64_t k, uint32_
     for (uint32_t j = threadIdx.x; j < p.ntiles; j += 256) {
       const uint64_t jb = static_cast<uint64_t>(j) * kTile;
       const double nj = static_cast<double>((p.shard_n - jb) < kTile ? (p.shard_n - jb) : kTile);
-      const double dm = sc1_load(&p.part[j].sum) / nj - mean;
+      // equal means add no between-tile term: the subtraction's own result when they are
+      // finite, and M2 = +inf (the literal formula's) instead of NaN when the sums overflowed
+      const double mj = sc1_load(&p.part[j].sum) / nj;
+      const double dm = mj == mean ? 0.0 : mj - mean;
       acc = acc + (sc1_load(&p.part[j].m2) + nj * (dm * dm));
     }
     m2 = block_tree_256(acc, red);
@@ -676,6 +679,14 @@ __global__ __launch_bounds__(256) void de_finalize_kernel(DeParams p, const doub
       if (rec[4] != 1.0) continue;
       const double v = rec[0];
       const uint64_t i = static_cast<uint64_t>(__double_as_longlong(rec[1]));
+      // a NaN incumbent stays: nothing is '< NaN' in the scan of :2432-2437, whatever an
+      // earlier rank's record holds
+      if (i == inc && v != v) {
+        bv = v;
+        bi = i;
+        win = r;
+        break;
+      }
       const bool better =
           win < 0 || v < bv || (v == bv && bi != inc && (i == inc || i < bi));
       if (better) {
@@ -698,7 +709,8 @@ __global__ __launch_bounds__(256) void de_finalize_kernel(DeParams p, const doub
         const double *rec = recs + static_cast<uint64_t>(r) * rec_stride;
         double term = rec[3];
         if (world > 1) {
-          const double dm = rec[2] / n_r - gmean;
+          const double mr = rec[2] / n_r;
+          const double dm = mr == gmean ? 0.0 : mr - gmean;  // as in the tile merge
           term = term + n_r * (dm * dm);
         }
         m2 = m2 + term;

@@ -99,7 +99,9 @@ __global__ __launch_bounds__(256) void pso_init_kernel(PsoParams p) {
   const double f = p.fmul * wave_objective<OBJ, CHUNKS>(xv, p.D);
   if (lane == 0) {
     p.cur_val[i] = f;
-    p.pbest_val[i] = f;  // +inf sentinel: the first value always wins
+    // +inf sentinel (B8): the first value wins when it is below it -- a NaN or +inf one is not
+    // (`temp < particle_best_values[i]`, :2730)
+    p.pbest_val[i] = f < __builtin_inf() ? f : __builtin_inf();
   }
 }
 
@@ -340,7 +342,7 @@ __global__ __launch_bounds__(256) void pso_init_long_kernel(PsoParams p) {
   const double f = p.fmul * objective_finish<OBJ>(acc, D);
   if (lane == 0) {
     p.cur_val[i] = f;
-    p.pbest_val[i] = f;
+    p.pbest_val[i] = f < __builtin_inf() ? f : __builtin_inf();  // as pso_init_kernel
   }
 }
 
@@ -680,7 +682,8 @@ __global__ __launch_bounds__(256) void pso_finalize_kernel(PsoParams p, const do
         const double *rec = recs + static_cast<uint64_t>(r) * rec_stride;
         double term = rec[3];
         if (world > 1) {
-          const double dm = rec[2] / n_r - gmean;
+          const double mr = rec[2] / n_r;
+          const double dm = mr == gmean ? 0.0 : mr - gmean;  // equal (also infinite) means: no term
           term = term + n_r * (dm * dm);
         }
         m2 = m2 + term;

@@ -271,6 +271,13 @@ int orc_de_apply_records(orc_de_sync *s, const double *recs, int world, double *
     if (rec[4] != 1.0) continue;
     const double v = rec[0];
     const uint64_t i = dbl_bits(rec[1]);
+    /* a NaN incumbent stays: nothing is '< NaN' in the scan of :2432-2437 */
+    if (i == inc && v != v) {
+      bv = v;
+      bi = i;
+      win = r;
+      break;
+    }
     /* lower value wins; on ties the incumbent, then the lower global index */
     const int better = win < 0 || v < bv || (v == bv && bi != inc && (i == inc || i < bi));
     if (better) {
@@ -297,7 +304,8 @@ int orc_de_apply_records(orc_de_sync *s, const double *recs, int world, double *
       const double *rec = recs + (size_t)r * stride;
       double term = rec[3];
       if (world > 1) {
-        const double dm = rec[2] / n_r - gmean;
+        const double mr = rec[2] / n_r;
+        const double dm = mr == gmean ? 0.0 : mr - gmean; /* as orc_tiled_m2_merged */
         term = term + n_r * (dm * dm);
       }
       m2 = m2 + term;

@@ -168,7 +168,7 @@ void orc_pso_sync_init(orc_pso_sync *s) {
     }
     const double f = fm * orc_objective_tree(s->obj, row, s->D);
     s->cur_val[i] = f;
-    s->pbest_val[i] = f; /* +inf sentinel: the first value always wins (B8) */
+    s->pbest_val[i] = f < INFINITY ? f : INFINITY; /* +inf sentinel (B8): `f < sentinel`, :2730 */
   }
   s->gbest_val = INFINITY;
   s->gbest_idx = 0;
@@ -242,7 +242,8 @@ int orc_pso_apply_records(orc_pso_sync *s, const double *recs, int world) {
       const double *rec = recs + (size_t)r * stride;
       double term = rec[3];
       if (world > 1) {
-        const double dm = rec[2] / n_r - gmean;
+        const double mr = rec[2] / n_r;
+        const double dm = mr == gmean ? 0.0 : mr - gmean; /* as orc_tiled_m2_merged */
         term = term + n_r * (dm * dm);
       }
       m2 = m2 + term;

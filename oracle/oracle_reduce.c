@@ -71,7 +71,10 @@ double orc_tiled_sumsq_dev(const double *v, size_t n, double mean) {
  * tile's own mean), both with the block tree; tiles are merged like shards are (Chan et al.):
  *   total = tree_t(sum_t), mean = total / n,
  *   M2 = tree_t( M2_t + n_t * (mean_t - mean)^2 ),  mean_t = sum_t / n_t.
- * One tile (n <= 1024): identical to orc_tiled_sumsq_dev about the mean. *sum_out = total. */
+ * One tile (n <= 1024): identical to orc_tiled_sumsq_dev about the mean. *sum_out = total.
+ * A tile whose mean EQUALS the global mean adds no between-tile term: for finite means that is
+ * what the subtraction gives anyway; for sums that overflowed (inf - inf) it keeps M2 = +inf,
+ * the literal formula's result, instead of NaN. */
 double orc_tiled_m2_merged(const double *v, size_t n, double *sum_out) {
   const size_t T = 1024;
   const size_t nt = (n + T - 1) / T;
@@ -86,7 +89,8 @@ double orc_tiled_m2_merged(const double *v, size_t n, double *sum_out) {
   const double mean = total / (double)n;
   for (size_t j = 0; j < nt; j++) {
     const size_t len = (n - j * T) < T ? (n - j * T) : T;
-    const double dm = sum[j] / (double)len - mean;
+    const double mj = sum[j] / (double)len;
+    const double dm = mj == mean ? 0.0 : mj - mean; /* equal means, infinite ones included */
     term[j] = term[j] + (double)len * (dm * dm);
   }
   const double m2 = block_tree(term, nt, 0, 0.0);

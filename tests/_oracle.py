@@ -226,6 +226,8 @@ def load():
         fn = getattr(lib, name)
         fn.restype = f64
         fn.argtypes = [pd, sz]
+    lib.orc_tiled_m2_merged.restype = f64
+    lib.orc_tiled_m2_merged.argtypes = [pd, sz, pd]
     lib.orc_de_serial.restype = Status
     lib.orc_de_serial.argtypes = [C.c_int, C.c_int, C.c_int, pd, sz, C.POINTER(XorShift),
                                   f64, f64, f64, sz, sz, sz, C.POINTER(EvalLog)]

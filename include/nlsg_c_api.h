@@ -655,6 +655,70 @@ int nlsg_de_ref_pick_donors(const double *draws_host, uint64_t n, uint64_t fixed
                             uint64_t *ids_host, uint64_t *used, int32_t *flag);
 
 /* ========================================================================== */
+/* Resident batch Differential Evolution — `batch` independent solves of the   */
+/* KEYED engine above (nlsg_de_*: counter draws, synchronous generation, tree  */
+/* sums) of one shape, each with its own 64-bit seed and x0. One workgroup per */
+/* solve; population and scores stay in LDS and the whole turn loop (head k:   */
+/* best scan, std_err, no-change counter, stop tests; then generation k + 1)   */
+/* runs inside one kernel, so a small solve costs a launch or two instead of   */
+/* one per generation. Solve b is bit-identical to nlsg_de_* created with      */
+/* seed = seeds[b] and driven by the same calls; it ends independently of its  */
+/* neighbours and freezes at the head that fired. 4 <= pop <= 1024,            */
+/* 1 <= dim <= 128, and nlsg_de_batch_lds_bytes(pop, dim) within a workgroup's */
+/* 160 KiB (about pop x dim <= 9 900): anything else is NLSG_ERR_UNSUPPORTED   */
+/* — no global-memory fallback, no shards, no trace. See DESIGN.md §3c.        */
+/* ========================================================================== */
+typedef struct nlsg_de_batch nlsg_de_batch;
+
+typedef struct {
+  uint32_t struct_size; /* sizeof(nlsg_de_batch_config)                           */
+  int32_t device;
+  void *stream;         /* as nlsg_de_config.stream                               */
+  int32_t objective;    /* nlsg_objective                                         */
+  int32_t minimize;     /* 1 = minimize(), 0 = maximize()                         */
+  int32_t strategy;     /* nlsg_de_strategy                                       */
+  int32_t reserved;
+  uint64_t batch;       /* independent solves, one workgroup each (>= 1)          */
+  uint64_t pop;         /* 4 .. 1024                                              */
+  uint64_t dim;         /* 1 .. 128                                               */
+  double CR, F, eps;
+  uint64_t max_iter, best_val_no_change;
+  uint64_t turns_per_launch; /* step / minimize are cut into launches of at most  */
+                             /* this many turns; 0 = the engine's default (1024)  */
+} nlsg_de_batch_config;
+
+/* LDS bytes a solve of this shape needs; 0 outside the pop / dim ranges. Host only, no device. */
+uint64_t nlsg_de_batch_lds_bytes(uint64_t pop, uint64_t dim);
+/* Checked before the device is touched, in this order: null pointers, struct_size (code 1),
+ * batch >= 1 (1), the pop / dim ranges (2), the LDS budget (2). */
+int nlsg_de_batch_create(const nlsg_de_batch_config *cfg, nlsg_de_batch **out);
+/* cfg->objective == NLSG_OBJ_CUSTOM, term / chain or whole-vector form, as nlsg_de_create_custom */
+int nlsg_de_batch_create_custom(const nlsg_de_batch_config *cfg, const nlsg_custom_objective *obj,
+                                nlsg_de_batch **out);
+int nlsg_de_batch_destroy(nlsg_de_batch *e);
+/* x0_host [batch][dim], seeds_host [batch]: nlsg_de_init of every solve under its own seed */
+int nlsg_de_batch_init(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host);
+/* `turns` turns of every solve that is not done (nlsg_de_step per solve). Asynchronous. */
+int nlsg_de_batch_step(nlsg_de_batch *e, uint64_t turns);
+/* out [batch]: what nlsg_de_status reports for each solve after the same calls. Synchronises. */
+int nlsg_de_batch_status(nlsg_de_batch *e, nlsg_status *out);
+/* x_host [batch][dim], f [batch], index [batch] as of each solve's last head (nlsg_de_best);
+ * NULL pointers are skipped */
+int nlsg_de_batch_best(nlsg_de_batch *e, double *x_host, double *f, uint64_t *index);
+/* solve b's current generation: pop_host [pop][dim], scores_host [pop]; NULL pointers are skipped */
+int nlsg_de_batch_download(nlsg_de_batch *e, uint64_t b, double *pop_host, double *scores_host);
+/* overwrites the current generation of every solve: pops_host [batch][pop][dim], scores_host
+ * [batch][pop] (nlsg_de_upload per solve) */
+int nlsg_de_batch_upload(nlsg_de_batch *e, const double *pops_host, const double *scores_host);
+/* init, then launches until every solve is done (one word read per launch); x_inout_host
+ * [batch][dim]: x0 in, the row of best_id out (nlsolver.h:2444); status_host [batch] may be NULL */
+int nlsg_de_batch_minimize(nlsg_de_batch *e, double *x_inout_host, const uint64_t *seeds_host,
+                           nlsg_status *status_host);
+/* `repeats` whole solves (init kernel and the host's polls included) bracketed by hipEvents */
+int nlsg_de_batch_time_solve(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host,
+                             uint32_t repeats, float *ms_total);
+
+/* ========================================================================== */
 /* Batched linear least squares by Givens QR — replaces tinyqr::lm             */
 /* (tinyqr.h:461-470: qr_decomposition :291-310 -> qr_impl :253-283 with        */
 /* givens_rotation :86-97 and rotate_matrix :126-139, then back_solve :437-459) */

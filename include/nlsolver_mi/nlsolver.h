@@ -337,6 +337,15 @@ class api {
   decltype(&nlsg_de_ref_destroy) de_ref_destroy = nullptr;
   decltype(&nlsg_de_ref_minimize) de_ref_minimize = nullptr;
   bool has_de_ref() const { return de_ref_create && de_ref_create_custom && de_ref_destroy && de_ref_minimize; }
+  // optional: null when the library was built without the resident batch DE
+  decltype(&nlsg_de_batch_lds_bytes) de_batch_lds_bytes = nullptr;
+  decltype(&nlsg_de_batch_create) de_batch_create = nullptr;
+  decltype(&nlsg_de_batch_create_custom) de_batch_create_custom = nullptr;
+  decltype(&nlsg_de_batch_destroy) de_batch_destroy = nullptr;
+  decltype(&nlsg_de_batch_minimize) de_batch_minimize = nullptr;
+  bool has_de_batch() const {
+    return de_batch_lds_bytes && de_batch_create && de_batch_create_custom && de_batch_destroy && de_batch_minimize;
+  }
 
   void check(int rc) const {
     if (rc != NLSG_OK)
@@ -387,6 +396,11 @@ class api {
     bind_optional(h, "nlsg_de_ref_create_custom", de_ref_create_custom);
     bind_optional(h, "nlsg_de_ref_destroy", de_ref_destroy);
     bind_optional(h, "nlsg_de_ref_minimize", de_ref_minimize);
+    bind_optional(h, "nlsg_de_batch_lds_bytes", de_batch_lds_bytes);
+    bind_optional(h, "nlsg_de_batch_create", de_batch_create);
+    bind_optional(h, "nlsg_de_batch_create_custom", de_batch_create_custom);
+    bind_optional(h, "nlsg_de_batch_destroy", de_batch_destroy);
+    bind_optional(h, "nlsg_de_batch_minimize", de_batch_minimize);
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
   }
@@ -474,6 +488,29 @@ inline de_generation &de_generation_mode() {
   }();
   return mode;
 }
+
+// How a keyed DE solve is driven on the device:
+//   turns     (default) the turn engine (nlsg_de_*): one launch per generation, any size.
+//   resident  one workgroup holds the population in LDS and runs the whole turn loop in one kernel
+//             (nlsg_de_batch_*, one solve): the same x and status bit for bit, a launch or two
+//             instead of one per generation. Taken when the population fits a workgroup's LDS
+//             (4 <= pop <= 1024, dim <= 128, about pop x dim <= 9 900: nlsg_de_batch_lds_bytes) and
+//             the library has the engine; the turn engine solves everything else.
+// Set before the solves it should govern: `nlsolver::device::de_driver_mode() = de_driver::resident`,
+// or the environment variable NLSG_DE_DRIVER = turns | resident (read at first use).
+enum class de_driver { turns, resident };
+inline de_driver &de_driver_mode() {
+  static de_driver mode = [] {
+    const char *e = std::getenv("NLSG_DE_DRIVER");
+    const std::string v = e ? e : "";
+    if (v == "resident") return de_driver::resident;
+    if (!v.empty() && v != "turns")
+      throw device_error("NLSG_DE_DRIVER must be turns or resident, not '" + v + "'");
+    return de_driver::turns;
+  }();
+  return mode;
+}
+constexpr uint64_t de_resident_lds_budget = 160 * 1024;  // bytes of LDS one gfx950 workgroup can take
 }  // namespace device
 
 // ---------------------------------------------------------------------------
@@ -522,6 +559,10 @@ class DE {
   solver_status<scalar_t> solve_device(std::vector<scalar_t> &x) {
     if (device::de_generation_mode() == device::de_generation::reference) return solve_reference<minimize>(x);
     const device::api &api = device::api::get();
+    if (device::de_driver_mode() == device::de_driver::resident && api.has_de_batch()) {
+      const uint64_t need = api.de_batch_lds_bytes(pop_size, x.size());
+      if (need != 0 && need <= device::de_resident_lds_budget) return solve_resident<minimize>(x);
+    }
     nlsg_de_config cfg{};
     cfg.struct_size = sizeof(cfg);
     if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
@@ -549,6 +590,41 @@ class DE {
     const int rc = api.de_minimize(eng, x.data(), 0, &st);
     const std::string msg = rc ? api.last_error() : "";
     api.de_destroy(eng);
+    if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
+    return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
+  }
+
+  // device::de_driver::resident: the same keyed solve through the resident batch engine (one solve)
+  template <bool minimize>
+  solver_status<scalar_t> solve_resident(std::vector<scalar_t> &x) {
+    const device::api &api = device::api::get();
+    nlsg_de_batch_config cfg{};
+    cfg.struct_size = sizeof(cfg);
+    if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+    cfg.objective = Callable::nlsg_objective;
+    cfg.minimize = minimize ? 1 : 0;
+    cfg.strategy = RecombinationType == best ? NLSG_DE_BEST : NLSG_DE_RANDOM;
+    cfg.batch = 1;
+    cfg.pop = pop_size;
+    cfg.dim = x.size();
+    cfg.CR = crossover_prob;
+    cfg.F = differential_weight;
+    cfg.eps = eps;
+    cfg.max_iter = max_iter;
+    cfg.best_val_no_change = best_value_no_change;
+    const uint64_t seed = device::seed_from(generator);
+    nlsg_de_batch *eng = nullptr;
+    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
+      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
+      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+      api.check(api.de_batch_create_custom(&cfg, &obj, &eng));
+    } else {
+      api.check(api.de_batch_create(&cfg, &eng));
+    }
+    nlsg_status st{};
+    const int rc = api.de_batch_minimize(eng, x.data(), &seed, &st);
+    const std::string msg = rc ? api.last_error() : "";
+    api.de_batch_destroy(eng);
     if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
     return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
   }

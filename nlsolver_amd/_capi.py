@@ -57,6 +57,14 @@ class DERefConfig(C.Structure):  # nlsg_de_ref_config
                 ("max_iter", u64), ("best_val_no_change", u64), ("log_capacity", u64)]
 
 
+class DEBatchConfig(C.Structure):  # nlsg_de_batch_config
+    _fields_ = [("struct_size", C.c_uint32), ("device", i32), ("stream", C.c_void_p),
+                ("objective", i32), ("minimize", i32), ("strategy", i32), ("reserved", i32),
+                ("batch", u64), ("pop", u64), ("dim", u64),
+                ("CR", f64), ("F", f64), ("eps", f64),
+                ("max_iter", u64), ("best_val_no_change", u64), ("turns_per_launch", u64)]
+
+
 class CustomObjectiveC(C.Structure):  # nlsg_custom_objective
     _fields_ = [("term_body", C.c_char_p), ("finish_body", C.c_char_p), ("chain", i32),
                 ("reserved", i32)]
@@ -236,9 +244,23 @@ OPTIONAL_SYMBOLS = {
     "nlsg_de_ref_time_solve": (C.c_int, [_H, pd, pu, C.c_uint32, C.POINTER(C.c_float)]),
     "nlsg_de_ref_jump_table": (C.c_int, [pu]),
     "nlsg_de_ref_pick_donors": (C.c_int, [pd, u64, u64, u64, pu, pu, C.POINTER(i32)]),
+    "nlsg_de_batch_lds_bytes": (u64, [u64, u64]),
+    "nlsg_de_batch_create": (C.c_int, [C.POINTER(DEBatchConfig), C.POINTER(_H)]),
+    "nlsg_de_batch_create_custom": (C.c_int, [C.POINTER(DEBatchConfig), C.POINTER(CustomObjectiveC),
+                                              C.POINTER(_H)]),
+    "nlsg_de_batch_destroy": (C.c_int, [_H]),
+    "nlsg_de_batch_init": (C.c_int, [_H, pd, pu]),
+    "nlsg_de_batch_step": (C.c_int, [_H, u64]),
+    "nlsg_de_batch_status": (C.c_int, [_H, C.POINTER(Status)]),
+    "nlsg_de_batch_best": (C.c_int, [_H, pd, pd, pu]),
+    "nlsg_de_batch_download": (C.c_int, [_H, u64, pd, pd]),
+    "nlsg_de_batch_upload": (C.c_int, [_H, pd, pd]),
+    "nlsg_de_batch_minimize": (C.c_int, [_H, pd, pu, C.POINTER(Status)]),
+    "nlsg_de_batch_time_solve": (C.c_int, [_H, pd, pu, C.c_uint32, C.POINTER(C.c_float)]),
 }
 SYMBOLS.update(OPTIONAL_SYMBOLS)
-_MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE"}
+_MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
+                    "nlsg_de_batch_": "library has no resident batch DE"}
 
 _lib = None
 

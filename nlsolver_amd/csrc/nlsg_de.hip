@@ -449,23 +449,7 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   p.shard_lo = cfg->shard_lo;
   p.shard_n = n;
   p.CR = cfg->CR;
-  {  // the crossover test u01(z) < CR on the draw itself: u01 is monotone in z, so there is a
-     // smallest z whose uniform reaches CR (none: every draw passes)
-    const double cr = cfg->CR;
-    if (u01(~0ull) < cr) {
-      p.cr_all = 1;
-      p.cr_thresh = ~0ull;
-    } else if (!(u01(0) < cr)) {  // CR <= 0 or NaN: no draw passes
-      p.cr_thresh = 0;
-    } else {
-      uint64_t lo = 0, hi = ~0ull;  // u01(lo) < CR <= u01(hi)
-      while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (u01(mid) < cr) lo = mid; else hi = mid;
-      }
-      p.cr_thresh = hi;
-    }
-  }
+  set_crossover_test(p, cfg->CR);
   p.F = cfg->F;
   p.eps = cfg->eps;
   p.fmul = cfg->minimize ? 1.0 : -1.0;  // f_multiplier, nlsolver.h:2418

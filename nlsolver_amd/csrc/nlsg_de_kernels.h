@@ -22,24 +22,11 @@
 #pragma once
 
 #include "nlsg_common.h"
+#include "nlsg_de_state.h"
 
 namespace nlsg {
 
-constexpr int kDeMaxTries = 64;       // bounded donor rejection loop
 constexpr int kTraceWords = 5;        // r1, r2, r3, jrand, accept
-
-// Device-resident solver state (one per engine).
-struct DeState {
-  uint64_t best_id;        // global index of the incumbent best
-  double best_f;           // its score
-  uint64_t iter;           // completed generations
-  uint64_t val_no_change;  // nlsolver.h:2439
-  uint64_t fcalls;
-  double std_err;
-  int32_t done;
-  int32_t parity;          // population / score buffer holding the current generation
-  int32_t pad[2];
-};
 
 // Where a row lives. A synchronous generation reads generation k and writes k + 1, but a row is
 // only stored when its trial is accepted: home[par][j] (0 or 1) says which of buf[0] / buf[1]
@@ -467,30 +454,6 @@ __global__ __launch_bounds__(256) void de_gather_kernel(DeParams p, int par, dou
 }
 
 // ---- best scan + stop tests -------------------------------------------------
-// Head number k looks at the population after k generations: buffer k & 1. It records
-// that position in the state; a head that fires a stop test freezes the state there.
-__device__ inline void head_position(DeState *st, const DeParams &p, uint64_t k) {
-  st->iter = k;
-  st->fcalls = p.pop * (k + 1);
-  st->parity = static_cast<int32_t>(k & 1);
-}
-
-// Counters and stop tests shared by the two finalisers (thread 0 only).
-__device__ inline void finish_turn(DeState *st, const DeParams &p, uint64_t bi, double bv,
-                                   bool have_best, double se) {
-  // not_updated <=> best_id did not move: the strict '<' scan (:2431-2437) can
-  // never return to the incumbent once it has left it.
-  const bool not_updated = (bi == st->best_id);
-  st->val_no_change = not_updated ? st->val_no_change + 1 : 0;  // :2439
-  st->best_id = bi;
-  if (have_best) st->best_f = bv;
-  st->std_err = se;
-  if (st->iter >= p.max_iter || st->val_no_change >= p.best_val_no_change ||
-      (p.eps > 0 && se < p.eps)) {  // :2441-2443
-    st->done = 1;
-  }
-}
-
 // ---- the head of a turn ---------------------------------------------------------
 // Separate scan / finisher launches cost a dependent dispatch each (~5 us; 10 us of a 59 us
 // turn at pop 65536 for eps <= 0, five launches and ~25 us with a two-pass std_err), so a head

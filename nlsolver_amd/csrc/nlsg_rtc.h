@@ -40,6 +40,13 @@ struct DeRefRtcKernels {  // reference-order DE (nlsg_de_ref_kernels.h)
 };
 int rtc_build_de_ref(const nlsg_custom_objective *obj, DeRefRtcKernels *out);
 void rtc_release(DeRefRtcKernels *k);
+struct DeBatchRtcKernels {  // resident batch DE (nlsg_de_batch_kernels.h)
+  hipModule_t mod = nullptr;
+  hipFunction_t init = nullptr, turns = nullptr;
+};
+// group: lanes per agent (4 / 8 / 16 / 32), or 64 for one wave per agent
+int rtc_build_de_batch(const nlsg_custom_objective *obj, int group, DeBatchRtcKernels *out);
+void rtc_release(DeBatchRtcKernels *k);
 struct LmRtcKernels {  // finite-difference model (default functors) around the user's objective
   hipModule_t mod = nullptr;
   hipFunction_t iter = nullptr;

@@ -214,6 +214,26 @@ int rtc_build_de(const nlsg_custom_objective *obj, int chunks, bool vec, int gro
   return NLSG_OK;
 }
 
+// the resident batch engine's two kernels, next to the turn kernels they restate
+int rtc_build_de_batch(const nlsg_custom_objective *obj, int group, DeBatchRtcKernels *out) {
+  const std::string id = std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM));
+  std::vector<hipFunction_t> f;
+  DeBatchRtcKernels k;
+  const int rc = rtc_compile(obj, "nlsg_de_batch_kernels.h",
+                             {"nlsg::de_batch_init_kernel<" + id + ">",
+                              "nlsg::de_batch_kernel<" + id + ", " + std::to_string(group) + ">"},
+                             &k.mod, &f);
+  if (rc) return rc;
+  k.init = f[0];
+  k.turns = f[1];
+  *out = k;
+  return NLSG_OK;
+}
+void rtc_release(DeBatchRtcKernels *k) {
+  if (k && k->mod) hipModuleUnload(k->mod);
+  if (k) *k = DeBatchRtcKernels();
+}
+
 int rtc_build_pso(const nlsg_custom_objective *obj, int chunks, bool vec, int type, int group,
                   PsoRtcKernels *out) {
   if (chunks == 0) {  // D > 1024: the segment-streaming kernels

@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import DE_BEST, DE_RANDOM, DEConfig, DERefConfig, Status, check, lib, require
+from ._capi import (DE_BEST, DE_RANDOM, DEBatchConfig, DEConfig, DERefConfig, NlsgError, Status, check,
+                    lib, require)
 from .rng import XorShift
 
 DEFAULT_SEED = 12374563468  # rng::splitmix seed, nlsolver.h:1265
@@ -278,6 +279,130 @@ class DERefEngine:
         return ms.value
 
 
+LDS_BUDGET = 160 * 1024  # bytes of LDS one gfx950 workgroup can take (DEBatchEngine's limit)
+
+
+class DEBatchEngine:
+    """Resident batch DE (nlsg_de_batch_*): `batch` independent solves of the keyed engine of one
+    shape, each with its own 64-bit seed and x0, one workgroup per solve with the population in LDS
+    and the whole turn loop inside one kernel. Solve b is bit-identical to
+    DEEngine(objective, pop, dim, seed=seeds[b], ...) driven by the same calls; it ends
+    independently of its neighbours. 4 <= pop <= 1024, 1 <= dim <= 128 and lds_bytes(pop, dim)
+    within LDS_BUDGET, else NlsgError (code 2): there is no global-memory fallback."""
+
+    @staticmethod
+    def lds_bytes(pop, dim):
+        """LDS bytes a solve of this shape needs; 0 outside the pop / dim ranges (host only)"""
+        return int(require("nlsg_de_batch_lds_bytes")(pop, dim))
+
+    @staticmethod
+    def fits(pop, dim):
+        need = DEBatchEngine.lds_bytes(pop, dim)
+        return 0 < need <= LDS_BUDGET
+
+    def __init__(self, objective, batch, pop, dim, *, minimize=True, strategy=DE_RANDOM, CR=0.9,
+                 F=0.8, eps=10e-4, max_iter=1000, best_val_no_change=50, turns_per_launch=0,
+                 device=0, stream=None):
+        cfg = DEBatchConfig()
+        cfg.struct_size = C.sizeof(DEBatchConfig)
+        cfg.device = device
+        cfg.stream = None if stream is None else (stream or 1)
+        custom = objective if isinstance(objective, CustomObjective) else None
+        cfg.objective = (_capi.OBJ_CUSTOM if custom else
+                         _capi.OBJECTIVES[objective] if isinstance(objective, str) else objective)
+        cfg.minimize, cfg.strategy = int(bool(minimize)), strategy
+        cfg.batch, cfg.pop, cfg.dim = batch, pop, dim
+        cfg.CR, cfg.F, cfg.eps = CR, F, eps
+        cfg.max_iter, cfg.best_val_no_change = max_iter, best_val_no_change
+        cfg.turns_per_launch = turns_per_launch
+        self.cfg = cfg
+        self._h = C.c_void_p()
+        if custom:
+            create = require("nlsg_de_batch_create_custom")
+            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
+            obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
+                                         int(custom.chain), 0)
+            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+        else:
+            check(require("nlsg_de_batch_create")(C.byref(cfg), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().nlsg_de_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _inputs(self, x0, seeds):
+        B, D = self.cfg.batch, self.cfg.dim
+        x0 = np.array(x0, dtype=np.float64).reshape(B, D)
+        seeds = np.array([int(s) & (2**64 - 1) for s in np.asarray(seeds, dtype=object).ravel()],
+                         dtype=np.uint64).reshape(B)
+        return x0, seeds
+
+    def init(self, x0, seeds):
+        """x0 [batch, dim], seeds [batch]: DEEngine.init of every solve under its own seed"""
+        x0, seeds = self._inputs(x0, seeds)
+        check(lib().nlsg_de_batch_init(self._h, x0.ctypes.data_as(_capi.pd), seeds.ctypes.data_as(_capi.pu)))
+
+    def step(self, turns=1):
+        check(lib().nlsg_de_batch_step(self._h, turns))
+
+    def status(self):
+        """[Status] * batch, each what DEEngine.status() returns after the same calls"""
+        st = (Status * self.cfg.batch)()
+        check(lib().nlsg_de_batch_status(self._h, st))
+        return list(st)
+
+    def best(self):
+        """(x [batch, dim], f [batch], index [batch]) as of every solve's last head"""
+        B, D = self.cfg.batch, self.cfg.dim
+        x, f, idx = np.empty((B, D)), np.empty(B), np.empty(B, dtype=np.uint64)
+        check(lib().nlsg_de_batch_best(self._h, x.ctypes.data_as(_capi.pd), f.ctypes.data_as(_capi.pd),
+                                       idx.ctypes.data_as(_capi.pu)))
+        return x, f, idx
+
+    def download(self, b):
+        """(pop [pop, dim], scores [pop]) of solve b's current generation"""
+        n, D = self.cfg.pop, self.cfg.dim
+        pop, scores = np.empty((n, D)), np.empty(n)
+        check(lib().nlsg_de_batch_download(self._h, b, pop.ctypes.data_as(_capi.pd),
+                                           scores.ctypes.data_as(_capi.pd)))
+        return pop, scores
+
+    def upload(self, pops, scores):
+        """overwrites the current generation of every solve: pops [batch, pop, dim], scores [batch, pop]"""
+        B, n, D = self.cfg.batch, self.cfg.pop, self.cfg.dim
+        pops = np.ascontiguousarray(pops, dtype=np.float64)
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        assert pops.shape == (B, n, D) and scores.shape == (B, n)
+        check(lib().nlsg_de_batch_upload(self._h, pops.ctypes.data_as(_capi.pd),
+                                         scores.ctypes.data_as(_capi.pd)))
+
+    def minimize(self, x, seeds):
+        """init, then turns until every solve is done -> (x [batch, dim], [Status] * batch): new
+        arrays, the inputs are kept"""
+        x, seeds = self._inputs(x, seeds)
+        st = (Status * self.cfg.batch)()
+        check(lib().nlsg_de_batch_minimize(self._h, x.ctypes.data_as(_capi.pd),
+                                           seeds.ctypes.data_as(_capi.pu), st))
+        return x, list(st)
+
+    def time_solve(self, x0, seeds, repeats=1):
+        """milliseconds of `repeats` whole solves from x0 / seeds (hipEvents)"""
+        x0, seeds = self._inputs(x0, seeds)
+        ms = C.c_float()
+        check(lib().nlsg_de_batch_time_solve(self._h, x0.ctypes.data_as(_capi.pd),
+                                             seeds.ctypes.data_as(_capi.pu), repeats, C.byref(ms)))
+        return ms.value
+
+
 def jump_table():
     """The nibble table of M^64 the reference-order engine advances its lanes with:
     uint64 [32, 16, 2] (entry (j, v) = xorshift128+ advanced 64 steps from the state whose nibble
@@ -303,13 +428,24 @@ class DE:
     generation="reference": the reference's own generation on the caller's generator, which must
     then be an XorShift; it is advanced in place exactly as the reference advances it, and x and the
     status are the reference's bit for bit (DERefEngine, batch 1). Default: the keyed engine
-    (synchronous generation, counter generator keyed by two draws of `generator`)."""
+    (synchronous generation, counter generator keyed by two draws of `generator`).
+
+    driver="resident": the keyed solve runs through a batch-1 DEBatchEngine -- the whole turn loop
+    in one kernel instead of a launch per generation -- when the population fits a workgroup's LDS
+    (DEBatchEngine.fits), through DEEngine otherwise; the bits are the same either way.
+    `driver_used` says which engine the last solve ran on. Default "turns": DEEngine."""
 
     def __init__(self, f, generator=None, crossover_prob=0.9, differential_weight=0.8, eps=10e-4,
                  pop_size=50, max_iter=1000, best_val_no_change=50, *, strategy=DE_RANDOM,
-                 device=0, generation="keyed"):
+                 device=0, generation="keyed", driver="turns"):
         if generation not in ("keyed", "reference"):
             raise ValueError(f"generation must be 'keyed' or 'reference', not {generation!r}")
+        if driver not in ("turns", "resident"):
+            raise ValueError(f"driver must be 'turns' or 'resident', not {driver!r}")
+        if driver == "resident" and generation == "reference":
+            raise ValueError("driver='resident' runs the keyed generation: it cannot be combined with "
+                             "generation='reference'")
+        self.driver, self.driver_used = driver, None
         if generation == "reference" and not isinstance(generator, XorShift):
             raise TypeError("generation='reference' draws from the caller's stream: generator must be an "
                             "nlsolver_amd.XorShift")
@@ -329,9 +465,22 @@ class DE:
             self.generator.state = tuple(int(v) for v in states[0])
             return st[0]
         seed = seed_from_generator(self.generator)
+        if self.driver == "resident" and self._resident_fits(x.size):
+            with DEBatchEngine(self.f, 1, self.pop_size, x.size, minimize=minimize, **self.args) as eng:
+                xo, st = eng.minimize(x[None, :], [seed])
+            x[:] = xo[0]
+            self.driver_used = "resident"
+            return st[0]
+        self.driver_used = "turns"
         with DEEngine(self.f, self.pop_size, x.size, minimize=minimize, seed=seed,
                       **self.args) as eng:
             return eng.minimize(x)
+
+    def _resident_fits(self, dim):
+        try:
+            return DEBatchEngine.fits(self.pop_size, dim)
+        except NlsgError:  # a library without the resident engine: the turn engine solves
+            return False
 
     def minimize(self, x):
         return self._solve(x, True)

@@ -719,6 +719,75 @@ int nlsg_de_batch_time_solve(nlsg_de_batch *e, const double *x0_host, const uint
                              uint32_t repeats, float *ms_total);
 
 /* ========================================================================== */
+/* Resident batch Particle Swarm Optimisation — `batch` independent solves of  */
+/* the keyed engine above (nlsg_pso_*) of one shape, each with its own 64-bit  */
+/* seed and its own lower[dim] / upper[dim] (the unbounded overload seeds the  */
+/* swarm from -+|x|, so the bounds differ from solve to solve). One workgroup  */
+/* per solve; the swarm stays in LDS and the whole turn loop (head: best scan  */
+/* of the last evaluation, std_err of the personal bests, no-change counter,   */
+/* stop tests; then the move) runs inside one kernel, so a small solve costs a */
+/* launch or two instead of up to seven per turn. Solve b is bit-identical to  */
+/* nlsg_pso_* created with seed = seeds[b] and driven by the same calls with   */
+/* lower[b], upper[b]; it ends independently of its neighbours and freezes at  */
+/* the head that fired. 1 <= n_particles <= 1024, 1 <= dim <= 128, and         */
+/* nlsg_pso_batch_lds_bytes(n, dim, type) within a workgroup's 160 KiB:        */
+/* anything else is NLSG_ERR_UNSUPPORTED — no global-memory fallback, no       */
+/* shards. See DESIGN.md §4c.                                                  */
+/* ========================================================================== */
+typedef struct nlsg_pso_batch nlsg_pso_batch;
+
+typedef struct {
+  uint32_t struct_size; /* sizeof(nlsg_pso_batch_config)                          */
+  int32_t device;
+  void *stream;         /* as nlsg_de_config.stream                               */
+  int32_t objective;    /* nlsg_objective                                         */
+  int32_t minimize;     /* 1 = minimize(), 0 = maximize()                         */
+  int32_t type;         /* nlsg_pso_type                                          */
+  int32_t bounded;      /* as nlsg_pso_config.bounded                             */
+  uint64_t batch;       /* independent solves, one workgroup each (>= 1)          */
+  uint64_t n_particles; /* 1 .. 1024                                              */
+  uint64_t dim;         /* 1 .. 128                                               */
+  double inertia, cognitive, social, eps;
+  uint64_t max_iter, best_val_no_change;
+  uint64_t turns_per_launch; /* step / minimize are cut into launches of at most  */
+                             /* this many turns; 0 = the engine's default (1024)  */
+} nlsg_pso_batch_config;
+
+/* LDS bytes a solve of this shape needs; 0 outside the n_particles / dim ranges or for an unknown
+ * type. Host only, no device. */
+uint64_t nlsg_pso_batch_lds_bytes(uint64_t n_particles, uint64_t dim, int32_t type);
+/* Checked before the device is touched, in this order: null pointers, struct_size (code 1),
+ * batch >= 1 (1), type (1), the n_particles / dim ranges (2), the LDS budget (2). */
+int nlsg_pso_batch_create(const nlsg_pso_batch_config *cfg, nlsg_pso_batch **out);
+/* cfg->objective == NLSG_OBJ_CUSTOM, term / chain or whole-vector form, as nlsg_pso_create_custom */
+int nlsg_pso_batch_create_custom(const nlsg_pso_batch_config *cfg, const nlsg_custom_objective *obj,
+                                 nlsg_pso_batch **out);
+int nlsg_pso_batch_destroy(nlsg_pso_batch *e);
+/* lower_host / upper_host [batch][dim], seeds_host [batch]: nlsg_pso_init of every solve under
+ * its own seed and bounds */
+int nlsg_pso_batch_init(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
+                        const uint64_t *seeds_host);
+/* `turns` turns of every solve that is not done (nlsg_pso_step per solve). Asynchronous. */
+int nlsg_pso_batch_step(nlsg_pso_batch *e, uint64_t turns);
+/* out [batch]: what nlsg_pso_status reports for each solve after the same calls. Synchronises. */
+int nlsg_pso_batch_status(nlsg_pso_batch *e, nlsg_status *out);
+/* x_host [batch][dim], f [batch], index [batch]: every solve's swarm best (nlsg_pso_best); NULL
+ * pointers are skipped */
+int nlsg_pso_batch_best(nlsg_pso_batch *e, double *x_host, double *f, uint64_t *index);
+/* solve b's swarm as nlsg_pso_download gives it: positions and (Vanilla) velocities [n][dim],
+ * personal-best values and values of the last evaluation [n]; NULL pointers are skipped */
+int nlsg_pso_batch_download(nlsg_pso_batch *e, uint64_t b, double *pos_host, double *vel_host,
+                            double *pbest_val_host, double *cur_val_host);
+/* init, then launches until every solve is done (one word read per launch); x_out_host
+ * [batch][dim] <- every solve's swarm best; status_host [batch] may be NULL */
+int nlsg_pso_batch_minimize(nlsg_pso_batch *e, double *x_out_host, const double *lower_host,
+                            const double *upper_host, const uint64_t *seeds_host,
+                            nlsg_status *status_host);
+/* `repeats` whole solves (init kernel and the host's polls included) bracketed by hipEvents */
+int nlsg_pso_batch_time_solve(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
+                              const uint64_t *seeds_host, uint32_t repeats, float *ms_total);
+
+/* ========================================================================== */
 /* Batched linear least squares by Givens QR — replaces tinyqr::lm             */
 /* (tinyqr.h:461-470: qr_decomposition :291-310 -> qr_impl :253-283 with        */
 /* givens_rotation :86-97 and rotate_matrix :126-139, then back_solve :437-459) */

@@ -346,6 +346,16 @@ class api {
   bool has_de_batch() const {
     return de_batch_lds_bytes && de_batch_create && de_batch_create_custom && de_batch_destroy && de_batch_minimize;
   }
+  // optional: null when the library was built without the resident batch PSO
+  decltype(&nlsg_pso_batch_lds_bytes) pso_batch_lds_bytes = nullptr;
+  decltype(&nlsg_pso_batch_create) pso_batch_create = nullptr;
+  decltype(&nlsg_pso_batch_create_custom) pso_batch_create_custom = nullptr;
+  decltype(&nlsg_pso_batch_destroy) pso_batch_destroy = nullptr;
+  decltype(&nlsg_pso_batch_minimize) pso_batch_minimize = nullptr;
+  bool has_pso_batch() const {
+    return pso_batch_lds_bytes && pso_batch_create && pso_batch_create_custom && pso_batch_destroy &&
+           pso_batch_minimize;
+  }
 
   void check(int rc) const {
     if (rc != NLSG_OK)
@@ -401,6 +411,11 @@ class api {
     bind_optional(h, "nlsg_de_batch_create_custom", de_batch_create_custom);
     bind_optional(h, "nlsg_de_batch_destroy", de_batch_destroy);
     bind_optional(h, "nlsg_de_batch_minimize", de_batch_minimize);
+    bind_optional(h, "nlsg_pso_batch_lds_bytes", pso_batch_lds_bytes);
+    bind_optional(h, "nlsg_pso_batch_create", pso_batch_create);
+    bind_optional(h, "nlsg_pso_batch_create_custom", pso_batch_create_custom);
+    bind_optional(h, "nlsg_pso_batch_destroy", pso_batch_destroy);
+    bind_optional(h, "nlsg_pso_batch_minimize", pso_batch_minimize);
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
   }
@@ -511,6 +526,29 @@ inline de_driver &de_driver_mode() {
   return mode;
 }
 constexpr uint64_t de_resident_lds_budget = 160 * 1024;  // bytes of LDS one gfx950 workgroup can take
+
+// How a PSO solve is driven on the device, as de_driver:
+//   turns     (default) the turn engine (nlsg_pso_*): up to seven launches per turn, any size.
+//   resident  one workgroup holds the swarm in LDS and runs the whole turn loop in one kernel
+//             (nlsg_pso_batch_*, one solve): the same x and status bit for bit, for both types and
+//             both overloads. Taken when the swarm fits a workgroup's LDS (n_particles <= 1024,
+//             dim <= 128, nlsg_pso_batch_lds_bytes within 160 KiB) and the library has the engine;
+//             the turn engine solves everything else.
+// Set before the solves it should govern: `nlsolver::device::pso_driver_mode() = pso_driver::resident`,
+// or the environment variable NLSG_PSO_DRIVER = turns | resident (read at first use).
+enum class pso_driver { turns, resident };
+inline pso_driver &pso_driver_mode() {
+  static pso_driver mode = [] {
+    const char *e = std::getenv("NLSG_PSO_DRIVER");
+    const std::string v = e ? e : "";
+    if (v == "resident") return pso_driver::resident;
+    if (!v.empty() && v != "turns")
+      throw device_error("NLSG_PSO_DRIVER must be turns or resident, not '" + v + "'");
+    return pso_driver::turns;
+  }();
+  return mode;
+}
+constexpr uint64_t pso_resident_lds_budget = 160 * 1024;
 }  // namespace device
 
 // ---------------------------------------------------------------------------
@@ -817,6 +855,12 @@ class PSO {
     if constexpr (device::is_device_objective<Callable>::value) {
       static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
       const device::api &api = device::api::get();
+      if (device::pso_driver_mode() == device::pso_driver::resident && api.has_pso_batch()) {
+        const uint64_t need = api.pso_batch_lds_bytes(
+            n_particles, x.size(), Type == Accelerated ? NLSG_PSO_ACCELERATED : NLSG_PSO_VANILLA);
+        if (need != 0 && need <= device::pso_resident_lds_budget)
+          return solve_resident<minimize, constrained>(x, lower, upper);
+      }
       nlsg_pso_config cfg{};
       cfg.struct_size = sizeof(cfg);
       if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
@@ -850,6 +894,44 @@ class PSO {
     } else {
       return solve_host<minimize, constrained>(x, lower, upper);
     }
+  }
+
+  // device::pso_driver::resident: the same solve through the resident batch engine (one solve)
+  template <bool minimize, bool constrained>
+  solver_status<scalar_t> solve_resident(std::vector<scalar_t> &x, const std::vector<scalar_t> &lower,
+                                         const std::vector<scalar_t> &upper) {
+    const device::api &api = device::api::get();
+    nlsg_pso_batch_config cfg{};
+    cfg.struct_size = sizeof(cfg);
+    if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+    cfg.objective = Callable::nlsg_objective;
+    cfg.minimize = minimize ? 1 : 0;
+    cfg.type = Type == Accelerated ? NLSG_PSO_ACCELERATED : NLSG_PSO_VANILLA;
+    cfg.bounded = constrained ? 1 : 0;
+    cfg.batch = 1;
+    cfg.n_particles = n_particles;
+    cfg.dim = x.size();
+    cfg.inertia = inertia0;
+    cfg.cognitive = cognitive_coef;
+    cfg.social = social_coef;
+    cfg.eps = eps;
+    cfg.max_iter = max_iter;
+    cfg.best_val_no_change = best_val_no_change;
+    const uint64_t seed = device::seed_from(generator);
+    nlsg_pso_batch *eng = nullptr;
+    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
+      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
+      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+      api.check(api.pso_batch_create_custom(&cfg, &obj, &eng));
+    } else {
+      api.check(api.pso_batch_create(&cfg, &eng));
+    }
+    nlsg_status st{};
+    const int rc = api.pso_batch_minimize(eng, x.data(), lower.data(), upper.data(), &seed, &st);
+    const std::string msg = rc ? api.last_error() : "";
+    api.pso_batch_destroy(eng);
+    if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
+    return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
   }
 
   // Host path for arbitrary callables: the reference's serial algorithm

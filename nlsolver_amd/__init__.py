@@ -18,7 +18,7 @@ Layout:
 from ._capi import DE_BEST, DE_RANDOM, PSO_ACCELERATED, PSO_VANILLA, NlsgError, pinned_empty  # noqa: F401
 from .de import DE, CustomObjective, DEBatchEngine, DEEngine, DERefEngine, DESolver  # noqa: F401
 from .rng import XorShift  # noqa: F401
-from .pso import PSO, PSOEngine, PSOSolver  # noqa: F401
+from .pso import PSO, PSOBatchEngine, PSOEngine, PSOSolver  # noqa: F401
 from .bfgs import BFGS, BFGSEngine, QuadDiagRank1  # noqa: F401
 from .lm import LevenbergMarquardt, LMEngine, TanhRegression  # noqa: F401
 from .nm import NelderMead, NMEngine  # noqa: F401

@@ -81,6 +81,14 @@ class PSOConfig(C.Structure):
                 ("max_iter", u64), ("best_val_no_change", u64), ("seed", u64)]
 
 
+class PSOBatchConfig(C.Structure):  # nlsg_pso_batch_config
+    _fields_ = [("struct_size", C.c_uint32), ("device", i32), ("stream", C.c_void_p),
+                ("objective", i32), ("minimize", i32), ("type", i32), ("bounded", i32),
+                ("batch", u64), ("n_particles", u64), ("dim", u64),
+                ("inertia", f64), ("cognitive", f64), ("social", f64), ("eps", f64),
+                ("max_iter", u64), ("best_val_no_change", u64), ("turns_per_launch", u64)]
+
+
 OBJ_QUAD_DIAG_RANK1 = 16
 
 
@@ -257,10 +265,23 @@ OPTIONAL_SYMBOLS = {
     "nlsg_de_batch_upload": (C.c_int, [_H, pd, pd]),
     "nlsg_de_batch_minimize": (C.c_int, [_H, pd, pu, C.POINTER(Status)]),
     "nlsg_de_batch_time_solve": (C.c_int, [_H, pd, pu, C.c_uint32, C.POINTER(C.c_float)]),
+    "nlsg_pso_batch_lds_bytes": (u64, [u64, u64, i32]),
+    "nlsg_pso_batch_create": (C.c_int, [C.POINTER(PSOBatchConfig), C.POINTER(_H)]),
+    "nlsg_pso_batch_create_custom": (C.c_int, [C.POINTER(PSOBatchConfig), C.POINTER(CustomObjectiveC),
+                                               C.POINTER(_H)]),
+    "nlsg_pso_batch_destroy": (C.c_int, [_H]),
+    "nlsg_pso_batch_init": (C.c_int, [_H, pd, pd, pu]),
+    "nlsg_pso_batch_step": (C.c_int, [_H, u64]),
+    "nlsg_pso_batch_status": (C.c_int, [_H, C.POINTER(Status)]),
+    "nlsg_pso_batch_best": (C.c_int, [_H, pd, pd, pu]),
+    "nlsg_pso_batch_download": (C.c_int, [_H, u64, pd, pd, pd, pd]),
+    "nlsg_pso_batch_minimize": (C.c_int, [_H, pd, pd, pd, pu, C.POINTER(Status)]),
+    "nlsg_pso_batch_time_solve": (C.c_int, [_H, pd, pd, pu, C.c_uint32, C.POINTER(C.c_float)]),
 }
 SYMBOLS.update(OPTIONAL_SYMBOLS)
 _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
-                    "nlsg_de_batch_": "library has no resident batch DE"}
+                    "nlsg_de_batch_": "library has no resident batch DE",
+                    "nlsg_pso_batch_": "library has no resident batch PSO"}
 
 _lib = None
 

@@ -47,6 +47,13 @@ struct DeBatchRtcKernels {  // resident batch DE (nlsg_de_batch_kernels.h)
 // group: lanes per agent (4 / 8 / 16 / 32), or 64 for one wave per agent
 int rtc_build_de_batch(const nlsg_custom_objective *obj, int group, DeBatchRtcKernels *out);
 void rtc_release(DeBatchRtcKernels *k);
+struct PsoBatchRtcKernels {  // resident batch PSO (nlsg_pso_batch_kernels.h)
+  hipModule_t mod = nullptr;
+  hipFunction_t init = nullptr, turns = nullptr;
+};
+// group: lanes per particle (4 / 8 / 16 / 32), or 64 for one wave per particle; type = nlsg_pso_type
+int rtc_build_pso_batch(const nlsg_custom_objective *obj, int group, int type, PsoBatchRtcKernels *out);
+void rtc_release(PsoBatchRtcKernels *k);
 struct LmRtcKernels {  // finite-difference model (default functors) around the user's objective
   hipModule_t mod = nullptr;
   hipFunction_t iter = nullptr;

@@ -234,6 +234,27 @@ void rtc_release(DeBatchRtcKernels *k) {
   if (k) *k = DeBatchRtcKernels();
 }
 
+// the resident batch PSO engine's two kernels, next to the turn kernels they restate
+int rtc_build_pso_batch(const nlsg_custom_objective *obj, int group, int type, PsoBatchRtcKernels *out) {
+  const std::string id = std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM));
+  std::vector<hipFunction_t> f;
+  PsoBatchRtcKernels k;
+  const int rc = rtc_compile(obj, "nlsg_pso_batch_kernels.h",
+                             {"nlsg::pso_batch_init_kernel<" + id + ">",
+                              "nlsg::pso_batch_kernel<" + id + ", " + std::to_string(group) + ", " +
+                                  std::to_string(type) + ">"},
+                             &k.mod, &f);
+  if (rc) return rc;
+  k.init = f[0];
+  k.turns = f[1];
+  *out = k;
+  return NLSG_OK;
+}
+void rtc_release(PsoBatchRtcKernels *k) {
+  if (k && k->mod) hipModuleUnload(k->mod);
+  if (k) *k = PsoBatchRtcKernels();
+}
+
 int rtc_build_pso(const nlsg_custom_objective *obj, int chunks, bool vec, int type, int group,
                   PsoRtcKernels *out) {
   if (chunks == 0) {  // D > 1024: the segment-streaming kernels

@@ -12,8 +12,9 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import PSO_ACCELERATED, PSO_VANILLA, PSOConfig, Status, check, lib
-from .de import DEFAULT_SEED, seed_from_generator
+from ._capi import (PSO_ACCELERATED, PSO_VANILLA, NlsgError, PSOBatchConfig, PSOConfig, Status, check, lib,
+                    require)
+from .de import DEFAULT_SEED, LDS_BUDGET, seed_from_generator
 
 
 class PSOEngine:
@@ -131,12 +132,141 @@ class PSOEngine:
         return w.value, r.value
 
 
+class PSOBatchEngine:
+    """Resident batch PSO (nlsg_pso_batch_*): `batch` independent solves of the keyed engine of one
+    shape, each with its own 64-bit seed and its own bounds, one workgroup per solve with the swarm
+    in LDS and the whole turn loop inside one kernel. Solve b is bit-identical to
+    PSOEngine(objective, n_particles, dim, seed=seeds[b], ...) driven by the same calls with
+    lower[b], upper[b]; it ends independently of its neighbours. 1 <= n_particles <= 1024,
+    1 <= dim <= 128 and lds_bytes(n_particles, dim, type) within LDS_BUDGET, else NlsgError
+    (code 2): there is no global-memory fallback."""
+
+    @staticmethod
+    def lds_bytes(n_particles, dim, type=PSO_VANILLA):
+        """LDS bytes a solve of this shape needs; 0 outside the ranges (host only)"""
+        return int(require("nlsg_pso_batch_lds_bytes")(n_particles, dim, type))
+
+    @staticmethod
+    def fits(n_particles, dim, type=PSO_VANILLA):
+        need = PSOBatchEngine.lds_bytes(n_particles, dim, type)
+        return 0 < need <= LDS_BUDGET
+
+    def __init__(self, objective, batch, n_particles, dim, *, type=PSO_VANILLA, bounded=False,
+                 minimize=True, inertia=0.8, cognitive=1.8, social=1.8, eps=10e-4, max_iter=5000,
+                 best_val_no_change=50, turns_per_launch=0, device=0, stream=None):
+        cfg = PSOBatchConfig()
+        cfg.struct_size = C.sizeof(PSOBatchConfig)
+        cfg.device = device
+        cfg.stream = None if stream is None else (stream or 1)
+        from .de import CustomObjective, rtc_library_path
+        custom = objective if isinstance(objective, CustomObjective) else None
+        cfg.objective = (_capi.OBJ_CUSTOM if custom else
+                         _capi.OBJECTIVES[objective] if isinstance(objective, str) else objective)
+        cfg.minimize, cfg.type, cfg.bounded = int(bool(minimize)), type, int(bool(bounded))
+        cfg.batch, cfg.n_particles, cfg.dim = batch, n_particles, dim
+        cfg.inertia, cfg.cognitive, cfg.social, cfg.eps = inertia, cognitive, social, eps
+        cfg.max_iter, cfg.best_val_no_change = max_iter, best_val_no_change
+        cfg.turns_per_launch = turns_per_launch
+        self.cfg = cfg
+        self._h = C.c_void_p()
+        if custom:
+            create = require("nlsg_pso_batch_create_custom")
+            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
+            obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
+                                         int(custom.chain), 0)
+            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+        else:
+            check(require("nlsg_pso_batch_create")(C.byref(cfg), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().nlsg_pso_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _inputs(self, lower, upper, seeds):
+        """lower / upper: anything that broadcasts to [batch, dim]; seeds [batch]"""
+        B, D = self.cfg.batch, self.cfg.dim
+        lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (B, D)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (B, D)))
+        seeds = np.array([int(s) & (2**64 - 1) for s in np.asarray(seeds, dtype=object).ravel()],
+                         dtype=np.uint64).reshape(B)
+        return lo, hi, seeds
+
+    def init(self, lower, upper, seeds):
+        """PSOEngine.init of every solve under its own seed and bounds"""
+        lo, hi, seeds = self._inputs(lower, upper, seeds)
+        check(lib().nlsg_pso_batch_init(self._h, lo.ctypes.data_as(_capi.pd), hi.ctypes.data_as(_capi.pd),
+                                        seeds.ctypes.data_as(_capi.pu)))
+
+    def step(self, turns=1):
+        check(lib().nlsg_pso_batch_step(self._h, turns))
+
+    def status(self):
+        """[Status] * batch, each what PSOEngine.status() returns after the same calls"""
+        st = (Status * self.cfg.batch)()
+        check(lib().nlsg_pso_batch_status(self._h, st))
+        return list(st)
+
+    def best(self):
+        """(x [batch, dim], f [batch], index [batch]): every solve's swarm best"""
+        B, D = self.cfg.batch, self.cfg.dim
+        x, f, idx = np.empty((B, D)), np.empty(B), np.empty(B, dtype=np.uint64)
+        check(lib().nlsg_pso_batch_best(self._h, x.ctypes.data_as(_capi.pd), f.ctypes.data_as(_capi.pd),
+                                        idx.ctypes.data_as(_capi.pu)))
+        return x, f, idx
+
+    def download(self, b):
+        """(pos, vel or None, pbest_val, cur_val) of solve b, as PSOEngine.download()"""
+        n, D = self.cfg.n_particles, self.cfg.dim
+        vanilla = self.cfg.type == PSO_VANILLA
+        pos, vel = np.empty((n, D)), (np.empty((n, D)) if vanilla else None)
+        pbest, cur = np.empty(n), np.empty(n)
+        check(lib().nlsg_pso_batch_download(self._h, b, pos.ctypes.data_as(_capi.pd),
+                                            vel.ctypes.data_as(_capi.pd) if vanilla else None,
+                                            pbest.ctypes.data_as(_capi.pd), cur.ctypes.data_as(_capi.pd)))
+        return pos, vel, pbest, cur
+
+    def minimize(self, lower, upper, seeds):
+        """init, then turns until every solve is done -> (x [batch, dim], [Status] * batch)"""
+        lo, hi, seeds = self._inputs(lower, upper, seeds)
+        x = np.empty((self.cfg.batch, self.cfg.dim))
+        st = (Status * self.cfg.batch)()
+        check(lib().nlsg_pso_batch_minimize(self._h, x.ctypes.data_as(_capi.pd), lo.ctypes.data_as(_capi.pd),
+                                            hi.ctypes.data_as(_capi.pd), seeds.ctypes.data_as(_capi.pu), st))
+        return x, list(st)
+
+    def time_solve(self, lower, upper, seeds, repeats=1):
+        """milliseconds of `repeats` whole solves (hipEvents)"""
+        lo, hi, seeds = self._inputs(lower, upper, seeds)
+        ms = C.c_float()
+        check(lib().nlsg_pso_batch_time_solve(self._h, lo.ctypes.data_as(_capi.pd),
+                                              hi.ctypes.data_as(_capi.pd), seeds.ctypes.data_as(_capi.pu),
+                                              repeats, C.byref(ms)))
+        return ms.value
+
+
 class PSO:
-    """Drop-in for nlsolver::PSO on a device objective (same ctor args/defaults/overloads)."""
+    """Drop-in for nlsolver::PSO on a device objective (same ctor args/defaults/overloads).
+
+    driver="resident": the solve runs through a batch-1 PSOBatchEngine -- the whole turn loop in one
+    kernel instead of up to seven launches per turn -- when the swarm fits a workgroup's LDS
+    (PSOBatchEngine.fits), through PSOEngine otherwise; the bits are the same either way.
+    `driver_used` says which engine the last solve ran on. Default "turns": PSOEngine."""
 
     def __init__(self, f, generator=None, inertia=0.8, cognitive_coef=1.8, social_coef=1.8,
                  n_particles=10, max_iter=5000, best_val_no_change=50, eps=10e-4, *,
-                 type=PSO_VANILLA, device=0):
+                 type=PSO_VANILLA, device=0, driver="turns"):
+        if driver not in ("turns", "resident"):
+            raise ValueError(f"driver must be 'turns' or 'resident', not {driver!r}")
+        self.driver, self.driver_used = driver, None
         self.f, self.generator, self.n_particles = f, generator, n_particles
         self.args = dict(inertia=inertia, cognitive=cognitive_coef, social=social_coef, eps=eps,
                          max_iter=max_iter, best_val_no_change=best_val_no_change, type=type,
@@ -149,9 +279,23 @@ class PSO:
         if not bounded:  # nlsolver.h:2553-2560: lower = -|x|, upper = |x|
             lower, upper = -np.abs(x), np.abs(x)
         seed = seed_from_generator(self.generator)
+        if self.driver == "resident" and self._resident_fits(x.size):
+            with PSOBatchEngine(self.f, 1, self.n_particles, x.size, bounded=bounded, minimize=minimize,
+                                **self.args) as eng:
+                xo, st = eng.minimize(lower, upper, [seed])
+            x[:] = xo[0]
+            self.driver_used = "resident"
+            return st[0]
+        self.driver_used = "turns"
         with PSOEngine(self.f, self.n_particles, x.size, bounded=bounded, minimize=minimize,
                        seed=seed, **self.args) as eng:
             return eng.minimize(x, lower, upper)
+
+    def _resident_fits(self, dim):
+        try:
+            return PSOBatchEngine.fits(self.n_particles, dim, self.args["type"])
+        except NlsgError:  # a library without the resident engine: the turn engine solves
+            return False
 
     def minimize(self, x, lower=None, upper=None):
         return self._solve(x, lower, upper, True)

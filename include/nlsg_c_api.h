@@ -80,12 +80,24 @@ typedef enum {
 #define NLSG_CUSTOM_TERMS 0   /* f = finish(sum_i term(x_i))            */
 #define NLSG_CUSTOM_CHAIN 1   /* f = finish(sum_{i<D-1} term(x_i, x_{i+1})) */
 #define NLSG_CUSTOM_VECTOR 2  /* f = body(x, D)                          */
+/* n_params > 0: the objective owns that many doubles of RUN-TIME data per solve. Every body (term,
+ * finish, whole-vector, and lambdas given to x.sum) reads them as  p(k),  k any uint64_t below
+ * n_params, which may differ from lane to lane (an index at or beyond n_params is the caller's
+ * error, as an index past an array is). Only the resident batch engines take such an objective
+ * (nlsg_de_batch_create_custom, nlsg_pso_batch_create_custom; values: nlsg_*_batch_set_params);
+ * every other *_create_custom answers NLSG_ERR_UNSUPPORTED. A body's own local named p shadows the
+ * accessor. 0: no parameters, the source compiled is what it was before parameters existed. */
+#define NLSG_CUSTOM_MAX_PARAMS 4096
 typedef struct {
   const char *term_body;
   const char *finish_body;
   int32_t chain;         /* NLSG_CUSTOM_TERMS / _CHAIN / _VECTOR */
-  int32_t reserved;
+  int32_t n_params;      /* 0 .. NLSG_CUSTOM_MAX_PARAMS (was `reserved`: 0 means what it meant) */
 } nlsg_custom_objective;
+/* LDS bytes the parameters of one solve take in a resident batch kernel, on top of
+ * nlsg_*_batch_lds_bytes: n_params doubles rounded up to 16 bytes; 0 for n_params <= 0 or above
+ * NLSG_CUSTOM_MAX_PARAMS. Host only, no device. */
+uint64_t nlsg_custom_params_lds_bytes(int32_t n_params);
 
 /* enum RecombinationStrategy { best, random } — nlsolver.h:2377 (same order). */
 typedef enum { NLSG_DE_BEST = 0, NLSG_DE_RANDOM = 1 } nlsg_de_strategy;
@@ -692,9 +704,20 @@ uint64_t nlsg_de_batch_lds_bytes(uint64_t pop, uint64_t dim);
 /* Checked before the device is touched, in this order: null pointers, struct_size (code 1),
  * batch >= 1 (1), the pop / dim ranges (2), the LDS budget (2). */
 int nlsg_de_batch_create(const nlsg_de_batch_config *cfg, nlsg_de_batch **out);
-/* cfg->objective == NLSG_OBJ_CUSTOM, term / chain or whole-vector form, as nlsg_de_create_custom */
+/* cfg->objective == NLSG_OBJ_CUSTOM, term / chain or whole-vector form, as nlsg_de_create_custom.
+ * obj->n_params is checked after batch and the pop / dim ranges and before the LDS budget:
+ * negative (1), above NLSG_CUSTOM_MAX_PARAMS (2); the budget check (2) then covers
+ * nlsg_de_batch_lds_bytes(pop, dim) + nlsg_custom_params_lds_bytes(n_params). */
 int nlsg_de_batch_create_custom(const nlsg_de_batch_config *cfg, const nlsg_custom_objective *obj,
                                 nlsg_de_batch **out);
+/* params_host [batch][n_params]: solve b's objective reads row b as p(k). Copied to a buffer the
+ * engine owns, on its stream; the host array is borrowed for this call only. May be called again
+ * at any time: the new rows hold from the next launch on (every launch stages its row afresh),
+ * nothing is recompiled, and scores already stored are NOT re-evaluated -- call init (or minimize)
+ * after it to start solves under the new rows. NLSG_ERR_INVALID_ARG on an engine whose objective
+ * has n_params == 0. With n_params > 0, init / minimize / time_solve before the first set_params
+ * return NLSG_ERR_STATE. */
+int nlsg_de_batch_set_params(nlsg_de_batch *e, const double *params_host);
 int nlsg_de_batch_destroy(nlsg_de_batch *e);
 /* x0_host [batch][dim], seeds_host [batch]: nlsg_de_init of every solve under its own seed */
 int nlsg_de_batch_init(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host);
@@ -759,9 +782,14 @@ uint64_t nlsg_pso_batch_lds_bytes(uint64_t n_particles, uint64_t dim, int32_t ty
 /* Checked before the device is touched, in this order: null pointers, struct_size (code 1),
  * batch >= 1 (1), type (1), the n_particles / dim ranges (2), the LDS budget (2). */
 int nlsg_pso_batch_create(const nlsg_pso_batch_config *cfg, nlsg_pso_batch **out);
-/* cfg->objective == NLSG_OBJ_CUSTOM, term / chain or whole-vector form, as nlsg_pso_create_custom */
+/* cfg->objective == NLSG_OBJ_CUSTOM, term / chain or whole-vector form, as nlsg_pso_create_custom.
+ * obj->n_params is checked after batch, type and the n_particles / dim ranges and before the LDS
+ * budget: negative (1), above NLSG_CUSTOM_MAX_PARAMS (2); the budget check (2) then covers
+ * nlsg_pso_batch_lds_bytes(n, dim, type) + nlsg_custom_params_lds_bytes(n_params). */
 int nlsg_pso_batch_create_custom(const nlsg_pso_batch_config *cfg, const nlsg_custom_objective *obj,
                                  nlsg_pso_batch **out);
+/* params_host [batch][n_params], exactly as nlsg_de_batch_set_params */
+int nlsg_pso_batch_set_params(nlsg_pso_batch *e, const double *params_host);
 int nlsg_pso_batch_destroy(nlsg_pso_batch *e);
 /* lower_host / upper_host [batch][dim], seeds_host [batch]: nlsg_pso_init of every solve under
  * its own seed and bounds */

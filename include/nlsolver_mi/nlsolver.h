@@ -219,6 +219,15 @@ struct Custom {
   static constexpr int nlsg_objective = NLSG_OBJ_CUSTOM;
   std::string term_body, finish_body;
   int chain;  // NLSG_CUSTOM_TERMS / NLSG_CUSTOM_CHAIN / NLSG_CUSTOM_VECTOR
+  // Run-time data the functor owns (the reference's "a callable that owns its data"): the bodies
+  // read params[k] as p(k) (nlsg_custom_objective.n_params). Non-empty: DE and PSO solve through
+  // the resident batch engine, whatever the driver mode (device_error when the shape does not fit
+  // its LDS or the library predates parameters); every other solver answers the library's
+  // "unsupported" error. At most NLSG_CUSTOM_MAX_PARAMS. (A batch of solves with a row each, and
+  // rows replaced without recompiling, is the C-ABI: nlsg_*_batch_set_params.)
+  //   Custom<double> f("double r = xi - p(0); return p(1) * r * r;");
+  //   f.params = {1.5, 2.0};
+  std::vector<T> params;
   explicit Custom(std::string term_body, bool chain = false, std::string finish_body = "return s;")
       : term_body(std::move(term_body)), finish_body(std::move(finish_body)), chain(chain ? 1 : 0) {}
   // the whole-vector form: `body` is the body of  double f(const X &x, uint64_t D)  with x(i),
@@ -231,6 +240,14 @@ struct Custom {
     return c;
   }
 };
+
+// nlsg_custom_objective.n_params of a Custom objective
+template <typename C>
+inline int32_t custom_n_params(const C &f) {
+  return f.params.size() > static_cast<size_t>(NLSG_CUSTOM_MAX_PARAMS)
+             ? NLSG_CUSTOM_MAX_PARAMS + 1  // the library rejects it by name
+             : static_cast<int32_t>(f.params.size());
+}
 
 // Objectives with an analytic gradient on the device (batched BFGS):
 // f(x) = 1/2 sum d_i x_i^2 + 1/2 c (sum x)^2 - sum b_i x_i  (SURVEY.md §8c G6).
@@ -356,6 +373,22 @@ class api {
     return pso_batch_lds_bytes && pso_batch_create && pso_batch_create_custom && pso_batch_destroy &&
            pso_batch_minimize;
   }
+  // optional: null when the library predates run-time objective parameters (Custom::params)
+  decltype(&nlsg_custom_params_lds_bytes) custom_params_lds_bytes = nullptr;
+  decltype(&nlsg_de_batch_set_params) de_batch_set_params = nullptr;
+  decltype(&nlsg_pso_batch_set_params) pso_batch_set_params = nullptr;
+  // the resident engine's LDS need with the parameter row; throws when the library cannot take
+  // parameters or the shape does not fit (`shape_need` = nlsg_*_batch_lds_bytes, 0 = out of range)
+  void require_params_fit(bool has_engine, bool has_set, uint64_t shape_need, int32_t n_params,
+                          uint64_t budget, const char *what) const {
+    if (!has_engine || !has_set || !custom_params_lds_bytes)
+      throw device_error(std::string("library has no run-time objective parameters for ") + what);
+    const uint64_t extra = custom_params_lds_bytes(n_params);
+    if (shape_need == 0 || extra == 0 || shape_need + extra > budget)
+      throw device_error(std::string("nlsg error 2: an objective with run-time parameters needs the resident ") +
+                         what + " engine, and this shape with " + std::to_string(n_params) +
+                         " parameters does not fit its " + std::to_string(budget) + " bytes of LDS");
+  }
 
   void check(int rc) const {
     if (rc != NLSG_OK)
@@ -416,6 +449,9 @@ class api {
     bind_optional(h, "nlsg_pso_batch_create_custom", pso_batch_create_custom);
     bind_optional(h, "nlsg_pso_batch_destroy", pso_batch_destroy);
     bind_optional(h, "nlsg_pso_batch_minimize", pso_batch_minimize);
+    bind_optional(h, "nlsg_custom_params_lds_bytes", custom_params_lds_bytes);
+    bind_optional(h, "nlsg_de_batch_set_params", de_batch_set_params);
+    bind_optional(h, "nlsg_pso_batch_set_params", pso_batch_set_params);
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
   }
@@ -597,6 +633,14 @@ class DE {
   solver_status<scalar_t> solve_device(std::vector<scalar_t> &x) {
     if (device::de_generation_mode() == device::de_generation::reference) return solve_reference<minimize>(x);
     const device::api &api = device::api::get();
+    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
+      if (!f.params.empty()) {  // run-time parameters live in the resident engine only
+        api.require_params_fit(api.has_de_batch(), api.de_batch_set_params != nullptr,
+                               api.has_de_batch() ? api.de_batch_lds_bytes(pop_size, x.size()) : 0,
+                               device::custom_n_params(f), device::de_resident_lds_budget, "DE");
+        return solve_resident<minimize>(x);
+      }
+    }
     if (device::de_driver_mode() == device::de_driver::resident && api.has_de_batch()) {
       const uint64_t need = api.de_batch_lds_bytes(pop_size, x.size());
       if (need != 0 && need <= device::de_resident_lds_budget) return solve_resident<minimize>(x);
@@ -619,7 +663,8 @@ class DE {
     if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
       // $NLSG_HIPRTC names the hiprtc of the HIP runtime in use (default: libhiprtc.so)
       api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
       api.check(api.de_create_custom(&cfg, &obj, &eng));
     } else {
       api.check(api.de_create(&cfg, &eng));
@@ -654,13 +699,21 @@ class DE {
     nlsg_de_batch *eng = nullptr;
     if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
       api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
       api.check(api.de_batch_create_custom(&cfg, &obj, &eng));
     } else {
       api.check(api.de_batch_create(&cfg, &eng));
     }
     nlsg_status st{};
-    const int rc = api.de_batch_minimize(eng, x.data(), &seed, &st);
+    int rc = NLSG_OK;
+    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
+      if (!f.params.empty()) {
+        const std::vector<double> row(f.params.begin(), f.params.end());
+        rc = api.de_batch_set_params(eng, row.data());
+      }
+    }
+    if (!rc) rc = api.de_batch_minimize(eng, x.data(), &seed, &st);
     const std::string msg = rc ? api.last_error() : "";
     api.de_batch_destroy(eng);
     if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
@@ -702,7 +755,8 @@ class DE {
       nlsg_de_ref *eng = nullptr;
       if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
         api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
         api.check(api.de_ref_create_custom(&cfg, &obj, &eng));
       } else {
         api.check(api.de_ref_create(&cfg, &eng));
@@ -855,6 +909,15 @@ class PSO {
     if constexpr (device::is_device_objective<Callable>::value) {
       static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
       const device::api &api = device::api::get();
+      if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
+        if (!f.params.empty()) {  // run-time parameters live in the resident engine only
+          const int32_t type = Type == Accelerated ? NLSG_PSO_ACCELERATED : NLSG_PSO_VANILLA;
+          api.require_params_fit(api.has_pso_batch(), api.pso_batch_set_params != nullptr,
+                                 api.has_pso_batch() ? api.pso_batch_lds_bytes(n_particles, x.size(), type) : 0,
+                                 device::custom_n_params(f), device::pso_resident_lds_budget, "PSO");
+          return solve_resident<minimize, constrained>(x, lower, upper);
+        }
+      }
       if (device::pso_driver_mode() == device::pso_driver::resident && api.has_pso_batch()) {
         const uint64_t need = api.pso_batch_lds_bytes(
             n_particles, x.size(), Type == Accelerated ? NLSG_PSO_ACCELERATED : NLSG_PSO_VANILLA);
@@ -880,7 +943,8 @@ class PSO {
       nlsg_pso *eng = nullptr;
       if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
         api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
         api.check(api.pso_create_custom(&cfg, &obj, &eng));
       } else {
         api.check(api.pso_create(&cfg, &eng));
@@ -921,13 +985,21 @@ class PSO {
     nlsg_pso_batch *eng = nullptr;
     if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
       api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
       api.check(api.pso_batch_create_custom(&cfg, &obj, &eng));
     } else {
       api.check(api.pso_batch_create(&cfg, &eng));
     }
     nlsg_status st{};
-    const int rc = api.pso_batch_minimize(eng, x.data(), lower.data(), upper.data(), &seed, &st);
+    int rc = NLSG_OK;
+    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
+      if (!f.params.empty()) {
+        const std::vector<double> row(f.params.begin(), f.params.end());
+        rc = api.pso_batch_set_params(eng, row.data());
+      }
+    }
+    if (!rc) rc = api.pso_batch_minimize(eng, x.data(), lower.data(), upper.data(), &seed, &st);
     const std::string msg = rc ? api.last_error() : "";
     api.pso_batch_destroy(eng);
     if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
@@ -1324,7 +1396,8 @@ class BFGS {
       cfg.objective = Callable::nlsg_objective;
       if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
         api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
         api.check(api.bfgs_create_custom(&cfg, &obj, &eng));
       } else {
         api.check(api.bfgs_create(&cfg, nullptr, nullptr, &eng));
@@ -1467,7 +1540,8 @@ class SANN {
     nlsg_sann *eng = nullptr;
     if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
       api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
       api.check(api.sann_create_custom(&cfg, &obj, &eng));
     } else {
       api.check(api.sann_create(&cfg, &eng));
@@ -1620,7 +1694,8 @@ class NelderMeadPSO {
     nlsg_nmpso *eng = nullptr;
     if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
       api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
       api.check(api.nmpso_create_custom(&cfg, &obj, &eng));
     } else {
       api.check(api.nmpso_create(&cfg, &eng));
@@ -1835,7 +1910,8 @@ class NelderMead {
       nlsg_nm *eng = nullptr;
       if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
         api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
         api.check(api.nm_create_custom(&cfg, &obj, &eng));
       } else {
         api.check(api.nm_create(&cfg, &eng));
@@ -2158,7 +2234,8 @@ class LevenbergMarquardt {
     if constexpr (device::is_device_objective<Callable>::value) {
       if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
         api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, 0};
+        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
+                                  device::custom_n_params(f)};
         api.check(api.lm_create_custom(&cfg, &obj, &eng));
         made = true;
       }

@@ -67,7 +67,7 @@ class DEBatchConfig(C.Structure):  # nlsg_de_batch_config
 
 class CustomObjectiveC(C.Structure):  # nlsg_custom_objective
     _fields_ = [("term_body", C.c_char_p), ("finish_body", C.c_char_p), ("chain", i32),
-                ("reserved", i32)]
+                ("n_params", i32)]  # run-time doubles per solve (resident batch engines), 0 = none
 
 
 PSO_VANILLA, PSO_ACCELERATED = 0, 1  # enum PSOType { Vanilla, Accelerated }, nlsolver.h:2496
@@ -252,10 +252,12 @@ OPTIONAL_SYMBOLS = {
     "nlsg_de_ref_time_solve": (C.c_int, [_H, pd, pu, C.c_uint32, C.POINTER(C.c_float)]),
     "nlsg_de_ref_jump_table": (C.c_int, [pu]),
     "nlsg_de_ref_pick_donors": (C.c_int, [pd, u64, u64, u64, pu, pu, C.POINTER(i32)]),
+    "nlsg_custom_params_lds_bytes": (u64, [i32]),
     "nlsg_de_batch_lds_bytes": (u64, [u64, u64]),
     "nlsg_de_batch_create": (C.c_int, [C.POINTER(DEBatchConfig), C.POINTER(_H)]),
     "nlsg_de_batch_create_custom": (C.c_int, [C.POINTER(DEBatchConfig), C.POINTER(CustomObjectiveC),
                                               C.POINTER(_H)]),
+    "nlsg_de_batch_set_params": (C.c_int, [_H, pd]),
     "nlsg_de_batch_destroy": (C.c_int, [_H]),
     "nlsg_de_batch_init": (C.c_int, [_H, pd, pu]),
     "nlsg_de_batch_step": (C.c_int, [_H, u64]),
@@ -269,6 +271,7 @@ OPTIONAL_SYMBOLS = {
     "nlsg_pso_batch_create": (C.c_int, [C.POINTER(PSOBatchConfig), C.POINTER(_H)]),
     "nlsg_pso_batch_create_custom": (C.c_int, [C.POINTER(PSOBatchConfig), C.POINTER(CustomObjectiveC),
                                                C.POINTER(_H)]),
+    "nlsg_pso_batch_set_params": (C.c_int, [_H, pd]),
     "nlsg_pso_batch_destroy": (C.c_int, [_H]),
     "nlsg_pso_batch_init": (C.c_int, [_H, pd, pd, pu]),
     "nlsg_pso_batch_step": (C.c_int, [_H, u64]),
@@ -280,6 +283,9 @@ OPTIONAL_SYMBOLS = {
 }
 SYMBOLS.update(OPTIONAL_SYMBOLS)
 _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
+                    "nlsg_custom_params_": "library has no run-time objective parameters",
+                    "nlsg_de_batch_set_params": "library has no run-time objective parameters",
+                    "nlsg_pso_batch_set_params": "library has no run-time objective parameters",
                     "nlsg_de_batch_": "library has no resident batch DE",
                     "nlsg_pso_batch_": "library has no resident batch PSO"}
 
@@ -312,6 +318,7 @@ def require(name):
 
 
 NLSG_ERR_INVALID_ARG, NLSG_ERR_UNSUPPORTED = 1, 2
+CUSTOM_MAX_PARAMS = 4096  # NLSG_CUSTOM_MAX_PARAMS
 
 
 def check(rc):

@@ -62,7 +62,7 @@ class BFGSEngine:
             self.cfg = cfg
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(objective.term_body.encode(), objective.finish_body.encode(),
-                                         int(objective.chain), 0)
+                                         int(objective.chain), objective.n_params)
             check(lib().nlsg_bfgs_create_custom(C.byref(cfg), C.byref(obj), C.byref(self._h)))
             return
         if isinstance(objective, str):  # built-in objective + finite-difference gradient

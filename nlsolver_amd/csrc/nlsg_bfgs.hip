@@ -142,6 +142,7 @@ int nlsg_bfgs_create_custom(const nlsg_bfgs_config *cfg, const nlsg_custom_objec
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int prc = reject_custom_params(obj)) return prc;
   PhaseClock clk;
   const int rc = bfgs_create(cfg, nullptr, nullptr, obj, out);
   call_timing().create_ms = clk.lap();

@@ -340,6 +340,50 @@ struct Objective<NLSG_OBJ_RASTRIGIN> {
   }
 };
 
+// ---------------------------------------------------------------------------
+// run-time parameters of a user objective (nlsg_custom_objective.n_params > 0; resident batch
+// engines only). rtc_compile defines NLSG_N_PARAMS ahead of the kernel header, so the block below
+// exists in that translation unit alone: static LDS in front of the kernels' dynamic block, one
+// solve's row, staged once per launch by the workgroup and read by Objective<NLSG_OBJ_CUSTOM>::p(k)
+// with ds_read. Rounded to an even count: 16-byte size, so the dynamic block behind it keeps the
+// 16-byte alignment the PSO kernel's double2 accesses need. Without the macro nothing is emitted
+// and stage_custom_params is empty: the built-in kernels are what they were.
+// ---------------------------------------------------------------------------
+#ifdef NLSG_N_PARAMS
+__shared__ __attribute__((aligned(16))) double custom_params_lds[(NLSG_N_PARAMS + 1) & ~1];
+#endif
+// Called by all threads of the block, uniformly. `params` is [batch][n_params]; the caller's next
+// barrier (or `sync`) publishes the row.
+__device__ inline void stage_custom_params(const double *params, uint64_t b, bool sync) {
+#ifdef NLSG_N_PARAMS
+  const double *__restrict__ row = params + b * static_cast<uint64_t>(NLSG_N_PARAMS);
+  for (uint32_t i = threadIdx.x; i < static_cast<uint32_t>(NLSG_N_PARAMS); i += blockDim.x)
+    custom_params_lds[i] = row[i];
+  if (sync) __syncthreads();
+#else
+  (void)params;
+  (void)b;
+  (void)sync;
+#endif
+}
+
+#ifndef __HIPCC_RTC__
+// static LDS of the row above; 0: no parameters, or a count outside 1 .. NLSG_CUSTOM_MAX_PARAMS
+inline uint64_t custom_params_lds_bytes(int64_t n_params) {
+  if (n_params <= 0 || n_params > NLSG_CUSTOM_MAX_PARAMS) return 0;
+  return 8 * ((static_cast<uint64_t>(n_params) + 1) & ~1ull);
+}
+// every engine but the two resident batch ones: among create_custom's argument checks
+inline int reject_custom_params(const nlsg_custom_objective *obj) {
+  if (obj && obj->n_params != 0)
+    return fail(NLSG_ERR_UNSUPPORTED,
+                "n_params = %d: run-time objective parameters are taken by nlsg_de_batch_create_custom "
+                "and nlsg_pso_batch_create_custom only",
+                obj->n_params);
+  return NLSG_OK;
+}
+#endif
+
 // What a whole-vector user objective (nlsg_custom_objective.chain == NLSG_CUSTOM_VECTOR) sees of
 // the point its wave — or its group of G lanes — holds:
 //   x(i)      coordinate i, for an index that is the same in every lane (literals, loop counters)

@@ -343,6 +343,7 @@ int nlsg_de_create_custom(const nlsg_de_config *cfg, const nlsg_custom_objective
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int prc = reject_custom_params(obj)) return prc;
   PhaseClock clk;
   const int rc = de_create(cfg, obj, out);
   call_timing().create_ms = clk.lap();

@@ -24,6 +24,9 @@ struct nlsg_de_batch {
   uint64_t turns_per_launch = 0;
   uint64_t *seeds_dev = nullptr;
   double *x0_dev = nullptr;
+  int32_t n_params = 0;          // run-time parameters per solve (custom objectives), 0 = none
+  double *params_dev = nullptr;  // [batch][n_params], filled by nlsg_de_batch_set_params
+  bool params_set = false;
   bool initialised = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
@@ -86,6 +89,13 @@ void launch_turns(nlsg_de_batch *e, uint64_t turns) {
     return;
   }
   (void)hipLaunchKernel(e->turn_fn, dim3(grid), dim3(256), args, e->lds, e->stream);
+}
+
+int params_ready(const nlsg_de_batch *e) {
+  if (e->n_params > 0 && !e->params_set)
+    return fail(NLSG_ERR_STATE, "the objective has %d parameters: nlsg_de_batch_set_params has not been called",
+                e->n_params);
+  return NLSG_OK;
 }
 
 // x0 and the seeds in, state reset, generation 0 scored. Asynchronous after the copies.
@@ -159,12 +169,25 @@ int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective
   if (cfg->dim < 1 || cfg->dim > kDeBatchMaxDim)
     return fail(NLSG_ERR_UNSUPPORTED, "resident DE takes 1 <= dim <= %llu, not dim %llu",
                 (unsigned long long)kDeBatchMaxDim, (unsigned long long)cfg->dim);
+  const int32_t n_params = custom ? custom->n_params : 0;
+  if (n_params < 0) return fail(NLSG_ERR_INVALID_ARG, "n_params must be >= 0, not %d", n_params);
+  if (n_params > NLSG_CUSTOM_MAX_PARAMS)
+    return fail(NLSG_ERR_UNSUPPORTED, "a custom objective takes at most %d parameters, not %d",
+                NLSG_CUSTOM_MAX_PARAMS, n_params);
   const uint64_t lds = de_batch_lds_bytes(cfg->pop, cfg->dim);
-  if (lds > kDeBatchLdsBudget)
+  const uint64_t params_lds = custom_params_lds_bytes(n_params);  // static, in front of `lds`
+  if (lds + params_lds > kDeBatchLdsBudget) {
+    if (params_lds)
+      return fail(NLSG_ERR_UNSUPPORTED,
+                  "resident DE: pop %llu x dim %llu needs %llu bytes of LDS and %d parameters %llu more, "
+                  "a workgroup has %llu",
+                  (unsigned long long)cfg->pop, (unsigned long long)cfg->dim, (unsigned long long)lds,
+                  n_params, (unsigned long long)params_lds, (unsigned long long)kDeBatchLdsBudget);
     return fail(NLSG_ERR_UNSUPPORTED,
                 "resident DE: pop %llu x dim %llu needs %llu bytes of LDS, a workgroup has %llu",
                 (unsigned long long)cfg->pop, (unsigned long long)cfg->dim, (unsigned long long)lds,
                 (unsigned long long)kDeBatchLdsBudget);
+  }
   if (cfg->batch >= (1ull << 23)) return fail(NLSG_ERR_UNSUPPORTED, "batch must be < 2^23 solves");
   if (!custom && (cfg->objective < 0 || cfg->objective > NLSG_OBJ_RASTRIGIN))
     return fail(NLSG_ERR_INVALID_ARG, "unknown objective %d", cfg->objective);
@@ -179,6 +202,7 @@ int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective
   e->cfg = *cfg;
   const uint64_t B = cfg->batch, n = cfg->pop, D = cfg->dim;
   e->lds = lds;
+  e->n_params = n_params;
   e->group = D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 64;  // the turn engine's mappings
   e->turns_per_launch = cfg->turns_per_launch ? cfg->turns_per_launch : kDeBatchTurnsPerLaunch;
   if (cfg->stream) {
@@ -200,9 +224,12 @@ int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.n_done), 8);
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->seeds_dev), B * 8);
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->x0_dev), B * D * 8);
+  if (he == hipSuccess && n_params)
+    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(n_params) * 8);
   if (he == hipSuccess) he = hipEventCreate(&e->ev0);
   if (he == hipSuccess) he = hipEventCreate(&e->ev1);
   p.seeds = e->seeds_dev;
+  p.params = e->params_dev;
   p.x0 = e->x0_dev;
   p.batch = B;
   p.pop = n;
@@ -229,9 +256,10 @@ int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective
       nlsg_de_batch_destroy(e);
       return rc2;
     }
+    // this module is the engine's own; its static LDS (the parameter row) comes off the budget
     he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.turns),
                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                             static_cast<int>(kDeBatchLdsBudget));
+                             static_cast<int>(kDeBatchLdsBudget - params_lds));
   }
   if (he != hipSuccess) {
     nlsg_de_batch_destroy(e);
@@ -281,6 +309,7 @@ int nlsg_de_batch_destroy(nlsg_de_batch *e) {
   pool_free(e->p.n_done);
   pool_free(e->seeds_dev);
   pool_free(e->x0_dev);
+  pool_free(e->params_dev);
   if (e->ev0) hipEventDestroy(e->ev0);
   if (e->ev1) hipEventDestroy(e->ev1);
   if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
@@ -289,8 +318,21 @@ int nlsg_de_batch_destroy(nlsg_de_batch *e) {
   return NLSG_OK;
 }
 
+int nlsg_de_batch_set_params(nlsg_de_batch *e, const double *params_host) {
+  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (e->n_params <= 0)
+    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (n_params == 0)");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
+                          hipMemcpyHostToDevice, e->stream));
+  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
+  e->params_set = true;
+  return NLSG_OK;
+}
+
 int nlsg_de_batch_init(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host) {
   if (!e || !x0_host || !seeds_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (int rc = params_ready(e)) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   return start(e, x0_host, seeds_host);
 }
@@ -361,6 +403,7 @@ int nlsg_de_batch_upload(nlsg_de_batch *e, const double *pops_host, const double
 int nlsg_de_batch_minimize(nlsg_de_batch *e, double *x_inout_host, const uint64_t *seeds_host,
                            nlsg_status *status_host) {
   if (!e || !x_inout_host || !seeds_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (int rc = params_ready(e)) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   PhaseClock clk;
   int rc = start(e, x_inout_host, seeds_host);
@@ -387,6 +430,7 @@ int nlsg_de_batch_minimize(nlsg_de_batch *e, double *x_inout_host, const uint64_
 int nlsg_de_batch_time_solve(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host,
                              uint32_t repeats, float *ms_total) {
   if (!e || !x0_host || !seeds_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (int rc = params_ready(e)) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   const uint64_t B = e->p.batch, D = e->p.D;
   NLSG_HIP(hipMemcpyAsync(e->x0_dev, x0_host, B * D * 8, hipMemcpyHostToDevice, e->stream));

@@ -20,6 +20,8 @@
 // the solve's loop before the generation, and the state freezes where the turn engine freezes it.
 // Between launches the state waits in HBM: rows [batch][pop][D] (unpadded), scores, best_x,
 // DeState per solve.
+// A user objective with run-time parameters (NLSG_N_PARAMS, nlsg_common.h) adds its solve's row
+// as static LDS in front of this block; both kernels stage it before the first evaluation.
 #pragma once
 
 #include "nlsg_de_state.h"
@@ -52,6 +54,7 @@ struct DeBatchParams {
   uint64_t cr_thresh;     // as DeParams.cr_thresh / cr_all
   int32_t cr_all;
   int32_t strategy;
+  const double *params;   // [batch][n_params] run-time objective parameters, or null (n_params == 0)
 };
 
 // ---- generation 0: de_reset_state_kernel + de_init_kernel of solve blockIdx.x / blocks_per ----
@@ -71,6 +74,7 @@ __global__ __launch_bounds__(256) void de_batch_init_kernel(DeBatchParams p, uin
     s->parity = 0;
     s->pad[0] = s->pad[1] = 0;
   }
+  stage_custom_params(p.params, b, true);  // (a user objective with parameters; else nothing)
   const uint64_t a = static_cast<uint64_t>(blk) * 4 +
                      __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
   if (a >= p.pop) return;
@@ -353,6 +357,7 @@ __global__ __launch_bounds__(256) void de_batch_kernel(DeBatchParams p, uint64_t
     }
     for (uint32_t i = threadIdx.x; i < n; i += 256) sc[i] = p.scores[b * n + i];
     for (uint32_t i = threadIdx.x; i < D; i += 256) best_x[i] = p.best_x[b * D + i];
+    stage_custom_params(p.params, b, false);  // once per launch, published by the barrier below
   }
   __syncthreads();
   const uint64_t seed = p.seeds[b];

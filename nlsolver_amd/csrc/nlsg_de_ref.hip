@@ -125,6 +125,7 @@ int nlsg_de_ref_create_custom(const nlsg_de_ref_config *cfg, const nlsg_custom_o
                               nlsg_de_ref **out) {
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM) return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int prc = reject_custom_params(obj)) return prc;
   return de_ref_create(cfg, obj, out);
 }
 

@@ -227,6 +227,7 @@ int nlsg_lm_create_custom(const nlsg_lm_config *cfg, const nlsg_custom_objective
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int prc = reject_custom_params(obj)) return prc;
   PhaseClock clk;
   const int rc = lm_create(cfg, obj, out);
   call_timing().create_ms = clk.lap();

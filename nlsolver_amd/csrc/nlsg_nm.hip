@@ -110,6 +110,7 @@ int nlsg_nm_create_custom(const nlsg_nm_config *cfg, const nlsg_custom_objective
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int prc = reject_custom_params(obj)) return prc;
   return nm_create(cfg, obj, out);
 }
 

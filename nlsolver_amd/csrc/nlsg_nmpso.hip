@@ -105,6 +105,7 @@ int nlsg_nmpso_create_custom(const nlsg_nmpso_config *cfg, const nlsg_custom_obj
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int prc = reject_custom_params(obj)) return prc;
   return hyb_create(cfg, obj, out);
 }
 

@@ -258,6 +258,7 @@ int nlsg_pso_create_custom(const nlsg_pso_config *cfg, const nlsg_custom_objecti
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int prc = reject_custom_params(obj)) return prc;
   PhaseClock clk;
   const int rc = pso_create(cfg, obj, out);
   call_timing().create_ms = clk.lap();

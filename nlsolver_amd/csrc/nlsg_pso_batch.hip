@@ -35,6 +35,9 @@ struct nlsg_pso_batch {
   uint64_t turns_per_launch = 0;
   uint64_t *seeds_dev = nullptr;
   double *lower_dev = nullptr, *upper_dev = nullptr, *tab_dev = nullptr;
+  int32_t n_params = 0;          // run-time parameters per solve (custom objectives), 0 = none
+  double *params_dev = nullptr;  // [batch][n_params], filled by nlsg_pso_batch_set_params
+  bool params_set = false;
   bool initialised = false;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
@@ -89,6 +92,13 @@ void launch_turns(nlsg_pso_batch *e, uint64_t turns) {
     return;
   }
   (void)hipLaunchKernel(e->turn_fn, dim3(grid), dim3(256), args, e->lds, e->stream);
+}
+
+int params_ready(const nlsg_pso_batch *e) {
+  if (e->n_params > 0 && !e->params_set)
+    return fail(NLSG_ERR_STATE, "the objective has %d parameters: nlsg_pso_batch_set_params has not been called",
+                e->n_params);
+  return NLSG_OK;
 }
 
 int upload_inputs(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
@@ -169,12 +179,26 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
   if (cfg->dim < 1 || cfg->dim > kPsoBatchMaxDim)
     return fail(NLSG_ERR_UNSUPPORTED, "resident PSO takes 1 <= dim <= %llu, not dim %llu",
                 (unsigned long long)kPsoBatchMaxDim, (unsigned long long)cfg->dim);
+  const int32_t n_params = custom ? custom->n_params : 0;
+  if (n_params < 0) return fail(NLSG_ERR_INVALID_ARG, "n_params must be >= 0, not %d", n_params);
+  if (n_params > NLSG_CUSTOM_MAX_PARAMS)
+    return fail(NLSG_ERR_UNSUPPORTED, "a custom objective takes at most %d parameters, not %d",
+                NLSG_CUSTOM_MAX_PARAMS, n_params);
   const uint64_t lds = pso_batch_lds_bytes(cfg->n_particles, cfg->dim, cfg->type);
-  if (lds > kPsoBatchLdsBudget)
+  const uint64_t params_lds = custom_params_lds_bytes(n_params);  // static, in front of `lds`
+  if (lds + params_lds > kPsoBatchLdsBudget) {
+    if (params_lds)
+      return fail(NLSG_ERR_UNSUPPORTED,
+                  "resident PSO: %llu particles x dim %llu need %llu bytes of LDS and %d parameters %llu "
+                  "more, a workgroup has %llu",
+                  (unsigned long long)cfg->n_particles, (unsigned long long)cfg->dim,
+                  (unsigned long long)lds, n_params, (unsigned long long)params_lds,
+                  (unsigned long long)kPsoBatchLdsBudget);
     return fail(NLSG_ERR_UNSUPPORTED,
                 "resident PSO: %llu particles x dim %llu need %llu bytes of LDS, a workgroup has %llu",
                 (unsigned long long)cfg->n_particles, (unsigned long long)cfg->dim, (unsigned long long)lds,
                 (unsigned long long)kPsoBatchLdsBudget);
+  }
   if (cfg->batch >= (1ull << 23)) return fail(NLSG_ERR_UNSUPPORTED, "batch must be < 2^23 solves");
   if (!custom && (cfg->objective < 0 || cfg->objective > NLSG_OBJ_RASTRIGIN))
     return fail(NLSG_ERR_INVALID_ARG, "unknown objective %d", cfg->objective);
@@ -188,6 +212,7 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
   const uint64_t B = cfg->batch, n = cfg->n_particles, D = cfg->dim;
   const bool vanilla = cfg->type == NLSG_PSO_VANILLA;
   e->lds = lds;
+  e->n_params = n_params;
   e->group = D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 64;  // the turn engine's mappings
   e->turns_per_launch = cfg->turns_per_launch ? cfg->turns_per_launch : kPsoBatchTurnsPerLaunch;
   if (cfg->stream) {
@@ -214,6 +239,8 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->seeds_dev), B * 8);
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->lower_dev), B * D * 8);
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->upper_dev), B * D * 8);
+  if (he == hipSuccess && n_params)
+    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(n_params) * 8);
   // the inertia schedule pow(inertia, iter) (:2613) from the host libm, exactly as nlsg_pso_create
   // builds it (max_iter + 1 entries, or up to the first fixed point; at most 2^22)
   const uint64_t want = cfg->max_iter == ~0ull ? ~0ull : cfg->max_iter + 1;
@@ -235,6 +262,7 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
   if (he == hipSuccess) he = hipEventCreate(&e->ev0);
   if (he == hipSuccess) he = hipEventCreate(&e->ev1);
   p.seeds = e->seeds_dev;
+  p.params = e->params_dev;
   p.batch = B;
   q.lower = e->lower_dev;
   q.upper = e->upper_dev;
@@ -267,9 +295,10 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
       nlsg_pso_batch_destroy(e);
       return rc2;
     }
+    // this module is the engine's own; its static LDS (the parameter row) comes off the budget
     he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.turns),
                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                             static_cast<int>(kPsoBatchLdsBudget));
+                             static_cast<int>(kPsoBatchLdsBudget - params_lds));
   }
   if (he != hipSuccess) {
     nlsg_pso_batch_destroy(e);
@@ -325,6 +354,7 @@ int nlsg_pso_batch_destroy(nlsg_pso_batch *e) {
   pool_free(e->seeds_dev);
   pool_free(e->lower_dev);
   pool_free(e->upper_dev);
+  pool_free(e->params_dev);
   pool_free(e->tab_dev);
   if (e->ev0) hipEventDestroy(e->ev0);
   if (e->ev1) hipEventDestroy(e->ev1);
@@ -334,9 +364,22 @@ int nlsg_pso_batch_destroy(nlsg_pso_batch *e) {
   return NLSG_OK;
 }
 
+int nlsg_pso_batch_set_params(nlsg_pso_batch *e, const double *params_host) {
+  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (e->n_params <= 0)
+    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (n_params == 0)");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
+                          hipMemcpyHostToDevice, e->stream));
+  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
+  e->params_set = true;
+  return NLSG_OK;
+}
+
 int nlsg_pso_batch_init(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
                         const uint64_t *seeds_host) {
   if (!e || !lower_host || !upper_host || !seeds_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (int rc = params_ready(e)) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   int rc = upload_inputs(e, lower_host, upper_host, seeds_host);
   if (rc) return rc;
@@ -408,6 +451,7 @@ int nlsg_pso_batch_minimize(nlsg_pso_batch *e, double *x_out_host, const double 
                             nlsg_status *status_host) {
   if (!e || !x_out_host || !lower_host || !upper_host || !seeds_host)
     return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (int rc = params_ready(e)) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   PhaseClock clk;
   int rc = upload_inputs(e, lower_host, upper_host, seeds_host);
@@ -437,6 +481,7 @@ int nlsg_pso_batch_time_solve(nlsg_pso_batch *e, const double *lower_host, const
                               const uint64_t *seeds_host, uint32_t repeats, float *ms_total) {
   if (!e || !lower_host || !upper_host || !seeds_host || !ms_total)
     return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (int rc = params_ready(e)) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   int rc = upload_inputs(e, lower_host, upper_host, seeds_host);
   if (rc) return rc;

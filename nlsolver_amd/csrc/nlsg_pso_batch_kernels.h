@@ -23,6 +23,9 @@
 // The pad column of an odd D holds 0.0 and is masked on every read.
 // Between launches the state waits in HBM: rows [batch][n][D] (unpadded), values, gbest_x, bounds
 // and PsoState per solve.
+// A user objective with run-time parameters (NLSG_N_PARAMS, nlsg_common.h) adds its solve's row
+// as static LDS in front of this block -- a multiple of 16 bytes, so the alignment above holds;
+// both kernels stage it before the first evaluation.
 #pragma once
 
 #include "nlsg_pso_kernels.h"
@@ -53,6 +56,7 @@ struct PsoBatchParams {
   const uint64_t *seeds;  // [batch]
   uint32_t *n_done;       // solves whose stop test has fired since the last init
   uint64_t batch;
+  const double *params;   // [batch][n_params] run-time objective parameters, or null (n_params == 0)
 };
 
 // ---- pso_reset_state_kernel + pso_init_kernel of solve blockIdx.x / blocks_per --------------------
@@ -72,6 +76,7 @@ __global__ __launch_bounds__(256) void pso_batch_init_kernel(PsoBatchParams p, u
     s->done = 0;
     s->pending = 0;
   }
+  stage_custom_params(p.params, b, true);  // (a user objective with parameters; else nothing)
   const uint64_t i = static_cast<uint64_t>(blk) * 4 +
                      __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
   if (i >= n) return;
@@ -322,6 +327,7 @@ __global__ __launch_bounds__(256) void pso_batch_kernel(PsoBatchParams p, uint64
       lower[i] = i < D ? q.lower[b * D + i] : 0.0;
       upper[i] = i < D ? q.upper[b * D + i] : 0.0;
     }
+    stage_custom_params(p.params, b, false);  // once per launch, published by the barrier below
   }
   __syncthreads();
   const uint64_t seed = p.seeds[b];

@@ -79,10 +79,18 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
   int rc = rtc_load(nullptr);
   if (rc) return rc;
   RtcApi &api = rtc_api();
-  std::string src = std::string("#include \"") + kernel_header + "\"\n"
-                    "namespace nlsg {\n"
-                    "template <>\n"
-                    "struct Objective<NLSG_OBJ_CUSTOM> {\n";
+  // n_params > 0 (resident batch engines; every other create_custom has rejected it): the macro
+  // puts the solve's row into static LDS (nlsg_common.h) and the bodies read it as p(k). With
+  // n_params == 0 the source is byte for byte what it was before parameters existed.
+  const int n_params = obj->n_params > 0 ? obj->n_params : 0;
+  std::string src;
+  if (n_params) src += "#define NLSG_N_PARAMS " + std::to_string(n_params) + "\n";
+  src += std::string("#include \"") + kernel_header + "\"\n"
+         "namespace nlsg {\n"
+         "template <>\n"
+         "struct Objective<NLSG_OBJ_CUSTOM> {\n";
+  if (n_params)
+    src += "  __device__ static inline double p(uint64_t k) { return custom_params_lds[k]; }\n";
   if (obj->chain == NLSG_CUSTOM_VECTOR) {
     // whole-vector form: term_body is the body of  double f(const X &x, uint64_t D)
     src += "  static constexpr bool kChain = false;\n"
@@ -412,3 +420,7 @@ void rtc_release(PsoRtcKernels *k) {
 }  // namespace nlsg
 
 extern "C" int nlsg_rtc_load(const char *hiprtc_path) { return nlsg::rtc_load(hiprtc_path); }
+
+extern "C" uint64_t nlsg_custom_params_lds_bytes(int32_t n_params) {
+  return nlsg::custom_params_lds_bytes(n_params);
+}

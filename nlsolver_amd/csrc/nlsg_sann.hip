@@ -147,6 +147,7 @@ int nlsg_sann_create_custom(const nlsg_sann_config *cfg, const nlsg_custom_objec
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int prc = reject_custom_params(obj)) return prc;
   return sann_create(cfg, obj, out);
 }
 

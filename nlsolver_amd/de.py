@@ -49,11 +49,23 @@ class CustomObjective:
     g(x_i, i) over the coordinates):
 
         CustomObjective("double a = x(0) * x(0) + x(1) - 11, b = x(0) + x(1) * x(1) - 7;"
-                        " return a * a + b * b;", vector=True)    # Himmelblau"""
+                        " return a * a + b * b;", vector=True)    # Himmelblau
 
-    def __init__(self, term_body, *, chain=False, finish_body="return s;", vector=False):
+    n_params > 0: the objective owns that many doubles of run-time data per solve, read in every
+    body (and in lambdas given to x.sum) as `p(k)`, k any uint64_t below n_params. The values come
+    from DEBatchEngine / PSOBatchEngine.set_params ([batch, n_params]: solve b sees row b) or from
+    `params=` of the DE / PSO drop-ins; they can be replaced without recompiling. Only the resident
+    batch engines take such an objective; at most CUSTOM_MAX_PARAMS.
+
+        CustomObjective("double r = xi - p(0); return p(1) * r * r;", n_params=2)"""
+
+    def __init__(self, term_body, *, chain=False, finish_body="return s;", vector=False, n_params=0):
         self.term_body, self.finish_body = term_body, finish_body
         self.chain = 2 if vector else int(bool(chain))  # nlsg_custom_objective.chain
+        n_params = int(n_params)
+        if not 0 <= n_params <= _capi.CUSTOM_MAX_PARAMS:
+            raise ValueError(f"n_params must be in 0 .. {_capi.CUSTOM_MAX_PARAMS}, not {n_params}")
+        self.n_params = n_params
 
 
 def rtc_library_path():
@@ -95,7 +107,7 @@ class DEEngine:
         if custom:
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), 0)
+                                         int(custom.chain), custom.n_params)
             check(lib().nlsg_de_create_custom(C.byref(cfg), C.byref(obj), C.byref(self._h)))
         else:
             check(lib().nlsg_de_create(C.byref(cfg), C.byref(self._h)))
@@ -225,7 +237,7 @@ class DERefEngine:
             create = require("nlsg_de_ref_create_custom")
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), 0)
+                                         int(custom.chain), custom.n_params)
             check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
         else:
             check(require("nlsg_de_ref_create")(C.byref(cfg), C.byref(self._h)))
@@ -279,6 +291,19 @@ class DERefEngine:
         return ms.value
 
 
+def _with_params_lds(need, n_params):
+    """need + nlsg_custom_params_lds_bytes(n_params); 0 when either is out of range"""
+    if not n_params:
+        return need
+    extra = int(require("nlsg_custom_params_lds_bytes")(n_params))
+    return need + extra if need and extra else 0
+
+
+def _params_rows(params, batch, n_params):
+    """params as a contiguous float64 [batch, n_params]"""
+    return np.ascontiguousarray(np.asarray(params, dtype=np.float64).reshape(batch, n_params))
+
+
 LDS_BUDGET = 160 * 1024  # bytes of LDS one gfx950 workgroup can take (DEBatchEngine's limit)
 
 
@@ -291,13 +316,15 @@ class DEBatchEngine:
     within LDS_BUDGET, else NlsgError (code 2): there is no global-memory fallback."""
 
     @staticmethod
-    def lds_bytes(pop, dim):
-        """LDS bytes a solve of this shape needs; 0 outside the pop / dim ranges (host only)"""
-        return int(require("nlsg_de_batch_lds_bytes")(pop, dim))
+    def lds_bytes(pop, dim, n_params=0):
+        """LDS bytes a solve of this shape needs, the row of n_params objective parameters
+        included; 0 outside the pop / dim / n_params ranges (host only)"""
+        need = int(require("nlsg_de_batch_lds_bytes")(pop, dim))
+        return _with_params_lds(need, n_params)
 
     @staticmethod
-    def fits(pop, dim):
-        need = DEBatchEngine.lds_bytes(pop, dim)
+    def fits(pop, dim, n_params=0):
+        need = DEBatchEngine.lds_bytes(pop, dim, n_params)
         return 0 < need <= LDS_BUDGET
 
     def __init__(self, objective, batch, pop, dim, *, minimize=True, strategy=DE_RANDOM, CR=0.9,
@@ -316,12 +343,15 @@ class DEBatchEngine:
         cfg.max_iter, cfg.best_val_no_change = max_iter, best_val_no_change
         cfg.turns_per_launch = turns_per_launch
         self.cfg = cfg
+        self.n_params = custom.n_params if custom else 0
         self._h = C.c_void_p()
         if custom:
             create = require("nlsg_de_batch_create_custom")
+            if self.n_params:
+                require("nlsg_de_batch_set_params")
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), 0)
+                                         int(custom.chain), self.n_params)
             check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
         else:
             check(require("nlsg_de_batch_create")(C.byref(cfg), C.byref(self._h)))
@@ -345,6 +375,15 @@ class DEBatchEngine:
         seeds = np.array([int(s) & (2**64 - 1) for s in np.asarray(seeds, dtype=object).ravel()],
                          dtype=np.uint64).reshape(B)
         return x0, seeds
+
+    def set_params(self, params):
+        """params [batch, n_params]: solve b's objective reads row b as p(k). The rows hold from the
+        next launch on and can be replaced at any time without recompiling; scores already stored
+        are not re-evaluated, so call init / minimize afterwards to solve under the new rows."""
+        if self.n_params == 0:
+            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
+        rows = _params_rows(params, self.cfg.batch, self.n_params)
+        check(require("nlsg_de_batch_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
 
     def init(self, x0, seeds):
         """x0 [batch, dim], seeds [batch]: DEEngine.init of every solve under its own seed"""
@@ -385,17 +424,22 @@ class DEBatchEngine:
         check(lib().nlsg_de_batch_upload(self._h, pops.ctypes.data_as(_capi.pd),
                                          scores.ctypes.data_as(_capi.pd)))
 
-    def minimize(self, x, seeds):
+    def minimize(self, x, seeds, params=None):
         """init, then turns until every solve is done -> (x [batch, dim], [Status] * batch): new
-        arrays, the inputs are kept"""
+        arrays, the inputs are kept. params: set_params(params) first."""
+        if params is not None:
+            self.set_params(params)
         x, seeds = self._inputs(x, seeds)
         st = (Status * self.cfg.batch)()
         check(lib().nlsg_de_batch_minimize(self._h, x.ctypes.data_as(_capi.pd),
                                            seeds.ctypes.data_as(_capi.pu), st))
         return x, list(st)
 
-    def time_solve(self, x0, seeds, repeats=1):
-        """milliseconds of `repeats` whole solves from x0 / seeds (hipEvents)"""
+    def time_solve(self, x0, seeds, repeats=1, params=None):
+        """milliseconds of `repeats` whole solves from x0 / seeds (hipEvents). params:
+        set_params(params) first."""
+        if params is not None:
+            self.set_params(params)
         x0, seeds = self._inputs(x0, seeds)
         ms = C.c_float()
         check(lib().nlsg_de_batch_time_solve(self._h, x0.ctypes.data_as(_capi.pd),
@@ -433,11 +477,15 @@ class DE:
     driver="resident": the keyed solve runs through a batch-1 DEBatchEngine -- the whole turn loop
     in one kernel instead of a launch per generation -- when the population fits a workgroup's LDS
     (DEBatchEngine.fits), through DEEngine otherwise; the bits are the same either way.
-    `driver_used` says which engine the last solve ran on. Default "turns": DEEngine."""
+    `driver_used` says which engine the last solve ran on. Default "turns": DEEngine.
+
+    params: the one row of run-time parameters of a CustomObjective with n_params > 0. Such an
+    objective always runs through the resident engine (the only one that takes parameters),
+    whatever `driver` says; a shape that does not fit there is NlsgError code 2."""
 
     def __init__(self, f, generator=None, crossover_prob=0.9, differential_weight=0.8, eps=10e-4,
                  pop_size=50, max_iter=1000, best_val_no_change=50, *, strategy=DE_RANDOM,
-                 device=0, generation="keyed", driver="turns"):
+                 device=0, generation="keyed", driver="turns", params=None):
         if generation not in ("keyed", "reference"):
             raise ValueError(f"generation must be 'keyed' or 'reference', not {generation!r}")
         if driver not in ("turns", "resident"):
@@ -446,6 +494,14 @@ class DE:
             raise ValueError("driver='resident' runs the keyed generation: it cannot be combined with "
                              "generation='reference'")
         self.driver, self.driver_used = driver, None
+        self.n_params = f.n_params if isinstance(f, CustomObjective) else 0
+        if self.n_params and generation == "reference":
+            raise ValueError("an objective with run-time parameters runs the keyed generation on the "
+                             "resident engine: it cannot be combined with generation='reference'")
+        if (params is not None) != bool(self.n_params):
+            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
+                             "objective needs it")
+        self.params = None if params is None else _params_rows(params, 1, self.n_params)
         if generation == "reference" and not isinstance(generator, XorShift):
             raise TypeError("generation='reference' draws from the caller's stream: generator must be an "
                             "nlsolver_amd.XorShift")
@@ -465,9 +521,14 @@ class DE:
             self.generator.state = tuple(int(v) for v in states[0])
             return st[0]
         seed = seed_from_generator(self.generator)
-        if self.driver == "resident" and self._resident_fits(x.size):
+        if self.n_params and not DEBatchEngine.fits(self.pop_size, x.size, self.n_params):
+            raise NlsgError(_capi.NLSG_ERR_UNSUPPORTED,
+                            f"an objective with run-time parameters needs the resident engine, and pop "
+                            f"{self.pop_size} x dim {x.size} with {self.n_params} parameters does not "
+                            f"fit its {LDS_BUDGET} bytes of LDS")
+        if self.n_params or (self.driver == "resident" and self._resident_fits(x.size)):
             with DEBatchEngine(self.f, 1, self.pop_size, x.size, minimize=minimize, **self.args) as eng:
-                xo, st = eng.minimize(x[None, :], [seed])
+                xo, st = eng.minimize(x[None, :], [seed], params=self.params)
             x[:] = xo[0]
             self.driver_used = "resident"
             return st[0]

@@ -41,7 +41,7 @@ class NMEngine:
         if custom:
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), 0)
+                                         int(custom.chain), custom.n_params)
             check(lib().nlsg_nm_create_custom(C.byref(cfg), C.byref(obj), C.byref(self._h)))
         else:
             check(lib().nlsg_nm_create(C.byref(cfg), C.byref(self._h)))

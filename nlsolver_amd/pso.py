@@ -14,7 +14,7 @@ import numpy as np
 from . import _capi
 from ._capi import (PSO_ACCELERATED, PSO_VANILLA, NlsgError, PSOBatchConfig, PSOConfig, Status, check, lib,
                     require)
-from .de import DEFAULT_SEED, LDS_BUDGET, seed_from_generator
+from .de import DEFAULT_SEED, LDS_BUDGET, _params_rows, _with_params_lds, seed_from_generator
 
 
 class PSOEngine:
@@ -43,7 +43,7 @@ class PSOEngine:
         if custom:
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), 0)
+                                         int(custom.chain), custom.n_params)
             check(lib().nlsg_pso_create_custom(C.byref(cfg), C.byref(obj), C.byref(self._h)))
         else:
             check(lib().nlsg_pso_create(C.byref(cfg), C.byref(self._h)))
@@ -142,13 +142,15 @@ class PSOBatchEngine:
     (code 2): there is no global-memory fallback."""
 
     @staticmethod
-    def lds_bytes(n_particles, dim, type=PSO_VANILLA):
-        """LDS bytes a solve of this shape needs; 0 outside the ranges (host only)"""
-        return int(require("nlsg_pso_batch_lds_bytes")(n_particles, dim, type))
+    def lds_bytes(n_particles, dim, type=PSO_VANILLA, n_params=0):
+        """LDS bytes a solve of this shape needs, the row of n_params objective parameters
+        included; 0 outside the ranges (host only)"""
+        need = int(require("nlsg_pso_batch_lds_bytes")(n_particles, dim, type))
+        return _with_params_lds(need, n_params)
 
     @staticmethod
-    def fits(n_particles, dim, type=PSO_VANILLA):
-        need = PSOBatchEngine.lds_bytes(n_particles, dim, type)
+    def fits(n_particles, dim, type=PSO_VANILLA, n_params=0):
+        need = PSOBatchEngine.lds_bytes(n_particles, dim, type, n_params)
         return 0 < need <= LDS_BUDGET
 
     def __init__(self, objective, batch, n_particles, dim, *, type=PSO_VANILLA, bounded=False,
@@ -168,12 +170,15 @@ class PSOBatchEngine:
         cfg.max_iter, cfg.best_val_no_change = max_iter, best_val_no_change
         cfg.turns_per_launch = turns_per_launch
         self.cfg = cfg
+        self.n_params = custom.n_params if custom else 0
         self._h = C.c_void_p()
         if custom:
             create = require("nlsg_pso_batch_create_custom")
+            if self.n_params:
+                require("nlsg_pso_batch_set_params")
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), 0)
+                                         int(custom.chain), self.n_params)
             check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
         else:
             check(require("nlsg_pso_batch_create")(C.byref(cfg), C.byref(self._h)))
@@ -199,6 +204,15 @@ class PSOBatchEngine:
         seeds = np.array([int(s) & (2**64 - 1) for s in np.asarray(seeds, dtype=object).ravel()],
                          dtype=np.uint64).reshape(B)
         return lo, hi, seeds
+
+    def set_params(self, params):
+        """params [batch, n_params]: solve b's objective reads row b as p(k). The rows hold from the
+        next launch on and can be replaced at any time without recompiling; values already stored
+        are not re-evaluated, so call init / minimize afterwards to solve under the new rows."""
+        if self.n_params == 0:
+            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
+        rows = _params_rows(params, self.cfg.batch, self.n_params)
+        check(require("nlsg_pso_batch_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
 
     def init(self, lower, upper, seeds):
         """PSOEngine.init of every solve under its own seed and bounds"""
@@ -234,8 +248,11 @@ class PSOBatchEngine:
                                             pbest.ctypes.data_as(_capi.pd), cur.ctypes.data_as(_capi.pd)))
         return pos, vel, pbest, cur
 
-    def minimize(self, lower, upper, seeds):
-        """init, then turns until every solve is done -> (x [batch, dim], [Status] * batch)"""
+    def minimize(self, lower, upper, seeds, params=None):
+        """init, then turns until every solve is done -> (x [batch, dim], [Status] * batch).
+        params: set_params(params) first."""
+        if params is not None:
+            self.set_params(params)
         lo, hi, seeds = self._inputs(lower, upper, seeds)
         x = np.empty((self.cfg.batch, self.cfg.dim))
         st = (Status * self.cfg.batch)()
@@ -243,8 +260,10 @@ class PSOBatchEngine:
                                             hi.ctypes.data_as(_capi.pd), seeds.ctypes.data_as(_capi.pu), st))
         return x, list(st)
 
-    def time_solve(self, lower, upper, seeds, repeats=1):
-        """milliseconds of `repeats` whole solves (hipEvents)"""
+    def time_solve(self, lower, upper, seeds, repeats=1, params=None):
+        """milliseconds of `repeats` whole solves (hipEvents). params: set_params(params) first."""
+        if params is not None:
+            self.set_params(params)
         lo, hi, seeds = self._inputs(lower, upper, seeds)
         ms = C.c_float()
         check(lib().nlsg_pso_batch_time_solve(self._h, lo.ctypes.data_as(_capi.pd),
@@ -259,14 +278,23 @@ class PSO:
     driver="resident": the solve runs through a batch-1 PSOBatchEngine -- the whole turn loop in one
     kernel instead of up to seven launches per turn -- when the swarm fits a workgroup's LDS
     (PSOBatchEngine.fits), through PSOEngine otherwise; the bits are the same either way.
-    `driver_used` says which engine the last solve ran on. Default "turns": PSOEngine."""
+    `driver_used` says which engine the last solve ran on. Default "turns": PSOEngine.
+
+    params: the one row of run-time parameters of a CustomObjective with n_params > 0. Such an
+    objective always runs through the resident engine (the only one that takes parameters),
+    whatever `driver` says; a shape that does not fit there is NlsgError code 2."""
 
     def __init__(self, f, generator=None, inertia=0.8, cognitive_coef=1.8, social_coef=1.8,
                  n_particles=10, max_iter=5000, best_val_no_change=50, eps=10e-4, *,
-                 type=PSO_VANILLA, device=0, driver="turns"):
+                 type=PSO_VANILLA, device=0, driver="turns", params=None):
         if driver not in ("turns", "resident"):
             raise ValueError(f"driver must be 'turns' or 'resident', not {driver!r}")
         self.driver, self.driver_used = driver, None
+        self.n_params = getattr(f, "n_params", 0)
+        if (params is not None) != bool(self.n_params):
+            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
+                             "objective needs it")
+        self.params = None if params is None else _params_rows(params, 1, self.n_params)
         self.f, self.generator, self.n_particles = f, generator, n_particles
         self.args = dict(inertia=inertia, cognitive=cognitive_coef, social=social_coef, eps=eps,
                          max_iter=max_iter, best_val_no_change=best_val_no_change, type=type,
@@ -279,10 +307,16 @@ class PSO:
         if not bounded:  # nlsolver.h:2553-2560: lower = -|x|, upper = |x|
             lower, upper = -np.abs(x), np.abs(x)
         seed = seed_from_generator(self.generator)
-        if self.driver == "resident" and self._resident_fits(x.size):
+        if self.n_params and not PSOBatchEngine.fits(self.n_particles, x.size, self.args["type"],
+                                                     self.n_params):
+            raise NlsgError(_capi.NLSG_ERR_UNSUPPORTED,
+                            f"an objective with run-time parameters needs the resident engine, and "
+                            f"{self.n_particles} particles x dim {x.size} with {self.n_params} parameters "
+                            f"do not fit its {LDS_BUDGET} bytes of LDS")
+        if self.n_params or (self.driver == "resident" and self._resident_fits(x.size)):
             with PSOBatchEngine(self.f, 1, self.n_particles, x.size, bounded=bounded, minimize=minimize,
                                 **self.args) as eng:
-                xo, st = eng.minimize(lower, upper, [seed])
+                xo, st = eng.minimize(lower, upper, [seed], params=self.params)
             x[:] = xo[0]
             self.driver_used = "resident"
             return st[0]

@@ -83,9 +83,11 @@ typedef enum {
 /* n_params > 0: the objective owns that many doubles of RUN-TIME data per solve. Every body (term,
  * finish, whole-vector, and lambdas given to x.sum) reads them as  p(k),  k any uint64_t below
  * n_params, which may differ from lane to lane (an index at or beyond n_params is the caller's
- * error, as an index past an array is). Only the resident batch engines take such an objective
- * (nlsg_de_batch_create_custom, nlsg_pso_batch_create_custom; values: nlsg_*_batch_set_params);
- * every other *_create_custom answers NLSG_ERR_UNSUPPORTED. A body's own local named p shadows the
+ * error, as an index past an array is). The engines whose kernel owns a workgroup per solve take such
+ * an objective: the resident batch engines (nlsg_de_batch_create_custom, nlsg_pso_batch_create_custom;
+ * values: nlsg_*_batch_set_params), Nelder-Mead and the NM/PSO hybrid (nlsg_nm_create_params,
+ * nlsg_nmpso_create_params; values: nlsg_nm_set_params, nlsg_nmpso_set_params); every other
+ * *_create_custom answers NLSG_ERR_UNSUPPORTED. A body's own local named p shadows the
  * accessor. 0: no parameters, the source compiled is what it was before parameters existed. */
 #define NLSG_CUSTOM_MAX_PARAMS 4096
 typedef struct {
@@ -514,6 +516,23 @@ typedef struct {
 int nlsg_nm_create(const nlsg_nm_config *cfg, nlsg_nm **out);
 /* cfg->objective == NLSG_OBJ_CUSTOM, as nlsg_de_create_custom */
 int nlsg_nm_create_custom(const nlsg_nm_config *cfg, const nlsg_custom_objective *obj, nlsg_nm **out);
+/* A custom objective with run-time parameters (obj->n_params >= 1), one row per start. Every check
+ * of nlsg_nm_create_custom in its order, then, still before the device is touched: n_params < 1 is
+ * NLSG_ERR_INVALID_ARG (zero is nlsg_nm_create_custom's), above NLSG_CUSTOM_MAX_PARAMS
+ * NLSG_ERR_UNSUPPORTED, and nlsg_nm_lds_bytes(dim, flags) + nlsg_custom_params_lds_bytes(n_params)
+ * above 163840 NLSG_ERR_UNSUPPORTED. In reference order fewer term buffers than waves may be left;
+ * the results do not depend on their number. */
+int nlsg_nm_create_params(const nlsg_nm_config *cfg, const nlsg_custom_objective *obj, nlsg_nm **out);
+/* params_host [batch][n_params]: start b's objective reads row b as p(k). Copied on the engine's
+ * stream before the call returns; the rows hold from the next launch on (a launch stages its row
+ * once, which covers every restart) and are replaced without recompiling. NLSG_ERR_INVALID_ARG on an
+ * engine of another creator. Until the first call, nlsg_nm_minimize, nlsg_nm_time_solve and
+ * nlsg_nm_phase_cycles answer NLSG_ERR_STATE. */
+int nlsg_nm_set_params(nlsg_nm *e, const double *params_host);
+/* Dynamic LDS bytes a workgroup of this shape needs at the least: the simplex image, and with
+ * NLSG_NM_REFERENCE_ORDER one term buffer behind it (the launch takes one per wave as far as the
+ * room goes). 0 outside 1 <= dim <= 1024 or for unknown flags. Host only, no device. */
+uint64_t nlsg_nm_lds_bytes(uint64_t dim, uint32_t flags);
 int nlsg_nm_destroy(nlsg_nm *e);
 /* x [batch][dim] in/out; upper/lower [dim] (shared by the batch; NULL when unbounded; note
  * the reference's argument order: upper first). One status per start; eps_out receives each
@@ -598,6 +617,17 @@ int nlsg_nmpso_create(const nlsg_nmpso_config *cfg, nlsg_nmpso **out);
 /* cfg->objective == NLSG_OBJ_CUSTOM, as nlsg_de_create_custom */
 int nlsg_nmpso_create_custom(const nlsg_nmpso_config *cfg, const nlsg_custom_objective *obj,
                              nlsg_nmpso **out);
+/* As nlsg_nm_create_params: every check of nlsg_nmpso_create_custom, then n_params (< 1:
+ * NLSG_ERR_INVALID_ARG, above NLSG_CUSTOM_MAX_PARAMS: NLSG_ERR_UNSUPPORTED) and
+ * nlsg_nmpso_lds_bytes(dim) + nlsg_custom_params_lds_bytes(n_params) <= 163840, before the device. */
+int nlsg_nmpso_create_params(const nlsg_nmpso_config *cfg, const nlsg_custom_objective *obj,
+                             nlsg_nmpso **out);
+/* params_host [batch][n_params], instance b reads row b; exactly as nlsg_nm_set_params
+ * (NLSG_ERR_STATE from nlsg_nmpso_minimize / _time_solve before the first call) */
+int nlsg_nmpso_set_params(nlsg_nmpso *e, const double *params_host);
+/* LDS bytes of an instance's workgroup: the packed kernel's block for dim <= 128, the wide kernels'
+ * view beyond; 0 outside 2 <= dim <= 1024. Host only, no device. */
+uint64_t nlsg_nmpso_lds_bytes(uint64_t dim);
 int nlsg_nmpso_destroy(nlsg_nmpso *e);
 /* x [batch][dim] in: starts, out: best particles; lower/upper [dim] shared by the batch (note
  * the reference's order: lower first, 3609-3612; NULL when unbounded). One status per

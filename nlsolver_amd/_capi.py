@@ -280,12 +280,25 @@ OPTIONAL_SYMBOLS = {
     "nlsg_pso_batch_download": (C.c_int, [_H, u64, pd, pd, pd, pd]),
     "nlsg_pso_batch_minimize": (C.c_int, [_H, pd, pd, pd, pu, C.POINTER(Status)]),
     "nlsg_pso_batch_time_solve": (C.c_int, [_H, pd, pd, pu, C.c_uint32, C.POINTER(C.c_float)]),
+    "nlsg_nm_create_params": (C.c_int, [C.POINTER(NMConfig), C.POINTER(CustomObjectiveC), C.POINTER(_H)]),
+    "nlsg_nm_set_params": (C.c_int, [_H, pd]),
+    "nlsg_nm_lds_bytes": (u64, [u64, C.c_uint32]),
+    "nlsg_nmpso_create_params": (C.c_int, [C.POINTER(NMPSOConfig), C.POINTER(CustomObjectiveC),
+                                           C.POINTER(_H)]),
+    "nlsg_nmpso_set_params": (C.c_int, [_H, pd]),
+    "nlsg_nmpso_lds_bytes": (u64, [u64]),
 }
 SYMBOLS.update(OPTIONAL_SYMBOLS)
 _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
                     "nlsg_custom_params_": "library has no run-time objective parameters",
                     "nlsg_de_batch_set_params": "library has no run-time objective parameters",
                     "nlsg_pso_batch_set_params": "library has no run-time objective parameters",
+                    "nlsg_nm_create_params": "library has no run-time objective parameters for Nelder-Mead",
+                    "nlsg_nm_set_params": "library has no run-time objective parameters for Nelder-Mead",
+                    "nlsg_nm_lds_bytes": "library has no run-time objective parameters for Nelder-Mead",
+                    "nlsg_nmpso_create_params": "library has no run-time objective parameters for the hybrid",
+                    "nlsg_nmpso_set_params": "library has no run-time objective parameters for the hybrid",
+                    "nlsg_nmpso_lds_bytes": "library has no run-time objective parameters for the hybrid",
                     "nlsg_de_batch_": "library has no resident batch DE",
                     "nlsg_pso_batch_": "library has no resident batch PSO"}
 

@@ -341,9 +341,10 @@ struct Objective<NLSG_OBJ_RASTRIGIN> {
 };
 
 // ---------------------------------------------------------------------------
-// run-time parameters of a user objective (nlsg_custom_objective.n_params > 0; resident batch
-// engines only). rtc_compile defines NLSG_N_PARAMS ahead of the kernel header, so the block below
-// exists in that translation unit alone: static LDS in front of the kernels' dynamic block, one
+// run-time parameters of a user objective (nlsg_custom_objective.n_params > 0; the engines whose
+// kernel owns a workgroup per solve: resident batch DE / PSO, Nelder-Mead and the NM/PSO hybrid
+// made by their *_create_params). rtc_compile defines NLSG_N_PARAMS ahead of the kernel header, so the
+// block below exists in that translation unit alone: static LDS in front of the kernels' dynamic block, one
 // solve's row, staged once per launch by the workgroup and read by Objective<NLSG_OBJ_CUSTOM>::p(k)
 // with ds_read. Rounded to an even count: 16-byte size, so the dynamic block behind it keeps the
 // 16-byte alignment the PSO kernel's double2 accesses need. Without the macro nothing is emitted
@@ -351,6 +352,9 @@ struct Objective<NLSG_OBJ_RASTRIGIN> {
 // ---------------------------------------------------------------------------
 #ifdef NLSG_N_PARAMS
 __shared__ __attribute__((aligned(16))) double custom_params_lds[(NLSG_N_PARAMS + 1) & ~1];
+constexpr size_t kCustomParamsLdsBytes = 8 * ((static_cast<size_t>(NLSG_N_PARAMS) + 1) & ~size_t(1));
+#else
+constexpr size_t kCustomParamsLdsBytes = 0;  // what a kernel that sizes its own dynamic LDS takes off the CU's
 #endif
 // Called by all threads of the block, uniformly. `params` is [batch][n_params]; the caller's next
 // barrier (or `sync`) publishes the row.
@@ -380,6 +384,24 @@ inline int reject_custom_params(const nlsg_custom_objective *obj) {
                 "n_params = %d: run-time objective parameters are taken by nlsg_de_batch_create_custom "
                 "and nlsg_pso_batch_create_custom only",
                 obj->n_params);
+  return NLSG_OK;
+}
+// nlsg_nm_create_params / nlsg_nmpso_create_params, after their shape checks and before the device:
+// the count (zero is `old_creator`'s), then the workgroup's LDS with the row in front of `shape_lds`
+inline int check_custom_params(const nlsg_custom_objective *obj, uint64_t shape_lds, const char *what,
+                               const char *old_creator) {
+  const int32_t n_params = obj->n_params;
+  if (n_params < 1)
+    return fail(NLSG_ERR_INVALID_ARG, "n_params = %d: %s_create_params takes 1 .. %d parameters; an objective "
+                "without parameters is made by %s", n_params, what, NLSG_CUSTOM_MAX_PARAMS, old_creator);
+  if (n_params > NLSG_CUSTOM_MAX_PARAMS)
+    return fail(NLSG_ERR_UNSUPPORTED, "a custom objective takes at most %d parameters, not %d",
+                NLSG_CUSTOM_MAX_PARAMS, n_params);
+  const uint64_t params_lds = custom_params_lds_bytes(n_params);
+  if (shape_lds + params_lds > 160ull * 1024)
+    return fail(NLSG_ERR_UNSUPPORTED, "%s: this shape needs %llu bytes of LDS and %d parameters %llu more, a "
+                "workgroup has %llu", what, (unsigned long long)shape_lds, n_params,
+                (unsigned long long)params_lds, 160ull * 1024);
   return NLSG_OK;
 }
 #endif

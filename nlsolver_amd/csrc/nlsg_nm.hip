@@ -19,6 +19,9 @@ struct nlsg_nm {
   bool driver = false;  // n <= 128: nm_solve_driver_kernel (NLSG_NM_DRIVER=0: the phase-per-barrier kernel)
   unsigned long long *phase_dev = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int32_t n_params = 0;          // nlsg_nm_create_params: the objective's run-time doubles per start
+  double *params_dev = nullptr;  // [batch][n_params]
+  bool params_set = false;
 };
 
 namespace {
@@ -86,6 +89,13 @@ void launch(nlsg_nm *e) {
   }
 }
 
+// a parametrised engine solves nothing before its first rows
+int params_ready(const nlsg_nm *e) {
+  if (e->n_params > 0 && !e->params_set)
+    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_nm_set_params first", e->n_params);
+  return NLSG_OK;
+}
+
 int upload_bounds(nlsg_nm *e, const double *upper_host, const double *lower_host) {
   if (!e->cfg.bounded) return NLSG_OK;
   if (!upper_host || !lower_host)
@@ -98,7 +108,8 @@ int upload_bounds(nlsg_nm *e, const double *upper_host, const double *lower_host
 
 extern "C" {
 
-static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *custom, nlsg_nm **out);
+static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *custom, nlsg_nm **out,
+                     bool with_params = false);
 
 int nlsg_nm_create(const nlsg_nm_config *cfg, nlsg_nm **out) {
   if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
@@ -114,7 +125,34 @@ int nlsg_nm_create_custom(const nlsg_nm_config *cfg, const nlsg_custom_objective
   return nm_create(cfg, obj, out);
 }
 
-static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *custom, nlsg_nm **out) {
+int nlsg_nm_create_params(const nlsg_nm_config *cfg, const nlsg_custom_objective *obj, nlsg_nm **out) {
+  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (cfg->objective != NLSG_OBJ_CUSTOM)
+    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  return nm_create(cfg, obj, out, true);
+}
+
+// The least dynamic LDS a launch of this shape takes (nm_launch_lds_bytes): the image, and in reference
+// order one term buffer behind it — the driver wave's own; more waves get one as far as the CU's LDS goes.
+uint64_t nlsg_nm_lds_bytes(uint64_t dim, uint32_t flags) {
+  if (dim < 1 || dim > 1024 || (flags & ~NLSG_NM_REFERENCE_ORDER)) return 0;
+  return nm_launch_lds_bytes(dim, 1, (flags & NLSG_NM_REFERENCE_ORDER) != 0);
+}
+
+int nlsg_nm_set_params(nlsg_nm *e, const double *params_host) {
+  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (e->n_params <= 0)
+    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_nm_create_params)");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
+                          hipMemcpyHostToDevice, e->stream));
+  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
+  e->params_set = true;
+  return NLSG_OK;
+}
+
+static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *custom, nlsg_nm **out,
+                     bool with_params) {
   if (!cfg || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(nlsg_nm_config))
@@ -133,6 +171,10 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
     return fail(NLSG_ERR_UNSUPPORTED,
                 "NLSG_NM_REFERENCE_ORDER needs an objective given by its terms whose arithmetic the device "
                 "shares with the reference (not Rastrigin: its cosine is the device's own; not a whole-vector body)");
+  if (with_params)
+    if (const int prc = check_custom_params(custom, nlsg_nm_lds_bytes(cfg->dim, cfg->flags), "nlsg_nm",
+                                            "nlsg_nm_create_custom"))
+      return prc;
   int rc = check_device(cfg->device);
   if (rc) return rc;
   NLSG_HIP(hipSetDevice(cfg->device));
@@ -153,7 +195,9 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
   std::memset(&p, 0, sizeof p);
   const uint64_t B = cfg->batch, n = cfg->dim;
   const bool seq = (cfg->flags & NLSG_NM_REFERENCE_ORDER) != 0;
-  e->lds = nm_launch_lds_bytes(n, nm_block_threads(n) / 64, seq);
+  // (the parameter row is static LDS of the run-time compiled module, in front of this dynamic block)
+  e->n_params = with_params ? custom->n_params : 0;
+  e->lds = nm_launch_lds_bytes(n, nm_block_threads(n) / 64, seq, custom_params_lds_bytes(e->n_params));
   hipError_t he = hipSuccess;
   const int chunks = nm_chunks(n);
   if (he == hipSuccess && chunks > 1)  // the simplexes themselves: past what LDS holds
@@ -162,6 +206,8 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.prob), B * sizeof(NmProblem));
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->upper_dev), n * 8);
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->lower_dev), n * 8);
+  if (he == hipSuccess && e->n_params)
+    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * 8);
   if (he == hipSuccess) he = hipEventCreate(&e->ev0);
   if (he == hipSuccess) he = hipEventCreate(&e->ev1);
   {
@@ -193,6 +239,7 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
   }
   p.upper = e->upper_dev;
   p.lower = e->lower_dev;
+  p.params = e->params_dev;
   p.batch = B;
   p.n = n;
   p.max_iter = cfg->max_iter;
@@ -227,6 +274,7 @@ int nlsg_nm_destroy(nlsg_nm *e) {
   pool_free(e->upper_dev);
   pool_free(e->lower_dev);
   pool_free(e->phase_dev);
+  pool_free(e->params_dev);
   if (e->ev0) hipEventDestroy(e->ev0);
   if (e->ev1) hipEventDestroy(e->ev1);
   if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
@@ -237,6 +285,7 @@ int nlsg_nm_destroy(nlsg_nm *e) {
 int nlsg_nm_minimize(nlsg_nm *e, double *x_inout_host, const double *upper_host,
                      const double *lower_host, nlsg_status *status_host, double *eps_out_host) {
   if (!e || !x_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   int rc = upload_bounds(e, upper_host, lower_host);
   if (rc) return rc;
@@ -269,6 +318,7 @@ int nlsg_nm_minimize(nlsg_nm *e, double *x_inout_host, const double *upper_host,
 
 int nlsg_nm_phase_cycles(nlsg_nm *e, const double *x0_host, uint64_t *cycles_host) {
   if (!e || !x0_host || !cycles_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   const uint64_t B = e->p.batch;
   // a measurement aid: its buffer exists from its first use on, and it profiles the unbounded
@@ -288,6 +338,7 @@ int nlsg_nm_phase_cycles(nlsg_nm *e, const double *x0_host, uint64_t *cycles_hos
 
 int nlsg_nm_time_solve(nlsg_nm *e, const double *x0_host, uint32_t repeats, float *ms_total) {
   if (!e || !x0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   float total = 0.f;
   for (uint32_t r = 0; r < repeats; r++) {

@@ -49,6 +49,7 @@ struct NmParams {
   // measurement aid (nlsg_nm_phase_cycles; nullptr otherwise): [batch][kNmPhases] shader-clock
   // cycles the start's decision chain spent per phase, and two counts
   unsigned long long *phase;
+  const double *params;  // [batch][n_params] (nlsg_nm_create_params), row b staged into LDS; else nullptr
 };
 // phases: 0 scan (std_err, best / worst / second worst, stop tests), 1 centroid, 2 reflection
 // (transform, evaluation, decision), 3 expansion or contraction (transform, evaluation, accept),
@@ -99,15 +100,20 @@ __device__ inline double nm_wave_f(const double *pt, uint64_t n, double fmul, do
 // reference's runs bit for bit: nm_solve_kernel with p.seq, every wave with a term buffer of its own
 // behind the workgroup's LDS image (as many waves as have room take part in a shrink's rescoring).
 __host__ __device__ inline size_t nm_seq_buffer_bytes(uint64_t n) { return 128ull * nm_chunks(n) * sizeof(double); }
-__host__ __device__ inline uint64_t nm_seq_buffers(uint64_t n, uint64_t nwaves, size_t lds_base) {
-  const size_t room = 160 * 1024 - ((lds_base + 15) & ~size_t(15)) - 64;  // (64: serial_sum_lds reads ahead)
+// static_lds: what the kernel's translation unit holds in front of the dynamic block (the parameter row
+// of a user objective, kCustomParamsLdsBytes on the device) — static plus dynamic is what the CU has
+__host__ __device__ inline uint64_t nm_seq_buffers(uint64_t n, uint64_t nwaves, size_t lds_base,
+                                                   size_t static_lds = 0) {
+  const size_t used = static_lds + ((lds_base + 15) & ~size_t(15)) + 64;  // (64: serial_sum_lds reads ahead)
+  const size_t room = used < 160 * 1024 ? 160 * 1024 - used : 0;
   const uint64_t fit = room / nm_seq_buffer_bytes(n);
   return fit < nwaves ? fit : nwaves;
 }
 // dynamic LDS of a launch: the image, and in reference order the term buffers behind it
-__host__ __device__ inline size_t nm_launch_lds_bytes(uint64_t n, uint64_t nwaves, bool seq) {
+__host__ __device__ inline size_t nm_launch_lds_bytes(uint64_t n, uint64_t nwaves, bool seq, size_t static_lds = 0) {
   const size_t base = nm_lds_bytes(n);
-  return seq ? ((base + 15) & ~size_t(15)) + nm_seq_buffers(n, nwaves, base) * nm_seq_buffer_bytes(n) + 64 : base;
+  return seq ? ((base + 15) & ~size_t(15)) + nm_seq_buffers(n, nwaves, base, static_lds) * nm_seq_buffer_bytes(n) + 64
+             : base;
 }
 
 template <int OBJ, int CHUNKS = 1>
@@ -128,7 +134,7 @@ __global__ __launch_bounds__(kNmThreads) void nm_solve_kernel(NmParams p) {
   const int lane = lane_id();
   // reference order: term buffers of 128 CHUNKS doubles behind the image (nm_lds_bytes), one per wave
   // as far as the CU's LDS goes; sbuf: this wave's (nullptr: tree order, or no room for this wave)
-  const uint64_t seq_waves = p.seq ? nm_seq_buffers(n, static_cast<uint64_t>(p.seq) < nwaves ? p.seq : nwaves, nm_lds_bytes(n)) : 0;
+  const uint64_t seq_waves = p.seq ? nm_seq_buffers(n, static_cast<uint64_t>(p.seq) < nwaves ? p.seq : nwaves, nm_lds_bytes(n), kCustomParamsLdsBytes) : 0;
   double *const seq_base = reinterpret_cast<double *>(nm_smem + ((nm_lds_bytes(n) + 15) & ~size_t(15)));
   double *const sbuf = static_cast<uint64_t>(wid) < seq_waves ? seq_base + static_cast<uint64_t>(wid) * (128 * CHUNKS) : nullptr;
 
@@ -137,6 +143,7 @@ __global__ __launch_bounds__(kNmThreads) void nm_solve_kernel(NmParams p) {
     up[j] = p.bounded ? p.upper[j] : 0.0;
     lo[j] = p.bounded ? p.lower[j] : 0.0;
   }
+  stage_custom_params(p.params, pid, false);  // (a user objective's row: the barrier below publishes it)
   if (t == 0) {
     ctl->eps = p.eps;
     ctl->fcalls = 0;
@@ -674,7 +681,7 @@ __global__ __launch_bounds__(kNmThreads) void nm_solve_driver_kernel(NmParams p)
   const uint64_t e0 = 2 * static_cast<uint64_t>(lane), e1 = e0 + 1;
   const bool in0 = e0 < n, in1 = e1 < n;
   // reference order: a term buffer of 128 doubles per wave behind the image (as in nm_solve_kernel)
-  const uint64_t seq_waves = SEQ ? nm_seq_buffers(n, static_cast<uint64_t>(p.seq) < nwaves ? p.seq : nwaves, nm_lds_bytes(n)) : 0;
+  const uint64_t seq_waves = SEQ ? nm_seq_buffers(n, static_cast<uint64_t>(p.seq) < nwaves ? p.seq : nwaves, nm_lds_bytes(n), kCustomParamsLdsBytes) : 0;
   double *const seq_base = reinterpret_cast<double *>(nm_smem + ((nm_lds_bytes(n) + 15) & ~size_t(15)));
   double *const sbuf = SEQ && static_cast<uint64_t>(wid) < seq_waves ? seq_base + static_cast<uint64_t>(wid) * 128 : nullptr;
 
@@ -683,6 +690,7 @@ __global__ __launch_bounds__(kNmThreads) void nm_solve_driver_kernel(NmParams p)
     up[j] = p.bounded ? p.upper[j] : 0.0;
     lo[j] = p.bounded ? p.lower[j] : 0.0;
   }
+  stage_custom_params(p.params, pid, false);  // (a user objective's row: the barrier below publishes it)
   if (t == 0) {
     ctl->eps = p.eps;
     ctl->fcalls = 0;

@@ -16,6 +16,9 @@ struct nlsg_nmpso {
   double *upper_dev = nullptr, *lower_dev = nullptr, *zero_dev = nullptr;
   HybRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int32_t n_params = 0;          // nlsg_nmpso_create_params: the objective's run-time doubles per instance
+  double *params_dev = nullptr;  // [batch][n_params]
+  bool params_set = false;
 };
 
 namespace {
@@ -78,6 +81,14 @@ void launch(nlsg_nmpso *e) {
   }
 }
 
+// a parametrised engine solves nothing before its first rows
+int params_ready(const nlsg_nmpso *e) {
+  if (e->n_params > 0 && !e->params_set)
+    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_nmpso_set_params first",
+                e->n_params);
+  return NLSG_OK;
+}
+
 int upload_bounds(nlsg_nmpso *e, const double *lower_host, const double *upper_host) {
   if (!e->p.bounded) return NLSG_OK;
   if (!lower_host || !upper_host)
@@ -90,7 +101,7 @@ int upload_bounds(nlsg_nmpso *e, const double *lower_host, const double *upper_h
 }  // namespace
 
 static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective *custom,
-                      nlsg_nmpso **out);
+                      nlsg_nmpso **out, bool with_params = false);
 
 extern "C" {
 
@@ -109,10 +120,36 @@ int nlsg_nmpso_create_custom(const nlsg_nmpso_config *cfg, const nlsg_custom_obj
   return hyb_create(cfg, obj, out);
 }
 
+int nlsg_nmpso_create_params(const nlsg_nmpso_config *cfg, const nlsg_custom_objective *obj,
+                             nlsg_nmpso **out) {
+  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (cfg->objective != NLSG_OBJ_CUSTOM)
+    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  return hyb_create(cfg, obj, out, true);
+}
+
+// the workgroup's LDS: the packed kernel's static block (n <= 128), the wide kernels' dynamic view beyond
+uint64_t nlsg_nmpso_lds_bytes(uint64_t dim) {
+  if (dim < 2 || dim > kHybWideMaxN) return 0;
+  return dim <= kHybMaxN ? sizeof(HybShared) : hyb_view_bytes(dim);
+}
+
+int nlsg_nmpso_set_params(nlsg_nmpso *e, const double *params_host) {
+  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (e->n_params <= 0)
+    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_nmpso_create_params)");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
+                          hipMemcpyHostToDevice, e->stream));
+  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
+  e->params_set = true;
+  return NLSG_OK;
+}
+
 }  // extern "C"
 
 static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective *custom,
-                      nlsg_nmpso **out) {
+                      nlsg_nmpso **out, bool with_params) {
   if (!cfg || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(nlsg_nmpso_config))
@@ -128,12 +165,17 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
                 "points live in one workgroup's shared memory)", (unsigned long long)cfg->dim,
                 kHybWideMaxN);
   if (cfg->batch > 0x7fffffffull) return fail(NLSG_ERR_UNSUPPORTED, "batch too large");
+  if (with_params)
+    if (const int prc = check_custom_params(custom, nlsg_nmpso_lds_bytes(cfg->dim), "nlsg_nmpso",
+                                            "nlsg_nmpso_create_custom"))
+      return prc;
   int rc = check_device(cfg->device);
   if (rc) return rc;
   NLSG_HIP(hipSetDevice(cfg->device));
   nlsg_nmpso *e = new (std::nothrow) nlsg_nmpso();
   if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
   e->cfg = *cfg;
+  e->n_params = with_params ? custom->n_params : 0;
   if (cfg->stream) {
     e->stream = borrowed_stream(cfg->stream);
   } else {
@@ -156,6 +198,8 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->lower_dev), n * 8);
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->zero_dev), 16);
   if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
+  if (he == hipSuccess && e->n_params)
+    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * 8);
   if (he == hipSuccess) he = hipEventCreate(&e->ev0);
   if (he == hipSuccess) he = hipEventCreate(&e->ev1);
   if (he == hipSuccess && n > kHybMaxN && !custom) {
@@ -181,6 +225,7 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
   p.upper = e->upper_dev;
   p.lower = e->lower_dev;
   p.zero = e->zero_dev;
+  p.params = e->params_dev;
   p.batch = B;
   p.n = n;
   p.max_iter = cfg->max_iter;
@@ -215,6 +260,7 @@ int nlsg_nmpso_destroy(nlsg_nmpso *e) {
   pool_free(e->upper_dev);
   pool_free(e->lower_dev);
   pool_free(e->zero_dev);
+  pool_free(e->params_dev);
   if (e->ev0) hipEventDestroy(e->ev0);
   if (e->ev1) hipEventDestroy(e->ev1);
   if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
@@ -225,6 +271,7 @@ int nlsg_nmpso_destroy(nlsg_nmpso *e) {
 int nlsg_nmpso_minimize(nlsg_nmpso *e, double *x_inout_host, const double *lower_host,
                         const double *upper_host, nlsg_status *status_host) {
   if (!e || !x_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   int rc = upload_bounds(e, lower_host, upper_host);
   if (rc) return rc;
@@ -256,6 +303,7 @@ int nlsg_nmpso_minimize(nlsg_nmpso *e, double *x_inout_host, const double *lower
 
 int nlsg_nmpso_time_solve(nlsg_nmpso *e, const double *x0_host, uint32_t repeats, float *ms_total) {
   if (!e || !x0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   if (e->p.bounded) return fail(NLSG_ERR_UNSUPPORTED, "timing aid of the unbounded overloads");
   NLSG_HIP(hipSetDevice(e->cfg.device));
   float total = 0.f;

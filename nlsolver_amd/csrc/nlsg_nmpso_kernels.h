@@ -53,6 +53,7 @@ struct HybParams {
   uint64_t batch, n, max_iter, no_change_iter, seed, inst_lo;
   double alpha, gamma, rho, sigma, inertia, cog, soc, eps, fmul;
   int32_t bounded, pad;
+  const double *params;  // [batch][n_params] (nlsg_nmpso_create_params), row `inst` staged into LDS; else nullptr
 };
 
 struct HybShared {
@@ -371,6 +372,7 @@ __device__ inline void nmpso_run(const HybParams &p, SH &sh) {
   const double *x0 = p.x + inst * n;
   const uint64_t kc = ctr_key(p.seed, p.inst_lo + inst);
 
+  stage_custom_params(p.params, inst, false);  // (a user objective's row: the first barrier below publishes it)
   // ---- bounds (3587-3593 for the unbounded overloads) and init_solver_state (3686-3738)
   if (t < static_cast<int>(n)) {
     if (p.bounded) {

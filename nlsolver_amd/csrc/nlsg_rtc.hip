@@ -79,7 +79,8 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
   int rc = rtc_load(nullptr);
   if (rc) return rc;
   RtcApi &api = rtc_api();
-  // n_params > 0 (resident batch engines; every other create_custom has rejected it): the macro
+  // n_params > 0 (resident batch engines, nlsg_nm_create_params, nlsg_nmpso_create_params; every
+  // *_create_custom besides has rejected it): the macro
   // puts the solve's row into static LDS (nlsg_common.h) and the bodies read it as p(k). With
   // n_params == 0 the source is byte for byte what it was before parameters existed.
   const int n_params = obj->n_params > 0 ? obj->n_params : 0;

@@ -54,8 +54,9 @@ class CustomObjective:
     n_params > 0: the objective owns that many doubles of run-time data per solve, read in every
     body (and in lambdas given to x.sum) as `p(k)`, k any uint64_t below n_params. The values come
     from DEBatchEngine / PSOBatchEngine.set_params ([batch, n_params]: solve b sees row b) or from
-    `params=` of the DE / PSO drop-ins; they can be replaced without recompiling. Only the resident
-    batch engines take such an objective; at most CUSTOM_MAX_PARAMS.
+    `params=` of the DE / PSO drop-ins; they can be replaced without recompiling. NMEngine and
+    NMPSOEngine take such an objective the same way (set_params: start / instance b sees row b), and
+    NelderMead / NelderMeadPSO take `params=`; no other engine does. At most CUSTOM_MAX_PARAMS.
 
         CustomObjective("double r = xi - p(0); return p(1) * r * r;", n_params=2)"""
 

@@ -83,11 +83,13 @@ typedef enum {
 /* n_params > 0: the objective owns that many doubles of RUN-TIME data per solve. Every body (term,
  * finish, whole-vector, and lambdas given to x.sum) reads them as  p(k),  k any uint64_t below
  * n_params, which may differ from lane to lane (an index at or beyond n_params is the caller's
- * error, as an index past an array is). The engines whose kernel owns a workgroup per solve take such
- * an objective: the resident batch engines (nlsg_de_batch_create_custom, nlsg_pso_batch_create_custom;
- * values: nlsg_*_batch_set_params), Nelder-Mead and the NM/PSO hybrid (nlsg_nm_create_params,
- * nlsg_nmpso_create_params; values: nlsg_nm_set_params, nlsg_nmpso_set_params); every other
- * *_create_custom answers NLSG_ERR_UNSUPPORTED. A body's own local named p shadows the
+ * error, as an index past an array is). The engines whose kernel owns a workgroup — or, BFGS, a wave —
+ * per solve take such an objective: the resident batch engines (nlsg_de_batch_create_custom,
+ * nlsg_pso_batch_create_custom; values: nlsg_*_batch_set_params), and through creators of their own
+ * Nelder-Mead, the NM/PSO hybrid, Levenberg-Marquardt and BFGS (nlsg_nm_create_params,
+ * nlsg_nmpso_create_params, nlsg_lm_create_params, nlsg_bfgs_create_params; values: nlsg_nm_set_params,
+ * nlsg_nmpso_set_params, nlsg_lm_set_params, nlsg_bfgs_set_params); every other *_create_custom
+ * (SANN's and the plain DE / PSO engines' included) answers NLSG_ERR_UNSUPPORTED. A body's own local named p shadows the
  * accessor. 0: no parameters, the source compiled is what it was before parameters existed. */
 #define NLSG_CUSTOM_MAX_PARAMS 4096
 typedef struct {
@@ -382,9 +384,26 @@ typedef struct {
 int nlsg_bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host,
                      const double *lin_host, nlsg_bfgs **out);
 /* cfg->objective == NLSG_OBJ_CUSTOM: a user objective (nlsg_custom_objective, as for
- * nlsg_de_create_custom) minimised with the default finite-difference gradient; dim <= 256. */
+ * nlsg_de_create_custom) minimised with the default finite-difference gradient; 1 <= dim <= 1024. */
 int nlsg_bfgs_create_custom(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
                             nlsg_bfgs **out);
+/* A custom objective with run-time parameters (obj->n_params >= 1), one row per problem. Every check
+ * of nlsg_bfgs_create_custom in its order, then, still before the device is touched: n_params < 1 is
+ * NLSG_ERR_INVALID_ARG (zero is nlsg_bfgs_create_custom's), above NLSG_CUSTOM_MAX_PARAMS
+ * NLSG_ERR_UNSUPPORTED, and nlsg_bfgs_lds_bytes(dim, flags) + 4 * nlsg_custom_params_lds_bytes(n_params)
+ * above 163840 NLSG_ERR_UNSUPPORTED: the search kernel runs four problems per workgroup, a wave and a
+ * row each. 4096 parameters fit everywhere but in reference order at dim > 512, where 3072 do. */
+int nlsg_bfgs_create_params(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
+                            nlsg_bfgs **out);
+/* params_host [batch][n_params]: problem b's objective reads row b as p(k). Copied on the engine's
+ * stream before the call returns; the rows hold from the next launch on and are replaced without
+ * recompiling. NLSG_ERR_INVALID_ARG on an engine of another creator. Until the first call,
+ * nlsg_bfgs_init, _step, _minimize and _time_steps answer NLSG_ERR_STATE. */
+int nlsg_bfgs_set_params(nlsg_bfgs *e, const double *params_host);
+/* Dynamic LDS bytes of a search / init launch before any parameter rows: the four waves' buffers with
+ * NLSG_BFGS_REFERENCE_ORDER, none without. 0 also outside 1 <= dim <= 1024, for unknown flags and for a
+ * combination of flags the engine rejects. Host only, no device. */
+uint64_t nlsg_bfgs_lds_bytes(uint64_t dim, uint32_t flags);
 int nlsg_bfgs_destroy(nlsg_bfgs *e);
 /* x0_host: batch*dim start points (row-major). H = I, g = grad(x0) (3212, 3234). */
 int nlsg_bfgs_init(nlsg_bfgs *e, const double *x0_host);
@@ -456,6 +475,22 @@ int nlsg_lm_create(const nlsg_lm_config *cfg, nlsg_lm **out);
 /* cfg->objective == NLSG_OBJ_CUSTOM, as nlsg_de_create_custom: LevenbergMarquardt with the
  * default functors on a user objective compiled at run time */
 int nlsg_lm_create_custom(const nlsg_lm_config *cfg, const nlsg_custom_objective *obj, nlsg_lm **out);
+/* A custom objective with run-time parameters (obj->n_params >= 1), one row per problem ("one fit per
+ * series"). Every check of nlsg_lm_create_custom in its order, then, still before the device is touched:
+ * n_params < 1 is NLSG_ERR_INVALID_ARG (zero is nlsg_lm_create_custom's), above NLSG_CUSTOM_MAX_PARAMS
+ * NLSG_ERR_UNSUPPORTED, and nlsg_lm_lds_bytes(n, solver) + nlsg_custom_params_lds_bytes(n_params) above
+ * 163840 NLSG_ERR_UNSUPPORTED (no shape the engine takes reaches it: the check states the rule). */
+int nlsg_lm_create_params(const nlsg_lm_config *cfg, const nlsg_custom_objective *obj, nlsg_lm **out);
+/* params_host [batch][n_params]: problem b's objective reads row b as p(k). Copied on the engine's
+ * stream before the call returns; the rows hold from the next launch on and are replaced without
+ * recompiling. NLSG_ERR_INVALID_ARG on an engine of another creator. Until the first call,
+ * nlsg_lm_minimize, _time_solve, _time_eval_kernel and _time_qr_kernel answer NLSG_ERR_STATE. */
+int nlsg_lm_set_params(nlsg_lm *e, const double *params_host);
+/* Dynamic LDS bytes of the launch that evaluates an objective of n parameters through the default
+ * finite-difference functors (what a custom objective runs), solver = NLSG_LM_CHOLESKY or
+ * NLSG_LM_CHOLESKY_REFERENCE_ORDER. 0 outside 1 <= n <= 1024 and for any other solver — and in tree
+ * order past 64 parameters, whose evaluation kernel takes none. Host only, no device. */
+uint64_t nlsg_lm_lds_bytes(uint64_t n, int32_t solver);
 int nlsg_lm_destroy(nlsg_lm *e);
 /* design matrices A [batch][m][n] row-major and targets y [batch][m] (copied to HBM, in chunks
  * that overlap their repacking on the device). From page-locked memory (nlsg_host_alloc) the

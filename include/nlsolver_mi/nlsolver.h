@@ -222,9 +222,9 @@ struct Custom {
   // Run-time data the functor owns (the reference's "a callable that owns its data"): the bodies
   // read params[k] as p(k) (nlsg_custom_objective.n_params). Non-empty: DE and PSO solve through
   // the resident batch engine, whatever the driver mode (device_error when the shape does not fit
-  // its LDS or the library predates parameters); NelderMead and NelderMeadPSO create their engine
-  // with nlsg_nm_create_params / nlsg_nmpso_create_params and show the one row to every start; every
-  // other solver (and these two on a library that predates those entry points) answers the library's
+  // its LDS or the library predates parameters); NelderMead, NelderMeadPSO, BFGS and LevenbergMarquardt
+  // create their engine with nlsg_nm / nmpso / bfgs / lm_create_params and show the one row to every
+  // start; every other solver (and these four on a library that predates those entry points) answers the library's
   // "unsupported" error. At most NLSG_CUSTOM_MAX_PARAMS. (A batch of solves with a row each, and
   // rows replaced without recompiling, is the C-ABI: nlsg_*_batch_set_params.)
   //   Custom<double> f("double r = xi - p(0); return p(1) * r * r;");
@@ -384,6 +384,11 @@ class api {
   decltype(&nlsg_nm_set_params) nm_set_params = nullptr;
   decltype(&nlsg_nmpso_create_params) nmpso_create_params = nullptr;
   decltype(&nlsg_nmpso_set_params) nmpso_set_params = nullptr;
+  // optional: null when the library predates parameters for BFGS and Levenberg-Marquardt
+  decltype(&nlsg_bfgs_create_params) bfgs_create_params = nullptr;
+  decltype(&nlsg_bfgs_set_params) bfgs_set_params = nullptr;
+  decltype(&nlsg_lm_create_params) lm_create_params = nullptr;
+  decltype(&nlsg_lm_set_params) lm_set_params = nullptr;
   // the resident engine's LDS need with the parameter row; throws when the library cannot take
   // parameters or the shape does not fit (`shape_need` = nlsg_*_batch_lds_bytes, 0 = out of range)
   void require_params_fit(bool has_engine, bool has_set, uint64_t shape_need, int32_t n_params,
@@ -463,6 +468,10 @@ class api {
     bind_optional(h, "nlsg_nm_set_params", nm_set_params);
     bind_optional(h, "nlsg_nmpso_create_params", nmpso_create_params);
     bind_optional(h, "nlsg_nmpso_set_params", nmpso_set_params);
+    bind_optional(h, "nlsg_bfgs_create_params", bfgs_create_params);
+    bind_optional(h, "nlsg_bfgs_set_params", bfgs_set_params);
+    bind_optional(h, "nlsg_lm_create_params", lm_create_params);
+    bind_optional(h, "nlsg_lm_set_params", lm_set_params);
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
   }
@@ -1409,7 +1418,19 @@ class BFGS {
         api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
         nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
                                   device::custom_n_params(f)};
-        api.check(api.bfgs_create_custom(&cfg, &obj, &eng));
+        if (!f.params.empty() && api.bfgs_create_params && api.bfgs_set_params) {
+          api.check(api.bfgs_create_params(&cfg, &obj, &eng));
+          std::vector<double> rows;  // the functor's one row, shown to every start
+          for (size_t b = 0; b < B; b++) rows.insert(rows.end(), f.params.begin(), f.params.end());
+          const int prc = api.bfgs_set_params(eng, rows.data());
+          if (prc) {
+            const std::string pmsg = api.last_error();
+            api.bfgs_destroy(eng);
+            throw device_error("nlsg error " + std::to_string(prc) + ": " + pmsg);
+          }
+        } else {  // (with parameters and a library that predates them: its "unsupported" error)
+          api.check(api.bfgs_create_custom(&cfg, &obj, &eng));
+        }
       } else {
         api.check(api.bfgs_create(&cfg, nullptr, nullptr, &eng));
       }
@@ -2270,7 +2291,19 @@ class LevenbergMarquardt {
         api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
         nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
                                   device::custom_n_params(f)};
-        api.check(api.lm_create_custom(&cfg, &obj, &eng));
+        if (!f.params.empty() && api.lm_create_params && api.lm_set_params) {
+          api.check(api.lm_create_params(&cfg, &obj, &eng));
+          std::vector<double> rows;  // the functor's one row, shown to every start
+          for (size_t b = 0; b < B; b++) rows.insert(rows.end(), f.params.begin(), f.params.end());
+          const int prc = api.lm_set_params(eng, rows.data());
+          if (prc) {
+            const std::string pmsg = api.last_error();
+            api.lm_destroy(eng);
+            throw device_error("nlsg error " + std::to_string(prc) + ": " + pmsg);
+          }
+        } else {  // (with parameters and a library that predates them: its "unsupported" error)
+          api.check(api.lm_create_custom(&cfg, &obj, &eng));
+        }
         made = true;
       }
     }

@@ -287,6 +287,12 @@ OPTIONAL_SYMBOLS = {
                                            C.POINTER(_H)]),
     "nlsg_nmpso_set_params": (C.c_int, [_H, pd]),
     "nlsg_nmpso_lds_bytes": (u64, [u64]),
+    "nlsg_lm_create_params": (C.c_int, [C.POINTER(LMConfig), C.POINTER(CustomObjectiveC), C.POINTER(_H)]),
+    "nlsg_lm_set_params": (C.c_int, [_H, pd]),
+    "nlsg_lm_lds_bytes": (u64, [u64, C.c_int32]),
+    "nlsg_bfgs_create_params": (C.c_int, [C.POINTER(BFGSConfig), C.POINTER(CustomObjectiveC), C.POINTER(_H)]),
+    "nlsg_bfgs_set_params": (C.c_int, [_H, pd]),
+    "nlsg_bfgs_lds_bytes": (u64, [u64, C.c_uint32]),
 }
 SYMBOLS.update(OPTIONAL_SYMBOLS)
 _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
@@ -299,6 +305,12 @@ _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
                     "nlsg_nmpso_create_params": "library has no run-time objective parameters for the hybrid",
                     "nlsg_nmpso_set_params": "library has no run-time objective parameters for the hybrid",
                     "nlsg_nmpso_lds_bytes": "library has no run-time objective parameters for the hybrid",
+                    "nlsg_lm_create_params": "library has no run-time objective parameters for Levenberg-Marquardt",
+                    "nlsg_lm_set_params": "library has no run-time objective parameters for Levenberg-Marquardt",
+                    "nlsg_lm_lds_bytes": "library has no run-time objective parameters for Levenberg-Marquardt",
+                    "nlsg_bfgs_create_params": "library has no run-time objective parameters for BFGS",
+                    "nlsg_bfgs_set_params": "library has no run-time objective parameters for BFGS",
+                    "nlsg_bfgs_lds_bytes": "library has no run-time objective parameters for BFGS",
                     "nlsg_de_batch_": "library has no resident batch DE",
                     "nlsg_pso_batch_": "library has no resident batch PSO"}
 

@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import BFGSConfig, Status, check, lib
+from ._capi import BFGSConfig, NlsgError, Status, check, lib, require
 
 
 class QuadDiagRank1:
@@ -40,7 +40,28 @@ class BFGSEngine:
     reference_order=True: every sum in index order, as the reference's sequential loops take it
     (NLSG_BFGS_REFERENCE_ORDER): the reference's own runs bit for bit, default gradient included —
     with the default gradient also the faster kernels (a probe per lane); with a gradient functor
-    1.5 x the tree kernels' time at dim = 1024."""
+    1.5 x the tree kernels' time at dim = 1024.
+
+    A CustomObjective with n_params > 0 (nlsg_bfgs_create_params): problem b minimises the objective
+    under row b of set_params(rows) ([batch, n_params], read as p(k)); rows are replaced without
+    recompiling. The search kernel runs four problems per workgroup, a wave each, so four rows share
+    the workgroup's LDS: fits() says whether a shape has room."""
+
+    @staticmethod
+    def lds_bytes(dim, reference_order=False, n_params=0):
+        """LDS bytes of a search / init launch: the reference-order buffers of its four waves (none in
+        tree order) and four rows of n_params objective parameters (host only)"""
+        need = int(require("nlsg_bfgs_lds_bytes")(dim, _capi.BFGS_REFERENCE_ORDER if reference_order else 0))
+        return need + (4 * int(require("nlsg_custom_params_lds_bytes")(n_params)) if n_params else 0)
+
+    @staticmethod
+    def fits(dim, reference_order=False, n_params=0):
+        """whether nlsg_bfgs_create_params takes the shape: 1 <= dim <= 1024, 0 <= n_params <= 4096
+        and lds_bytes within the workgroup's 160 KiB"""
+        from .de import LDS_BUDGET
+        if not (1 <= dim <= 1024 and 0 <= n_params <= _capi.CUSTOM_MAX_PARAMS):
+            return False
+        return BFGSEngine.lds_bytes(dim, reference_order, n_params) <= LDS_BUDGET
 
     def __init__(self, objective, batch, *, dim=None, max_iter=100, grad_eps=5e-3, alpha=1.0,
                  device=0, stream=None, symmetric=False, reference_order=False):
@@ -54,16 +75,22 @@ class BFGSEngine:
         cfg.batch = batch
         cfg.max_iter, cfg.grad_eps, cfg.alpha = max_iter, grad_eps, alpha
         self._h = C.c_void_p()
+        self.n_params = 0
         from .de import CustomObjective, rtc_library_path
         if isinstance(objective, CustomObjective):  # user objective + finite-difference gradient
             if dim is None:
                 raise TypeError("a custom objective needs dim=")
             cfg.objective, cfg.dim, cfg.quad_c = _capi.OBJ_CUSTOM, dim, 0.0
             self.cfg = cfg
+            self.n_params = objective.n_params
+            create = lib().nlsg_bfgs_create_custom
+            if self.n_params:  # (zero stays with the creator it always had)
+                create = require("nlsg_bfgs_create_params")
+                require("nlsg_bfgs_set_params")
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(objective.term_body.encode(), objective.finish_body.encode(),
-                                         int(objective.chain), objective.n_params)
-            check(lib().nlsg_bfgs_create_custom(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+                                         int(objective.chain), self.n_params)
+            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
             return
         if isinstance(objective, str):  # built-in objective + finite-difference gradient
             if dim is None:
@@ -95,6 +122,15 @@ class BFGSEngine:
         x = np.ascontiguousarray(x, dtype=np.float64)
         assert x.shape == (self.cfg.batch, self.cfg.dim)
         return x
+
+    def set_params(self, params):
+        """params [batch, n_params]: problem b's objective reads row b as p(k). The rows hold from the
+        next launch on and can be replaced at any time without recompiling."""
+        if self.n_params == 0:
+            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
+        from .de import _params_rows
+        rows = _params_rows(params, self.cfg.batch, self.n_params)
+        check(require("nlsg_bfgs_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
 
     def init(self, x0):
         check(lib().nlsg_bfgs_init(self._h, self._x(x0).ctypes.data_as(_capi.pd)))
@@ -129,7 +165,10 @@ class BFGSEngine:
                                              H.ctypes.data_as(_capi.pd) if hessian else None))
         return g, H
 
-    def minimize(self, x):
+    def minimize(self, x, params=None):
+        """params: set_params(params) first."""
+        if params is not None:
+            self.set_params(params)
         x = self._x(x)
         st = (Status * self.cfg.batch)()
         check(lib().nlsg_bfgs_minimize(self._h, x.ctypes.data_as(_capi.pd), st))
@@ -156,10 +195,19 @@ class BFGS:
     order wherever the reference's arithmetic exists on the device — the quadratic, the default
     gradient on Rosenbrock / Sphere / Styblinski-Tang or a custom objective given by its terms; literal
     update — i.e. the reference's runs bit for bit. With the default gradient those are also the
-    faster kernels; the quadratic pays 1.18 x on large batches. True / False force it."""
+    faster kernels; the quadratic pays 1.18 x on large batches. True / False force it.
+
+    params: the run-time parameters of a CustomObjective with n_params > 0: one row (n_params,) shown
+    to every start, or (batch, n_params) with a 2-D x, a row per start."""
 
     def __init__(self, f, g=None, max_iter=100, grad_eps=5e-3, alpha=1.0, *, device=0,
-                 symmetric=False, reference_order=None):
+                 symmetric=False, reference_order=None, params=None):
+        from .nm import _drop_in_rows
+        self.n_params = getattr(f, "n_params", 0)
+        if (params is not None) != bool(self.n_params):
+            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
+                             "objective needs it")
+        self.params = None if params is None else _drop_in_rows(params, self.n_params)
         if g is not None:
             raise TypeError("device objectives carry their analytic gradient or use the default "
                             "finite-difference one; pass g=None")
@@ -180,8 +228,10 @@ class BFGS:
                 (isinstance(self.f, CustomObjective) and self.f.chain != 2)  # (terms: index order is the body's own loop)
             quad = isinstance(self.f, QuadDiagRank1)
             args["reference_order"] = (fd or quad) and not args["symmetric"]
+        from .nm import _rows_for_batch
+        rows = _rows_for_batch(self.params, xb.shape[0])
         with BFGSEngine(self.f, xb.shape[0], **extra, **args) as eng:
-            out, st = eng.minimize(xb)
+            out, st = eng.minimize(xb, params=rows)
         xb[...] = out
         return st[0] if x.ndim == 1 else st
 

@@ -21,6 +21,11 @@ struct nlsg_bfgs {
   uint32_t bpp = 0;  // blocks per problem in the H-streaming kernels
   bool symmetric = false;  // NLSG_BFGS_SYMMETRIC: upper blocks of H only
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
+  int32_t n_params = 0;          // nlsg_bfgs_create_params: the objective's run-time doubles per problem
+  double *params_dev = nullptr;  // [batch][n_params]
+  bool params_set = false;
+  unsigned fd_lds = 0;  // dynamic LDS of the module's search / init launches: the reference-order buffers,
+                        // and behind them a parameter row per wave
 };
 
 namespace {
@@ -86,8 +91,7 @@ void launch_iteration(nlsg_bfgs *e, bool timed) {
   const unsigned row_grid = static_cast<unsigned>(e->p.batch * e->bpp);
   if (e->p.model == NLSG_OBJ_CUSTOM) {
     void *args[] = {&e->p};
-    launch_module_kernel(e->rtc.search, wave_grid, 256,
-                         e->p.seq ? static_cast<unsigned>(bfgs_fd_seq_lds_bytes(e->chunks)) : 0u, e->stream, args);
+    launch_module_kernel(e->rtc.search, wave_grid, 256, e->fd_lds, e->stream, args);
   } else {
     BFGS_DISPATCH_MODEL(bfgs_search_kernel, wave_grid, e->p);
   }
@@ -120,12 +124,21 @@ void launch_iteration(nlsg_bfgs *e, bool timed) {
   if (timed) hipEventRecord(e->ev3, e->stream);
 }
 
+// a parametrised engine launches no evaluation before its first rows
+int params_ready(const nlsg_bfgs *e) {
+  if (e->n_params > 0 && !e->params_set)
+    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_bfgs_set_params first", e->n_params);
+  return NLSG_OK;
+}
+
+constexpr int bfgs_chunks(uint64_t n) { return n <= 128 ? 1 : n <= 256 ? 2 : n <= 512 ? 4 : 8; }
+
 }  // namespace
 
 extern "C" {
 
 static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const double *lin_host,
-                       const nlsg_custom_objective *custom, nlsg_bfgs **out);
+                       const nlsg_custom_objective *custom, nlsg_bfgs **out, bool with_params = false);
 
 int nlsg_bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const double *lin_host,
                      nlsg_bfgs **out) {
@@ -149,8 +162,40 @@ int nlsg_bfgs_create_custom(const nlsg_bfgs_config *cfg, const nlsg_custom_objec
   return rc;
 }
 
+int nlsg_bfgs_create_params(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
+                            nlsg_bfgs **out) {
+  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (cfg->objective != NLSG_OBJ_CUSTOM)
+    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  PhaseClock clk;
+  const int rc = bfgs_create(cfg, nullptr, nullptr, obj, out, true);
+  call_timing().create_ms = clk.lap();
+  return rc;
+}
+
+// The dynamic LDS of a search / init launch without parameter rows: the four waves' reference-order
+// buffers, or nothing. 0 also outside 1 <= dim <= 1024, for unknown flags and for reference order with
+// the symmetric restatement (which the engine rejects).
+uint64_t nlsg_bfgs_lds_bytes(uint64_t dim, uint32_t flags) {
+  if (dim < 1 || dim > 1024 || (flags & ~(NLSG_BFGS_SYMMETRIC | NLSG_BFGS_REFERENCE_ORDER))) return 0;
+  if (!(flags & NLSG_BFGS_REFERENCE_ORDER) || (flags & NLSG_BFGS_SYMMETRIC)) return 0;
+  return bfgs_fd_seq_lds_bytes(bfgs_chunks(dim));
+}
+
+int nlsg_bfgs_set_params(nlsg_bfgs *e, const double *params_host) {
+  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (e->n_params <= 0)
+    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_bfgs_create_params)");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
+                          hipMemcpyHostToDevice, e->stream));
+  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
+  e->params_set = true;
+  return NLSG_OK;
+}
+
 static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const double *lin_host,
-                       const nlsg_custom_objective *custom, nlsg_bfgs **out) {
+                       const nlsg_custom_objective *custom, nlsg_bfgs **out, bool with_params) {
   if (!cfg || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(nlsg_bfgs_config))
@@ -182,6 +227,10 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
     return fail(NLSG_ERR_UNSUPPORTED,
                 "NLSG_BFGS_REFERENCE_ORDER: Rastrigin's cosine is the device's deterministic one, not "
                 "libm's — there is no reference arithmetic to reproduce");
+  if (with_params)  // (a row per wave, four to the block, behind the reference-order buffers)
+    if (const int prc = check_custom_params(custom, nlsg_bfgs_lds_bytes(cfg->dim, cfg->flags), "nlsg_bfgs",
+                                            "nlsg_bfgs_create_custom", 4))
+      return prc;
   int rc = check_device(cfg->device);
   if (rc) return rc;
   NLSG_HIP(hipSetDevice(cfg->device));
@@ -189,7 +238,12 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
   e->cfg = *cfg;
   const uint64_t n = cfg->dim, B = cfg->batch;
-  e->chunks = n <= 128 ? 1 : n <= 256 ? 2 : n <= 512 ? 4 : 8;
+  e->chunks = bfgs_chunks(n);
+  e->n_params = with_params ? custom->n_params : 0;
+  // the launch's dynamic block: the reference-order buffers, then the rows — ONE layout, from which both the
+  // launch size and the offset the kernels are compiled with (NLSG_PARAMS_PER_WAVE) are taken
+  const size_t rows_at = seq ? bfgs_fd_seq_lds_bytes(e->chunks) : 0;
+  e->fd_lds = static_cast<unsigned>(rows_at + 4 * custom_params_lds_bytes(e->n_params));
   e->vec = n % 2 == 0;
   e->bpp = static_cast<uint32_t>((n + 4 * kBfgsRowsPerWave - 1) / (4 * kBfgsRowsPerWave));
   e->symmetric = (cfg->flags & NLSG_BFGS_SYMMETRIC) != 0;
@@ -233,6 +287,8 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->zero_dev), 16);
   if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
   if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->count_dev), 8);
+  if (he == hipSuccess && e->n_params)
+    he = alloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * sizeof(double));
   if (he == hipSuccess)
     he = quad ? hipMemcpy(e->qd_dev, diag_host, n * sizeof(double), hipMemcpyHostToDevice)
               : hipMemset(e->qd_dev, 0, n * sizeof(double));
@@ -251,6 +307,7 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   p.qd = e->qd_dev;
   p.qb = e->qb_dev;
   p.zero = e->zero_dev;
+  p.params = e->params_dev;
   p.batch = B;
   p.n = n;
   p.max_iter = cfg->max_iter;
@@ -262,10 +319,23 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   p.nb = nb;
   p.nstored = nstored;
   if (custom) {
-    const int rc2 = rtc_build_bfgs(custom, e->chunks, e->vec, &e->rtc);
+    const int rc2 = rtc_build_bfgs(custom, e->chunks, e->vec, static_cast<long>(rows_at / sizeof(double)), &e->rtc);
     if (rc2) {
       nlsg_bfgs_destroy(e);
       return rc2;
+    }
+    // the module API's counterpart of hipFuncSetAttribute on a kernel symbol: four rows of parameters go
+    // past the 64 KiB a launch may take without it
+    if (e->fd_lds > 64 * 1024) {
+      he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.search),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->fd_lds));
+      if (he == hipSuccess)
+        he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.init),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->fd_lds));
+      if (he != hipSuccess) {
+        nlsg_bfgs_destroy(e);
+        return fail(NLSG_ERR_HIP, "raising the kernels' dynamic LDS limit failed: %s", hipGetErrorString(he));
+      }
     }
   }
   *out = e;
@@ -292,6 +362,7 @@ int nlsg_bfgs_destroy(nlsg_bfgs *e) {
   pool_free(e->qb_dev);
   pool_free(e->zero_dev);
   pool_free(e->count_dev);
+  pool_free(e->params_dev);
   for (hipEvent_t ev : {e->ev0, e->ev1, e->ev2, e->ev3})
     if (ev) hipEventDestroy(ev);
   if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
@@ -302,14 +373,15 @@ int nlsg_bfgs_destroy(nlsg_bfgs *e) {
 
 int nlsg_bfgs_init(nlsg_bfgs *e, const double *x0_host) {
   if (!e || !x0_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   NLSG_HIP(hipMemcpyAsync(e->p.x, x0_host, e->p.batch * e->p.n * sizeof(double),
                           hipMemcpyHostToDevice, e->stream));
   NLSG_HIP(hipStreamSynchronize(e->stream));
   if (e->p.model == NLSG_OBJ_CUSTOM) {
     void *args[] = {&e->p};
-    launch_module_kernel(e->rtc.init, static_cast<unsigned>((e->p.batch + 3) / 4), 256,
-                         e->p.seq ? static_cast<unsigned>(bfgs_fd_seq_lds_bytes(e->chunks)) : 0u, e->stream, args);
+    launch_module_kernel(e->rtc.init, static_cast<unsigned>((e->p.batch + 3) / 4), 256, e->fd_lds, e->stream,
+                         args);
   } else {
     BFGS_DISPATCH_MODEL(bfgs_init_kernel, static_cast<unsigned>((e->p.batch + 3) / 4), e->p);
   }
@@ -320,6 +392,7 @@ int nlsg_bfgs_init(nlsg_bfgs *e, const double *x0_host) {
 
 int nlsg_bfgs_step(nlsg_bfgs *e, uint64_t iters) {
   if (!e) return fail(NLSG_ERR_INVALID_ARG, "null engine");
+  if (const int prc = params_ready(e)) return prc;
   if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_bfgs_init has not been called");
   NLSG_HIP(hipSetDevice(e->cfg.device));
   for (uint64_t k = 0; k < iters; k++) launch_iteration(e, false);
@@ -414,6 +487,7 @@ int nlsg_bfgs_download_state(nlsg_bfgs *e, double *g_host, double *h_host) {
 
 int nlsg_bfgs_minimize(nlsg_bfgs *e, double *x_inout_host, nlsg_status *status_host) {
   if (!e || !x_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   PhaseClock clk;
   int rc = nlsg_bfgs_init(e, x_inout_host);
   if (rc) return rc;
@@ -438,6 +512,7 @@ int nlsg_bfgs_minimize(nlsg_bfgs *e, double *x_inout_host, nlsg_status *status_h
 
 int nlsg_bfgs_time_steps(nlsg_bfgs *e, uint64_t iters, float *ms_total, float *ms_hessian) {
   if (!e || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_bfgs_init has not been called");
   NLSG_HIP(hipSetDevice(e->cfg.device));
   float hess = 0.f;

@@ -46,6 +46,8 @@ struct BfgsParams {
   double *Hs;    // [batch][nstored][128][128]
   double *part;  // [batch][nb][nb][128]
   uint32_t nb, nstored;
+  const double *params;  // [batch][n_params] (nlsg_bfgs_create_params): the search and init kernels stage
+                         // row b into the LDS slice of the wave that owns problem b; else nullptr
 };
 
 // ---- wave-level vector helpers (vectors replicated in every lane layout) --------
@@ -174,7 +176,9 @@ __device__ inline void quad_g(const double (&x)[CHUNKS][2], const double (&d)[CH
 constexpr int kBfgsQuad = -1;
 
 // LDS of the search / init kernels: only the reference-order finite-difference gradient uses any — per
-// wave the point and its objective terms, 2 x 128 CHUNKS doubles (the launch passes 0 bytes otherwise)
+// wave the point and its objective terms, 2 x 128 CHUNKS doubles (the launch passes 0 bytes otherwise).
+// A user objective with run-time parameters (nlsg_bfgs_create_params) adds, behind these buffers, a
+// row per wave: four rows of nlsg_custom_params_lds_bytes(n_params) (nlsg_common.h NLSG_PARAMS_PER_WAVE).
 __host__ __device__ constexpr size_t bfgs_fd_seq_lds_bytes(int chunks) {
   return 4 * 2 * 128 * static_cast<size_t>(chunks) * sizeof(double);  // (serial_sum_lds reads ahead inside it)
 }
@@ -513,6 +517,8 @@ bfgs_search_kernel(BfgsParams p) {
   double x[CHUNKS][2], g[CHUNKS][2], dir[CHUNKS][2];
   BfgsModel<MODEL, CHUNKS> model;
   model.template load<VEC>(p);
+  stage_custom_params_wave(p.params, pid);  // (a user objective's row, into this wave's slice: the waves
+                                            // that returned above are gone, so no block barrier)
   load_vec<CHUNKS, VEC>(p.x + pid * n, n, p.zero, x);
   load_vec<CHUNKS, VEC>(p.g + pid * n, n, p.zero, g);
   load_vec<CHUNKS, VEC>(p.dir + pid * n, n, p.zero, dir);
@@ -668,6 +674,7 @@ __global__ __launch_bounds__(256) void bfgs_init_kernel(BfgsParams p) {
   double x[CHUNKS][2], g[CHUNKS][2];
   BfgsModel<MODEL, CHUNKS> model;
   model.template load<VEC>(p);
+  stage_custom_params_wave(p.params, pid);  // (as in bfgs_search_kernel)
   load_vec<CHUNKS, VEC>(p.x + pid * n, n, p.zero, x);
   uint64_t fcalls = 0, gcalls = 0;
   model.grad(x, g, fcalls, gcalls);

@@ -342,15 +342,31 @@ struct Objective<NLSG_OBJ_RASTRIGIN> {
 
 // ---------------------------------------------------------------------------
 // run-time parameters of a user objective (nlsg_custom_objective.n_params > 0; the engines whose
-// kernel owns a workgroup per solve: resident batch DE / PSO, Nelder-Mead and the NM/PSO hybrid
-// made by their *_create_params). rtc_compile defines NLSG_N_PARAMS ahead of the kernel header, so the
+// kernel owns a workgroup per solve: resident batch DE / PSO, Nelder-Mead, the NM/PSO hybrid and
+// Levenberg-Marquardt made by their *_create_params — and BFGS, whose kernels own a WAVE per solve,
+// below). rtc_compile defines NLSG_N_PARAMS ahead of the kernel header, so the
 // block below exists in that translation unit alone: static LDS in front of the kernels' dynamic block, one
 // solve's row, staged once per launch by the workgroup and read by Objective<NLSG_OBJ_CUSTOM>::p(k)
 // with ds_read. Rounded to an even count: 16-byte size, so the dynamic block behind it keeps the
 // 16-byte alignment the PSO kernel's double2 accesses need. Without the macro nothing is emitted
 // and stage_custom_params is empty: the built-in kernels are what they were.
+//
+// NLSG_PARAMS_PER_WAVE (beside NLSG_N_PARAMS; rtc_build_bfgs): the kernels run one wave per solve,
+// four solves per 256-thread block, and a wave leaves early when its solve is done — one row per
+// block cannot serve them. Each wave has a row of its own in the DYNAMIC block (four rows of 4096
+// doubles are past the 64 KiB of static LDS): the macro's value is the rows' offset in doubles
+// from the start of the dynamic block (behind the reference-order xs | ts buffers, a multiple of
+// two), wave w's row follows w rows of kCustomParamsRow doubles. The wave stages its row itself
+// and publishes it with a wavefront fence and wave_barrier: no block barrier anywhere.
 // ---------------------------------------------------------------------------
-#ifdef NLSG_N_PARAMS
+#if defined(NLSG_N_PARAMS) && defined(NLSG_PARAMS_PER_WAVE)
+constexpr uint32_t kCustomParamsRow = (static_cast<uint32_t>(NLSG_N_PARAMS) + 1) & ~1u;
+constexpr size_t kCustomParamsLdsBytes = 0;  // (no static row)
+extern __shared__ __align__(16) double custom_params_dyn[];  // the kernel's dynamic block
+__device__ inline double *custom_params_wave_row() {
+  return custom_params_dyn + static_cast<uint32_t>(NLSG_PARAMS_PER_WAVE) + (threadIdx.x >> 6) * kCustomParamsRow;
+}
+#elif defined(NLSG_N_PARAMS)
 __shared__ __attribute__((aligned(16))) double custom_params_lds[(NLSG_N_PARAMS + 1) & ~1];
 constexpr size_t kCustomParamsLdsBytes = 8 * ((static_cast<size_t>(NLSG_N_PARAMS) + 1) & ~size_t(1));
 #else
@@ -359,7 +375,7 @@ constexpr size_t kCustomParamsLdsBytes = 0;  // what a kernel that sizes its own
 // Called by all threads of the block, uniformly. `params` is [batch][n_params]; the caller's next
 // barrier (or `sync`) publishes the row.
 __device__ inline void stage_custom_params(const double *params, uint64_t b, bool sync) {
-#ifdef NLSG_N_PARAMS
+#if defined(NLSG_N_PARAMS) && !defined(NLSG_PARAMS_PER_WAVE)
   const double *__restrict__ row = params + b * static_cast<uint64_t>(NLSG_N_PARAMS);
   for (uint32_t i = threadIdx.x; i < static_cast<uint32_t>(NLSG_N_PARAMS); i += blockDim.x)
     custom_params_lds[i] = row[i];
@@ -368,6 +384,29 @@ __device__ inline void stage_custom_params(const double *params, uint64_t b, boo
   (void)params;
   (void)b;
   (void)sync;
+#endif
+}
+// A block that is ONE wave (lm_fd_iter_kernel): stage, then publish with the wave's own fence — no
+// block barrier. Empty without the macro.
+__device__ inline void stage_custom_params_one_wave(const double *params, uint64_t b) {
+  stage_custom_params(params, b, false);
+#if defined(NLSG_N_PARAMS) && !defined(NLSG_PARAMS_PER_WAVE)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#endif
+}
+// One wave per solve (NLSG_PARAMS_PER_WAVE): called by the 64 lanes of the wave that owns solve b,
+// after the wave's early returns; the row is published to the wave when the call returns.
+__device__ inline void stage_custom_params_wave(const double *params, uint64_t b) {
+#if defined(NLSG_N_PARAMS) && defined(NLSG_PARAMS_PER_WAVE)
+  const double *__restrict__ row = params + b * static_cast<uint64_t>(NLSG_N_PARAMS);
+  double *dst = custom_params_wave_row();
+  for (uint32_t i = threadIdx.x & 63u; i < static_cast<uint32_t>(NLSG_N_PARAMS); i += 64) dst[i] = row[i];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#else
+  (void)params;
+  (void)b;
 #endif
 }
 
@@ -386,10 +425,11 @@ inline int reject_custom_params(const nlsg_custom_objective *obj) {
                 obj->n_params);
   return NLSG_OK;
 }
-// nlsg_nm_create_params / nlsg_nmpso_create_params, after their shape checks and before the device:
-// the count (zero is `old_creator`'s), then the workgroup's LDS with the row in front of `shape_lds`
+// nlsg_nm_create_params / nlsg_nmpso_create_params / nlsg_lm_create_params / nlsg_bfgs_create_params,
+// after their shape checks and before the device: the count (zero is `old_creator`'s), then the
+// workgroup's LDS with its `rows` rows (BFGS: one per wave, four) next to `shape_lds`
 inline int check_custom_params(const nlsg_custom_objective *obj, uint64_t shape_lds, const char *what,
-                               const char *old_creator) {
+                               const char *old_creator, uint64_t rows = 1) {
   const int32_t n_params = obj->n_params;
   if (n_params < 1)
     return fail(NLSG_ERR_INVALID_ARG, "n_params = %d: %s_create_params takes 1 .. %d parameters; an objective "
@@ -397,11 +437,11 @@ inline int check_custom_params(const nlsg_custom_objective *obj, uint64_t shape_
   if (n_params > NLSG_CUSTOM_MAX_PARAMS)
     return fail(NLSG_ERR_UNSUPPORTED, "a custom objective takes at most %d parameters, not %d",
                 NLSG_CUSTOM_MAX_PARAMS, n_params);
-  const uint64_t params_lds = custom_params_lds_bytes(n_params);
+  const uint64_t params_lds = rows * custom_params_lds_bytes(n_params);
   if (shape_lds + params_lds > 160ull * 1024)
-    return fail(NLSG_ERR_UNSUPPORTED, "%s: this shape needs %llu bytes of LDS and %d parameters %llu more, a "
-                "workgroup has %llu", what, (unsigned long long)shape_lds, n_params,
-                (unsigned long long)params_lds, 160ull * 1024);
+    return fail(NLSG_ERR_UNSUPPORTED, "%s: this shape needs %llu bytes of LDS and %llu row%s of %d parameters "
+                "%llu more, a workgroup has %llu", what, (unsigned long long)shape_lds, (unsigned long long)rows,
+                rows == 1 ? "" : "s", n_params, (unsigned long long)params_lds, 160ull * 1024);
   return NLSG_OK;
 }
 #endif

@@ -27,6 +27,9 @@ struct nlsg_lm {
   uint64_t ldt = kLmN; // row stride of theta / gg on the device: 64, or n when wide
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   LmRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it
+  int32_t n_params = 0;          // nlsg_lm_create_params: the objective's run-time doubles per problem
+  double *params_dev = nullptr;  // [batch][n_params]
+  bool params_set = false;
 };
 
 namespace {
@@ -54,11 +57,25 @@ bool lm_fd_objective(int objective) {
          objective == NLSG_OBJ_CUSTOM;
 }
 
+// dynamic LDS of the launch that evaluates an objective of n parameters (lm_fd_iter_kernel up to 64,
+// the wide kernels beyond: none in tree order)
+// (+ 66: the point and a zero behind it, for the reference-order evaluation's lanes)
+size_t lm_fd_launch_lds_bytes(uint64_t n, bool ref_order) {
+  if (n <= kLmN) return (64 * static_cast<size_t>(lm_fd_chunks(n)) + 128 + 66) * sizeof(double);
+  return ref_order ? lm_wide_fd_lanes_lds_bytes(n) : 0;
+}
+
+// a parametrised engine solves nothing before its first rows
+int params_ready(const nlsg_lm *e) {
+  if (e->n_params > 0 && !e->params_set)
+    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_lm_set_params first", e->n_params);
+  return NLSG_OK;
+}
+
 // finite-difference model: step k + evaluation k + 1 (first: the evaluation at x0 only)
 void launch_fd_iter(nlsg_lm *e, int first) {
   const dim3 grid(static_cast<unsigned>(e->p.batch));
-  // (+ 66: the point and a zero behind it, for the reference-order evaluation's lanes)
-  const unsigned lds = (64 * lm_fd_chunks(e->p.n) + 128 + 66) * sizeof(double);
+  const unsigned lds = static_cast<unsigned>(lm_fd_launch_lds_bytes(e->p.n, false));
   if (e->cfg.objective == NLSG_OBJ_CUSTOM) {
     void *args[] = {&e->p, &first};
     launch_module_kernel(e->rtc.iter, grid.x, 64, lds, e->stream, args);
@@ -210,7 +227,8 @@ int launch_solve(nlsg_lm *e) {
 }
 }  // namespace
 
-static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *custom, nlsg_lm **out);
+static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *custom, nlsg_lm **out,
+                     bool with_params = false);
 
 extern "C" {
 
@@ -234,9 +252,41 @@ int nlsg_lm_create_custom(const nlsg_lm_config *cfg, const nlsg_custom_objective
   return rc;
 }
 
+int nlsg_lm_create_params(const nlsg_lm_config *cfg, const nlsg_custom_objective *obj, nlsg_lm **out) {
+  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (cfg->objective != NLSG_OBJ_CUSTOM)
+    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  PhaseClock clk;
+  const int rc = lm_create(cfg, obj, out, true);
+  call_timing().create_ms = clk.lap();
+  return rc;
+}
+
+// The dynamic LDS of the launch that evaluates an objective (the finite-difference model, which is what a
+// custom objective runs): 0 for a shape that model rejects (n outside 1 .. 1024, the QR solver, an
+// unknown solver) — and for tree order past 64 parameters, whose evaluation kernel takes none.
+uint64_t nlsg_lm_lds_bytes(uint64_t n, int32_t solver) {
+  if (n < 1 || n > kLmWideMaxN) return 0;
+  if (solver != NLSG_LM_CHOLESKY && solver != NLSG_LM_CHOLESKY_REFERENCE_ORDER) return 0;
+  return lm_fd_launch_lds_bytes(n, solver == NLSG_LM_CHOLESKY_REFERENCE_ORDER);
+}
+
+int nlsg_lm_set_params(nlsg_lm *e, const double *params_host) {
+  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (e->n_params <= 0)
+    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_lm_create_params)");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
+                          hipMemcpyHostToDevice, e->stream));
+  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
+  e->params_set = true;
+  return NLSG_OK;
+}
+
 }  // extern "C"
 
-static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *custom, nlsg_lm **out) {
+static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *custom, nlsg_lm **out,
+                     bool with_params) {
   if (!cfg || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(nlsg_lm_config))
@@ -267,6 +317,10 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
     return fail(NLSG_ERR_UNSUPPORTED, "the tinyqr solve is built for n <= 64; n = %llu runs the "
                 "class's own Cholesky solve", (unsigned long long)cfg->n);
   if (cfg->batch > 0x7fffffffull) return fail(NLSG_ERR_UNSUPPORTED, "batch too large");
+  if (with_params)  // (the row is static LDS of the run-time compiled module, next to the launch's dynamic block)
+    if (const int prc = check_custom_params(custom, nlsg_lm_lds_bytes(cfg->n, cfg->solver), "nlsg_lm",
+                                            "nlsg_lm_create_custom"))
+      return prc;
   int rc = check_device(cfg->device);
   if (rc) return rc;
   NLSG_HIP(hipSetDevice(cfg->device));
@@ -274,6 +328,7 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
   e->cfg = *cfg;
   e->wide = wide;
+  e->n_params = with_params ? custom->n_params : 0;
   {
     const char *sw = std::getenv("NLSG_LM_WIDE_MFMA");
     e->wide_valu = sw && sw[0] == '0';
@@ -318,6 +373,8 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->count_dev), 8);
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->zero_dev), 16);
   if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
+  if (he == hipSuccess && e->n_params)
+    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * 8);
   if (he == hipSuccess) he = hipEventCreate(&e->ev0);
   if (he == hipSuccess) he = hipEventCreate(&e->ev1);
   if (he == hipSuccess)
@@ -356,6 +413,7 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   p.Aw = e->A_dev;
   p.yw = e->y_dev;
   p.zero = e->zero_dev;
+  p.params = e->params_dev;
   p.batch = B;
   p.m = m;
   p.n = cfg->n;
@@ -390,6 +448,7 @@ int nlsg_lm_destroy(nlsg_lm *e) {
   pool_free(e->p.gg);
   pool_free(e->count_dev);
   pool_free(e->zero_dev);
+  pool_free(e->params_dev);
   if (e->ev0) hipEventDestroy(e->ev0);
   if (e->ev1) hipEventDestroy(e->ev1);
   rtc_release(&e->rtc);
@@ -499,6 +558,7 @@ int nlsg_lm_minimize(nlsg_lm *e, double *theta_inout_host, nlsg_status *status_h
                      double *lambda_out_host) {
   if (!e || !theta_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (!e->has_data) return fail(NLSG_ERR_STATE, "nlsg_lm_set_data has not been called");
+  if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   PhaseClock clk;
   int rc = upload_theta(e, theta_inout_host);
@@ -544,6 +604,7 @@ int nlsg_lm_minimize(nlsg_lm *e, double *theta_inout_host, nlsg_status *status_h
 
 int nlsg_lm_time_solve(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total) {
   if (!e || !theta0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   if (!e->has_data) return fail(NLSG_ERR_STATE, "nlsg_lm_set_data has not been called");
   NLSG_HIP(hipSetDevice(e->cfg.device));
   float total = 0.f;
@@ -568,6 +629,7 @@ int nlsg_lm_time_solve(nlsg_lm *e, const double *theta0_host, uint32_t repeats, 
 // for every problem) on the engine's stream, HIP events around each launch.
 int nlsg_lm_time_eval_kernel(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total) {
   if (!e || !theta0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;  // (before anything that could launch an evaluation)
   if (e->p.fd) return fail(NLSG_ERR_UNSUPPORTED, "Gauss-Newton model only");
   if (!e->has_data) return fail(NLSG_ERR_STATE, "nlsg_lm_set_data has not been called");
   NLSG_HIP(hipSetDevice(e->cfg.device));
@@ -596,6 +658,7 @@ int nlsg_lm_time_eval_kernel(nlsg_lm *e, const double *theta0_host, uint32_t rep
 // back-substitution, update) after one evaluation at theta0 has produced H and g.
 int nlsg_lm_time_qr_kernel(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total) {
   if (!e || !theta0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;  // (before anything that could launch an evaluation)
   if (e->p.fd) return fail(NLSG_ERR_UNSUPPORTED, "Gauss-Newton model only");
   if (e->wide) return fail(NLSG_ERR_UNSUPPORTED, "the tinyqr step kernel: n <= 64 only");
   if (!e->has_data) return fail(NLSG_ERR_STATE, "nlsg_lm_set_data has not been called");

@@ -67,6 +67,8 @@ struct LmParams {
   const double *Aw;  // [batch][m][n] design matrices in the caller's layout
   const double *yw;  // [batch][m]
   double *rw;        // [batch][2][m] residuals r_i and weights 1 - tanh^2 of the current evaluation
+  const double *params;  // [batch][n_params] (nlsg_lm_create_params), row b staged into LDS by the three
+                         // kernels that evaluate a user objective; else nullptr
 };
 
 // The damped matrix as the Cholesky solve sees it: the packed lower triangle (the solve only
@@ -1099,6 +1101,9 @@ __global__ __launch_bounds__(64) void lm_fd_iter_kernel(LmParams p, int first) {
     if (!lm_step_wave<true, REF>(p, pid, LmStepShared{lm_fd_smem, g, g + 64}, chunks)) return;
     theta_lds = g + 64;
   }
+  // (a user objective's row, behind the block-uniform returns; the block is one wave, whose own fence
+  // publishes it)
+  stage_custom_params_one_wave(p.params, pid);
   if constexpr (REF && !Objective<OBJ>::kWhole) {
     // (the triangle's LDS image is dead during the evaluation; its first 64 doubles and the 65 past
     // g | upd hold the base terms and the point)
@@ -1603,6 +1608,9 @@ __global__ __launch_bounds__(lm_wide_fd_threads(CHUNKS)) void lm_wide_fd_eval_ke
   const uint64_t pid = blockIdx.x;
   LmProblem *pr = p.prob + pid;
   if (!first && pr->done) return;
+  // (a user objective's row: each of the problem's workgroups stages it; the return above is block-uniform
+  // and nothing below is skipped by part of the block before this barrier)
+  stage_custom_params(p.params, pid, true);
   // gridDim.y workgroups share a problem (a single start would otherwise keep one CU busy): the
   // gradient coordinates and Hessian entries are dealt over all their waves
   const int W = (lm_wide_fd_threads(CHUNKS) / 64) * static_cast<int>(gridDim.y);
@@ -1710,6 +1718,7 @@ __global__ __launch_bounds__(256) void lm_wide_fd_lanes_kernel(LmParams p, int f
   const int W = 4 * static_cast<int>(gridDim.y), w = wid + 4 * static_cast<int>(blockIdx.y);
   double *xs = lm_wfl_smem, *ts = xs + n + 2, *S = ts + n;
   const double *th = p.theta + pid * p.n;
+  stage_custom_params(p.params, pid, false);  // (a user objective's row: the barrier below publishes it)
   for (int i = t; i < n + 2; i += 256) xs[i] = i < n ? th[i] : 0.0;
   __syncthreads();
   for (int e = t; e < nt; e += 256) ts[e] = O::term(xs[e], xs[e + 1]);

@@ -26,7 +26,11 @@ struct BfgsRtcKernels {  // finite-difference model around the user's objective
   hipModule_t mod = nullptr;
   hipFunction_t init = nullptr, search = nullptr;
 };
-int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, BfgsRtcKernels *out);
+// wave_rows_offset: where the per-wave parameter rows (obj->n_params > 0) start in the kernels' dynamic
+// LDS block, in doubles — the caller's own launch layout (behind bfgs_fd_seq_lds_bytes(chunks) in
+// reference order, else 0); it becomes NLSG_PARAMS_PER_WAVE
+int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long wave_rows_offset,
+                   BfgsRtcKernels *out);
 void rtc_release(BfgsRtcKernels *k);
 struct NmRtcKernels {
   hipModule_t mod = nullptr;

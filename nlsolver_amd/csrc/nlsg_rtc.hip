@@ -71,26 +71,33 @@ int rtc_load(const char *path_in) {
 
 // Compiles `kernel_header` around the user's Objective<NLSG_OBJ_CUSTOM> and returns the module
 // with one function per name expression (kernel template-ids).
+// wave_rows_offset >= 0 (rtc_build_bfgs, with n_params > 0 only): the kernels own a wave per solve, so the
+// rows live per wave in the dynamic LDS block, that many doubles from its start (NLSG_PARAMS_PER_WAVE).
 static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_header,
                        const std::vector<std::string> &name_exprs, hipModule_t *mod_out,
-                       std::vector<hipFunction_t> *fns_out) {
+                       std::vector<hipFunction_t> *fns_out, long wave_rows_offset = -1) {
   if (!obj || !obj->term_body || !obj->term_body[0])
     return fail(NLSG_ERR_INVALID_ARG, "a custom objective needs a term body");
   int rc = rtc_load(nullptr);
   if (rc) return rc;
   RtcApi &api = rtc_api();
-  // n_params > 0 (resident batch engines, nlsg_nm_create_params, nlsg_nmpso_create_params; every
+  // n_params > 0 (resident batch engines and nlsg_nm / nmpso / lm / bfgs_create_params; every
   // *_create_custom besides has rejected it): the macro
-  // puts the solve's row into static LDS (nlsg_common.h) and the bodies read it as p(k). With
-  // n_params == 0 the source is byte for byte what it was before parameters existed.
+  // puts the solve's row into static LDS (nlsg_common.h) and the bodies read it as p(k); for BFGS a
+  // second macro puts a row per wave into the dynamic block and p(k) indexes the wave's own. With
+  // n_params == 0 the source is byte for byte what it was before parameters existed, for every engine.
   const int n_params = obj->n_params > 0 ? obj->n_params : 0;
+  const bool per_wave = n_params && wave_rows_offset >= 0;
   std::string src;
   if (n_params) src += "#define NLSG_N_PARAMS " + std::to_string(n_params) + "\n";
+  if (per_wave) src += "#define NLSG_PARAMS_PER_WAVE " + std::to_string(wave_rows_offset) + "\n";
   src += std::string("#include \"") + kernel_header + "\"\n"
          "namespace nlsg {\n"
          "template <>\n"
          "struct Objective<NLSG_OBJ_CUSTOM> {\n";
-  if (n_params)
+  if (per_wave)  // the row of wave threadIdx.x >> 6
+    src += "  __device__ static inline double p(uint64_t k) { return custom_params_wave_row()[k]; }\n";
+  else if (n_params)
     src += "  __device__ static inline double p(uint64_t k) { return custom_params_lds[k]; }\n";
   if (obj->chain == NLSG_CUSTOM_VECTOR) {
     // whole-vector form: term_body is the body of  double f(const X &x, uint64_t D)
@@ -296,7 +303,8 @@ int rtc_build_pso(const nlsg_custom_objective *obj, int chunks, bool vec, int ty
   return NLSG_OK;
 }
 
-int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, BfgsRtcKernels *out) {
+int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long wave_rows_offset,
+                   BfgsRtcKernels *out) {
   // <CHUNKS, VEC, MODEL>: MODEL = the objective id selects the finite-difference BfgsModel
   const std::string t = std::to_string(chunks) + ", " + (vec ? "true" : "false") + ", " +
                         std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM));
@@ -304,7 +312,7 @@ int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, BfgsR
   BfgsRtcKernels k;
   const int rc = rtc_compile(obj, "nlsg_bfgs_kernels.h",
                              {"nlsg::bfgs_init_kernel<" + t + ">", "nlsg::bfgs_search_kernel<" + t + ">"},
-                             &k.mod, &f);
+                             &k.mod, &f, wave_rows_offset);  // (a row per wave in the dynamic block)
   if (rc) return rc;
   k.init = f[0];
   k.search = f[1];

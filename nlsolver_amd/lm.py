@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import LMConfig, Status, check, lib
+from ._capi import LMConfig, NlsgError, Status, check, lib, require
 
 
 class TanhRegression:
@@ -35,7 +35,28 @@ class TanhRegression:
 class LMEngine:
     """model: a TanhRegression, or the name / id of a built-in objective ("rosenbrock", "sphere",
     "styblinski_tang") or a CustomObjective, with batch= and n= (default functors: fin_diff +
-    fin_diff_h)."""
+    fin_diff_h).
+
+    A CustomObjective with n_params > 0 (nlsg_lm_create_params): problem b minimises the objective under
+    row b of set_params(rows) ([batch, n_params], read as p(k)) — one fit per series; rows are replaced
+    without recompiling. The row lives in the workgroup's LDS: fits() says whether a shape has room."""
+
+    @staticmethod
+    def lds_bytes(n, reference_order=False, n_params=0):
+        """LDS bytes of the launch that evaluates an objective of n parameters, the row of n_params
+        objective parameters included (host only; tree order past 64 parameters takes none of its own)"""
+        solver = _capi.LM_CHOLESKY_REFERENCE_ORDER if reference_order else _capi.LM_CHOLESKY
+        need = int(require("nlsg_lm_lds_bytes")(n, solver))
+        return need + (int(require("nlsg_custom_params_lds_bytes")(n_params)) if n_params else 0)
+
+    @staticmethod
+    def fits(n, reference_order=False, n_params=0):
+        """whether nlsg_lm_create_params takes the shape: 1 <= n <= 1024, 0 <= n_params <= 4096 and
+        lds_bytes within the workgroup's 160 KiB"""
+        from .de import LDS_BUDGET
+        if not (1 <= n <= 1024 and 0 <= n_params <= _capi.CUSTOM_MAX_PARAMS):
+            return False
+        return LMEngine.lds_bytes(n, reference_order, n_params) <= LDS_BUDGET
 
     def __init__(self, model, *, lam=10.0, up=10.0, down=10.0, max_iter=100, f_delta=1e-12,
                  solver=_capi.LM_CHOLESKY, device=0, stream=None, batch=None, n=None):
@@ -59,12 +80,17 @@ class LMEngine:
         cfg.batch, cfg.m, cfg.n = B, m, n
         cfg.lambda_, cfg.up, cfg.down, cfg.max_iter, cfg.f_delta = lam, up, down, max_iter, f_delta
         self.cfg = cfg
+        self.n_params = custom.n_params if custom else 0
         self._h = C.c_void_p()
         if custom:
+            create = lib().nlsg_lm_create_custom
+            if self.n_params:  # (zero stays with the creator it always had)
+                create = require("nlsg_lm_create_params")
+                require("nlsg_lm_set_params")
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), custom.n_params)
-            check(lib().nlsg_lm_create_custom(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+                                         int(custom.chain), self.n_params)
+            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
         else:
             check(lib().nlsg_lm_create(C.byref(cfg), C.byref(self._h)))
         if not fd:
@@ -89,7 +115,19 @@ class LMEngine:
         check(lib().nlsg_lm_set_solver(self._h, solver))
         self.cfg.solver = solver
 
-    def minimize(self, theta):
+    def set_params(self, params):
+        """params [batch, n_params]: problem b's objective reads row b as p(k). The rows hold from the
+        next solve on and can be replaced at any time without recompiling."""
+        if self.n_params == 0:
+            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
+        from .de import _params_rows
+        rows = _params_rows(params, self.cfg.batch, self.n_params)
+        check(require("nlsg_lm_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
+
+    def minimize(self, theta, params=None):
+        """params: set_params(params) first."""
+        if params is not None:
+            self.set_params(params)
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         assert theta.shape == (self.cfg.batch, self.cfg.n)
         st = (Status * self.cfg.batch)()
@@ -98,7 +136,9 @@ class LMEngine:
                                      lam.ctypes.data_as(_capi.pd)))
         return theta, list(st), lam
 
-    def time_solve(self, theta0, repeats=1):
+    def time_solve(self, theta0, repeats=1, params=None):
+        if params is not None:
+            self.set_params(params)
         theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
         ms = C.c_float()
         check(lib().nlsg_lm_time_solve(self._h, theta0.ctypes.data_as(_capi.pd), repeats, C.byref(ms)))
@@ -127,10 +167,19 @@ class LevenbergMarquardt:
     (by name); x: (n,) or (batch, n). solver=None (as include/nlsolver_mi/nlsolver.h's
     device::summation() default): the default-functor model on Rosenbrock / Sphere / Styblinski-Tang solves
     in reference order (LM_CHOLESKY_REFERENCE_ORDER: the reference's run bit for bit, and — a probe
-    per lane — the faster evaluation); everything else with LM_CHOLESKY."""
+    per lane — the faster evaluation); everything else with LM_CHOLESKY.
+
+    params: the run-time parameters of a CustomObjective with n_params > 0: one row (n_params,) shown
+    to every start, or (batch, n_params) with a 2-D x, a row per start."""
 
     def __init__(self, f, lam=10.0, upward_mult=10.0, downward_mult=10.0, max_iter=100,
-                 f_delta=1e-12, g=None, h=None, *, solver=None, device=0):
+                 f_delta=1e-12, g=None, h=None, *, solver=None, device=0, params=None):
+        from .nm import _drop_in_rows
+        self.n_params = getattr(f, "n_params", 0)
+        if (params is not None) != bool(self.n_params):
+            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
+                             "objective needs it")
+        self.params = None if params is None else _drop_in_rows(params, self.n_params)
         if g is not None or h is not None:
             raise TypeError("device models carry their functors (Gauss-Newton for NLLS models, "
                             "the reference's finite-difference defaults for objectives)")
@@ -150,8 +199,10 @@ class LevenbergMarquardt:
                 (isinstance(self.f, CustomObjective) and self.f.chain != 2)  # (given by its terms)
             ref = has_it
             args["solver"] = _capi.LM_CHOLESKY_REFERENCE_ORDER if ref else _capi.LM_CHOLESKY
+        from .nm import _rows_for_batch
+        rows = _rows_for_batch(self.params, xb.shape[0])
         with LMEngine(self.f, **args, **shape) as eng:
-            out, st, lam = eng.minimize(xb)
+            out, st, lam = eng.minimize(xb, params=rows)
         xb[...] = out
         self.lambdas = lam  # the reference keeps lambda as a member across calls (:3436)
         return st[0] if x.ndim == 1 else st

@@ -120,9 +120,12 @@ int nlsg_call_timing(double *ms_out6);
  * minimize() releases the next one takes: the reference's one-call-per-solve API would otherwise
  * pay a dozen hipMalloc / hipFree pairs per call). At most $NLSG_POOL_BYTES (default 40 GiB; 0
  * turns the cache off) sit idle per device. nlsg_release_cached frees all of it now;
- * nlsg_cached_bytes reports how much is parked. */
+ * nlsg_cached_bytes reports how much is parked. nlsg_pool_poison is a test aid: the byte that
+ * $NLSG_POOL_POISON ("1": 0xFF, "0x<two hex digits>": that byte; read once, when the cache is first
+ * used) has every block handed out filled with, 0 .. 255, or -1 when it is off. */
 int nlsg_release_cached(void);
 uint64_t nlsg_cached_bytes(void);
+int nlsg_pool_poison(void);
 
 /* The device's deterministic math primitives (the log / cos of rnorm nlsolver.h:2479-2485, the
  * exp / tanh of the NLLS model, the cosine of Rastrigin test_functions.h:74-76) evaluated on n

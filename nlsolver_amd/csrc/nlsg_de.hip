@@ -303,6 +303,7 @@ int nlsg_release_cached(void) {
   return NLSG_OK;
 }
 uint64_t nlsg_cached_bytes(void) { return pool_idle_bytes(); }
+int nlsg_pool_poison(void) { return pool_poison(); }
 int nlsg_call_timing(double *ms_out6) {
   if (!ms_out6) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   const CallTiming &t = call_timing();

@@ -39,10 +39,23 @@ struct DevicePool {
   std::unordered_map<int, std::vector<hipStream_t>> streams;  // parked non-blocking streams
   size_t cap = 40ull << 30;
   bool enabled = true;
-  bool poison = false;  // NLSG_POOL_POISON=1 (tests): every block handed out is filled with 0xFF bytes
-                        // (NaNs / huge integers), so an engine that reads what it never wrote shows
+  // NLSG_POOL_POISON (tests): every block handed out, fresh or recycled, is filled with one byte, so an
+  // engine that reads what it never wrote shows. "1" fills with 0xFF (NaNs / huge integers: what a
+  // comparison, an fmin or a stop test ignores), "0x<two hex digits>" with that byte (0xC0: the
+  // finite double -8577.5..., which beats every honest score in a min-scan, and a negative int32).
+  // Unset, empty or "0": off (-1). Read once, here; nlsg_pool_poison() (C-ABI) reports it.
+  int poison = -1;
+  static int parse_poison(const char *c) {
+    auto hex = [](char h) { return h >= '0' && h <= '9' ? h - '0' : h >= 'a' && h <= 'f' ? h - 'a' + 10
+                                   : h >= 'A' && h <= 'F' ? h - 'A' + 10 : -1; };
+    if (!c || !c[0] || (c[0] == '0' && !c[1])) return -1;
+    if (c[0] == '1' && !c[1]) return 0xFF;
+    if (c[0] == '0' && (c[1] == 'x' || c[1] == 'X') && c[2] && c[3] && !c[4] && hex(c[2]) >= 0 && hex(c[3]) >= 0)
+      return hex(c[2]) * 16 + hex(c[3]);
+    return -1;
+  }
   DevicePool() {
-    if (const char *c = std::getenv("NLSG_POOL_POISON")) poison = c[0] == '1';
+    poison = parse_poison(std::getenv("NLSG_POOL_POISON"));
     if (const char *c = std::getenv("NLSG_POOL_BYTES")) {
       cap = std::strtoull(c, nullptr, 10);
       enabled = cap > 0;
@@ -82,7 +95,14 @@ inline DevicePool &device_pool() {
 // hipMalloc on the current device, served from the cache when a block of the size is parked
 inline hipError_t pool_malloc(void **ptr, size_t bytes) {
   DevicePool &pool = device_pool();
-  if (!pool.enabled) return hipMalloc(ptr, bytes);
+  if (!pool.enabled) {  // (NLSG_POOL_BYTES=0: nothing is recycled; a poison byte in force still fills)
+    hipError_t hm = hipMalloc(ptr, bytes);
+    if (hm == hipSuccess && pool.poison >= 0) {
+      hm = hipMemset(*ptr, pool.poison, bytes);
+      if (hm == hipSuccess) hm = hipDeviceSynchronize();
+    }
+    return hm;
+  }
   int dev = 0;
   hipError_t he = hipGetDevice(&dev);
   if (he != hipSuccess) return he;
@@ -103,8 +123,8 @@ inline hipError_t pool_malloc(void **ptr, size_t bytes) {
     if (he != hipSuccess) return he;
   }
   pool.live[*ptr] = {dev, sz};
-  if (pool.poison) {
-    he = hipMemset(*ptr, 0xFF, sz);
+  if (pool.poison >= 0) {
+    he = hipMemset(*ptr, pool.poison, sz);
     if (he == hipSuccess) he = hipDeviceSynchronize();
   }
   return he;
@@ -172,6 +192,7 @@ inline void pool_release_all() {
     kv.second.clear();
   }
 }
+inline int pool_poison() { return device_pool().poison; }
 inline size_t pool_idle_bytes() {
   DevicePool &pool = device_pool();
   std::lock_guard<std::mutex> lock(pool.mu);

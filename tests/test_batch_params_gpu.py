@@ -10,6 +10,7 @@ rotation of the first, so the literal engines serve both.
 
 Shapes are one per lane mapping that can differ: D 2 (4 lanes per agent), D 9 (8 lanes, odd D), D 65
 (one wave per agent); pop / particles 8, 12, 6 -- no multiple of the agents per pass."""
+import contextlib
 import json
 import os
 import subprocess
@@ -114,8 +115,8 @@ DE_ARGS = dict(CR=0.9, F=0.8, eps=10e-4, max_iter=40, best_val_no_change=50)
 PSO_ARGS = dict(eps=10e-4, max_iter=40, best_val_no_change=50)
 
 
-@pytest.fixture(scope="module")
-def ENGINES(m):
+@contextlib.contextmanager
+def engines(m):
     """(kind, form, n, D, extra, row or None, batch) -> engine; closed when the module is done"""
     made = {}
 
@@ -130,9 +131,18 @@ def ENGINES(m):
                 made[key] = m.PSOBatchEngine(obj, batch, n, D, **dict(PSO_ARGS, **dict(extra)))
         return made[key]
 
-    yield get
-    for eng in made.values():
-        eng.close()
+    try:
+        yield get
+    finally:
+        for eng in made.values():
+            eng.close()
+
+
+@pytest.fixture(scope="module")
+def ENGINES(m):
+    """engines(m), made once for the module"""
+    with engines(m) as get:
+        yield get
 
 
 def inputs(kind, D, salt=0):

@@ -42,6 +42,27 @@ def test_bfgs_batch_bit_exact_vs_tree_oracle(mod, oracle, n, batch, kw):
         assert st[p].done == 1
 
 
+def assert_gradient_within_rounding(g, x, d, b, c):
+    """The downloaded gradient of the G6 quadratic against the exact one at the device's own iterate:
+    g*_i = d_i x_i + c sum(x) - b_i in rationals. Whatever the order of the n - 1 additions of sum(x),
+    the product with c, the product d_i x_i and the two additions that join them, the computed value
+    is within gamma_{n+2} (|d_i x_i| + |c| sum|x_j| + |b_i|) of it, gamma_k = k u / (1 - k u),
+    u = 2^-53 (the standard bound of a sum of k + 1 terms in any order, each term carrying at most
+    one more rounding): derived, nothing measured."""
+    from fractions import Fraction as Fr
+    n = len(x)
+    k, u = n + 2, Fr(1, 2**53)
+    gamma = k * u / (1 - k * u)
+    xs = [Fr(float(v)) for v in x]
+    sx, sabs = sum(xs), sum(abs(v) for v in xs)
+    cf = Fr(float(c))
+    for i in range(n):
+        di, bi = Fr(float(d[i])), Fr(float(b[i]))
+        exact = di * xs[i] + cf * sx - bi
+        bound = gamma * (abs(di * xs[i]) + abs(cf) * sabs + abs(bi))
+        assert abs(Fr(float(g[i])) - exact) <= bound, (i, float(g[i]), float(exact), float(bound))
+
+
 def test_bfgs_inverse_hessian_and_gradient_after_k_iterations(mod, oracle):
     """State after exactly k turns (max_iter = k): gradient and H^-1 bit-exact."""
     n, batch, k = 96, 3, 4
@@ -58,12 +79,15 @@ def test_bfgs_inverse_hessian_and_gradient_after_k_iterations(mod, oracle):
         # replay the oracle by hand for k iterations to obtain H: run k and k-1 ... simpler:
         # the quadratic's gradient at the device iterate must equal the device gradient, and
         # the device iterate must equal the oracle's iterate after k iterations
-        ref, xr, _ = O.bfgs_quad(oracle, x0[p], tree=1, **kw)
+        Href = np.zeros((n, n))
+        ref, xr, _ = O.bfgs_quad(oracle, x0[p], tree=1, hessian=Href, **kw)
         assert np.array_equal(x[p], xr)
         sx = x[p].sum()
         assert np.allclose(g[p], d * x[p] + c * sx - b, rtol=1e-13, atol=1e-13)
+        assert_gradient_within_rounding(g[p], x[p], d, b, c)
         # H stays symmetric up to the rounding of the (denom*s_i)*s_j term and maps y to ~s
         assert np.allclose(H[p], H[p].T, rtol=0, atol=1e-9)
+        assert np.array_equal(H[p], Href), (p, np.argwhere(H[p] != Href)[:4])
 
 
 def test_bfgs_matches_reference_arithmetic_within_1e12(mod, oracle, golden):

@@ -32,6 +32,46 @@ def x0_for(D, val=0.6):
     return val * (1.0 + 0.001 * np.arange(D))
 
 
+def accepting_generations(eng_mod, oracle, pop, D, strategy, CR, *, minimize=True, trace=True, turns=6):
+    """`turns` single turns from x0 0.6 with F 0.5: trace (where kept), population, scores and counters of
+    every generation equal the oracle's, then one more turn whose head scans the last generation and
+    copies the best row through the selector. trace=False with strategy random runs the fused turn (head k
+    and generation k + 1 in one launch), which a trace buffer switches off. Returns the number of accepted
+    trials."""
+    x0 = x0_for(D)
+    kw = dict(strategy=strategy, CR=CR, F=0.5, eps=0.0, best_val_no_change=10**6, minimize=minimize)
+    ref = O.DESyncRun(oracle, "rosenbrock", pop, D, x0, trace=trace, **kw)
+    accepted = 0
+    tag = f"pop {pop} D {D} strategy {strategy} minimize {minimize} trace {trace}"
+    with eng_mod.DEEngine("rosenbrock", pop, D, trace=trace, **kw) as eng:
+        eng.init(x0)
+        P, S = eng.download()
+        assert np.array_equal(P, ref.population) and np.array_equal(S, ref.scores), f"{tag}: init"
+        for g in range(turns):
+            before = ref.scores.copy()
+            eng.step(1)
+            ref.step(1)
+            if trace:
+                P, S, T = eng.download(trace=True)
+                assert np.array_equal(T, ref.trace), f"{tag}: trace gen {g}"
+                assert int(T[:, 4].sum()) == int(np.sum(ref.scores != before)), f"{tag}: accept mask gen {g}"
+            else:
+                P, S = eng.download()
+            assert np.array_equal(P, ref.population), f"{tag}: population gen {g}"
+            assert np.array_equal(S, ref.scores), f"{tag}: scores gen {g}"
+            st = eng.status()
+            assert (st.iteration, st.function_calls_used, st.best_index, st.val_no_change) == \
+                (ref.s.iter, ref.s.fcalls, ref.s.best_id, ref.s.val_no_change), f"{tag}: counters gen {g}"
+            accepted += int(np.sum(ref.scores != before))
+        # one more turn: its head scans the last generation and copies the best row through the selector
+        Pk, Sk = ref.population.copy(), ref.scores.copy()
+        eng.step(1)
+        ref.step(1)
+        bx, bf, bi = eng.best()
+        assert bi == ref.s.best_id and bf == Sk[bi] and np.array_equal(bx, Pk[bi]), f"{tag}: best"
+    return accepted
+
+
 # D = 16 / 64: packed groups; 128: one wave per agent; 1000: 8 chunks, odd row length per lane
 # pair; 1025 / 2048: the segment-streaming kernel (odd and even rows)
 @pytest.mark.parametrize("D", [16, 64, 128, 1000, 1025, 2048])
@@ -40,27 +80,7 @@ def x0_for(D, val=0.6):
 def test_accepting_generations_bit_exact(eng_mod, oracle, D, strategy, CR):
     """CR 0.2, F 0.5 from x0 0.6 accepts ~10 % of the trials at D <= 128; CR 0.01 (about one
     crossed coordinate) keeps accepting at D >= 1000, where CR 0.2 accepts next to nothing."""
-    pop = 128 if D <= 128 else 64
-    x0 = x0_for(D)
-    kw = dict(strategy=strategy, CR=CR, F=0.5, eps=0.0, best_val_no_change=10**6)
-    ref = O.DESyncRun(oracle, "rosenbrock", pop, D, x0, trace=True, **kw)
-    accepted = 0
-    with eng_mod.DEEngine("rosenbrock", pop, D, trace=True, **kw) as eng:
-        eng.init(x0)
-        for g in range(6):
-            eng.step(1)
-            ref.step(1)
-            P, S, T = eng.download(trace=True)
-            assert np.array_equal(T, ref.trace), f"trace gen {g}"
-            assert np.array_equal(P, ref.population), f"population gen {g}"
-            assert np.array_equal(S, ref.scores), f"scores gen {g}"
-            accepted += int(T[:, 4].sum())
-        # one more turn: its head scans generation 6 and copies the best row through the selector
-        P6, S6 = ref.population.copy(), ref.scores.copy()
-        eng.step(1)
-        ref.step(1)
-        bx, bf, bi = eng.best()
-        assert bi == ref.s.best_id and bf == S6[bi] and np.array_equal(bx, P6[bi])
+    accepted = accepting_generations(eng_mod, oracle, 128 if D <= 128 else 64, D, strategy, CR)
     assert accepted > 0 or CR == 0.2
 
 
@@ -127,15 +147,13 @@ def test_stop_inside_a_fused_turn_with_accepted_rows(eng_mod, oracle, D, mode, m
         assert np.array_equal(bx, ref.best_x) and bf == ref.scores[bi]
 
 
-@pytest.mark.parametrize("strategy", [1, 0])
-def test_eight_shards_on_one_gpu_accepting_bit_exact(eng_mod, oracle, strategy):
-    """Eight shard engines on one device (island donors, one record exchange per turn), the best
-    row of each shard's record read through its selectors, over enough accepting turns that every
-    shard's rows are spread over both buffers."""
+def shards_on_one_gpu(eng_mod, oracle, shards, n, D, strategy, turns=6):
+    """`shards` shard engines of n agents each on one device (island donors, one record exchange per
+    turn) over accepting turns: every shard's rows, scores and counters equal the oracle's, the best row
+    of each shard's record is read through its selectors."""
     import torch
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    shards, n, D, turns = 8, 1024, 128, 6
     pop = shards * n
     x0 = x0_for(D)
     kw = dict(strategy=strategy, eps=0.0, best_val_no_change=1000, CR=0.2, F=0.5)
@@ -145,32 +163,43 @@ def test_eight_shards_on_one_gpu_accepting_bit_exact(eng_mod, oracle, strategy):
     ref.step(1)
     engs = [eng_mod.DEEngine("rosenbrock", pop, D, shard_lo=r * n, shard_n=n, stream=stream, **kw)
             for r in range(shards)]
-    rec = engs[0].record_doubles()
-    gathered = torch.zeros(shards * rec, dtype=torch.float64, device=dev)
-    for e in engs:
-        e.init(x0)
-    speculate = engs[0].can_speculate()
-    for _ in range(turns):
+    try:
+        rec = engs[0].record_doubles()
+        gathered = torch.zeros(shards * rec, dtype=torch.float64, device=dev)
+        for e in engs:
+            e.init(x0)
+        speculate = engs[0].can_speculate()
+        for _ in range(turns):
+            for r, e in enumerate(engs):
+                e.turn_begin(gathered[r * rec:(r + 1) * rec].data_ptr())
+            if speculate:
+                for e in engs:
+                    e.turn_generation()
+                for e in engs:
+                    e.turn_finalize(gathered.data_ptr(), shards)
+            else:
+                for e in engs:
+                    e.turn_end(gathered.data_ptr(), shards)
         for r, e in enumerate(engs):
-            e.turn_begin(gathered[r * rec:(r + 1) * rec].data_ptr())
-        if speculate:
-            for e in engs:
-                e.turn_generation()
-            for e in engs:
-                e.turn_finalize(gathered.data_ptr(), shards)
-        else:
-            for e in engs:
-                e.turn_end(gathered.data_ptr(), shards)
-    for r, e in enumerate(engs):
-        P, S = e.download()
-        assert np.array_equal(P, ref.population[r * n:(r + 1) * n]), f"shard {r} population"
-        assert np.array_equal(S, ref.scores[r * n:(r + 1) * n]), f"shard {r} scores"
-        st = e.status()
-        assert (st.best_index, st.iteration, st.function_calls_used) == \
-            (ref.s.best_id, ref.s.iter, ref.s.fcalls)
-        bx, bf, bi = e.best()
-        assert np.array_equal(bx, P_last_head[bi])
-        e.close()
+            P, S = e.download()
+            assert np.array_equal(P, ref.population[r * n:(r + 1) * n]), f"shard {r} population"
+            assert np.array_equal(S, ref.scores[r * n:(r + 1) * n]), f"shard {r} scores"
+            st = e.status()
+            assert (st.best_index, st.iteration, st.function_calls_used) == \
+                (ref.s.best_id, ref.s.iter, ref.s.fcalls)
+            bx, bf, bi = e.best()
+            assert np.array_equal(bx, P_last_head[bi])
+    finally:
+        for e in engs:
+            e.close()
+
+
+@pytest.mark.parametrize("strategy", [1, 0])
+def test_eight_shards_on_one_gpu_accepting_bit_exact(eng_mod, oracle, strategy):
+    """Eight shard engines on one device (island donors, one record exchange per turn), the best
+    row of each shard's record read through its selectors, over enough accepting turns that every
+    shard's rows are spread over both buffers."""
+    shards_on_one_gpu(eng_mod, oracle, 8, 1024, 128, strategy)
 
 
 @pytest.mark.parametrize("D", [16, 128, 2048])

@@ -133,19 +133,33 @@ _SHAPES = [(4, 1), (4, 65), (5, 2), (5, 1025), (40, 63), (40, 128), (63, 64), (6
            (64, 65), (64, 1000), (65, 2), (65, 64), (256, 128), (256, 63), (4096, 2), (4096, 128)]
 
 
+def shape_case(oracle, rs, obj, pop, D, gens, strategy, minimize, *, batch=1, log=False):
+    """`batch` solves of `gens` generations from starts and generator states drawn from `rs`: x, status
+    and final state equal the serial oracle's; with `log`, every evaluation's point and value too."""
+    x0s = rs.uniform(-3, 3, (batch, D))
+    states = [_random_state(rs) for _ in range(batch)]
+    kw = dict(minimize=minimize, strategy=strategy, CR=0.9, F=0.8, eps=0.0, max_iter=gens)
+    cap = pop * (gens + 1) if log else 0
+    with nlsolver_amd.DERefEngine(obj, batch, pop, D, best_val_no_change=1000, log_capacity=cap, **kw) as eng:
+        x, st, out = eng.minimize(x0s, states)
+        logs = [eng.log(b) for b in range(batch)] if log else None
+    for b in range(batch):
+        want = oracle_run(oracle, OBJ[obj], x0s[b], states[b], pop=pop, bvnc=1000, log_cap=cap, **kw)
+        assert_same(want, x[b], st[b], out[b])
+        if log:
+            lx, lf, n = logs[b]
+            olx, olf = want[3]
+            assert n == st[b].function_calls_used == len(olf), (pop, D, b)
+            assert np.array_equal(lx, olx) and np.array_equal(lf, olf), (pop, D, b)
+
+
 @pytest.mark.parametrize("pop, D", _SHAPES)
 def test_shape_matrix_against_oracle(oracle, pop, D):
     rs = np.random.default_rng(pop * 10007 + D)
     k = _SHAPES.index((pop, D))
     obj = ["rosenbrock", "sphere", "styblinski_tang"][k % 3]
     for strategy, minimize in ((DE_RANDOM, k % 2 == 0), (DE_BEST, k % 2 == 1)):
-        x0 = rs.uniform(-3, 3, D)
-        state = _random_state(rs)
-        gens = 3 if pop * D >= 100_000 else 6
-        kw = dict(minimize=minimize, strategy=strategy, CR=0.9, F=0.8, eps=0.0, max_iter=gens)
-        want = oracle_run(oracle, OBJ[obj], x0, state, pop=pop, bvnc=1000, **kw)
-        x, st, states = device_run(obj, [x0], [state], pop=pop, best_val_no_change=1000, **kw)
-        assert_same(want, x[0], st[0], states[0])
+        shape_case(oracle, rs, obj, pop, D, 3 if pop * D >= 100_000 else 6, strategy, minimize)
 
 
 @pytest.mark.parametrize("strategy", [DE_BEST, DE_RANDOM])

@@ -20,6 +20,7 @@ The starts and rows were chosen on the CPU, from the reference's own BFGS / Leve
 same functions (the reference-order device solves are its runs bit for bit): every solve iterates at
 least three times, and in each BFGS batch of six two problems of one block stop at different
 iteration counts, so a wave does leave while its neighbours go on."""
+import contextlib
 import json
 import os
 import subprocess
@@ -154,8 +155,8 @@ def make_engine(m, kind, obj, batch, D, extra):
     return m.BFGSEngine(obj, batch, dim=D, reference_order=ref, **kw)
 
 
-@pytest.fixture(scope="module")
-def ENGINES(m):
+@contextlib.contextmanager
+def engines(m):
     """(kind, form, D, B, extra, row or None) -> engine; closed when the module is done"""
     made = {}
 
@@ -166,9 +167,18 @@ def ENGINES(m):
             made[key] = make_engine(m, kind, objective(m, form, D, row), B if row is None else 1, D, extra)
         return made[key]
 
-    yield get
-    for eng in made.values():
-        eng.close()
+    try:
+        yield get
+    finally:
+        for eng in made.values():
+            eng.close()
+
+
+@pytest.fixture(scope="module")
+def ENGINES(m):
+    """engines(m), made once for the module"""
+    with engines(m) as get:
+        yield get
 
 
 def solve(eng, kind, x0, params=None):

@@ -12,6 +12,7 @@ of the first, so the literal engines serve both.
 Shapes, Nelder-Mead: n 2 (one wave), 9 (odd n, three waves, scalar shrink), 16 (128-bit shrink),
 128 (the full-row shrink, LDS nearly full), 130 (two chunks per lane, simplex in global memory).
 Hybrid: n 2, 9, 33 (packed kernel), 130 (wide kernel)."""
+import contextlib
 import json
 import os
 import subprocess
@@ -138,8 +139,8 @@ def bounds_for(D):
 
 
 # ---- engines, made once ------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def ENGINES(m):
+@contextlib.contextmanager
+def engines(m):
     """(kind, form, D, extra, row or None[, b]) -> engine; closed when the module is done"""
     made = {}
 
@@ -156,9 +157,18 @@ def ENGINES(m):
                                           **dict(extra))
         return made[key]
 
-    yield get
-    for eng in made.values():
-        eng.close()
+    try:
+        yield get
+    finally:
+        for eng in made.values():
+            eng.close()
+
+
+@pytest.fixture(scope="module")
+def ENGINES(m):
+    """engines(m), made once for the module"""
+    with engines(m) as get:
+        yield get
 
 
 def solve(eng, kind, D, x0, bounded, params=None):

@@ -84,6 +84,32 @@ def test_bfgs_reference_order_batches_equal_the_serial_oracle(mod, oracle, obj, 
         assert st[p].f_value == ref.f_value and np.array_equal(x[p], xr), p
 
 
+@pytest.mark.parametrize("n", [130, 512])
+def test_bfgs_reference_order_inverse_hessian_bit_exact(mod, oracle, n):
+    """The inverse Hessian and the gradient that download_state hands back in reference order after
+    exactly k updates: H equals the serial oracle's (tree 0: the reference's update_inverse_hessian
+    restated) bit for bit, x its iterate. n = 130: rows of the device matrix are n doubles apart;
+    n = 512 (n * 8 a multiple of 4096): they are n + 16 apart and the download steps over the padding."""
+    from tests.test_bfgs_gpu import assert_gradient_within_rounding, starts
+    batch, k = 3, 3
+    d, b, c = O.quad_problem(n)
+    x0 = starts(batch, n, seed=40 + n)
+    kw = dict(max_iter=k, grad_eps=0.0, alpha=1.0)
+    with mod.BFGSEngine(mod.QuadDiagRank1(d, b, c), batch, reference_order=True, **kw) as eng:
+        eng.init(x0)
+        eng.step(k)
+        g, H = eng.download_state()
+        x, st = eng.download()
+    assert H.shape == (batch, n, n) and g.shape == (batch, n)
+    for p in range(batch):
+        Href = np.zeros((n, n))
+        ref, xr, _ = O.bfgs_quad(oracle, x0[p], tree=0, hessian=Href, **kw)
+        assert st[p].iteration == ref.iteration == k
+        assert np.array_equal(x[p], xr), p
+        assert np.array_equal(H[p], Href), (p, np.argwhere(H[p] != Href)[:4])
+        assert_gradient_within_rounding(g[p], x[p], d, b, c)
+
+
 def test_bfgs_reference_order_limits(mod):
     for args, kw in ((("rastrigin", 1), dict(dim=4)),                          # no libm cosine on the device
                      (("rosenbrock", 1), dict(dim=4, symmetric=True))):        # a different arithmetic

@@ -435,13 +435,18 @@ int nlsg_bfgs_time_steps(nlsg_bfgs *e, uint64_t iters, float *ms_total, float *m
 /* (nlsolver.h:3465-3544) driven with Gauss-Newton functors (f = sum r^2,       */
 /* Grad = 2 J^T r, Hess = 2 J^T J), math::get_update_with_hessian (251-330) and */
 /* — solver = QR — tinyqr::lm on the damped matrix (tinyqr.h:253-310, 437-470), */
-/* for `batch` independent problems of one residual model.                      */
+/* for `batch` independent problems of one residual model: the built-in tanh     */
+/* regression, or r_i = y_i - phi(a_i . theta) with phi given as source text     */
+/* (nlsg_lm_create_link) — the same kernels instantiated on another link.        */
 /* ========================================================================== */
 typedef struct nlsg_lm nlsg_lm;
 
 typedef enum {
   /* r_i(theta) = y_i - tanh(sum_j A_ij theta_j)   */
-  NLSG_OBJ_TANH_REGRESSION = 32
+  NLSG_OBJ_TANH_REGRESSION = 32,
+  /* r_i(theta) = y_i - phi(sum_j A_ij theta_j), phi and phi' from an nlsg_lm_link
+   * (nlsg_lm_create_link only) */
+  NLSG_OBJ_LINK_REGRESSION = 33
 } nlsg_nlls_objective;
 /* NLSG_LM_CHOLESKY_REFERENCE_ORDER: the class's own solve with the reference's literal arithmetic
  * — every probe of fin_diff / fin_diff_h sums its objective in INDEX order (the reference's
@@ -489,6 +494,29 @@ int nlsg_lm_create_params(const nlsg_lm_config *cfg, const nlsg_custom_objective
  * recompiling. NLSG_ERR_INVALID_ARG on an engine of another creator. Until the first call,
  * nlsg_lm_minimize, _time_solve, _time_eval_kernel and _time_qr_kernel answer NLSG_ERR_STATE. */
 int nlsg_lm_set_params(nlsg_lm *e, const double *params_host);
+/* The link phi of an NLSG_OBJ_LINK_REGRESSION model, as HIP source compiled at engine creation:
+ *   value_body   the body of  double value(double z)            — phi(z)
+ *   slope_body   the body of  double slope(double z, double v)  — phi'(z), with v = value(z) at hand
+ * Both may call the deterministic primitives of the library's device math (det_exp, det_log, det_tanh,
+ * det_sqrt, ...). Example, the logistic link:
+ *   value_body = "return 1.0 / (1.0 + det_exp(-z));"   slope_body = "return v * (1.0 - v);"
+ * Compiled with the flags of the library's own kernels (no contraction, no fast math): bodies that
+ * restate tanh ("return det_tanh(z);", "return 1 - v * v;") give NLSG_OBJ_TANH_REGRESSION's bits. */
+typedef struct {
+  const char *value_body;
+  const char *slope_body;
+} nlsg_lm_link;
+/* An engine of the Gauss-Newton kernels (J^T J on the matrix cores, either step) on the link `link`.
+ * cfg->objective must be NLSG_OBJ_LINK_REGRESSION. Before the device is touched: every shape and solver
+ * check of nlsg_lm_create for an NLLS model, in its order (NLSG_LM_QR to n = 64, n <= 1024,
+ * NLSG_LM_CHOLESKY_REFERENCE_ORDER unsupported), then NULL or empty bodies (NLSG_ERR_INVALID_ARG). A
+ * body that does not compile is NLSG_ERR_INVALID_ARG with the compiler's message, which names the body
+ * and the line in it. nlsg_lm_set_data / _set_solver / _minimize / _time_* work as on a tanh engine;
+ * nlsg_lm_set_params answers as for any engine without parameters. Rows past m contribute nothing
+ * whatever phi(0) is. The evaluation kernel is always the matrix-core one of the shape: the
+ * NLSG_LM_WIDE_MFMA / NLSG_LM_WIDE256 / NLSG_LM_WIDE_CHOL switches of the built-in engine are ignored.
+ * Optional symbol (NLSG_ABI_VERSION stays 1): look it up before relying on it. */
+int nlsg_lm_create_link(const nlsg_lm_config *cfg, const nlsg_lm_link *link, nlsg_lm **out);
 /* Dynamic LDS bytes of the launch that evaluates an objective of n parameters through the default
  * finite-difference functors (what a custom objective runs), solver = NLSG_LM_CHOLESKY or
  * NLSG_LM_CHOLESKY_REFERENCE_ORDER. 0 outside 1 <= n <= 1024 and for any other solver — and in tree

@@ -294,7 +294,33 @@ struct TanhRegression {
     return acc;
   }
 };
+// The same model with a link of the caller's: r_i(theta) = y_i - phi(sum_j A_ij theta_j). value_body is
+// the body of `double value(double z)` (phi), slope_body that of `double slope(double z, double v)`
+// (phi', with v = value(z)): HIP source compiled when the engine is made (nlsg_lm_create_link), which
+// may call det_exp / det_log / det_tanh / ... The logistic link:
+//   LinkRegression<double>(m, n, A, y, "return 1.0 / (1.0 + det_exp(-z));", "return v * (1.0 - v);")
+// phi exists on the device only: operator() throws.
+template <typename T = double>
+struct LinkRegression {
+  static constexpr int nlsg_nlls_objective = NLSG_OBJ_LINK_REGRESSION;
+  size_t m, n;
+  std::vector<T> A, y;  // problems*m*n, problems*m
+  std::string value_body, slope_body;
+  LinkRegression(size_t m, size_t n, std::vector<T> A, std::vector<T> y, std::string value_body,
+                 std::string slope_body)
+      : m(m), n(n), A(std::move(A)), y(std::move(y)), value_body(std::move(value_body)),
+        slope_body(std::move(slope_body)) {}
+  size_t problems() const { return y.size() / m; }
+  T operator()(const std::vector<T> &) const {
+    throw std::logic_error("LinkRegression: the link is device source text, there is no host evaluation");
+  }
+};
 struct gauss_newton {};  // Grad / Hess tag of device NLLS models
+template <typename C, typename = void>
+struct has_link_bodies : std::false_type {};
+template <typename C>
+struct has_link_bodies<C, std::void_t<decltype(std::declval<const C &>().value_body),
+                                      decltype(std::declval<const C &>().slope_body)>> : std::true_type {};
 template <typename C, typename = void>
 struct has_nlls_objective : std::false_type {};
 template <typename C>
@@ -389,6 +415,7 @@ class api {
   decltype(&nlsg_bfgs_set_params) bfgs_set_params = nullptr;
   decltype(&nlsg_lm_create_params) lm_create_params = nullptr;
   decltype(&nlsg_lm_set_params) lm_set_params = nullptr;
+  decltype(&nlsg_lm_create_link) lm_create_link = nullptr;
   // the resident engine's LDS need with the parameter row; throws when the library cannot take
   // parameters or the shape does not fit (`shape_need` = nlsg_*_batch_lds_bytes, 0 = out of range)
   void require_params_fit(bool has_engine, bool has_set, uint64_t shape_need, int32_t n_params,
@@ -472,6 +499,7 @@ class api {
     bind_optional(h, "nlsg_bfgs_set_params", bfgs_set_params);
     bind_optional(h, "nlsg_lm_create_params", lm_create_params);
     bind_optional(h, "nlsg_lm_set_params", lm_set_params);
+    bind_optional(h, "nlsg_lm_create_link", lm_create_link);
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
   }
@@ -2306,6 +2334,14 @@ class LevenbergMarquardt {
         }
         made = true;
       }
+    }
+    if constexpr (device::has_nlls_objective<Callable>::value && device::has_link_bodies<Callable>::value) {
+      if (!api.lm_create_link)
+        throw device_error("the loaded library has no nlsg_lm_create_link (user-supplied link functions)");
+      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
+      const nlsg_lm_link link{f.value_body.c_str(), f.slope_body.c_str()};
+      api.check(api.lm_create_link(&cfg, &link, &eng));
+      made = true;
     }
     if (!made) api.check(api.lm_create(&cfg, &eng));
     std::vector<scalar_t> flat(B * n), lam(B);

@@ -103,6 +103,7 @@ BFGS_REFERENCE_ORDER = 2  # NLSG_BFGS_REFERENCE_ORDER
 
 
 OBJ_TANH_REGRESSION = 32
+OBJ_LINK_REGRESSION = 33  # NLSG_OBJ_LINK_REGRESSION: nlsg_lm_create_link
 LM_CHOLESKY, LM_QR, LM_CHOLESKY_REFERENCE_ORDER = 0, 1, 2
 
 
@@ -110,6 +111,10 @@ class LMConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("device", i32), ("stream", C.c_void_p),
                 ("objective", i32), ("solver", i32), ("batch", u64), ("m", u64), ("n", u64),
                 ("lambda_", f64), ("up", f64), ("down", f64), ("max_iter", u64), ("f_delta", f64)]
+
+
+class LMLinkC(C.Structure):  # nlsg_lm_link
+    _fields_ = [("value_body", C.c_char_p), ("slope_body", C.c_char_p)]
 
 
 NM_REFERENCE_ORDER = 1  # NLSG_NM_REFERENCE_ORDER
@@ -291,6 +296,7 @@ OPTIONAL_SYMBOLS = {
     "nlsg_lm_create_params": (C.c_int, [C.POINTER(LMConfig), C.POINTER(CustomObjectiveC), C.POINTER(_H)]),
     "nlsg_lm_set_params": (C.c_int, [_H, pd]),
     "nlsg_lm_lds_bytes": (u64, [u64, C.c_int32]),
+    "nlsg_lm_create_link": (C.c_int, [C.POINTER(LMConfig), C.POINTER(LMLinkC), C.POINTER(_H)]),
     "nlsg_bfgs_create_params": (C.c_int, [C.POINTER(BFGSConfig), C.POINTER(CustomObjectiveC), C.POINTER(_H)]),
     "nlsg_bfgs_set_params": (C.c_int, [_H, pd]),
     "nlsg_bfgs_lds_bytes": (u64, [u64, C.c_uint32]),
@@ -309,6 +315,7 @@ _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
                     "nlsg_lm_create_params": "library has no run-time objective parameters for Levenberg-Marquardt",
                     "nlsg_lm_set_params": "library has no run-time objective parameters for Levenberg-Marquardt",
                     "nlsg_lm_lds_bytes": "library has no run-time objective parameters for Levenberg-Marquardt",
+                    "nlsg_lm_create_link": "library has no user-supplied link functions for Levenberg-Marquardt",
                     "nlsg_bfgs_create_params": "library has no run-time objective parameters for BFGS",
                     "nlsg_bfgs_set_params": "library has no run-time objective parameters for BFGS",
                     "nlsg_bfgs_lds_bytes": "library has no run-time objective parameters for BFGS",

@@ -26,7 +26,9 @@ struct nlsg_lm {
                            // n <= 128, column by column beyond (A/B switch)
   uint64_t ldt = kLmN; // row stride of theta / gg on the device: 64, or n when wide
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  LmRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it
+  LmRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it;
+                     // NLSG_OBJ_LINK_REGRESSION: the Gauss-Newton evaluation kernel on the user's link
+  bool link = false;  // nlsg_lm_create_link
   int32_t n_params = 0;          // nlsg_lm_create_params: the objective's run-time doubles per problem
   double *params_dev = nullptr;  // [batch][n_params]
   bool params_set = false;
@@ -111,6 +113,17 @@ void launch_fd_iter(nlsg_lm *e, int first) {
   }
 }
 
+// Gauss-Newton model up to 64 parameters: step k (with_step) + evaluation k + 1, one wave per problem
+void launch_gn_iter(nlsg_lm *e, int first, int with_step) {
+  const unsigned grid = static_cast<unsigned>(e->p.batch);
+  if (e->link) {
+    void *args[] = {&e->p, &first, &with_step};
+    launch_module_kernel(e->rtc.iter, grid, 64, 0, e->stream, args);
+    return;
+  }
+  hipLaunchKernelGGL(lm_iter_kernel<>, dim3(grid), dim3(64), 0, e->stream, e->p, first, with_step);
+}
+
 // n > 64: evaluation (f, g, H at the current point) as one launch, a workgroup per problem
 template <int OBJ>
 void launch_wide_fd_ref(nlsg_lm *e, dim3 grid, int first) {  // NLSG_LM_CHOLESKY_REFERENCE_ORDER past 64 parameters
@@ -147,16 +160,24 @@ void launch_wide_eval(nlsg_lm *e, int first) {
   const unsigned split = e->p.fd ? static_cast<unsigned>(std::min<uint64_t>(
                                        64, std::max<uint64_t>(1, 2048 / e->p.batch))) : 1u;
   const dim3 grid(static_cast<unsigned>(e->p.batch), split);
+  if (e->link) {  // the built-in selection below, on the module's one kernel
+    void *args[] = {&e->p, &first};
+    const bool one_pass = e->p.n <= 256;
+    launch_module_kernel(e->rtc.iter, grid.x, one_pass ? 512 : 256,
+                         e->p.n > 128 && one_pass ? static_cast<unsigned>(sizeof(LmWide256Shared)) : 0u,
+                         e->stream, args);
+    return;
+  }
   if (!e->p.fd) {
     // up to 128 parameters: one pass over A, J^T J on the matrix cores
     if (e->wide_valu)
       hipLaunchKernelGGL(lm_wide_tanh_eval_kernel, grid, dim3(kLmWideThreads), 0, e->stream, e->p, first);
     else if (e->p.n <= 128)
-      hipLaunchKernelGGL(lm_wide128x8_tanh_eval_kernel, grid, dim3(512), 0, e->stream, e->p, first);
+      hipLaunchKernelGGL(lm_wide128x8_tanh_eval_kernel<>, grid, dim3(512), 0, e->stream, e->p, first);
     else if (e->p.n <= 256 && e->wide256)  // one pass over A still: 136 tiles on eight waves
-      hipLaunchKernelGGL(lm_wide256x8_tanh_eval_kernel, grid, dim3(512), sizeof(LmWide256Shared), e->stream, e->p, first);
+      hipLaunchKernelGGL(lm_wide256x8_tanh_eval_kernel<>, grid, dim3(512), sizeof(LmWide256Shared), e->stream, e->p, first);
     else  // super-blocks of 128 x 128, each on the matrix cores
-      hipLaunchKernelGGL(lm_wide_mfma_tanh_eval_kernel, grid, dim3(256), 0, e->stream, e->p, first);
+      hipLaunchKernelGGL(lm_wide_mfma_tanh_eval_kernel<>, grid, dim3(256), 0, e->stream, e->p, first);
     return;
   }
   if (e->cfg.objective == NLSG_OBJ_CUSTOM) {
@@ -185,7 +206,7 @@ int launch_solve(nlsg_lm *e) {
   else if (fd)
     launch_fd_iter(e, 1);
   else
-    hipLaunchKernelGGL(lm_iter_kernel, grid, dim3(64), 0, e->stream, e->p, 1, 0);
+    launch_gn_iter(e, 1, 0);
   uint64_t launched = 0;
   for (;;) {
     // max_iter iterations plus the turn whose stop test fires
@@ -207,9 +228,9 @@ int launch_solve(nlsg_lm *e) {
         launch_fd_iter(e, 0);
       } else if (qr) {
         hipLaunchKernelGGL(lm_qr_step_kernel<kLmQrThreads>, grid, dim3(kLmQrThreads), sizeof(LmQrShared), e->stream, e->p);
-        hipLaunchKernelGGL(lm_iter_kernel, grid, dim3(64), 0, e->stream, e->p, 0, 0);
+        launch_gn_iter(e, 0, 0);
       } else {
-        hipLaunchKernelGGL(lm_iter_kernel, grid, dim3(64), 0, e->stream, e->p, 0, 1);
+        launch_gn_iter(e, 0, 1);
       }
     }
     launched += chunk;
@@ -228,13 +249,15 @@ int launch_solve(nlsg_lm *e) {
 }  // namespace
 
 static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *custom, nlsg_lm **out,
-                     bool with_params = false);
+                     bool with_params = false, const nlsg_lm_link *link = nullptr);
 
 extern "C" {
 
 int nlsg_lm_create(const nlsg_lm_config *cfg, nlsg_lm **out) {
   if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_lm_create_custom");
+  if (cfg && cfg->objective == NLSG_OBJ_LINK_REGRESSION)
+    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_LINK_REGRESSION engines are made by nlsg_lm_create_link");
   PhaseClock clk;
   const int rc = lm_create(cfg, nullptr, out);
   call_timing().create_ms = clk.lap();
@@ -258,6 +281,16 @@ int nlsg_lm_create_params(const nlsg_lm_config *cfg, const nlsg_custom_objective
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
   PhaseClock clk;
   const int rc = lm_create(cfg, obj, out, true);
+  call_timing().create_ms = clk.lap();
+  return rc;
+}
+
+int nlsg_lm_create_link(const nlsg_lm_config *cfg, const nlsg_lm_link *link, nlsg_lm **out) {
+  if (!cfg || !link) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (cfg->objective != NLSG_OBJ_LINK_REGRESSION)
+    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_LINK_REGRESSION");
+  PhaseClock clk;
+  const int rc = lm_create(cfg, nullptr, out, false, link);
   call_timing().create_ms = clk.lap();
   return rc;
 }
@@ -286,14 +319,14 @@ int nlsg_lm_set_params(nlsg_lm *e, const double *params_host) {
 }  // extern "C"
 
 static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *custom, nlsg_lm **out,
-                     bool with_params) {
+                     bool with_params, const nlsg_lm_link *link) {
   if (!cfg || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(nlsg_lm_config))
     return fail(NLSG_ERR_INVALID_ARG, "nlsg_lm_config size mismatch (%u vs %zu)", cfg->struct_size,
                 sizeof(nlsg_lm_config));
   const bool fd = lm_fd_objective(cfg->objective);
-  if (cfg->objective != NLSG_OBJ_TANH_REGRESSION && !fd)
+  if (cfg->objective != NLSG_OBJ_TANH_REGRESSION && !(link && cfg->objective == NLSG_OBJ_LINK_REGRESSION) && !fd)
     return fail(NLSG_ERR_INVALID_ARG, "unknown objective %d", cfg->objective);
   const bool ref_order = cfg->solver == NLSG_LM_CHOLESKY_REFERENCE_ORDER;
   if (cfg->solver != NLSG_LM_CHOLESKY && cfg->solver != NLSG_LM_QR && !ref_order)
@@ -321,6 +354,8 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
     if (const int prc = check_custom_params(custom, nlsg_lm_lds_bytes(cfg->n, cfg->solver), "nlsg_lm",
                                             "nlsg_lm_create_custom"))
       return prc;
+  if (link && (!link->value_body || !link->value_body[0] || !link->slope_body || !link->slope_body[0]))
+    return fail(NLSG_ERR_INVALID_ARG, "a link needs a value body and a slope body (nlsg_lm_link)");
   int rc = check_device(cfg->device);
   if (rc) return rc;
   NLSG_HIP(hipSetDevice(cfg->device));
@@ -329,7 +364,8 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   e->cfg = *cfg;
   e->wide = wide;
   e->n_params = with_params ? custom->n_params : 0;
-  {
+  e->link = link != nullptr;
+  if (!e->link) {  // (a link engine has one evaluation kernel per shape, and the blocked step: no A/B forms)
     const char *sw = std::getenv("NLSG_LM_WIDE_MFMA");
     e->wide_valu = sw && sw[0] == '0';
     const char *w2 = std::getenv("NLSG_LM_WIDE256");
@@ -384,7 +420,7 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
     he = hipFuncSetAttribute(reinterpret_cast<const void *>(lm_wide128_step_kernel),
                              hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(LmWide128StepShared));
   if (he == hipSuccess)
-    he = hipFuncSetAttribute(reinterpret_cast<const void *>(lm_wide256x8_tanh_eval_kernel),
+    he = hipFuncSetAttribute(reinterpret_cast<const void *>(lm_wide256x8_tanh_eval_kernel<>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(LmWide256Shared));
   for (int ev = 0; ev < 2 && he == hipSuccess; ev++) {  // 139 KB at 1024 threads, 70 KB at 512
     he = hipFuncSetAttribute(ev ? reinterpret_cast<const void *>(lm_wide_chol_step_kernel<1024, true>)
@@ -403,6 +439,19 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   if (custom) {
     const uint64_t n = cfg->n;
     const int rc2 = rtc_build_lm(custom, !wide ? 0 : lm_wide_chunks(n), ref_order, &e->rtc);
+    if (rc2) {
+      nlsg_lm_destroy(e);
+      return rc2;
+    }
+  }
+  if (link) {
+    int rc2 = rtc_build_lm_link(link, cfg->n, &e->rtc);
+    if (!rc2 && cfg->n > 128 && cfg->n <= 256) {  // 70 KB of dynamic LDS: the module API's opt-in
+      const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.iter),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                static_cast<int>(sizeof(LmWide256Shared)));
+      if (ae != hipSuccess) rc2 = fail(NLSG_ERR_HIP, "device setup failed: %s", hipGetErrorString(ae));
+    }
     if (rc2) {
       nlsg_lm_destroy(e);
       return rc2;
@@ -641,8 +690,7 @@ int nlsg_lm_time_eval_kernel(nlsg_lm *e, const double *theta0_host, uint32_t rep
     if (e->wide)
       launch_wide_eval(e, 1);
     else
-      hipLaunchKernelGGL(lm_iter_kernel, dim3(static_cast<unsigned>(e->p.batch)), dim3(64), 0,
-                         e->stream, e->p, 1, 0);
+      launch_gn_iter(e, 1, 0);
     NLSG_HIP(hipEventRecord(e->ev1, e->stream));
     NLSG_HIP(hipEventSynchronize(e->ev1));
     NLSG_HIP(launches_status());
@@ -666,7 +714,7 @@ int nlsg_lm_time_qr_kernel(nlsg_lm *e, const double *theta0_host, uint32_t repea
   int rc = upload_theta(e, theta0_host);
   if (rc) return rc;
   const dim3 grid(static_cast<unsigned>(e->p.batch));
-  hipLaunchKernelGGL(lm_iter_kernel, grid, dim3(64), 0, e->stream, e->p, 1, 0);
+  launch_gn_iter(e, 1, 0);
   float total = 0.f;
   for (uint32_t r = 0; r < repeats; r++) {
     NLSG_HIP(hipEventRecord(e->ev0, e->stream));

@@ -555,7 +555,23 @@ __device__ inline void lm_publish_state(const LmParams &p, LmProblem *pr, int fi
   }
 }
 
+// ---- The link of the Gauss-Newton model r_i = y_i - phi(a_i . theta): value(z) = phi(z) and
+// slope(z, v) = phi'(z), given v = phi(z). Everything an evaluation does after these two (J = -slope a,
+// J^T J, J^T r, both steps, the stop tests) knows nothing of the model. The built-in link is tanh; any
+// other one is compiled at run time from two bodies (nlsg_lm_create_link, rtc_build_lm_link).
+// kZeroAtZero: phi(0) = 0. The narrow kernel pads its row groups with zero rows of A and y, which then
+// have r = 0 by themselves; a link without it masks the rows >= m (if constexpr: tanh pays nothing).
+// The wide kernels mask r by the row index for every link already; their padded rows of A are zeros in
+// registers, so a J row is -(slope * 0) — a zero whatever the slope, as long as it is finite: a custom
+// link's slope is masked too, which takes phi'(0) = inf or NaN out of the picture.
+struct LmTanhLink {
+  static constexpr bool kZeroAtZero = true;
+  __device__ static inline double value(double z) { return det_tanh(z); }
+  __device__ static inline double slope(double, double v) { return 1 - v * v; }
+};
+
 // theta_lds: the parameters as the step left them in LDS (nullptr: read them from global)
+template <typename Link>
 __device__ inline void lm_eval_wave(const LmParams &p, int first, uint64_t pid, LmWaveShared sh,
                                     const double *theta_lds) {
   LmProblem *pr = p.prob + pid;
@@ -605,9 +621,14 @@ __device__ inline void lm_eval_wave(const LmParams &p, int first, uint64_t pid, 
     zsel = zsel + lane_xor<1>(zsel);
     // tanh / residual / weight once per row: the lanes of a half with the same lp >> 2 hold row
     // k = lp >> 2 (rows 2k + half of the group)
-    const double tsel = det_tanh(zsel);
-    const double rsel = ysel - tsel;
-    const double wsel = 1 - tsel * tsel;
+    const double tsel = Link::value(zsel);
+    double rsel = ysel - tsel;
+    double wsel = Link::slope(zsel, tsel);
+    if constexpr (!Link::kZeroAtZero) {  // a padded row: phi(0) is no residual, phi'(0) no weight
+      const bool in = 16 * s + 2 * static_cast<uint64_t>(lp >> 2) + half < p.m;
+      rsel = in ? rsel : 0.0;
+      wsel = in ? wsel : 0.0;
+    }
     if ((lp & 3) == 0) sh.r[2 * (lp >> 2) + half] = rsel;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
@@ -734,6 +755,7 @@ __device__ inline bool lm_step_wave(const LmParams &p, uint64_t pid, LmStepShare
 // tile | r (the new parameters wait in `upd`, which the tile does not reach).
 // `with_step` = 0: evaluation only (the first launch, and every launch of the QR pipeline, whose
 // step is lm_qr_step_kernel).
+template <typename Link = LmTanhLink>
 __global__ __launch_bounds__(64, 2) void lm_iter_kernel(LmParams p, int first, int with_step) {
   __shared__ __align__(16) double smem[kLmTri + 128];
   static_assert(16 * kLmJStride + 16 <= kLmTri + 64, "the Jacobian tile must not reach upd");
@@ -746,7 +768,7 @@ __global__ __launch_bounds__(64, 2) void lm_iter_kernel(LmParams p, int first, i
       theta_lds = smem + kLmTri + 64;
     }
   }
-  lm_eval_wave(p, first, pid, LmWaveShared{smem, smem + 16 * kLmJStride}, theta_lds);
+  lm_eval_wave<Link>(p, first, pid, LmWaveShared{smem, smem + 16 * kLmJStride}, theta_lds);
 }
 
 // ---- The reference's default functors on a built-in objective: when the
@@ -2254,7 +2276,7 @@ __host__ __device__ constexpr int lm_w128_slot(const LmW128Tiles &t, int b) {
 }
 
 // returns: some off-diagonal entry this wave published exceeds is_diagonal's threshold (:295-307)
-template <int W>
+template <int W, typename Link>
 __device__ inline bool lm_wide128_run8(const LmParams &p, int first, uint64_t pid, LmWide128Shared &sh,
                                        bool vec) {
   constexpr LmW128Tiles T = lm_w128_tiles(W);
@@ -2293,9 +2315,10 @@ __device__ inline bool lm_wide128_run8(const LmParams &p, int first, uint64_t pi
     double z = __builtin_fma(a[3], t3, __builtin_fma(a[2], t2, __builtin_fma(a[1], t1, a[0] * t0)));
     butterfly_levels<16>([&](auto off) { z = z + lane_xor<decltype(off)::value>(z); });
     const bool in = 16 * s + rr < m;
-    const double tz = det_tanh(z);
+    const double tz = Link::value(z);
     const double res = in ? yv - tz : 0.0;
-    const double wgt = 1 - tz * tz;
+    double wgt = Link::slope(z, tz);
+    if constexpr (!Link::kZeroAtZero) wgt = in ? wgt : 0.0;  // (the row's a[] are zeros: J = -(0 * 0))
     double *row = &sh.J[buf][rr * S];
     double2 lo, hi;
     lo.x = -(wgt * a[0]);
@@ -2388,6 +2411,7 @@ __device__ inline bool lm_wide128_run8(const LmParams &p, int first, uint64_t pi
   return offd;
 }
 
+template <typename Link = LmTanhLink>
 __global__ __launch_bounds__(512, 4) void lm_wide128x8_tanh_eval_kernel(LmParams p, int first) {
   __shared__ __align__(16) LmWide128Shared sh;
   const uint64_t pid = blockIdx.x;
@@ -2395,14 +2419,14 @@ __global__ __launch_bounds__(512, 4) void lm_wide128x8_tanh_eval_kernel(LmParams
   const bool vec = (p.n & 1) == 0;
   bool offd;
   switch (__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6)) {
-    case 0: offd = lm_wide128_run8<0>(p, first, pid, sh, vec); break;
-    case 1: offd = lm_wide128_run8<1>(p, first, pid, sh, vec); break;
-    case 2: offd = lm_wide128_run8<2>(p, first, pid, sh, vec); break;
-    case 3: offd = lm_wide128_run8<3>(p, first, pid, sh, vec); break;
-    case 4: offd = lm_wide128_run8<4>(p, first, pid, sh, vec); break;
-    case 5: offd = lm_wide128_run8<5>(p, first, pid, sh, vec); break;
-    case 6: offd = lm_wide128_run8<6>(p, first, pid, sh, vec); break;
-    default: offd = lm_wide128_run8<7>(p, first, pid, sh, vec); break;
+    case 0: offd = lm_wide128_run8<0, Link>(p, first, pid, sh, vec); break;
+    case 1: offd = lm_wide128_run8<1, Link>(p, first, pid, sh, vec); break;
+    case 2: offd = lm_wide128_run8<2, Link>(p, first, pid, sh, vec); break;
+    case 3: offd = lm_wide128_run8<3, Link>(p, first, pid, sh, vec); break;
+    case 4: offd = lm_wide128_run8<4, Link>(p, first, pid, sh, vec); break;
+    case 5: offd = lm_wide128_run8<5, Link>(p, first, pid, sh, vec); break;
+    case 6: offd = lm_wide128_run8<6, Link>(p, first, pid, sh, vec); break;
+    default: offd = lm_wide128_run8<7, Link>(p, first, pid, sh, vec); break;
   }
   // is_diagonal's verdict on the matrix just published, for the step (it saves the step a pass over H)
   const int any = __syncthreads_or(offd);
@@ -2424,7 +2448,7 @@ struct LmWide256Shared {  // 70 KB: dynamic LDS
   double r[2][16];
 };
 
-template <int W>
+template <int W, typename Link>
 __device__ inline bool lm_wide256_run8(const LmParams &p, int first, uint64_t pid, LmWide256Shared &sh,
                                        bool vec) {
   constexpr int S = kLmW256Stride;
@@ -2470,9 +2494,10 @@ __device__ inline bool lm_wide256_run8(const LmParams &p, int first, uint64_t pi
     for (int b = 1; b < 4; b++) z = __builtin_fma(a[2 * b + 1], tv[2 * b + 1], __builtin_fma(a[2 * b], tv[2 * b], z));
     butterfly_levels<16>([&](auto off) { z = z + lane_xor<decltype(off)::value>(z); });
     const bool in = 16 * s + rr < m;
-    const double tz = det_tanh(z);
+    const double tz = Link::value(z);
     const double res = in ? yv - tz : 0.0;
-    const double wgt = 1 - tz * tz;
+    double wgt = Link::slope(z, tz);
+    if constexpr (!Link::kZeroAtZero) wgt = in ? wgt : 0.0;  // (the row's a[] are zeros: J = -(0 * 0))
     double *row = &sh.J[buf][rr * S];
 #pragma unroll
     for (int b = 0; b < 4; b++) {
@@ -2573,6 +2598,7 @@ __device__ inline bool lm_wide256_run8(const LmParams &p, int first, uint64_t pi
   return offd;
 }
 
+template <typename Link = LmTanhLink>
 __global__ __launch_bounds__(512, 2) void lm_wide256x8_tanh_eval_kernel(LmParams p, int first) {
   extern __shared__ __align__(16) unsigned char lm_w256_smem[];
   LmWide256Shared &sh = *reinterpret_cast<LmWide256Shared *>(lm_w256_smem);
@@ -2581,14 +2607,14 @@ __global__ __launch_bounds__(512, 2) void lm_wide256x8_tanh_eval_kernel(LmParams
   const bool vec = (p.n & 1) == 0;
   bool offd;
   switch (__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6)) {
-    case 0: offd = lm_wide256_run8<0>(p, first, pid, sh, vec); break;
-    case 1: offd = lm_wide256_run8<1>(p, first, pid, sh, vec); break;
-    case 2: offd = lm_wide256_run8<2>(p, first, pid, sh, vec); break;
-    case 3: offd = lm_wide256_run8<3>(p, first, pid, sh, vec); break;
-    case 4: offd = lm_wide256_run8<4>(p, first, pid, sh, vec); break;
-    case 5: offd = lm_wide256_run8<5>(p, first, pid, sh, vec); break;
-    case 6: offd = lm_wide256_run8<6>(p, first, pid, sh, vec); break;
-    default: offd = lm_wide256_run8<7>(p, first, pid, sh, vec); break;
+    case 0: offd = lm_wide256_run8<0, Link>(p, first, pid, sh, vec); break;
+    case 1: offd = lm_wide256_run8<1, Link>(p, first, pid, sh, vec); break;
+    case 2: offd = lm_wide256_run8<2, Link>(p, first, pid, sh, vec); break;
+    case 3: offd = lm_wide256_run8<3, Link>(p, first, pid, sh, vec); break;
+    case 4: offd = lm_wide256_run8<4, Link>(p, first, pid, sh, vec); break;
+    case 5: offd = lm_wide256_run8<5, Link>(p, first, pid, sh, vec); break;
+    case 6: offd = lm_wide256_run8<6, Link>(p, first, pid, sh, vec); break;
+    default: offd = lm_wide256_run8<7, Link>(p, first, pid, sh, vec); break;
   }
   const int any = __syncthreads_or(offd);  // is_diagonal's verdict, for the step
   if (threadIdx.x == 0) p.prob[pid].upper = 2 | (any ? 1 : 0);
@@ -2767,6 +2793,7 @@ __device__ __attribute__((noinline)) bool lm_wide_mfma_pass(const LmParams &p, u
   return offd;
 }
 
+template <typename Link = LmTanhLink>
 __global__ __launch_bounds__(256, 2) void lm_wide_mfma_tanh_eval_kernel(LmParams p, int first) {
   __shared__ __align__(16) LmWideMfmaShared sh;
   const uint64_t pid = blockIdx.x;
@@ -2822,11 +2849,11 @@ __global__ __launch_bounds__(256, 2) void lm_wide_mfma_tanh_eval_kernel(LmParams
 #pragma unroll
       for (int q = 0; q < 2; q++) {
         const uint64_t i = 16 * s + 2 * (k0 + q) + half;
-        const double tz = det_tanh(z[q]);
+        const double tz = Link::value(z[q]);
         const double res = in[q] ? yv[q] - tz : 0.0;
-        if (lp == 0 && in[q]) {
-          rg[i] = res;
-          wg[i] = 1 - tz * tz;
+        if (lp == 0 && in[q]) {  // (rw holds 2 m doubles per problem: rows >= m have no slot, and
+          rg[i] = res;           // lm_wide_mfma_pass takes 0 for their r and weight without reading)
+          wg[i] = Link::slope(z[q], tz);
         }
         fw = __builtin_fma(res, res, fw);
       }

@@ -65,6 +65,9 @@ struct LmRtcKernels {  // finite-difference model (default functors) around the 
 // wide_chunks != 0: the evaluation kernel of the n > 64 path (a probe point of wide_chunks x 128
 // coordinates per wave) instead of the one-wave iteration kernel
 int rtc_build_lm(const nlsg_custom_objective *obj, int wide_chunks, bool reference_order, LmRtcKernels *out);
+// the Gauss-Newton evaluation kernel of n parameters (lm_iter_kernel to 64, the one-pass kernels to 128
+// and 256, the super-block kernel beyond) on the link `value_body` / `slope_body` describe; k->iter
+int rtc_build_lm_link(const nlsg_lm_link *link, uint64_t n, LmRtcKernels *out);
 void rtc_release(LmRtcKernels *k);
 struct HybRtcKernels {
   hipModule_t mod = nullptr;

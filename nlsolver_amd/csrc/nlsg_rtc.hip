@@ -2,6 +2,7 @@
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -69,6 +70,10 @@ int rtc_load(const char *path_in) {
 
 }  // namespace
 
+static int rtc_compile_source(const std::string &src, const char *what,
+                              const std::vector<std::string> &name_exprs, hipModule_t *mod_out,
+                              std::vector<hipFunction_t> *fns_out, bool keep_code = false);
+
 // Compiles `kernel_header` around the user's Objective<NLSG_OBJ_CUSTOM> and returns the module
 // with one function per name expression (kernel template-ids).
 // wave_rows_offset >= 0 (rtc_build_bfgs, with n_params > 0 only): the kernels own a wave per solve, so the
@@ -78,9 +83,6 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
                        std::vector<hipFunction_t> *fns_out, long wave_rows_offset = -1) {
   if (!obj || !obj->term_body || !obj->term_body[0])
     return fail(NLSG_ERR_INVALID_ARG, "a custom objective needs a term body");
-  int rc = rtc_load(nullptr);
-  if (rc) return rc;
-  RtcApi &api = rtc_api();
   // n_params > 0 (resident batch engines and nlsg_nm / nmpso / lm / bfgs_create_params; every
   // *_create_custom besides has rejected it): the macro
   // puts the solve's row into static LDS (nlsg_common.h) and the bodies read it as p(k); for BFGS a
@@ -128,7 +130,68 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
            "  __device__ static inline double whole(const X &, uint64_t) { return 0.0; }\n"
            "};\n}  // namespace nlsg\n";
   }
+  return rtc_compile_source(src, "custom objective", name_exprs, mod_out, fns_out);
+}
 
+// A compiled code object and the lowered names of its kernels, kept by source text: a second engine
+// of the same link and kernel (another max_iter, another solver, the drop-in class's engine per call)
+// loads it instead of compiling for seconds. The oldest entries go once there are kRtcKeptMax.
+struct RtcKept {
+  std::vector<char> code;
+  std::vector<std::string> lowered;
+  uint64_t age = 0;
+};
+constexpr size_t kRtcKeptMax = 32;
+static std::map<std::string, RtcKept> &rtc_kept() {
+  static std::map<std::string, RtcKept> m;
+  return m;
+}
+static std::mutex &rtc_kept_mutex() {
+  static std::mutex m;
+  return m;
+}
+
+static int rtc_load_code(const std::vector<char> &code, const std::vector<std::string> &lowered,
+                         const char *what, hipModule_t *mod_out, std::vector<hipFunction_t> *fns_out) {
+  hipModule_t mod = nullptr;
+  hipError_t he = hipModuleLoadData(&mod, code.data());
+  std::vector<hipFunction_t> fns(lowered.size(), nullptr);
+  for (size_t i = 0; i < lowered.size() && he == hipSuccess; i++)
+    he = hipModuleGetFunction(&fns[i], mod, lowered[i].c_str());
+  if (he != hipSuccess) {
+    if (mod) hipModuleUnload(mod);
+    return fail(NLSG_ERR_HIP, "loading the compiled %s failed: %s", what, hipGetErrorString(he));
+  }
+  *mod_out = mod;
+  *fns_out = fns;
+  return NLSG_OK;
+}
+
+// `src` (which includes the embedded headers by name) to a loaded module, one function per name
+// expression; `what` names the user's part of it in the error of a failed compilation.
+// keep_code: look the source up among the kept code objects first, and keep this one
+static int rtc_compile_source(const std::string &src, const char *what,
+                              const std::vector<std::string> &name_exprs, hipModule_t *mod_out,
+                              std::vector<hipFunction_t> *fns_out, bool keep_code) {
+  const int rc = rtc_load(nullptr);
+  if (rc) return rc;
+  RtcApi &api = rtc_api();
+  std::string key;
+  if (keep_code) {
+    key = src;
+    for (const std::string &n : name_exprs) key += '\n' + n;
+    RtcKept hit;
+    bool found = false;
+    {
+      std::lock_guard<std::mutex> hold(rtc_kept_mutex());
+      const auto it = rtc_kept().find(key);
+      if (it != rtc_kept().end()) {
+        hit = it->second;
+        found = true;
+      }
+    }
+    if (found) return rtc_load_code(hit.code, hit.lowered, what, mod_out, fns_out);
+  }
   const int nh = static_cast<int>(sizeof(kEmbedded) / sizeof(kEmbedded[0]));
   std::vector<const char *> names(nh), texts(nh);
   for (int i = 0; i < nh; i++) {
@@ -155,7 +218,7 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
     if (ls) api.GetProgramLog(prog, &log[0]);
     api.DestroyProgram(&prog);
     if (log.size() > 400) log.resize(400);
-    return fail(NLSG_ERR_INVALID_ARG, "custom objective does not compile: %s", log.c_str());
+    return fail(NLSG_ERR_INVALID_ARG, "%s does not compile: %s", what, log.c_str());
   }
   size_t cs = 0;
   if (api.GetCodeSize(prog, &cs) != HIPRTC_SUCCESS || cs == 0) {
@@ -167,25 +230,33 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
     api.DestroyProgram(&prog);
     return fail(NLSG_ERR_HIP, "hiprtcGetCode failed");
   }
-  hipModule_t mod = nullptr;
-  hipError_t he = hipModuleLoadData(&mod, code.data());
-  std::vector<hipFunction_t> fns(name_exprs.size(), nullptr);
-  for (size_t i = 0; i < name_exprs.size() && he == hipSuccess; i++) {
-    const char *lowered = nullptr;  // lives in the program: look the function up before destroying it
-    if (api.GetLoweredName(prog, name_exprs[i].c_str(), &lowered) != HIPRTC_SUCCESS) {
-      he = hipErrorNotFound;
-      break;
+  std::vector<std::string> lowered_names;
+  for (const std::string &n : name_exprs) {
+    const char *lowered = nullptr;  // lives in the program: copied before it is destroyed
+    if (api.GetLoweredName(prog, n.c_str(), &lowered) != HIPRTC_SUCCESS || !lowered) {
+      api.DestroyProgram(&prog);
+      return fail(NLSG_ERR_HIP, "loading the compiled %s failed: %s", what, hipGetErrorString(hipErrorNotFound));
     }
-    he = hipModuleGetFunction(&fns[i], mod, lowered);
+    lowered_names.push_back(lowered);
   }
   api.DestroyProgram(&prog);
-  if (he != hipSuccess) {
-    if (mod) hipModuleUnload(mod);
-    return fail(NLSG_ERR_HIP, "loading the compiled objective failed: %s", hipGetErrorString(he));
+  const int lrc = rtc_load_code(code, lowered_names, what, mod_out, fns_out);
+  if (!lrc && keep_code) {
+    static uint64_t clock = 0;
+    std::lock_guard<std::mutex> hold(rtc_kept_mutex());
+    std::map<std::string, RtcKept> &kept = rtc_kept();
+    if (kept.size() >= kRtcKeptMax) {
+      auto oldest = kept.begin();
+      for (auto it = kept.begin(); it != kept.end(); ++it)
+        if (it->second.age < oldest->second.age) oldest = it;
+      kept.erase(oldest);
+    }
+    RtcKept &slot = kept[key];
+    slot.code = std::move(code);
+    slot.lowered = std::move(lowered_names);
+    slot.age = ++clock;
   }
-  *mod_out = mod;
-  *fns_out = fns;
-  return NLSG_OK;
+  return lrc;
 }
 
 static std::string targs(int chunks, bool vec) {
@@ -407,6 +478,36 @@ int rtc_build_lm(const nlsg_custom_objective *obj, int wide_chunks, bool referen
                                      : "nlsg::lm_wide_fd_eval_kernel<" + id + ", " + std::to_string(wide_chunks) + ">")
                   : "nlsg::lm_fd_iter_kernel<" + id + (reference_order ? ", true>" : ">");
   const int rc = rtc_compile(obj, "nlsg_lm_kernels.h", {name}, &k.mod, &f);
+  if (rc) return rc;
+  k.iter = f[0];
+  *out = k;
+  return NLSG_OK;
+}
+// The Gauss-Newton evaluation kernel of the shape, instantiated on a link made of the two bodies
+// (nlsg_lm_kernels.h LmTanhLink is the pattern). The same selection by n as the built-in engine's, the
+// same flags as the offline build (rtc_compile_source): a body that restates tanh gives the built-in
+// kernel's bits.
+int rtc_build_lm_link(const nlsg_lm_link *link, uint64_t n, LmRtcKernels *out) {
+  if (!link || !link->value_body || !link->value_body[0] || !link->slope_body || !link->slope_body[0])
+    return fail(NLSG_ERR_INVALID_ARG, "a link needs a value body and a slope body");
+  std::string src =
+      "#include \"nlsg_lm_kernels.h\"\n"
+      "namespace nlsg {\n"
+      "struct LmUserLink {\n"
+      "  static constexpr bool kZeroAtZero = false;\n"  // (not known of a body: the rows >= m are masked)
+      "  __device__ static inline double value(double z) {\n#line 1 \"value_body\"\n";
+  src += link->value_body;
+  src += "\n  }\n"
+         "  __device__ static inline double slope(double z, double v) {\n    (void)z;\n    (void)v;\n#line 1 "
+         "\"slope_body\"\n";
+  src += link->slope_body;
+  src += "\n  }\n};\n}  // namespace nlsg\n";
+  const char *kernel = n <= 64 ? "lm_iter_kernel" : n <= 128 ? "lm_wide128x8_tanh_eval_kernel"
+                     : n <= 256 ? "lm_wide256x8_tanh_eval_kernel" : "lm_wide_mfma_tanh_eval_kernel";
+  std::vector<hipFunction_t> f;
+  LmRtcKernels k;
+  const int rc = rtc_compile_source(src, "link", {std::string("nlsg::") + kernel + "<nlsg::LmUserLink>"},
+                                    &k.mod, &f, true);
   if (rc) return rc;
   k.iter = f[0];
   *out = k;

@@ -5,7 +5,8 @@ reference's default functors (finite-difference gradient and Hessian, nlsolver.h
 Reference interface (nlsolver.h:3428-3463):
     LevenbergMarquardt<Callable, scalar_t, Grad, Hess>(f, lambda = 10, upward_mult = 10,
         downward_mult = 10, max_iter = 100, f_delta = 1e-12, g, h).minimize(x)
-Here `f` is a TanhRegression model (f = sum r^2, Grad = 2 J^T r, Hess = 2 J^T J evaluated by the
+Here `f` is a TanhRegression model, or a LinkRegression (the same model with another link function,
+given as source text) (f = sum r^2, Grad = 2 J^T r, Hess = 2 J^T J evaluated by the
 kernels); minimize() takes one start (n,) or a batch (batch, n) — BASELINE config 4.
 """
 import ctypes as C
@@ -32,8 +33,59 @@ class TanhRegression:
         return float(r @ r)
 
 
+class LinkRegression:
+    """r_i(theta) = y_i - phi(sum_j A_ij theta_j); A: (batch, m, n), y: (batch, m) as TanhRegression.
+
+    value: the body of `double value(double z)` — phi(z); slope: the body of
+    `double slope(double z, double v)` — phi'(z) with v = value(z) at hand. Both are HIP source compiled
+    when an engine is made, and may call the library's deterministic device math (det_exp, det_log,
+    det_tanh, ...). The engine runs the Gauss-Newton kernels of TanhRegression (J^T J on the matrix
+    cores, Cholesky or QR step) instantiated on this link.
+
+    host: an optional numpy callable phi(z) for __call__ (f at a point, on the CPU); the device never
+    uses it."""
+    nlsg_nlls_objective = _capi.OBJ_LINK_REGRESSION
+
+    def __init__(self, A, y, value, slope, host=None):
+        self.A = np.ascontiguousarray(A, dtype=np.float64)
+        self.y = np.ascontiguousarray(y, dtype=np.float64)
+        if self.A.ndim == 2:
+            self.A, self.y = self.A[None], self.y[None]
+        if self.A.ndim != 3 or self.y.shape != self.A.shape[:2]:
+            raise ValueError(f"A must be (batch, m, n) or (m, n) and y its (batch, m) or (m,): got "
+                             f"{self.A.shape} and {self.y.shape}")
+        if not isinstance(value, str) or not isinstance(slope, str) or not value.strip() or not slope.strip():
+            raise TypeError("value and slope are the source text of the link's two function bodies")
+        self.value_body, self.slope_body, self.host = value, slope, host
+
+    def __call__(self, theta, problem=0):
+        if self.host is None:
+            raise TypeError("this LinkRegression has no host= link: its phi exists as device source only")
+        r = self.y[problem] - self.host(self.A[problem] @ np.asarray(theta, dtype=np.float64))
+        return float(r @ r)
+
+    @classmethod
+    def tanh(cls, A, y):
+        """TanhRegression through the link mechanism: the same bits"""
+        return cls(A, y, "return det_tanh(z);", "return 1 - v * v;", host=np.tanh)
+
+    @classmethod
+    def logistic(cls, A, y):
+        return cls(A, y, "return 1.0 / (1.0 + det_exp(-z));", "return v * (1.0 - v);",
+                   host=lambda z: 1.0 / (1.0 + np.exp(-z)))
+
+    @classmethod
+    def exp(cls, A, y):
+        return cls(A, y, "return det_exp(z);", "return v;", host=np.exp)
+
+    @classmethod
+    def identity(cls, A, y):
+        """plain linear least squares, r = y - A theta"""
+        return cls(A, y, "return z;", "return 1.0;", host=lambda z: z)
+
+
 class LMEngine:
-    """model: a TanhRegression, or the name / id of a built-in objective ("rosenbrock", "sphere",
+    """model: a TanhRegression or a LinkRegression, or the name / id of a built-in objective ("rosenbrock", "sphere",
     "styblinski_tang") or a CustomObjective, with batch= and n= (default functors: fin_diff +
     fin_diff_h).
 
@@ -91,6 +143,11 @@ class LMEngine:
             obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
                                          int(custom.chain), self.n_params)
             check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+        elif isinstance(model, LinkRegression):
+            create = require("nlsg_lm_create_link")
+            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
+            link = _capi.LMLinkC(model.value_body.encode(), model.slope_body.encode())
+            check(create(C.byref(cfg), C.byref(link), C.byref(self._h)))
         else:
             check(lib().nlsg_lm_create(C.byref(cfg), C.byref(self._h)))
         if not fd:

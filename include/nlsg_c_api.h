@@ -225,6 +225,21 @@ int nlsg_de_download(nlsg_de *e, double *pop_host, double *scores_host,
 /* Replace the current shard population and scores (tests, checkpoint/resume). */
 int nlsg_de_upload(nlsg_de *e, const double *pop_host, const double *scores_host);
 
+/* Test access to the generation's lower-bound rejection (65 <= dim <= 1024, strategy random,
+ * minimising, Rosenbrock or Sphere, a high crossover rate; NLSG_DE_BOUND=0 in the environment at
+ * create switches it off): a trial whose terms over mutant coordinates alone already reach the
+ * agent's score is rejected without reading the agent's row. No result depends on it.
+ *   nlsg_de_bound_counts : out3 = agents since nlsg_de_init for which the bound decided / it did
+ *                          not and the trial was rejected / it did not (or no coordinate was
+ *                          kept) and the trial was accepted. Requires cfg.trace. Synchronises.
+ *   nlsg_de_bound_state  : whether this engine uses the bound, and the period (a power of two, in
+ *                          generations) at which an agent it did not decide tries it again
+ *   nlsg_de_bound_gate   : 1 when an engine of these settings would use it (host only)
+ * Optional symbols (NLSG_ABI_VERSION stays 1): look them up before relying on them. */
+int nlsg_de_bound_counts(nlsg_de *e, uint64_t *out3);
+int nlsg_de_bound_state(const nlsg_de *e, int32_t *enabled, uint32_t *retry_period);
+int nlsg_de_bound_gate(int32_t objective, int32_t strategy, int32_t minimize, double CR, uint64_t dim);
+
 /* Measurement aid for bench.py: launches ONLY the generation kernel `launches`
  * times back to back on the engine's stream (buffers ping-pong, solver state is
  * restored afterwards) bracketed by two hipEvents; returns total milliseconds. */

@@ -531,6 +531,62 @@ __device__ inline double wave_objective(const double (&xv)[CHUNKS][2], uint64_t 
   return O::finish(wave_sum(acc), D);
 }
 
+// Objectives whose every computed term is >= +0 or NaN and whose finish is the identity: a sum of
+// squares evaluated without a subtraction at its top. Not Styblinski-Tang (negative terms), not
+// Rastrigin (the device cosine can leave a term a few ulps below 0), not a user objective
+// (unknown): false unless specialised.
+template <int OBJ>
+struct TermsNonNegative {
+  static constexpr bool value = false;
+};
+template <>
+struct TermsNonNegative<NLSG_OBJ_ROSENBROCK> {
+  static constexpr bool value = true;
+};
+template <>
+struct TermsNonNegative<NLSG_OBJ_SPHERE> {
+  static constexpr bool value = true;
+};
+
+// wave_objective over the terms whose coordinates are all `known`, +0.0 added in place of every
+// other term: the same per-lane order and the same butterfly, so for TermsNonNegative objectives
+// the result is <= wave_objective(xv) bit for bit whatever the unknown coordinates hold (round-to-
+// nearest addition is monotone in each operand; a NaN among the known terms gives NaN, which
+// compares false), and equal to it when every coordinate is known (acc >= +0 or NaN, and
+// acc + +0.0 == acc). The neighbour's flag travels the way its value does.
+template <int OBJ, int CHUNKS>
+__device__ inline double wave_objective_masked(const double (&xv)[CHUNKS][2], const bool (&known)[CHUNKS][2],
+                                               uint64_t D) {
+  using O = Objective<OBJ>;
+  static_assert(!O::kWhole, "term objectives only");
+  const int lane = lane_id();
+  const uint64_t nt = O::n_terms(D);
+  double acc = 0.0;
+#pragma unroll
+  for (int c = 0; c < CHUNKS; c++) {
+    const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+    double xn = 0.0;
+    bool kn = true, k1 = true;  // without a chain a term reads x[i] alone
+    if (O::kChain) {
+      const double same = lane_down1(xv[c][0]);
+      const uint32_t f0 = known[c][0] ? 1u : 0u;
+      const uint32_t fsame = dpp_mov32<0x130, 0xF>(f0, f0);
+      double next = 0.0;
+      uint32_t fnext = 0;
+      if (c + 1 < CHUNKS) {
+        next = lane_first(xv[c + 1][0]);
+        fnext = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(known[c + 1][0] ? 1 : 0));
+      }
+      xn = (lane == 63) ? next : same;
+      kn = ((lane == 63) ? fnext : fsame) != 0;
+      k1 = known[c][1];
+    }
+    if (e0 < nt) acc = acc + ((known[c][0] && k1) ? O::term(xv[c][0], xv[c][1]) : 0.0);
+    if (e0 + 1 < nt) acc = acc + ((known[c][1] && kn) ? O::term(xv[c][1], xn) : 0.0);
+  }
+  return O::finish(wave_sum(acc), D);
+}
+
 
 // The lane's share of wave_objective (its terms, added in order) before the butterfly, for callers
 // that reduce several points at once (wave_sum4); term objectives only.

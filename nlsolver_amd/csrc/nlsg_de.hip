@@ -3,6 +3,7 @@
 // the kernels of nlsg_de_kernels.h. No CPU fallback: every entry point either
 // runs on a gfx950 device or returns an error.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <new>
 #include <vector>
@@ -169,15 +170,19 @@ void launch_generation(nlsg_de *e, int par, uint64_t generation, int ignore_done
     }
     return;
   }
-#define CALL(OBJ, C)                                                                          \
-  if (e->p.vec)                                                                               \
-    hipLaunchKernelGGL((de_generation_kernel<OBJ, C, true>), grid, block, 0, e->stream, e->p, \
-                       par, generation, ignore_done);                                         \
-  else                                                                                        \
-    hipLaunchKernelGGL((de_generation_kernel<OBJ, C, false>), grid, block, 0, e->stream,      \
-                       e->p, par, generation, ignore_done)
+  // (an engine that uses the bound launches the instantiation that has it: DeParams.bound)
+#define CALL_B(OBJ, C, V, B)                                                                   \
+  hipLaunchKernelGGL((de_generation_kernel<OBJ, C, V, B>), grid, block, 0, e->stream, e->p, par, \
+                     generation, ignore_done)
+#define CALL(OBJ, C)                                                   \
+  if (e->p.bound) {                                                    \
+    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value);  \
+    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value);          \
+  } else if (e->p.vec) CALL_B(OBJ, C, true, false);                    \
+  else CALL_B(OBJ, C, false, false)
   NLSG_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
 #undef CALL
+#undef CALL_B
 }
 
 template <int OBJ>
@@ -221,15 +226,17 @@ void launch_fused_turn(nlsg_de *e, int par, uint64_t generation) {
     }
     return;
   }
-#define CALL(OBJ, C)                                                                        \
-  if (e->p.vec)                                                                             \
-    hipLaunchKernelGGL((de_turn_kernel<OBJ, C, true>), grid, block, 0, e->stream, e->p, par, \
-                       generation);                                                         \
-  else                                                                                      \
-    hipLaunchKernelGGL((de_turn_kernel<OBJ, C, false>), grid, block, 0, e->stream, e->p,    \
-                       par, generation)
+#define CALL_B(OBJ, C, V, B) \
+  hipLaunchKernelGGL((de_turn_kernel<OBJ, C, V, B>), grid, block, 0, e->stream, e->p, par, generation)
+#define CALL(OBJ, C)                                                   \
+  if (e->p.bound) {                                                    \
+    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value);  \
+    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value);          \
+  } else if (e->p.vec) CALL_B(OBJ, C, true, false);                    \
+  else CALL_B(OBJ, C, false, false)
   NLSG_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
 #undef CALL
+#undef CALL_B
 }
 
 // Head of turn k outside a fused turn, one launch. rec_dev == nullptr: one GPU, the head
@@ -412,6 +419,8 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.best_x), D * sizeof(double));
   if (he == hipSuccess && cfg->trace)
     he = alloc(reinterpret_cast<void **>(&p.trace), n * kTraceWords * sizeof(uint64_t));
+  if (he == hipSuccess && cfg->trace)  // the bound's path counters (cleared by init)
+    he = alloc(reinterpret_cast<void **>(&p.counts), 3 * sizeof(uint64_t));
   if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.state), sizeof(DeState));
   p.ntiles = static_cast<uint32_t>((n + kTile - 1) / kTile);
   if (he == hipSuccess)
@@ -464,6 +473,25 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   // buffers inside the Infinity Cache): 47.8 -> 46.6 us — the streamed stores win at both sizes
   p.stream = 1;
   if (const char *sv = std::getenv("NLSG_DE_STREAM")) p.stream = sv[0] == '1' ? 1 : 0;  // A/B switch
+  // reject on the mutant-only terms (DeParams.bound). A/B switches, read here like NLSG_DE_STREAM:
+  // NLSG_DE_BOUND=0 off; NLSG_DE_BOUND_CR / NLSG_DE_BOUND_RETRY another threshold / retry period
+  // (the sweeps of DESIGN.md section 3)
+  double min_cr = kDeBoundMinCR, max_cr = kDeBoundMaxCR;
+  uint32_t retry = kDeBoundRetry;
+  if (const char *bc = std::getenv("NLSG_DE_BOUND_CR")) {  // from this rate up, CR >= 1 included
+    min_cr = std::atof(bc);
+    max_cr = HUGE_VAL;
+  }
+  if (const char *br = std::getenv("NLSG_DE_BOUND_RETRY")) {
+    const long r = std::atol(br);
+    if (r >= 1 && r <= (1l << 30) && (r & (r - 1)) == 0) retry = static_cast<uint32_t>(r);
+  }
+  const char *bo = std::getenv("NLSG_DE_BOUND");
+  p.bound = !custom && !e->group && !e->long_rows && !(bo && bo[0] == '0') &&
+                    de_bound_gate(cfg->objective, cfg->strategy, cfg->minimize != 0, cfg->CR, D, min_cr, max_cr)
+                ? 1
+                : 0;
+  p.retry_mask = retry - 1;
   if (custom) {
     const int rc2 = rtc_build_de(custom, e->long_rows ? 0 : e->chunks, p.vec != 0, e->group, &e->rtc);
     if (rc2) {
@@ -496,6 +524,7 @@ int nlsg_de_destroy(nlsg_de *e) {
   }
   pool_free(e->p.best_x);
   pool_free(e->p.trace);
+  pool_free(e->p.counts);
   pool_free(e->p.state);
   pool_free(e->p.part);
   pool_free(e->p.ticket);
@@ -522,6 +551,7 @@ int nlsg_de_init(nlsg_de *e, const double *x0_host) {
   int rcj = join_side(e);  // a previous run's last head may still be queued on the side stream
   if (rcj) return rcj;
   hipLaunchKernelGGL(de_reset_state_kernel, dim3(1), dim3(1), 0, e->stream, e->p);
+  if (e->p.counts) NLSG_HIP(hipMemsetAsync(e->p.counts, 0, 3 * sizeof(uint64_t), e->stream));
   launch_init(e);
   e->k = 0;
   if (e->overlap) NLSG_HIP(hipEventRecord(e->ev_gen[0], e->stream));
@@ -603,6 +633,30 @@ int nlsg_de_download(nlsg_de *e, double *pop_host, double *scores_host, uint64_t
                        hipMemcpyDeviceToHost));
   }
   return NLSG_OK;
+}
+
+int nlsg_de_bound_counts(nlsg_de *e, uint64_t *out3) {
+  if (!e || !out3) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_de_init has not been called");
+  if (!e->p.counts) return fail(NLSG_ERR_STATE, "engine was created without cfg.trace");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  int rc = join_side(e);
+  if (rc) return rc;
+  NLSG_HIP(hipMemcpyAsync(out3, e->p.counts, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, e->stream));
+  NLSG_HIP(hipStreamSynchronize(e->stream));
+  NLSG_HIP(launches_status());
+  return NLSG_OK;
+}
+
+int nlsg_de_bound_state(const nlsg_de *e, int32_t *enabled, uint32_t *retry_period) {
+  if (!e) return fail(NLSG_ERR_INVALID_ARG, "null engine");
+  if (enabled) *enabled = e->p.bound;
+  if (retry_period) *retry_period = e->p.retry_mask + 1;
+  return NLSG_OK;
+}
+
+int nlsg_de_bound_gate(int32_t objective, int32_t strategy, int32_t minimize, double CR, uint64_t dim) {
+  return de_bound_gate(objective, strategy, minimize != 0, CR, dim) ? 1 : 0;
 }
 
 int nlsg_de_upload(nlsg_de *e, const double *pop_host, const double *scores_host) {

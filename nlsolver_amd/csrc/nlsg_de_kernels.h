@@ -39,6 +39,13 @@ constexpr int kTraceWords = 5;        // r1, r2, r3, jrand, accept
 // nobody reads buf[1 - home_k[a]] row a; and a speculative generation that a stop test
 // discards leaves home_k, scores_k and the rows they point to untouched: it is never adopted,
 // exactly as when every row was copied into the other buffer.
+//
+// Bit 1 of a selector byte is not part of the selector: the register-resident generation
+// (de_fetch_agent / de_process_agent, 65 <= D <= 1024) keeps its per-agent bound hint there
+// (DeParams.bound below). Every reader of a selector therefore takes `& 1`: de_row, the `row`
+// lambdas of de_fetch_agent and of the packed generation, DeAgent.home, de_gather_kernel and the
+// head's best row (both through de_row). Init stores 0 and upload's memset stores the parity
+// (0 or 1), so both clear the hint.
 struct DeParams {
   double *buf[2];      // population ping-pong, rows addressed through `home`
   double *scores[2];   // [shard_n] each, ping-pong with the population: a generation reads
@@ -64,8 +71,26 @@ struct DeParams {
   uint64_t gen_key;    // ctr_key(seed, generation) of the generation being launched
   uint64_t cr_thresh;  // u01(z) < CR  <=>  z < cr_thresh (u01 is monotone in z): the crossover
   int32_t cr_all;      // test on the draw's bits; cr_all: CR > 1, every draw passes
-  int32_t pad2;
+  // Reject on the mutant-only terms (host-set, wave-uniform; de_bound_gate in nlsg_de_state.h).
+  // For an objective whose computed terms are all >= 0 (TermsNonNegative), the lane tree over the
+  // terms whose coordinates all come from the mutant, with +0.0 in place of every other term, is
+  // a lower bound of the trial's computed score bit for bit: round-to-nearest addition is
+  // monotone in each operand. bound >= old_score therefore implies !(score < old_score), and the
+  // trial is rejected without the agent's own row ever being read (a rejected trial stores
+  // old_score, not its own score: nothing observable changes). An agent whose bound did not
+  // decide carries a hint (bit 1 of its selector byte, see above) and takes the plain path --
+  // own row loaded with the donors, one evaluation -- except in the generations where
+  // (generation + a) & retry_mask == 0, when it tries the bound again. The path taken never
+  // changes an output.
+  int32_t bound;
+  uint64_t *counts;    // cfg.trace only, else nullptr: [3] agents per path (kDeBound*), for tests
+  uint32_t retry_mask; // R - 1, R a power of two
+  uint32_t pad2;
 };
+
+// DeParams.counts: the bound decided / it did not and the trial was rejected / it did not (or every
+// coordinate came from the mutant: the bound is the score) and the trial was accepted
+constexpr int kDeBoundDecided = 0, kDeBoundRejected = 1, kDeBoundAccepted = 2;
 
 // agent `local`'s row in buffer h (a home selector value; the select keeps DeParams out of
 // scratch and any stray byte inside the two buffers)
@@ -119,37 +144,40 @@ __global__ void de_reset_state_kernel(DeParams p) {
 template <int CHUNKS>
 struct DeAgent {
   uint64_t a, ka, r0, r1, r2, jrand;
-  uint32_t home;          // home[par][a]: the buffer holding the agent's row
+  uint32_t home;          // home[par][a] & 1: the buffer holding the agent's row
+  uint32_t hint;          // home[par][a] & 2: the bound did not decide this agent's last try
+  bool bound;             // wave-uniform: this generation tries the bound, `keep` is not loaded yet
   bool cross[CHUNKS][2];  // the trial takes the mutant here (crossover draw or jrand)
   double keep[CHUNKS][2], d1[CHUNKS][2], d2[CHUNKS][2], d3[CHUNKS][2];
   double old_score;
 };
 
 // load_row where the trial keeps the old coordinate only: a lane whose coordinates all take the
-// mutant (`skip`) reads the zero pad instead (at CR 0.9 about 4 lanes in 5)
+// mutant (`skip`) reads the zero pad instead (at CR 0.9 about 4 lanes in 5); `none` (wave-uniform):
+// every lane does
 template <int CHUNKS, bool VEC>
 __device__ inline void load_row_kept(const double *__restrict__ row, uint64_t D,
                                      const double *__restrict__ zero, const bool (&skip)[CHUNKS][2],
-                                     double (&v)[CHUNKS][2]) {
+                                     double (&v)[CHUNKS][2], bool none = false) {
   const int lane = lane_id();
 #pragma unroll
   for (int c = 0; c < CHUNKS; c++) {
     const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
     if (VEC) {
-      const double *src = (e0 < D && !(skip[c][0] && skip[c][1])) ? row + e0 : zero;
+      const double *src = (e0 < D && !(skip[c][0] && skip[c][1]) && !none) ? row + e0 : zero;
       const double2 t = *reinterpret_cast<const double2 *>(src);
       v[c][0] = t.x;
       v[c][1] = t.y;
     } else {
-      v[c][0] = *((e0 < D && !skip[c][0]) ? row + e0 : zero);
-      v[c][1] = *((e0 + 1 < D && !skip[c][1]) ? row + e0 + 1 : zero);
+      v[c][0] = *((e0 < D && !skip[c][0] && !none) ? row + e0 : zero);
+      v[c][1] = *((e0 + 1 < D && !skip[c][1] && !none) ? row + e0 + 1 : zero);
     }
   }
 }
 
-template <int CHUNKS, bool VEC>
-__device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, uint64_t best_id,
-                                      uint64_t a, DeAgent<CHUNKS> &c) {
+template <bool BOUND, int CHUNKS, bool VEC>
+__device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, uint64_t generation,
+                                      uint64_t best_id, uint64_t a, DeAgent<CHUNKS> &c) {
   const uint64_t D = p.D;
   const uint64_t ga = p.shard_lo + a;  // the global agent id keys the RNG
   // the agent's key and its wave-uniform draws are computed on the vector unit (see on_valu):
@@ -243,7 +271,14 @@ __device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, u
   c.r0 = r0;
   c.r1 = r1;
   c.r2 = r2;
-  c.home = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hsel), 0));
+  const uint32_t hraw = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hsel), 0));
+  c.home = hraw & 1u;
+  c.hint = 0;
+  c.bound = false;
+  if constexpr (BOUND) {
+    c.hint = hraw & 2u;
+    c.bound = p.bound && (c.hint == 0 || ((generation + a) & p.retry_mask) == 0);
+  }
   // rows: 3 donors and the non-crossed source -- the agent's own row for strategy random, the
   // row of best_id (L2-resident) for strategy best -- where the trial keeps it
   // (shard-local indices and D fit 32 bits: one scalar multiply pair per row offset)
@@ -254,17 +289,85 @@ __device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, u
   load_row<CHUNKS, VEC>(row(h0, r0 - p.shard_lo), D, p.zero, c.d1);
   load_row<CHUNKS, VEC>(row(h1, r1 - p.shard_lo), D, p.zero, c.d2);
   load_row<CHUNKS, VEC>(row(h2, r2 - p.shard_lo), D, p.zero, c.d3);
+  // (a wave that tries the bound reads the own row only if the bound does not decide: here every
+  // lane of it reads the zero pad, one line, and the code stays free of a branch)
   load_row_kept<CHUNKS, VEC>(p.strategy == NLSG_DE_RANDOM ? row(c.home, a) : p.best_x, D, p.zero,
-                             c.cross, c.keep);
+                             c.cross, c.keep, BOUND && c.bound);
   c.old_score = p.scores[par][a];
 }
 
-template <int OBJ, int CHUNKS, bool VEC>
-__device__ inline void de_process_agent(const DeParams &p, int par, const DeAgent<CHUNKS> &c) {
+template <int OBJ, int CHUNKS, bool VEC, bool BOUND>
+__device__ inline void de_process_agent(const DeParams &p, int par, DeAgent<CHUNKS> &c) {
+  static_assert(!BOUND || TermsNonNegative<OBJ>::value, "the bound needs terms >= 0");
   const int lane = lane_id();
   const uint64_t D = p.D;
+  // selection (:2466) and what a generation leaves behind; `hint` is 0 or 2 (DeParams.bound)
+  auto select = [&](bool accept, double score, const double (&trial)[CHUNKS][2], uint32_t hint) {
+    if (accept) {  // a rejected trial stores nothing: the row stays where home says it is
+      double *out = de_row(p, c.home ^ 1u, c.a);
+      if (p.stream)  // wave-uniform
+        store_row_stream<CHUNKS, VEC>(out, D, trial);
+      else
+        store_row<CHUNKS, VEC>(out, D, trial);
+    }
+    if (lane == 0) {
+      p.scores[par ^ 1][c.a] = accept ? score : c.old_score;
+      p.home[par ^ 1][c.a] = static_cast<uint8_t>((accept ? c.home ^ 1u : c.home) | hint);
+    }
+    if (p.trace != nullptr && lane == 0) {
+      uint64_t *t = p.trace + c.a * kTraceWords;
+      t[0] = c.r0;
+      t[1] = c.r1;
+      t[2] = c.r2;
+      t[3] = c.jrand;
+      t[4] = accept ? 1u : 0u;
+    }
+  };
+  auto count = [&](int which) {  // engines created with cfg.trace only
+    if (p.counts != nullptr && lane == 0)
+      atomicAdd(reinterpret_cast<unsigned long long *>(p.counts + which), 1ull);
+  };
   // propose_new_agent (nlsolver.h:2357-2375)
   double trial[CHUNKS][2];
+  if constexpr (BOUND) {
+    if (c.bound) {  // wave-uniform; fmul == 1 here, so the objective's value is the score
+      bool keeps = false;  // a coordinate inside D that the trial takes from the old row
+#pragma unroll
+      for (int ch = 0; ch < CHUNKS; ch++) {
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+          const uint64_t e = static_cast<uint64_t>(ch) * 128 + 2 * static_cast<uint64_t>(lane) + k;
+          trial[ch][k] = c.d1[ch][k] + p.F * (c.d2[ch][k] - c.d3[ch][k]);  // the mutant everywhere
+          keeps = keeps || (e < D && !c.cross[ch][k]);
+        }
+      }
+      const bool any_kept = __ballot(keeps) != 0ull;
+      const double bound = wave_objective_masked<OBJ, CHUNKS>(trial, c.cross, D);
+      if (bound >= c.old_score) {  // (false for NaN) the score cannot be lower: rejected unread
+        select(false, bound, trial, 0u);
+        count(kDeBoundDecided);
+        return;
+      }
+      if (!any_kept) {  // CR >= 1: the mutant is the trial and the bound its score
+        const bool accept = bound < c.old_score;
+        select(accept, bound, trial, 0u);
+        count(accept ? kDeBoundAccepted : kDeBoundRejected);
+        return;
+      }
+      // not decided: the own row now, a dependent load, and the full evaluation
+      load_row_kept<CHUNKS, VEC>(de_row(p, c.home, c.a), D, p.zero, c.cross, c.keep);
+#pragma unroll
+      for (int ch = 0; ch < CHUNKS; ch++) {
+#pragma unroll
+        for (int k = 0; k < 2; k++) trial[ch][k] = c.cross[ch][k] ? trial[ch][k] : c.keep[ch][k];
+      }
+      const double score = wave_objective<OBJ, CHUNKS>(trial, D);  // :2463
+      const bool accept = score < c.old_score;                     // :2466 (NaN -> keep)
+      select(accept, score, trial, 2u);
+      count(accept ? kDeBoundAccepted : kDeBoundRejected);
+      return;
+    }
+  }
 #pragma unroll
   for (int ch = 0; ch < CHUNKS; ch++) {
 #pragma unroll
@@ -275,26 +378,7 @@ __device__ inline void de_process_agent(const DeParams &p, int par, const DeAgen
   }
   // (elements >= D are 0 in every loaded row, hence 0 in the trial as well)
   const double score = p.fmul * wave_objective<OBJ, CHUNKS>(trial, D);  // :2463
-  const bool accept = score < c.old_score;                               // :2466 (NaN -> keep)
-  if (accept) {  // a rejected trial stores nothing: the row stays where home says it is
-    double *out = de_row(p, c.home ^ 1u, c.a);
-    if (p.stream)  // wave-uniform
-      store_row_stream<CHUNKS, VEC>(out, D, trial);
-    else
-      store_row<CHUNKS, VEC>(out, D, trial);
-  }
-  if (lane == 0) {
-    p.scores[par ^ 1][c.a] = accept ? score : c.old_score;
-    p.home[par ^ 1][c.a] = static_cast<uint8_t>(accept ? c.home ^ 1u : c.home);
-  }
-  if (p.trace != nullptr && lane == 0) {
-    uint64_t *t = p.trace + c.a * kTraceWords;
-    t[0] = c.r0;
-    t[1] = c.r1;
-    t[2] = c.r2;
-    t[3] = c.jrand;
-    t[4] = accept ? 1u : 0u;
-  }
+  select(score < c.old_score, score, trial, c.hint);                    // :2466 (NaN -> keep)
 }
 
 // ---- agents of at most 64 coordinates: 64 / G agents per wave, one per group of G lanes (G = 4, 8,
@@ -421,7 +505,9 @@ __global__ __launch_bounds__(256) void de_generation_groups_kernel(DeParams p, i
 
 // One agent per wave. (Two agents per wave — ten gathers in flight — measured -7 % kernel time at
 // pop = 65536 but +9 % at pop = 2^20 and only -2 % per turn; not kept.)
-template <int OBJ, int CHUNKS, bool VEC>
+// BOUND: the instantiation an engine with DeParams.bound set launches (TermsNonNegative objectives
+// only); every other engine runs BOUND = false, the code without the bound.
+template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false>
 __device__ inline void de_generation_block(const DeParams &p, int par, uint64_t generation,
                                            int ignore_done, uint64_t block) {
   // `generation` (k+1) and the source buffer `par` (k & 1) come from the host: the k-th
@@ -435,14 +521,14 @@ __device__ inline void de_generation_block(const DeParams &p, int par, uint64_t 
   const uint64_t kg = p.gen_key;  // = ctr_key(p.seed, generation), from the host
   const uint64_t best_id = st->best_id;
   DeAgent<CHUNKS> A;
-  de_fetch_agent<CHUNKS, VEC>(p, par, kg, best_id, a0, A);
-  de_process_agent<OBJ, CHUNKS, VEC>(p, par, A);
+  de_fetch_agent<BOUND, CHUNKS, VEC>(p, par, kg, generation, best_id, a0, A);
+  de_process_agent<OBJ, CHUNKS, VEC, BOUND>(p, par, A);
 }
 
-template <int OBJ, int CHUNKS, bool VEC>
+template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false>
 __global__ __launch_bounds__(256) void de_generation_kernel(DeParams p, int par, uint64_t generation,
                                                           int ignore_done) {
-  de_generation_block<OBJ, CHUNKS, VEC>(p, par, generation, ignore_done, blockIdx.x);
+  de_generation_block<OBJ, CHUNKS, VEC, BOUND>(p, par, generation, ignore_done, blockIdx.x);
 }
 
 // Gather of the population `par` into one contiguous [shard_n][D] block (host download)
@@ -604,13 +690,13 @@ __global__ __launch_bounds__(256) void de_scan_head_kernel(DeParams p, uint64_t 
 // k at the same time. Random donors do not depend on the head's result; if head k fires a
 // stop test, generation k+1 went to the other buffers and is never adopted (exactly the
 // speculative turn of the sharded path), so results equal the serial order head -> generation.
-template <int OBJ, int CHUNKS, bool VEC>
+template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false>
 __global__ __launch_bounds__(256) void de_turn_kernel(DeParams p, int par, uint64_t generation) {
   if (blockIdx.x < p.ntiles) {
     de_scan_head_block(p, generation - 1, blockIdx.x, nullptr);
     return;
   }
-  de_generation_block<OBJ, CHUNKS, VEC>(p, par, generation, 0, blockIdx.x - p.ntiles);
+  de_generation_block<OBJ, CHUNKS, VEC, BOUND>(p, par, generation, 0, blockIdx.x - p.ntiles);
 }
 
 // the same turn with the packed generation (agents of at most 64 coordinates, several per wave)

@@ -71,4 +71,23 @@ inline void set_crossover_test(P &p, double cr) {
   }
 }
 
+#ifndef __HIPCC_RTC__
+// Host side, at create: may the register-resident generation reject on the mutant-only terms
+// (DeParams.bound)? Strategy random (the kept coordinates are the agent's own row), minimising
+// (fmul == 1: the objective's value is the score), an objective whose terms are >= 0
+// (TermsNonNegative), one agent per wave with the row in registers, and a crossover rate at which
+// enough terms are known for the bound to decide: at CR 0.9 81 % of Rosenbrock's terms are, at
+// CR 0.5 25 %. kDeBoundMinCR and kDeBoundRetry come from the sweeps in DESIGN.md section 3.
+// From CR 1 up no coordinate is kept: the plain path reads no own row either, and the bound only
+// adds its bookkeeping (measured slower), so the gate closes again there.
+constexpr double kDeBoundMinCR = 0.8, kDeBoundMaxCR = 1.0;
+constexpr uint32_t kDeBoundRetry = 256;  // a hinted agent tries the bound every R-th generation
+inline bool de_bound_gate(int objective, int strategy, bool minimize, double cr, uint64_t dim,
+                          double min_cr = kDeBoundMinCR, double max_cr = kDeBoundMaxCR) {
+  return (objective == NLSG_OBJ_ROSENBROCK || objective == NLSG_OBJ_SPHERE) &&
+         strategy == NLSG_DE_RANDOM && minimize && dim >= 65 && dim <= 1024 && cr >= min_cr &&
+         cr < max_cr;
+}
+#endif
+
 }  // namespace nlsg

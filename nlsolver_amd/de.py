@@ -164,6 +164,21 @@ class DEEngine:
         check(lib().nlsg_de_upload(self._h, pop.ctypes.data_as(_capi.pd),
                                    scores.ctypes.data_as(_capi.pd)))
 
+    def bound_counts(self):
+        """(decided, fell through and rejected, accepted): agents since init() whose trial the
+        generation's lower bound rejected unread / did not decide and selection rejected / did not
+        decide (or had no kept coordinate) and selection accepted. Needs trace=True; all zero in
+        an engine that does not use the bound (bound_state)."""
+        out = np.zeros(3, dtype=np.uint64)
+        check(require("nlsg_de_bound_counts")(self._h, out.ctypes.data_as(_capi.pu)))
+        return tuple(int(v) for v in out)
+
+    def bound_state(self):
+        """(enabled, retry period in generations) of the generation's lower-bound rejection"""
+        on, r = C.c_int32(), C.c_uint32()
+        check(require("nlsg_de_bound_state")(self._h, C.byref(on), C.byref(r)))
+        return bool(on.value), r.value
+
     def minimize(self, x, poll_every=0):
         st = Status()
         check(lib().nlsg_de_minimize(self._h, x.ctypes.data_as(_capi.pd), poll_every, C.byref(st)))

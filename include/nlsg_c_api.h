@@ -413,6 +413,43 @@ int nlsg_bfgs_create_custom(const nlsg_bfgs_config *cfg, const nlsg_custom_objec
  * row each. 4096 parameters fit everywhere but in reference order at dim > 512, where 3072 do. */
 int nlsg_bfgs_create_params(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
                             nlsg_bfgs **out);
+/* The objective's ANALYTIC GRADIENT as one more body, compiled with the objective when the engine is made:
+ * the reference's BFGS<Callable, scalar_t, Grad> with a Grad functor of the caller's. The search and init
+ * kernels evaluate the body instead of the default finite differences — about one evaluation of the
+ * objective per gradient instead of 4 dim — and, as with such a functor in the reference (g_lam,
+ * nlsolver.h:3218-3230), a gradient counts in gradient_evals_used only.
+ *   chain == NLSG_CUSTOM_TERMS / _CHAIN: grad_body is the body of
+ *       double grad(double xm, double xi, double xn, uint64_t i, uint64_t D, double s)
+ *     and returns df/dx_i. xm = x_{i-1} (+0.0 at i = 0), xn = x_{i+1} (+0.0 at i = D - 1); s is the sum of
+ *     the objective's terms at x in the engine's summation order — what finish_body receives (a non-linear
+ *     finish needs it; computing it is no function call of the solver's). Every lane runs the body for its
+ *     own two coordinates: plain per-lane code, no cross-lane calls.
+ *       e.g. the Rosenbrock chain: "double g = 0.0; if (i + 1 < D) g = -2.0 * (1.0 - xi) - 400.0 * xi * (xn - xi * xi);"
+ *                                  " if (i > 0) g = g + 200.0 * (xi - xm * xm); return g;"
+ *   chain == NLSG_CUSTOM_VECTOR: grad_body is the body of
+ *       double grad(const X &x, uint64_t i, uint64_t D)
+ *     with x(i), x.size(), x.sum(g) as in the objective's body. It is called for i = 0 .. D - 1 in order with
+ *     an i that is the same in every lane; every lane returns the same value and the lane that owns
+ *     coordinate i keeps it: D evaluations of the body per gradient (against 4 D evaluations of the objective
+ *     with finite differences). NLSG_BFGS_REFERENCE_ORDER stays unsupported for this form.
+ *   p(k) reads the problem's parameters in either form; a compiler error names the line in "grad_body".
+ * In reference order a gradient of the terms form costs one index-order sum of the D terms (for s) beside the
+ * body, whether or not the body reads s.
+ * Checks, all before the device is touched, in this order: a NULL cfg, obj or grad; cfg->objective other than
+ * NLSG_OBJ_CUSTOM; grad->struct_size other than sizeof(nlsg_bfgs_gradient); a NULL or empty grad_body — each
+ * NLSG_ERR_INVALID_ARG —; then the remaining checks of nlsg_bfgs_create_custom in its order (cfg->struct_size,
+ * dim and batch, dim <= 1024, flags, reference order x whole-vector body); then obj->n_params: < 0 is
+ * NLSG_ERR_INVALID_ARG, 0 an objective without parameters, >= 1 gets the checks of nlsg_bfgs_create_params
+ * (above NLSG_CUSTOM_MAX_PARAMS and the LDS budget: NLSG_ERR_UNSUPPORTED) and the engine takes
+ * nlsg_bfgs_set_params (NLSG_ERR_STATE until the first rows).
+ * An optional symbol: NLSG_ABI_VERSION stays 1 (resolve it with dlsym). */
+typedef struct {
+  uint32_t struct_size;  /* sizeof(nlsg_bfgs_gradient) */
+  uint32_t reserved;     /* 0 */
+  const char *grad_body;
+} nlsg_bfgs_gradient;
+int nlsg_bfgs_create_gradient(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
+                              const nlsg_bfgs_gradient *grad, nlsg_bfgs **out);
 /* params_host [batch][n_params]: problem b's objective reads row b as p(k). Copied on the engine's
  * stream before the call returns; the rows hold from the next launch on and are replaced without
  * recompiling. NLSG_ERR_INVALID_ARG on an engine of another creator. Until the first call,

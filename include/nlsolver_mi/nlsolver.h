@@ -230,6 +230,16 @@ struct Custom {
   //   Custom<double> f("double r = xi - p(0); return p(1) * r * r;");
   //   f.params = {1.5, 2.0};
   std::vector<T> params;
+  // The objective's analytic gradient as one more body (nlsg_bfgs_gradient in include/nlsg_c_api.h: terms /
+  // chain form  double grad(double xm, double xi, double xn, uint64_t i, uint64_t D, double s)  = df/dx_i;
+  // whole-vector form  double grad(const X &x, uint64_t i, uint64_t D)). It is evaluated by
+  // BFGS<Custom<T>, T, device::analytic_grad>; as in the reference the Grad TYPE decides: the default Grad
+  // (fin_diff) differentiates numerically whatever this holds, and analytic_grad with an empty body throws
+  // device_error. Every other solver ignores it.
+  //   Custom<double> f("return xi * xi;");
+  //   f.grad_body = "return 2.0 * xi;";
+  //   auto st = BFGS<Custom<double>, double, device::analytic_grad>(f).minimize(x);
+  std::string grad_body;
   explicit Custom(std::string term_body, bool chain = false, std::string finish_body = "return s;")
       : term_body(std::move(term_body)), finish_body(std::move(finish_body)), chain(chain ? 1 : 0) {}
   // the whole-vector form: `body` is the body of  double f(const X &x, uint64_t D)  with x(i),
@@ -416,6 +426,7 @@ class api {
   decltype(&nlsg_lm_create_params) lm_create_params = nullptr;
   decltype(&nlsg_lm_set_params) lm_set_params = nullptr;
   decltype(&nlsg_lm_create_link) lm_create_link = nullptr;
+  decltype(&nlsg_bfgs_create_gradient) bfgs_create_gradient = nullptr;
   // the resident engine's LDS need with the parameter row; throws when the library cannot take
   // parameters or the shape does not fit (`shape_need` = nlsg_*_batch_lds_bytes, 0 = out of range)
   void require_params_fit(bool has_engine, bool has_set, uint64_t shape_need, int32_t n_params,
@@ -500,6 +511,7 @@ class api {
     bind_optional(h, "nlsg_lm_create_params", lm_create_params);
     bind_optional(h, "nlsg_lm_set_params", lm_set_params);
     bind_optional(h, "nlsg_lm_create_link", lm_create_link);
+    bind_optional(h, "nlsg_bfgs_create_gradient", bfgs_create_gradient);
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
   }
@@ -1365,8 +1377,15 @@ class BFGS {
     else
       return false;
   }
+  // A Custom objective under device::analytic_grad: its grad_body is the gradient (nlsg_bfgs_create_gradient).
+  static constexpr bool device_custom_grad() {
+    if constexpr (device::is_device_objective<Callable>::value && std::is_same_v<Grad, device::analytic_grad>)
+      return Callable::nlsg_objective == NLSG_OBJ_CUSTOM;
+    else
+      return false;
+  }
   solver_status<scalar_t> minimize(std::vector<scalar_t> &x) {
-    if constexpr (device::has_grad_objective<Callable>::value) {
+    if constexpr (device::has_grad_objective<Callable>::value || device_custom_grad()) {
       std::vector<std::vector<scalar_t>> one{x};
       auto st = solve_device(one);
       x = one[0];
@@ -1410,6 +1429,8 @@ class BFGS {
   bool use_reference_order() const {
     if constexpr (device::has_grad_objective<Callable>::value) {
       return device::reference_order();
+    } else if constexpr (device_custom_grad()) {
+      return f.chain != NLSG_CUSTOM_VECTOR && device::reference_order();
     } else if constexpr (device_fd()) {
       if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM)
         return f.chain != NLSG_CUSTOM_VECTOR && device::reference_order();
@@ -1420,7 +1441,7 @@ class BFGS {
     }
   }
   std::vector<solver_status<scalar_t>> solve_device(std::vector<std::vector<scalar_t>> &xs) {
-    static_assert(device::has_grad_objective<Callable>::value || device_fd(),
+    static_assert(device::has_grad_objective<Callable>::value || device_fd() || device_custom_grad(),
                   "minimize_batch needs a device objective: one with an analytic gradient, or "
                   "Rosenbrock / Sphere / StyblinskiTang with the default finite-difference one");
     static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
@@ -1440,6 +1461,30 @@ class BFGS {
       cfg.objective = Callable::nlsg_grad_objective;
       cfg.quad_c = f.c;
       api.check(api.bfgs_create(&cfg, f.d.data(), f.b.data(), &eng));
+    } else if constexpr (device_custom_grad()) {  // the objective's own gradient body
+      if (f.grad_body.empty())
+        throw device_error("BFGS<Custom, scalar_t, device::analytic_grad> needs Custom::grad_body (the default "
+                           "Grad differentiates numerically)");
+      if (!api.bfgs_create_gradient)
+        throw device_error("the loaded library has no nlsg_bfgs_create_gradient (analytic gradients of compiled "
+                           "objectives)");
+      if (!f.params.empty() && !api.bfgs_set_params)
+        throw device_error("library has no run-time objective parameters for BFGS");
+      cfg.objective = Callable::nlsg_objective;
+      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
+      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, device::custom_n_params(f)};
+      const nlsg_bfgs_gradient grad{sizeof(nlsg_bfgs_gradient), 0, f.grad_body.c_str()};
+      api.check(api.bfgs_create_gradient(&cfg, &obj, &grad, &eng));
+      if (!f.params.empty()) {
+        std::vector<double> rows;  // the functor's one row, shown to every start
+        for (size_t b = 0; b < B; b++) rows.insert(rows.end(), f.params.begin(), f.params.end());
+        const int prc = api.bfgs_set_params(eng, rows.data());
+        if (prc) {
+          const std::string pmsg = api.last_error();
+          api.bfgs_destroy(eng);
+          throw device_error("nlsg error " + std::to_string(prc) + ": " + pmsg);
+        }
+      }
     } else {  // fin_diff (nlsolver.h:2849-2855) evaluated on the device
       cfg.objective = Callable::nlsg_objective;
       if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {

@@ -98,6 +98,10 @@ class BFGSConfig(C.Structure):
                 ("max_iter", u64), ("grad_eps", f64), ("alpha", f64), ("quad_c", f64)]
 
 
+class BFGSGradientC(C.Structure):  # nlsg_bfgs_gradient
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("grad_body", C.c_char_p)]
+
+
 BFGS_SYMMETRIC = 1  # NLSG_BFGS_SYMMETRIC
 BFGS_REFERENCE_ORDER = 2  # NLSG_BFGS_REFERENCE_ORDER
 
@@ -303,6 +307,8 @@ OPTIONAL_SYMBOLS = {
     "nlsg_bfgs_create_params": (C.c_int, [C.POINTER(BFGSConfig), C.POINTER(CustomObjectiveC), C.POINTER(_H)]),
     "nlsg_bfgs_set_params": (C.c_int, [_H, pd]),
     "nlsg_bfgs_lds_bytes": (u64, [u64, C.c_uint32]),
+    "nlsg_bfgs_create_gradient": (C.c_int, [C.POINTER(BFGSConfig), C.POINTER(CustomObjectiveC),
+                                            C.POINTER(BFGSGradientC), C.POINTER(_H)]),
 }
 SYMBOLS.update(OPTIONAL_SYMBOLS)
 _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
@@ -320,6 +326,7 @@ _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
                     "nlsg_lm_set_params": "library has no run-time objective parameters for Levenberg-Marquardt",
                     "nlsg_lm_lds_bytes": "library has no run-time objective parameters for Levenberg-Marquardt",
                     "nlsg_lm_create_link": "library has no user-supplied link functions for Levenberg-Marquardt",
+                    "nlsg_bfgs_create_gradient": "library has no analytic gradients of compiled objectives for BFGS",
                     "nlsg_bfgs_create_params": "library has no run-time objective parameters for BFGS",
                     "nlsg_bfgs_set_params": "library has no run-time objective parameters for BFGS",
                     "nlsg_bfgs_lds_bytes": "library has no run-time objective parameters for BFGS",

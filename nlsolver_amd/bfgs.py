@@ -45,7 +45,17 @@ class BFGSEngine:
     A CustomObjective with n_params > 0 (nlsg_bfgs_create_params): problem b minimises the objective
     under row b of set_params(rows) ([batch, n_params], read as p(k)); rows are replaced without
     recompiling. The search kernel runs four problems per workgroup, a wave each, so four rows share
-    the workgroup's LDS: fits() says whether a shape has room."""
+    the workgroup's LDS: fits() says whether a shape has room.
+
+    gradient: None — a CustomObjective's grad_body when it has one (nlsg_bfgs_create_gradient: the
+    kernels evaluate that body, about one objective evaluation per gradient instead of 4 dim, and a
+    gradient counts in gradient_evals_used only, as a Grad functor does in the reference), else the
+    objective's own path; "finite_difference" forces the default gradient whatever the objective
+    carries; "analytic" insists and raises ValueError when there is no gradient to evaluate.
+    gradient_used says which ran: "analytic" or "finite_difference". In reference order a gradient of the
+    terms form costs one index-order sum of the D terms (the body's `s`) beside the body, read or not."""
+
+    GRADIENTS = (None, "analytic", "finite_difference")
 
     @staticmethod
     def lds_bytes(dim, reference_order=False, n_params=0):
@@ -64,7 +74,18 @@ class BFGSEngine:
         return BFGSEngine.lds_bytes(dim, reference_order, n_params) <= LDS_BUDGET
 
     def __init__(self, objective, batch, *, dim=None, max_iter=100, grad_eps=5e-3, alpha=1.0,
-                 device=0, stream=None, symmetric=False, reference_order=False):
+                 device=0, stream=None, symmetric=False, reference_order=False, gradient=None):
+        from .de import CustomObjective, rtc_library_path
+        if gradient not in self.GRADIENTS:
+            raise ValueError(f"gradient must be one of {self.GRADIENTS}, not {gradient!r}")
+        custom = isinstance(objective, CustomObjective)
+        has_analytic = bool(objective.grad_body) if custom else not isinstance(objective, str)
+        if gradient == "analytic" and not has_analytic:
+            raise ValueError("gradient='analytic' needs an objective that carries its gradient: a "
+                             "CustomObjective with grad_body=, or QuadDiagRank1")
+        if gradient == "finite_difference" and not custom and not isinstance(objective, str):
+            raise ValueError("QuadDiagRank1 is minimised with its analytic gradient only")
+        self.gradient_used = "analytic" if has_analytic and gradient != "finite_difference" else "finite_difference"
         cfg = BFGSConfig()
         cfg.flags = (_capi.BFGS_SYMMETRIC if symmetric else 0) | \
             (_capi.BFGS_REFERENCE_ORDER if reference_order else 0)
@@ -76,21 +97,26 @@ class BFGSEngine:
         cfg.max_iter, cfg.grad_eps, cfg.alpha = max_iter, grad_eps, alpha
         self._h = C.c_void_p()
         self.n_params = 0
-        from .de import CustomObjective, rtc_library_path
-        if isinstance(objective, CustomObjective):  # user objective + finite-difference gradient
+        if custom:  # user objective + its gradient body or the finite-difference gradient
             if dim is None:
                 raise TypeError("a custom objective needs dim=")
             cfg.objective, cfg.dim, cfg.quad_c = _capi.OBJ_CUSTOM, dim, 0.0
             self.cfg = cfg
             self.n_params = objective.n_params
-            create = lib().nlsg_bfgs_create_custom
+            analytic = self.gradient_used == "analytic"
+            create = require("nlsg_bfgs_create_gradient") if analytic else lib().nlsg_bfgs_create_custom
             if self.n_params:  # (zero stays with the creator it always had)
-                create = require("nlsg_bfgs_create_params")
+                if not analytic:
+                    create = require("nlsg_bfgs_create_params")
                 require("nlsg_bfgs_set_params")
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             obj = _capi.CustomObjectiveC(objective.term_body.encode(), objective.finish_body.encode(),
                                          int(objective.chain), self.n_params)
-            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+            if analytic:
+                grad = _capi.BFGSGradientC(C.sizeof(_capi.BFGSGradientC), 0, objective.grad_body.encode())
+                check(create(C.byref(cfg), C.byref(obj), C.byref(grad), C.byref(self._h)))
+            else:
+                check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
             return
         if isinstance(objective, str):  # built-in objective + finite-difference gradient
             if dim is None:
@@ -198,7 +224,11 @@ class BFGS:
     faster kernels; the quadratic pays 1.18 x on large batches. True / False force it.
 
     params: the run-time parameters of a CustomObjective with n_params > 0: one row (n_params,) shown
-    to every start, or (batch, n_params) with a 2-D x, a row per start."""
+    to every start, or (batch, n_params) with a 2-D x, a row per start.
+
+    A CustomObjective that carries grad_body is minimised with that gradient (BFGSEngine gradient=None);
+    gradient_used says which path the last minimize() took. g stays None: the gradient of a device
+    objective is part of the objective."""
 
     def __init__(self, f, g=None, max_iter=100, grad_eps=5e-3, alpha=1.0, *, device=0,
                  symmetric=False, reference_order=None, params=None):
@@ -212,6 +242,8 @@ class BFGS:
             raise TypeError("device objectives carry their analytic gradient or use the default "
                             "finite-difference one; pass g=None")
         self.f = f
+        self.gradient_used = "analytic" if getattr(f, "grad_body", None) or isinstance(f, QuadDiagRank1) \
+            else "finite_difference"
         self.args = dict(max_iter=max_iter, grad_eps=grad_eps, alpha=alpha, device=device,
                          symmetric=symmetric, reference_order=reference_order)
 
@@ -231,6 +263,7 @@ class BFGS:
         from .nm import _rows_for_batch
         rows = _rows_for_batch(self.params, xb.shape[0])
         with BFGSEngine(self.f, xb.shape[0], **extra, **args) as eng:
+            self.gradient_used = eng.gradient_used
             out, st = eng.minimize(xb, params=rows)
         xb[...] = out
         return st[0] if x.ndim == 1 else st

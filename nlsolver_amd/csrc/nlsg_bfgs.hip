@@ -9,7 +9,8 @@
 using namespace nlsg;
 
 struct nlsg_bfgs {
-  BfgsRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: finite-difference kernels hiprtc built
+  BfgsRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernels hiprtc built (finite differences, or the
+                       // objective's gradient body: nlsg_bfgs_create_gradient)
   nlsg_bfgs_config cfg;
   BfgsParams p;
   hipStream_t stream = nullptr;
@@ -138,7 +139,8 @@ constexpr int bfgs_chunks(uint64_t n) { return n <= 128 ? 1 : n <= 256 ? 2 : n <
 extern "C" {
 
 static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const double *lin_host,
-                       const nlsg_custom_objective *custom, nlsg_bfgs **out, bool with_params = false);
+                       const nlsg_custom_objective *custom, nlsg_bfgs **out, bool with_params = false,
+                       const char *grad_body = nullptr);
 
 int nlsg_bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const double *lin_host,
                      nlsg_bfgs **out) {
@@ -173,6 +175,25 @@ int nlsg_bfgs_create_params(const nlsg_bfgs_config *cfg, const nlsg_custom_objec
   return rc;
 }
 
+// The objective with its gradient as a second body: the kernels evaluate it instead of finite differences.
+// Parameters are optional here (n_params == 0 is an objective without any).
+int nlsg_bfgs_create_gradient(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
+                              const nlsg_bfgs_gradient *grad, nlsg_bfgs **out) {
+  if (!cfg || !obj || !grad) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (cfg->objective != NLSG_OBJ_CUSTOM)
+    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (grad->struct_size != sizeof(nlsg_bfgs_gradient))
+    return fail(NLSG_ERR_INVALID_ARG, "nlsg_bfgs_gradient size mismatch (%u vs %zu)", grad->struct_size,
+                sizeof(nlsg_bfgs_gradient));
+  if (!grad->grad_body || !grad->grad_body[0])
+    return fail(NLSG_ERR_INVALID_ARG, "nlsg_bfgs_create_gradient needs a gradient body (finite differences are "
+                "nlsg_bfgs_create_custom's)");
+  PhaseClock clk;
+  const int rc = bfgs_create(cfg, nullptr, nullptr, obj, out, obj->n_params != 0, grad->grad_body);
+  call_timing().create_ms = clk.lap();
+  return rc;
+}
+
 // The dynamic LDS of a search / init launch without parameter rows: the four waves' reference-order
 // buffers, or nothing. 0 also outside 1 <= dim <= 1024, for unknown flags and for reference order with
 // the symmetric restatement (which the engine rejects).
@@ -195,7 +216,8 @@ int nlsg_bfgs_set_params(nlsg_bfgs *e, const double *params_host) {
 }
 
 static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const double *lin_host,
-                       const nlsg_custom_objective *custom, nlsg_bfgs **out, bool with_params) {
+                       const nlsg_custom_objective *custom, nlsg_bfgs **out, bool with_params,
+                       const char *grad_body) {
   if (!cfg || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(nlsg_bfgs_config))
@@ -227,6 +249,9 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
     return fail(NLSG_ERR_UNSUPPORTED,
                 "NLSG_BFGS_REFERENCE_ORDER: Rastrigin's cosine is the device's deterministic one, not "
                 "libm's — there is no reference arithmetic to reproduce");
+  if (grad_body && custom->n_params < 0)  // (zero is an objective without parameters: no row, no check)
+    return fail(NLSG_ERR_INVALID_ARG, "n_params = %d: nlsg_bfgs_create_gradient takes 0 .. %d parameters",
+                custom->n_params, NLSG_CUSTOM_MAX_PARAMS);
   if (with_params)  // (a row per wave, four to the block, behind the reference-order buffers)
     if (const int prc = check_custom_params(custom, nlsg_bfgs_lds_bytes(cfg->dim, cfg->flags), "nlsg_bfgs",
                                             "nlsg_bfgs_create_custom", 4))
@@ -319,7 +344,8 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   p.nb = nb;
   p.nstored = nstored;
   if (custom) {
-    const int rc2 = rtc_build_bfgs(custom, e->chunks, e->vec, static_cast<long>(rows_at / sizeof(double)), &e->rtc);
+    const int rc2 = rtc_build_bfgs(custom, e->chunks, e->vec, static_cast<long>(rows_at / sizeof(double)), &e->rtc,
+                                   grad_body);
     if (rc2) {
       nlsg_bfgs_destroy(e);
       return rc2;

@@ -39,7 +39,8 @@ struct BfgsParams {
   const double *zero;
   uint64_t batch, n, max_iter;
   double grad_eps, alpha, qc;
-  int32_t model;  // kBfgsQuad, or the nlsg_objective minimised with a finite-difference gradient
+  int32_t model;  // kBfgsQuad, or the nlsg_objective minimised with a finite-difference gradient (NLSG_OBJ_CUSTOM
+                  // also for a user objective with a gradient body: its module is built on kBfgsCustomGrad)
   int32_t seq;    // NLSG_BFGS_REFERENCE_ORDER: every sum in index order (nlsg_common.h wave_sum_seq)
   // symmetric restatement (NLSG_BFGS_SYMMETRIC): the upper 128 x 128 blocks of H, and the block
   // partials of the two products (see "symmetric restatement" below)
@@ -374,6 +375,116 @@ struct BfgsModel<kBfgsQuad, CHUNKS> {
   }
 };
 
+// kBfgsCustomGrad: a user objective that comes with its gradient as a second body (nlsg_bfgs_create_gradient;
+// rtc_compile emits Objective<NLSG_OBJ_CUSTOM>::grad). f is the finite-difference model's — the same
+// wave_objective / wave_objective_seq_buf — and the gradient costs about one evaluation instead of 4 n. As with
+// a Grad functor of the caller's in the reference (g_lam, nlsolver.h:3218-3230) a gradient counts in
+// gradient_evals_used only: the sum of terms handed to the body as `s` is no call of the solver's.
+//   terms form   grad(xm, xi, xn, i, D, s) = df/dx_i per coordinate: every lane evaluates the body for its own
+//                two coordinates; xm = x_{i-1} (+0.0 at i = 0) and xn = x_{i+1} (+0.0 at i = D - 1) arrive by
+//                wave shifts (lane_up1 / lane_down1; lane_last / lane_first across a chunk boundary); s is the
+//                sum of the objective's terms at x in the engine's summation order, what finish receives.
+//   whole vector grad(x, i, D), called for i = 0 .. D - 1 with a wave-uniform i; every lane returns the same
+//                value and the lane that owns coordinate i keeps it: D evaluations of the body per gradient.
+constexpr int kBfgsCustomGrad = -2;
+
+template <int CHUNKS>
+struct BfgsModel<kBfgsCustomGrad, CHUNKS> {
+  // (the objective exists in the run-time compiled translation unit only: named through CHUNKS, so that
+  // nothing is looked up where this template is merely defined)
+  static constexpr int kObj = CHUNKS ? static_cast<int>(NLSG_OBJ_CUSTOM) : 0;
+  uint64_t n;
+  int seq;
+  double *lds;  // this wave's 2 x 128 CHUNKS doubles (reference order only)
+  template <bool VEC>
+  __device__ inline void load(const BfgsParams &p) {
+    extern __shared__ __align__(16) double bfgs_smem[];
+    n = p.n;
+    seq = p.seq;
+    lds = bfgs_smem + (threadIdx.x >> 6) * (2 * 128 * CHUNKS);
+  }
+  __device__ inline double f(const double (&x)[CHUNKS][2], uint64_t &fcalls) const {
+    fcalls++;
+    if (!seq) return wave_objective<kObj, CHUNKS>(x, n);
+    return wave_objective_seq_buf<kObj, CHUNKS>(x, n, lds);  // (whole-vector bodies: rejected at engine creation)
+  }
+  // x_{e+1} of a lane's second coordinate (element 128 c + 2 lane + 1); +0.0 past the last coordinate
+  __device__ inline double next_of(const double (&x)[CHUNKS][2], int c, int lane) const {
+    const double same = lane_down1(x[c][0]);
+    double next = 0.0;
+    if (c + 1 < CHUNKS) next = lane_first(x[c + 1][0]);
+    return (lane == 63) ? next : same;
+  }
+  // the sum of the objective's terms at x before `finish`, in the engine's summation order: the additions of
+  // wave_objective / wave_objective_seq_buf, so finish(s) has the bits of f(x)
+  __device__ inline double term_sum(const double (&x)[CHUNKS][2]) const {
+    using O = Objective<kObj>;
+    const int lane = lane_id();
+    const uint64_t nt = O::n_terms(n);
+    if (seq) {
+      double t[CHUNKS][2];
+#pragma unroll
+      for (int c = 0; c < CHUNKS; c++) {
+        double xn = 0.0;
+        if (O::kChain) xn = next_of(x, c, lane);
+        t[c][0] = O::term(x[c][0], x[c][1]);
+        t[c][1] = O::term(x[c][1], xn);
+      }
+      return wave_sum_seq_buf<CHUNKS>(t, nt, lds);
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int c = 0; c < CHUNKS; c++) {
+      const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+      double xn = 0.0;
+      if (O::kChain) xn = next_of(x, c, lane);
+      if (e0 < nt) acc = acc + O::term(x[c][0], x[c][1]);
+      if (e0 + 1 < nt) acc = acc + O::term(x[c][1], xn);
+    }
+    return wave_sum(acc);
+  }
+  __device__ inline void grad(const double (&x)[CHUNKS][2], double (&g)[CHUNKS][2], uint64_t &,
+                              uint64_t &gcalls) const {
+    using O = Objective<kObj>;
+    gcalls++;
+    const int lane = lane_id();
+    if constexpr (O::kWhole) {
+#pragma unroll
+      for (int c = 0; c < CHUNKS; c++) g[c][0] = g[c][1] = 0.0;
+      const WavePoint<CHUNKS> pt{x, n};
+      for (uint64_t i = 0; i < n; i++) {
+        const double gi = O::grad(pt, i, n);
+        const int cc = static_cast<int>(i >> 7), kk = static_cast<int>(i & 1);
+        const bool mine = lane == static_cast<int>((i & 127) >> 1);
+#pragma unroll
+        for (int c = 0; c < CHUNKS; c++)
+#pragma unroll
+          for (int k = 0; k < 2; k++)
+            if (mine && c == cc && k == kk) g[c][k] = gi;
+      }
+    } else {
+      const double s = term_sum(x);
+#pragma unroll
+      for (int c = 0; c < CHUNKS; c++) {
+        const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+        // x_{e0-1}: the previous lane's second coordinate, lane 63 of the previous chunk for lane 0
+        const double same = lane_up1(x[c][1]);
+        double prev = 0.0;
+        if (c > 0) prev = lane_last(x[c - 1][1]);
+        const double xm = (lane == 0) ? prev : same;
+        const double nx = next_of(x, c, lane);  // (the shifts run in every lane: selected afterwards)
+        const double xn1 = e0 + 2 < n ? nx : 0.0;
+        const double xn0 = e0 + 1 < n ? x[c][1] : 0.0;
+        double g0 = 0.0, g1 = 0.0;  // lanes past n hold zeros in every vector
+        if (e0 < n) g0 = O::grad(xm, x[c][0], xn0, e0, n, s);
+        if (e0 + 1 < n) g1 = O::grad(x[c][0], x[c][1], xn1, e0 + 1, n, s);
+        g[c][0] = g0;
+        g[c][1] = g1;
+      }
+    }
+  }
+};
+
 // ---- More-Thuente (scalar code, identical in every lane) -------------------------
 __device__ inline double mt_max_abs3(double x, double y, double z) {
   return fmax(fabs(x), fmax(fabs(y), fabs(z)));
@@ -469,19 +580,19 @@ __device__ inline int mt_cstep(double &stx, double &fx, double &dx, double &sty,
       stpf = stpmin;
     }
   }
-  if (fp > fx) {
-    sty = stp;
-    fy = fp;
-    dy = dp;
-  } else {
-    if (sgnd < 0.0) {
-      sty = stx;
-      fy = fx;
-      dy = dx;
-    }
-    stx = stp;
-    fx = fp;
-    dx = dp;
+  {  // the interval's update, chosen by value (assignments to one of two references under a branch become
+     // stores to a selected address, which keeps the bracket in scratch memory)
+    const bool upper = fp > fx, swap = !upper && sgnd < 0.0;
+    const double sty_n = upper ? stp : (swap ? stx : sty);
+    const double fy_n = upper ? fp : (swap ? fx : fy);
+    const double dy_n = upper ? dp : (swap ? dx : dy);
+    const double stx_n = upper ? stx : stp, fx_n = upper ? fx : fp, dx_n = upper ? dx : dp;
+    sty = sty_n;
+    fy = fy_n;
+    dy = dy_n;
+    stx = stx_n;
+    fx = fx_n;
+    dx = dx_n;
   }
   stpf = mt_clamp(stpf, stpmin, stpmax);
   stp = stpf;
@@ -608,18 +719,28 @@ bfgs_search_kernel(BfgsParams p) {
         if ((fcur <= ftest1) & (fabs(dg) <= gtol * (-dginit))) info = 1;
         if (info != 0) break;
         if (stage1 & (fcur <= ftest1) & (dg >= mt_min(ftol, gtol) * dginit)) stage1 = 0;
-        if (stage1 & (fcur <= fx) & (fcur > ftest1)) {
-          const double fm = fcur - stp * dgtest;
-          double fxm = fx - stx * dgtest, fym = fy - sty * dgtest;
-          const double dgm = dg - dgtest;
-          double dgxm = dgx - dgtest, dgym = dgy - dgtest;
-          mt_cstep(stx, fxm, dgxm, sty, fym, dgym, stp, fm, dgm, brackt, stmin, stmax, infoc);
+        // ONE call site, on copies chosen by value: with two calls on different references the compiler
+        // merges them into one call on a selected address, and the bracket then lives in scratch memory
+        const bool modified = stage1 & (fcur <= fx) & (fcur > ftest1);  // the modified function of stage 1
+        double fxm = fx, fym = fy, dgxm = dgx, dgym = dgy, fm = fcur, dgm = dg;
+        if (modified) {
+          fm = fcur - stp * dgtest;
+          fxm = fx - stx * dgtest;
+          fym = fy - sty * dgtest;
+          dgm = dg - dgtest;
+          dgxm = dgx - dgtest;
+          dgym = dgy - dgtest;
+        }
+        mt_cstep(stx, fxm, dgxm, sty, fym, dgym, stp, fm, dgm, brackt, stmin, stmax, infoc);
+        fx = fxm;
+        fy = fym;
+        dgx = dgxm;
+        dgy = dgym;
+        if (modified) {
           fx = fxm + stx * dgtest;
           fy = fym + sty * dgtest;
           dgx = dgxm + dgtest;
           dgy = dgym + dgtest;
-        } else {
-          mt_cstep(stx, fx, dgx, sty, fy, dgy, stp, fcur, dg, brackt, stmin, stmax, infoc);
         }
         if (brackt) {
           if (fabs(sty - stx) >= 0.66 * width1) stp = stx + 0.5 * (sty - stx);

@@ -230,6 +230,13 @@ __device__ inline double lane_first(double v) {
   const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<int>(b >> 32));
   return __longlong_as_double(static_cast<long long>((static_cast<uint64_t>(hi) << 32) | lo));
 }
+// lane 63's value through scalar registers (lane_up1's counterpart of lane_first across a chunk boundary)
+__device__ inline double lane_last(double v) {
+  const uint64_t b = static_cast<uint64_t>(__double_as_longlong(v));
+  const uint32_t lo = __builtin_amdgcn_readlane(static_cast<int>(b & 0xffffffffu), 63);
+  const uint32_t hi = __builtin_amdgcn_readlane(static_cast<int>(b >> 32), 63);
+  return __longlong_as_double(static_cast<long long>((static_cast<uint64_t>(hi) << 32) | lo));
+}
 // ---- scalar-issue relief. A CU has ONE scalar unit for its four SIMDs: per SIMD it issues at
 // most one scalar instruction every four cycles, the same rate as the SIMD's vector instructions,
 // and wave-uniform 64-bit integer work (the keyed RNG of a whole agent: ~25 scalar instructions

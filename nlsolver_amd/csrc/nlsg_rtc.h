@@ -22,15 +22,17 @@ struct PsoRtcKernels {
 int rtc_build_de(const nlsg_custom_objective *obj, int chunks, bool vec, int group,
                  DeRtcKernels *out);
 void rtc_release(DeRtcKernels *k);
-struct BfgsRtcKernels {  // finite-difference model around the user's objective
+struct BfgsRtcKernels {  // finite-difference model around the user's objective, or the one on its gradient body
   hipModule_t mod = nullptr;
   hipFunction_t init = nullptr, search = nullptr;
 };
 // wave_rows_offset: where the per-wave parameter rows (obj->n_params > 0) start in the kernels' dynamic
 // LDS block, in doubles — the caller's own launch layout (behind bfgs_fd_seq_lds_bytes(chunks) in
 // reference order, else 0); it becomes NLSG_PARAMS_PER_WAVE
+// grad_body != nullptr (nlsg_bfgs_create_gradient): the kernels are instantiated on kBfgsCustomGrad, whose
+// gradient is that body (Objective<NLSG_OBJ_CUSTOM>::grad) instead of finite differences
 int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long wave_rows_offset,
-                   BfgsRtcKernels *out);
+                   BfgsRtcKernels *out, const char *grad_body = nullptr);
 void rtc_release(BfgsRtcKernels *k);
 struct NmRtcKernels {
   hipModule_t mod = nullptr;

@@ -78,9 +78,12 @@ static int rtc_compile_source(const std::string &src, const char *what,
 // with one function per name expression (kernel template-ids).
 // wave_rows_offset >= 0 (rtc_build_bfgs, with n_params > 0 only): the kernels own a wave per solve, so the
 // rows live per wave in the dynamic LDS block, that many doubles from its start (NLSG_PARAMS_PER_WAVE).
+// grad_body (rtc_build_bfgs for nlsg_bfgs_create_gradient only): one more member, Objective::grad, made of it;
+// without one the source is byte for byte what it is without this argument.
 static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_header,
                        const std::vector<std::string> &name_exprs, hipModule_t *mod_out,
-                       std::vector<hipFunction_t> *fns_out, long wave_rows_offset = -1) {
+                       std::vector<hipFunction_t> *fns_out, long wave_rows_offset = -1,
+                       const char *grad_body = nullptr) {
   if (!obj || !obj->term_body || !obj->term_body[0])
     return fail(NLSG_ERR_INVALID_ARG, "a custom objective needs a term body");
   // n_params > 0 (resident batch engines and nlsg_nm / nmpso / lm / bfgs_create_params; every
@@ -112,7 +115,15 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
            "  __device__ static inline double whole(const X &x, uint64_t D) {\n    (void)D;\n#line 1 "
            "\"vector_body\"\n";
     src += obj->term_body;
-    src += "\n  }\n};\n}  // namespace nlsg\n";
+    src += "\n  }\n";
+    if (grad_body) {  // the body of  double grad(const X &x, uint64_t i, uint64_t D)  = df/dx_i, i wave-uniform
+      src += "  template <typename X>\n"
+             "  __device__ static inline double grad(const X &x, uint64_t i, uint64_t D) {\n"
+             "    (void)x;\n    (void)i;\n    (void)D;\n#line 1 \"grad_body\"\n";
+      src += grad_body;
+      src += "\n  }\n";
+    }
+    src += "};\n}  // namespace nlsg\n";
   } else {
     src += "  static constexpr bool kWhole = false;\n"
            "  static constexpr bool kChain = ";
@@ -127,8 +138,16 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
     src += (obj->finish_body && obj->finish_body[0]) ? obj->finish_body : "return s;";
     src += "\n  }\n"
            "  template <typename X>\n"
-           "  __device__ static inline double whole(const X &, uint64_t) { return 0.0; }\n"
-           "};\n}  // namespace nlsg\n";
+           "  __device__ static inline double whole(const X &, uint64_t) { return 0.0; }\n";
+    if (grad_body) {  // df/dx_i from x_{i-1}, x_i, x_{i+1} and the sum of terms s, per lane
+      src += "  __device__ static inline double grad(double xm, double xi, double xn, uint64_t i, uint64_t D, "
+             "double s) {\n"
+             "    (void)xm;\n    (void)xi;\n    (void)xn;\n    (void)i;\n    (void)D;\n    (void)s;\n#line 1 "
+             "\"grad_body\"\n";
+      src += grad_body;
+      src += "\n  }\n";
+    }
+    src += "};\n}  // namespace nlsg\n";
   }
   return rtc_compile_source(src, "custom objective", name_exprs, mod_out, fns_out);
 }
@@ -375,15 +394,17 @@ int rtc_build_pso(const nlsg_custom_objective *obj, int chunks, bool vec, int ty
 }
 
 int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long wave_rows_offset,
-                   BfgsRtcKernels *out) {
-  // <CHUNKS, VEC, MODEL>: MODEL = the objective id selects the finite-difference BfgsModel
+                   BfgsRtcKernels *out, const char *grad_body) {
+  // <CHUNKS, VEC, MODEL>: MODEL = the objective id selects the finite-difference BfgsModel, kBfgsCustomGrad
+  // (-2, nlsg_bfgs_kernels.h) the one that evaluates the objective's own gradient body
   const std::string t = std::to_string(chunks) + ", " + (vec ? "true" : "false") + ", " +
-                        std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM));
+                        (grad_body ? std::string("nlsg::kBfgsCustomGrad")
+                                   : std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)));
   std::vector<hipFunction_t> f;
   BfgsRtcKernels k;
   const int rc = rtc_compile(obj, "nlsg_bfgs_kernels.h",
                              {"nlsg::bfgs_init_kernel<" + t + ">", "nlsg::bfgs_search_kernel<" + t + ">"},
-                             &k.mod, &f, wave_rows_offset);  // (a row per wave in the dynamic block)
+                             &k.mod, &f, wave_rows_offset, grad_body);  // (a row per wave in the dynamic block)
   if (rc) return rc;
   k.init = f[0];
   k.search = f[1];

@@ -58,9 +58,29 @@ class CustomObjective:
     NMPSOEngine take such an objective the same way (set_params: start / instance b sees row b), and
     NelderMead / NelderMeadPSO take `params=`; no other engine does. At most CUSTOM_MAX_PARAMS.
 
-        CustomObjective("double r = xi - p(0); return p(1) * r * r;", n_params=2)"""
+        CustomObjective("double r = xi - p(0); return p(1) * r * r;", n_params=2)
 
-    def __init__(self, term_body, *, chain=False, finish_body="return s;", vector=False, n_params=0):
+    grad_body: the objective's analytic gradient as one more body, which BFGSEngine / BFGS evaluate
+    instead of the default finite differences (nlsg_bfgs_create_gradient); every other engine ignores
+    it. Terms and chain objectives: the body of
+    `double grad(double xm, double xi, double xn, uint64_t i, uint64_t D, double s)`, returning
+    df/dx_i, with xm = x_{i-1} (+0.0 at i = 0), xn = x_{i+1} (+0.0 at i = D - 1) and s the sum of the
+    objective's terms at x, what `finish` receives; plain per-lane code. vector=True: the body of
+    `double grad(const X &x, uint64_t i, uint64_t D)` with x(i), x.size(), x.sum(g); it is called for
+    i = 0 .. D - 1 with the same i in every lane — D evaluations of the body per gradient, against
+    4 D evaluations of the objective with finite differences. p(k) works in either.
+
+        CustomObjective("double t1 = 1 - xi; double t2 = xn - xi * xi; return t1 * t1 + 100 * t2 * t2;",
+                        chain=True,
+                        grad_body="double g = 0.0;"
+                                  " if (i + 1 < D) g = -2.0 * (1.0 - xi) - 400.0 * xi * (xn - xi * xi);"
+                                  " if (i > 0) g = g + 200.0 * (xi - xm * xm); return g;")"""
+
+    def __init__(self, term_body, *, chain=False, finish_body="return s;", vector=False, n_params=0,
+                 grad_body=None):
+        if grad_body is not None and (not isinstance(grad_body, str) or not grad_body.strip()):
+            raise ValueError("grad_body must be a non-empty string of source text, or None")
+        self.grad_body = grad_body
         self.term_body, self.finish_body = term_body, finish_body
         self.chain = 2 if vector else int(bool(chain))  # nlsg_custom_objective.chain
         n_params = int(n_params)

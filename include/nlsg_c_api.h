@@ -144,7 +144,9 @@ typedef enum {
   NLSG_PROBE_LOG_UNIT = 7,  /* the table logarithm of rnorm, x in [2^-64, 1]               */
   NLSG_PROBE_RNORM_COS = 8, /* draw -> rnorm's signed cosine factor cos(2 pi_ u2)          */
   NLSG_PROBE_GIVENS_T = 9,  /* r -> 1 / sqrt(r^2 + 1), the Givens rotation of tinyqr / LM   */
-  NLSG_PROBE_SQRT = 10      /* x -> sqrt(x), x = 0, +inf or x >= 2^-767                     */
+  NLSG_PROBE_SQRT = 10,     /* x -> sqrt(x), x = 0, +inf or x >= 2^-767                     */
+  NLSG_PROBE_WAVE_SUM = 11  /* n a multiple of 64: every lane returns the kernels' xor-butterfly
+                             * sum (wave_sum) over the 64 arguments of its wave               */
 } nlsg_probe_fn;
 int nlsg_probe_math(int32_t fn, const uint64_t *in_host, uint64_t *out_host, uint64_t n,
                     int32_t device);

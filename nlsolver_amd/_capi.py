@@ -405,13 +405,15 @@ def pinned_empty(shape, dtype="float64"):
 
 
 PROBE_FUNCTIONS = {"log": 0, "cos": 1, "exp": 2, "tanh": 3, "cos_2pi": 4, "u01": 5, "rnorm": 6,
-                   "log_unit": 7, "rnorm_cos": 8, "givens_t": 9, "sqrt": 10}
+                   "log_unit": 7, "rnorm_cos": 8, "givens_t": 9, "sqrt": 10, "wave_sum": 11}
 
 
 def probe_math(fn, bits, device=0):
     """nlsg_probe_math: the device's deterministic primitive `fn` ("log", "cos", "exp", "tanh",
     "cos_2pi", "log_unit", "givens_t", "sqrt": argument = a double's bit pattern; "u01", "rnorm",
-    "rnorm_cos": argument = a 64-bit draw) on a uint64 array; returns the results' bit patterns."""
+    "rnorm_cos": argument = a 64-bit draw) on a uint64 array; returns the results' bit patterns.
+    "wave_sum": the array's size is a multiple of 64, and element i is the kernels' butterfly sum
+    over the 64 doubles of its wave, as lane i % 64 holds it."""
     import numpy as np
     bits = np.ascontiguousarray(bits, dtype=np.uint64)
     out = np.empty_like(bits)

@@ -166,6 +166,19 @@ __host__ __device__ inline uint64_t clamp_index(double u, uint64_t n) {
   return p >= n ? n - 1 : p;
 }
 
+// kGolden * i for an index that fits 32 bits: a 32 x 64 product (one v_mad_u64_u32 and one
+// v_mul_lo_u32), where the 64 x 64 one costs three multiplies -- one of them by a zero the compiler
+// does not see. The low 64 bits of the product, as the full multiply gives them.
+__host__ __device__ inline uint64_t golden_times(uint32_t i) {
+  return static_cast<uint64_t>(i) * static_cast<uint32_t>(kGolden) +
+         (static_cast<uint64_t>(i * static_cast<uint32_t>(kGolden >> 32)) << 32);
+}
+// n as a 32-bit limit: e < n for a 32-bit e is e < limit32(n), a one-instruction compare per lane
+// without the set-up a 64-bit one needs (n wave-uniform: the clamp is two scalar instructions)
+__host__ __device__ inline uint32_t limit32(uint64_t n) {
+  return static_cast<uint32_t>(n >> 32) != 0 ? 0xffffffffu : static_cast<uint32_t>(n);  // (no 64-bit scalar '<')
+}
+
 // ---------------------------------------------------------------------------
 // wave64 helpers
 // ---------------------------------------------------------------------------
@@ -267,6 +280,20 @@ __device__ inline double lane_broadcast(double v, int src) {
   return __longlong_as_double(static_cast<long long>(
       readlane64(static_cast<uint64_t>(__double_as_longlong(v)), src)));
 }
+// ---- predicates as lane masks. A per-lane bool IS a 64-bit mask in scalar registers; kept as a
+// uint64_t, combining predicates (and, or, not, "any lane", "the next lane's") is scalar work on
+// values the compares already left there, where __ballot of a combined bool goes through the
+// vector unit (a 0/1 select and a compare per ballot). lane_bit(m): this lane's bit of m as a bool.
+// (a run-time compiler older than the builtin takes a select on the mask and a compare instead)
+__device__ inline bool lane_bit(uint64_t m) {
+#if __has_builtin(__builtin_amdgcn_inverse_ballot_w64)
+  return __builtin_amdgcn_inverse_ballot_w64(m);
+#else
+  uint32_t r;
+  asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(r) : "s"(m));
+  return r != 0;
+#endif
+}
 // f(int_c<OFF>) for OFF = FIRST, FIRST/2, ..., 1
 template <int N>
 struct int_c {
@@ -278,9 +305,51 @@ __device__ inline void butterfly_levels(F &&f) {
   if constexpr (FIRST > 1) butterfly_levels<FIRST / 2>(f);
 }
 
+// xor_add<OFF>(v) = v + lane_xor<OFF>(v), one level of the sum butterflies, in fewer vector
+// instructions than the exchange followed by the addition:
+//  - the DPP levels (8, 4, 2, 1) move out of v into a fresh register (no tied `old` operand, so
+//    no copy of v in front of the move); level 4's second bank-masked move completes the first;
+//  - the swap levels (16, 32) add the two results of the swap instead of selecting the partner's:
+//    r[0] is the lower (even row / lower half) side's value in both sides, r[1] the upper side's,
+//    so r[0] + r[1] is own + partner on the lower side and partner + own on the upper one -- the
+//    same bits for every non-NaN pair (fp64 addition is commutative), without the lane predicate
+//    and the selects. Lane 0 is on the lower side of every level: there the operand order is
+//    own first, as in v + lane_xor<OFF>(v), even for a NaN's payload.
+template <int CTRL, int BANK>
+__device__ inline uint32_t dpp_fresh32(uint32_t src) {
+  return static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(src), CTRL, 0xF, BANK, true));
+}
+template <int OFF>
+__device__ inline double xor_add(double v) {
+  static_assert(OFF == 1 || OFF == 2 || OFF == 4 || OFF == 8 || OFF == 16 || OFF == 32, "");
+  const uint64_t b = static_cast<uint64_t>(__double_as_longlong(v));
+  const uint32_t lo = static_cast<uint32_t>(b), hi = static_cast<uint32_t>(b >> 32);
+  auto f64 = [](uint32_t l, uint32_t h) {
+    return __longlong_as_double(static_cast<long long>((static_cast<uint64_t>(h) << 32) | l));
+  };
+  if constexpr (OFF == 16 || OFF == 32) {
+    if constexpr (OFF == 16) {
+      const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+      const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+      return f64(rl[0], rh[0]) + f64(rl[1], rh[1]);
+    } else {
+      const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+      const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+      return f64(rl[0], rh[0]) + f64(rl[1], rh[1]);
+    }
+  } else if constexpr (OFF == 4) {  // row_shl:4 -> banks 0,2, then row_shr:4 -> banks 1,3
+    const uint32_t pl = dpp_mov32<0x114, 0xA>(dpp_fresh32<0x104, 0x5>(lo), lo);
+    const uint32_t ph = dpp_mov32<0x114, 0xA>(dpp_fresh32<0x104, 0x5>(hi), hi);
+    return v + f64(pl, ph);
+  } else {
+    constexpr int ctrl = OFF == 1 ? 0xB1 : OFF == 2 ? 0x4E : 0x128;  // as lane_xor32
+    return v + f64(dpp_fresh32<ctrl, 0xF>(lo), dpp_fresh32<ctrl, 0xF>(hi));
+  }
+}
+
 // xor butterfly (32,16,8,4,2,1): every lane ends with the same bit pattern.
 __device__ inline double wave_sum(double v) {
-  butterfly_levels<32>([&](auto off) { v = v + lane_xor<decltype(off)::value>(v); });
+  butterfly_levels<32>([&](auto off) { v = xor_add<decltype(off)::value>(v); });
   return v;
 }
 
@@ -519,11 +588,13 @@ __device__ inline double wave_objective(const double (&xv)[CHUNKS][2], uint64_t 
   using O = Objective<OBJ>;
   if constexpr (O::kWhole) return O::whole(WavePoint<CHUNKS>{xv, D}, D);
   const int lane = lane_id();
-  const uint64_t nt = O::n_terms(D);
+  // (the point is in the registers, D <= 128 CHUNKS: said to the compiler, the wave-uniform term
+  // count is 32-bit scalar work, and the lanes' range tests one compare each)
+  const uint32_t nt = limit32(O::n_terms(static_cast<uint32_t>(D)));
   double acc = 0.0;
 #pragma unroll
   for (int c = 0; c < CHUNKS; c++) {
-    const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+    const uint32_t e0 = static_cast<uint32_t>(c) * 128 + 2 * static_cast<uint32_t>(lane);
     double xn = 0.0;
     if (O::kChain) {
       // x[e0+2]: lane+1's first element (DPP wave shift), or lane 0 of the next chunk for lane 63
@@ -562,34 +633,36 @@ struct TermsNonNegative<NLSG_OBJ_SPHERE> {
 // compares false), and equal to it when every coordinate is known (acc >= +0 or NaN, and
 // acc + +0.0 == acc). The neighbour's flag travels the way its value does.
 template <int OBJ, int CHUNKS>
-__device__ inline double wave_objective_masked(const double (&xv)[CHUNKS][2], const bool (&known)[CHUNKS][2],
-                                               uint64_t D) {
+__device__ inline double wave_objective_masked(const double (&xv)[CHUNKS][2], const uint64_t (&known)[CHUNKS][2],
+                                               uint64_t D) {  // known: lane masks (lane_bit)
   using O = Objective<OBJ>;
   static_assert(!O::kWhole, "term objectives only");
   const int lane = lane_id();
-  const uint64_t nt = O::n_terms(D);
+  // (the point is in the registers, D <= 128 CHUNKS: said to the compiler, the wave-uniform term
+  // count is 32-bit scalar work, and the lanes' range tests one compare each)
+  const uint32_t nt = limit32(O::n_terms(static_cast<uint32_t>(D)));
   double acc = 0.0;
 #pragma unroll
   for (int c = 0; c < CHUNKS; c++) {
-    const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+    const uint32_t e0 = static_cast<uint32_t>(c) * 128 + 2 * static_cast<uint32_t>(lane);
     double xn = 0.0;
     bool kn = true, k1 = true;  // without a chain a term reads x[i] alone
     if (O::kChain) {
       const double same = lane_down1(xv[c][0]);
-      const uint32_t f0 = known[c][0] ? 1u : 0u;
-      const uint32_t fsame = dpp_mov32<0x130, 0xF>(f0, f0);
+      // lane l + 1's flag: the lane mask of known[c][0] shifted down by one, lane 63's bit from
+      // lane 0 of the next chunk -- scalar work on masks the compares already left there
+      uint64_t next_known = known[c][0] >> 1;
       double next = 0.0;
-      uint32_t fnext = 0;
       if (c + 1 < CHUNKS) {
         next = lane_first(xv[c + 1][0]);
-        fnext = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(known[c + 1][0] ? 1 : 0));
+        next_known |= known[c + 1][0] << 63;
       }
       xn = (lane == 63) ? next : same;
-      kn = ((lane == 63) ? fnext : fsame) != 0;
-      k1 = known[c][1];
+      kn = lane_bit(next_known);
+      k1 = lane_bit(known[c][1]);
     }
-    if (e0 < nt) acc = acc + ((known[c][0] && k1) ? O::term(xv[c][0], xv[c][1]) : 0.0);
-    if (e0 + 1 < nt) acc = acc + ((known[c][1] && kn) ? O::term(xv[c][1], xn) : 0.0);
+    if (e0 < nt) acc = acc + ((lane_bit(known[c][0]) && k1) ? O::term(xv[c][0], xv[c][1]) : 0.0);
+    if (e0 + 1 < nt) acc = acc + ((lane_bit(known[c][1]) && kn) ? O::term(xv[c][1], xn) : 0.0);
   }
   return O::finish(wave_sum(acc), D);
 }
@@ -880,17 +953,18 @@ template <int CHUNKS, bool VEC>
 __device__ inline void load_row(const double *__restrict__ row, uint64_t D,
                                 const double *__restrict__ zero, double (&v)[CHUNKS][2]) {
   const int lane = lane_id();
+  const uint32_t n = limit32(D);  // e0 < 128 CHUNKS: 32-bit compares
 #pragma unroll
   for (int c = 0; c < CHUNKS; c++) {
-    const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+    const uint32_t e0 = static_cast<uint32_t>(c) * 128 + 2 * static_cast<uint32_t>(lane);
     if (VEC) {
-      const double *src = (e0 < D) ? row + e0 : zero;  // D even: e0 + 1 < D as well
+      const double *src = (e0 < n) ? row + e0 : zero;  // D even: e0 + 1 < n as well
       const double2 t = *reinterpret_cast<const double2 *>(src);
       v[c][0] = t.x;
       v[c][1] = t.y;
     } else {
-      v[c][0] = *((e0 < D) ? row + e0 : zero);
-      v[c][1] = *((e0 + 1 < D) ? row + e0 + 1 : zero);
+      v[c][0] = *((e0 < n) ? row + e0 : zero);
+      v[c][1] = *((e0 + 1 < n) ? row + e0 + 1 : zero);
     }
   }
 }
@@ -898,14 +972,15 @@ template <int CHUNKS, bool VEC>
 __device__ inline void store_row(double *__restrict__ row, uint64_t D,
                                  const double (&v)[CHUNKS][2]) {
   const int lane = lane_id();
+  const uint32_t n = limit32(D);  // e0 < 128 CHUNKS: 32-bit compares
 #pragma unroll
   for (int c = 0; c < CHUNKS; c++) {
-    const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+    const uint32_t e0 = static_cast<uint32_t>(c) * 128 + 2 * static_cast<uint32_t>(lane);
     if (VEC) {
-      if (e0 < D) *reinterpret_cast<double2 *>(row + e0) = make_double2(v[c][0], v[c][1]);
+      if (e0 < n) *reinterpret_cast<double2 *>(row + e0) = make_double2(v[c][0], v[c][1]);
     } else {
-      if (e0 < D) row[e0] = v[c][0];
-      if (e0 + 1 < D) row[e0 + 1] = v[c][1];
+      if (e0 < n) row[e0] = v[c][0];
+      if (e0 + 1 < n) row[e0 + 1] = v[c][1];
     }
   }
 }
@@ -918,16 +993,17 @@ template <int CHUNKS, bool VEC>
 __device__ inline void load_row_stream(const double *__restrict__ row, uint64_t D,
                                        const double *__restrict__ zero, double (&v)[CHUNKS][2]) {
   const int lane = lane_id();
+  const uint32_t n = limit32(D);  // e0 < 128 CHUNKS: 32-bit compares
 #pragma unroll
   for (int c = 0; c < CHUNKS; c++) {
-    const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+    const uint32_t e0 = static_cast<uint32_t>(c) * 128 + 2 * static_cast<uint32_t>(lane);
     if (VEC) {
-      const nlsg_v2d t = __builtin_nontemporal_load(reinterpret_cast<const nlsg_v2d *>((e0 < D) ? row + e0 : zero));
+      const nlsg_v2d t = __builtin_nontemporal_load(reinterpret_cast<const nlsg_v2d *>((e0 < n) ? row + e0 : zero));
       v[c][0] = t.x;
       v[c][1] = t.y;
     } else {
-      v[c][0] = __builtin_nontemporal_load((e0 < D) ? row + e0 : zero);
-      v[c][1] = __builtin_nontemporal_load((e0 + 1 < D) ? row + e0 + 1 : zero);
+      v[c][0] = __builtin_nontemporal_load((e0 < n) ? row + e0 : zero);
+      v[c][1] = __builtin_nontemporal_load((e0 + 1 < n) ? row + e0 + 1 : zero);
     }
   }
 }
@@ -935,17 +1011,18 @@ template <int CHUNKS, bool VEC>
 __device__ inline void store_row_stream(double *__restrict__ row, uint64_t D,
                                         const double (&v)[CHUNKS][2]) {
   const int lane = lane_id();
+  const uint32_t n = limit32(D);  // e0 < 128 CHUNKS: 32-bit compares
 #pragma unroll
   for (int c = 0; c < CHUNKS; c++) {
-    const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+    const uint32_t e0 = static_cast<uint32_t>(c) * 128 + 2 * static_cast<uint32_t>(lane);
     if (VEC) {
       nlsg_v2d t;
       t.x = v[c][0];
       t.y = v[c][1];
-      if (e0 < D) __builtin_nontemporal_store(t, reinterpret_cast<nlsg_v2d *>(row + e0));
+      if (e0 < n) __builtin_nontemporal_store(t, reinterpret_cast<nlsg_v2d *>(row + e0));
     } else {
-      if (e0 < D) __builtin_nontemporal_store(v[c][0], row + e0);
-      if (e0 + 1 < D) __builtin_nontemporal_store(v[c][1], row + e0 + 1);
+      if (e0 < n) __builtin_nontemporal_store(v[c][0], row + e0);
+      if (e0 + 1 < n) __builtin_nontemporal_store(v[c][1], row + e0 + 1);
     }
   }
 }

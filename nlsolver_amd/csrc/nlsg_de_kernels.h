@@ -147,30 +147,31 @@ struct DeAgent {
   uint32_t home;          // home[par][a] & 1: the buffer holding the agent's row
   uint32_t hint;          // home[par][a] & 2: the bound did not decide this agent's last try
   bool bound;             // wave-uniform: this generation tries the bound, `keep` is not loaded yet
-  bool cross[CHUNKS][2];  // the trial takes the mutant here (crossover draw or jrand)
+  uint64_t cross[CHUNKS][2];  // lane masks (lane_bit): the trial takes the mutant here (crossover draw or jrand)
   double keep[CHUNKS][2], d1[CHUNKS][2], d2[CHUNKS][2], d3[CHUNKS][2];
   double old_score;
 };
 
 // load_row where the trial keeps the old coordinate only: a lane whose coordinates all take the
-// mutant (`skip`) reads the zero pad instead (at CR 0.9 about 4 lanes in 5); `none` (wave-uniform):
+// mutant (`skip`, lane masks) reads the zero pad instead (at CR 0.9 about 4 lanes in 5); `none` (wave-uniform):
 // every lane does
 template <int CHUNKS, bool VEC>
 __device__ inline void load_row_kept(const double *__restrict__ row, uint64_t D,
-                                     const double *__restrict__ zero, const bool (&skip)[CHUNKS][2],
+                                     const double *__restrict__ zero, const uint64_t (&skip)[CHUNKS][2],
                                      double (&v)[CHUNKS][2], bool none = false) {
   const int lane = lane_id();
+  const uint32_t n = none ? 0u : limit32(D);  // `none` folded into the wave-uniform limit
 #pragma unroll
   for (int c = 0; c < CHUNKS; c++) {
-    const uint64_t e0 = static_cast<uint64_t>(c) * 128 + 2 * static_cast<uint64_t>(lane);
+    const uint32_t e0 = static_cast<uint32_t>(c) * 128 + 2 * static_cast<uint32_t>(lane);
     if (VEC) {
-      const double *src = (e0 < D && !(skip[c][0] && skip[c][1]) && !none) ? row + e0 : zero;
+      const double *src = (e0 < n && !lane_bit(skip[c][0] & skip[c][1])) ? row + e0 : zero;
       const double2 t = *reinterpret_cast<const double2 *>(src);
       v[c][0] = t.x;
       v[c][1] = t.y;
     } else {
-      v[c][0] = *((e0 < D && !skip[c][0] && !none) ? row + e0 : zero);
-      v[c][1] = *((e0 + 1 < D && !skip[c][1] && !none) ? row + e0 + 1 : zero);
+      v[c][0] = *((e0 < n && !lane_bit(skip[c][0])) ? row + e0 : zero);
+      v[c][1] = *((e0 + 1 < n && !lane_bit(skip[c][1])) ? row + e0 + 1 : zero);
     }
   }
 }
@@ -189,8 +190,10 @@ __device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, u
   // generate_index (:2325-2329), size_t(u * max): shard sizes and D fit 32 bits, so the
   // conversion is the one-instruction 32-bit one (same truncation)
   const uint32_t lim = static_cast<uint32_t>(lane == 0 ? p.D : p.shard_n);
-  const uint32_t idx = static_cast<uint32_t>(u01(ctr_key(ka, p.D + static_cast<uint64_t>(lane))) *
-                                             static_cast<double>(lim));
+  // (draw D + lane: its index + 1 fits 32 bits like D, golden_times)
+  const uint32_t idx = static_cast<uint32_t>(
+      u01(mix64(ka + golden_times(static_cast<uint32_t>(p.D) + static_cast<uint32_t>(lane) + 1u))) *
+      static_cast<double>(lim));
   const uint64_t drawn = idx >= lim ? lim - 1 : idx;  // the u == 1.0 corner clamped (B10)
   // Home selectors, loaded here so that their latency hides behind the donor picks: lane 0 the
   // agent's own, lanes 1..7 those of donor candidates 0..6 (a pick past candidate 6 -- tiny
@@ -204,14 +207,16 @@ __device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, u
   // ctr_key(ka, e) = mix64(ka + G (e + 1)), e + 1 = (2 lane + 1) + (128 ch + k): one 64-bit
   // multiply per lane, the rest are compile-time constants; u01(z) < CR is decided on the
   // draw's bits (cr_thresh: the smallest z whose uniform is >= CR)
-  const uint64_t ka_lane = ka + kGolden * (2 * static_cast<uint64_t>(lane) + 1);
+  const uint64_t ka_lane = ka + golden_times(2 * static_cast<uint32_t>(lane) + 1u);
+  const uint32_t jrand32 = static_cast<uint32_t>(c.jrand);  // < D <= 1024
+  const uint64_t cr_all = p.cr_all ? ~0ull : 0ull;
 #pragma unroll
   for (int ch = 0; ch < CHUNKS; ch++) {
 #pragma unroll
     for (int k = 0; k < 2; k++) {
-      const uint64_t e = static_cast<uint64_t>(ch) * 128 + 2 * static_cast<uint64_t>(lane) + k;
+      const uint32_t e = static_cast<uint32_t>(ch) * 128 + 2 * static_cast<uint32_t>(lane) + k;
       const uint64_t z = mix64(ka_lane + kGolden * static_cast<uint64_t>(128 * ch + k));
-      c.cross[ch][k] = z < p.cr_thresh || p.cr_all || e == c.jrand;
+      c.cross[ch][k] = __ballot(z < p.cr_thresh) | cr_all | __ballot(e == jrand32);
     }
   }
   // generate_indices (nlsolver.h:2331-2355): three distinct donors != fixed,
@@ -260,12 +265,23 @@ __device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, u
       }
     }
   }
-  // candidate i - 1 sits in lane i
-  auto home_of = [&](int i, uint64_t r) -> uint32_t {
-    return (!slow && i < 8) ? static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hsel), i))
-                            : hp[r - p.shard_lo];
+  // candidate i - 1 sits in lane i: the selector is read from lane min(i, 7) without a branch, and
+  // one wave-uniform branch for all three donors replaces it by a load where that lane is not the
+  // candidate's (a pick past candidate 6, or the literal loop: tiny shards). Without the literal
+  // loop i0 < i1 < i2, so i2 decides for the three. The loaded bytes go back to scalar registers:
+  // the buffer select below then stays on the scalar unit.
+  auto sel_lane = [&](int i) {
+    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hsel), i < 7 ? i : 7));
   };
-  const uint32_t h0 = home_of(i0, r0), h1 = home_of(i1, r1), h2 = home_of(i2, r2);
+  uint32_t h0 = sel_lane(i0), h1 = sel_lane(i1), h2 = sel_lane(i2);
+  if (slow || i2 >= 8) {
+    auto sel_load = [&](uint64_t r) {
+      return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(hp[r - p.shard_lo])));
+    };
+    h0 = sel_load(r0);
+    h1 = sel_load(r1);
+    h2 = sel_load(r2);
+  }
   c.a = a;
   c.ka = ka;
   c.r0 = r0;
@@ -282,9 +298,17 @@ __device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, u
   // rows: 3 donors and the non-crossed source -- the agent's own row for strategy random, the
   // row of best_id (L2-resident) for strategy best -- where the trial keeps it
   // (shard-local indices and D fit 32 bits: one scalar multiply pair per row offset)
+  // Both buffer bases are taken out of the kernel arguments once and the selector -- in a scalar
+  // register -- selects between the two values: left to itself the compiler loads the base from
+  // the argument block at an offset made from the selector, a dependent scalar load per row behind
+  // a detour through the vector unit.
   const uint32_t d32 = static_cast<uint32_t>(p.D);
+  // (global address space spelled out: behind the asm the compiler no longer sees a kernel argument)
+  typedef double __attribute__((address_space(1))) global_double;
+  global_double *b0 = (global_double *)p.buf[0], *b1 = (global_double *)p.buf[1];
+  asm("" : "+s"(b0), "+s"(b1));
   auto row = [&](uint32_t h, uint64_t local) {
-    return ((h & 1u) ? p.buf[1] : p.buf[0]) + static_cast<uint64_t>(static_cast<uint32_t>(local)) * d32;
+    return (double *)((h & 1u) ? b1 : b0) + static_cast<uint64_t>(static_cast<uint32_t>(local)) * d32;
   };
   load_row<CHUNKS, VEC>(row(h0, r0 - p.shard_lo), D, p.zero, c.d1);
   load_row<CHUNKS, VEC>(row(h1, r1 - p.shard_lo), D, p.zero, c.d2);
@@ -331,17 +355,18 @@ __device__ inline void de_process_agent(const DeParams &p, int par, DeAgent<CHUN
   double trial[CHUNKS][2];
   if constexpr (BOUND) {
     if (c.bound) {  // wave-uniform; fmul == 1 here, so the objective's value is the score
-      bool keeps = false;  // a coordinate inside D that the trial takes from the old row
+      uint64_t kept = 0;  // lanes with a coordinate inside D that the trial takes from the old row
+      const uint32_t d32 = static_cast<uint32_t>(D);
 #pragma unroll
       for (int ch = 0; ch < CHUNKS; ch++) {
 #pragma unroll
         for (int k = 0; k < 2; k++) {
-          const uint64_t e = static_cast<uint64_t>(ch) * 128 + 2 * static_cast<uint64_t>(lane) + k;
+          const uint32_t e = static_cast<uint32_t>(ch) * 128 + 2 * static_cast<uint32_t>(lane) + k;
           trial[ch][k] = c.d1[ch][k] + p.F * (c.d2[ch][k] - c.d3[ch][k]);  // the mutant everywhere
-          keeps = keeps || (e < D && !c.cross[ch][k]);
+          kept |= __ballot(e < d32) & ~c.cross[ch][k];
         }
       }
-      const bool any_kept = __ballot(keeps) != 0ull;
+      const bool any_kept = kept != 0ull;
       const double bound = wave_objective_masked<OBJ, CHUNKS>(trial, c.cross, D);
       if (bound >= c.old_score) {  // (false for NaN) the score cannot be lower: rejected unread
         select(false, bound, trial, 0u);
@@ -359,7 +384,7 @@ __device__ inline void de_process_agent(const DeParams &p, int par, DeAgent<CHUN
 #pragma unroll
       for (int ch = 0; ch < CHUNKS; ch++) {
 #pragma unroll
-        for (int k = 0; k < 2; k++) trial[ch][k] = c.cross[ch][k] ? trial[ch][k] : c.keep[ch][k];
+        for (int k = 0; k < 2; k++) trial[ch][k] = lane_bit(c.cross[ch][k]) ? trial[ch][k] : c.keep[ch][k];
       }
       const double score = wave_objective<OBJ, CHUNKS>(trial, D);  // :2463
       const bool accept = score < c.old_score;                     // :2466 (NaN -> keep)
@@ -373,7 +398,7 @@ __device__ inline void de_process_agent(const DeParams &p, int par, DeAgent<CHUN
 #pragma unroll
     for (int k = 0; k < 2; k++) {
       const double mut = c.d1[ch][k] + p.F * (c.d2[ch][k] - c.d3[ch][k]);
-      trial[ch][k] = c.cross[ch][k] ? mut : c.keep[ch][k];
+      trial[ch][k] = lane_bit(c.cross[ch][k]) ? mut : c.keep[ch][k];
     }
   }
   // (elements >= D are 0 in every loaded row, hence 0 in the trial as well)

@@ -15,7 +15,7 @@ __global__ __launch_bounds__(256) void probe_kernel(int fn, const uint64_t *in, 
   __shared__ double rn_tab[kRnormTabDoubles];
   rnorm_table_to_lds(rn_tab);
   const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-  if (i >= n) return;
+  if (i >= n) return;  // (NLSG_PROBE_WAVE_SUM: n is a multiple of 64, a wave leaves whole)
   const uint64_t b = in[i];
   const double x = __longlong_as_double(static_cast<long long>(b));
   double r;
@@ -30,6 +30,7 @@ __global__ __launch_bounds__(256) void probe_kernel(int fn, const uint64_t *in, 
     case NLSG_PROBE_LOG_UNIT: r = det_log_unit(x, rn_tab); break;
     case NLSG_PROBE_RNORM_COS: r = det_rnorm_cos(static_cast<double>(static_cast<uint32_t>(b))); break;
     // the expression of nlsg_tinyqr_kernels.h's and nlsg_lm_kernels.h's Givens rotations
+    case NLSG_PROBE_WAVE_SUM: r = wave_sum(x); break;  // (wave-uniform branch: all 64 lanes are here)
     case NLSG_PROBE_GIVENS_T: r = div_unscaled(1.0, sqrt_unscaled(x * x + 1.0)); break;
     default: r = sqrt_unscaled<true>(x); break;  // NLSG_PROBE_SQRT
   }
@@ -41,8 +42,11 @@ __global__ __launch_bounds__(256) void probe_kernel(int fn, const uint64_t *in, 
 extern "C" int nlsg_probe_math(int32_t fn, const uint64_t *in_host, uint64_t *out_host, uint64_t n,
                                int32_t device) {
   if (!in_host || !out_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (fn < NLSG_PROBE_LOG || fn > NLSG_PROBE_SQRT)
+  if (fn < NLSG_PROBE_LOG || fn > NLSG_PROBE_WAVE_SUM)
     return fail(NLSG_ERR_INVALID_ARG, "unknown probe function %d", fn);
+  if (fn == NLSG_PROBE_WAVE_SUM && n % 64 != 0)
+    return fail(NLSG_ERR_INVALID_ARG, "NLSG_PROBE_WAVE_SUM takes whole waves: n = %llu is no multiple of 64",
+                (unsigned long long)n);
   if (n == 0) return NLSG_OK;
   if (n > (1ull << 31)) return fail(NLSG_ERR_UNSUPPORTED, "more than 2^31 arguments per call");
   const int rc = check_device(device);

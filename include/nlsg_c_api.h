@@ -86,10 +86,11 @@ typedef enum {
  * error, as an index past an array is). The engines whose kernel owns a workgroup — or, BFGS, a wave —
  * per solve take such an objective: the resident batch engines (nlsg_de_batch_create_custom,
  * nlsg_pso_batch_create_custom; values: nlsg_*_batch_set_params), and through creators of their own
- * Nelder-Mead, the NM/PSO hybrid, Levenberg-Marquardt and BFGS (nlsg_nm_create_params,
- * nlsg_nmpso_create_params, nlsg_lm_create_params, nlsg_bfgs_create_params; values: nlsg_nm_set_params,
- * nlsg_nmpso_set_params, nlsg_lm_set_params, nlsg_bfgs_set_params); every other *_create_custom
- * (SANN's and the plain DE / PSO engines' included) answers NLSG_ERR_UNSUPPORTED. A body's own local named p shadows the
+ * Nelder-Mead, the NM/PSO hybrid, Levenberg-Marquardt, BFGS and simulated annealing (nlsg_nm_create_params,
+ * nlsg_nmpso_create_params, nlsg_lm_create_params, nlsg_bfgs_create_params, nlsg_sann_create_params — a row
+ * per chain, also where several chains share a wave; values: nlsg_nm_set_params,
+ * nlsg_nmpso_set_params, nlsg_lm_set_params, nlsg_bfgs_set_params, nlsg_sann_set_params); every other
+ * *_create_custom (SANN's and the plain DE / PSO engines' included) answers NLSG_ERR_UNSUPPORTED. A body's own local named p shadows the
  * accessor. 0: no parameters, the source compiled is what it was before parameters existed. */
 #define NLSG_CUSTOM_MAX_PARAMS 4096
 typedef struct {
@@ -695,6 +696,28 @@ int nlsg_sann_create(const nlsg_sann_config *cfg, nlsg_sann **out);
 /* cfg->objective == NLSG_OBJ_CUSTOM, as nlsg_de_create_custom */
 int nlsg_sann_create_custom(const nlsg_sann_config *cfg, const nlsg_custom_objective *obj,
                             nlsg_sann **out);
+/* A custom objective with run-time parameters (obj->n_params >= 1), one row per chain. Every check
+ * of nlsg_sann_create_custom in its order, then, still before the device is touched: n_params < 1 is
+ * NLSG_ERR_INVALID_ARG (zero is nlsg_sann_create_custom's), above NLSG_CUSTOM_MAX_PARAMS
+ * NLSG_ERR_UNSUPPORTED. Every count up to NLSG_CUSTOM_MAX_PARAMS fits at every dim: where the rows of
+ * the chains that would share a wave (dim <= 64) do not fit in the workgroup's LDS, the shape runs one
+ * chain per wave, with the same results (nlsg_sann_chains_per_wave). */
+int nlsg_sann_create_params(const nlsg_sann_config *cfg, const nlsg_custom_objective *obj,
+                            nlsg_sann **out);
+/* params_host [batch][n_params]: the engine's local chain b reads row b as p(k) (the draws stay keyed
+ * by chain_lo + b). Copied on the engine's stream before the call returns; the rows hold from the
+ * next launch on (every launch of a cut schedule stages its rows again) and are replaced without
+ * recompiling. NLSG_ERR_INVALID_ARG on an engine of another creator. Until the first call,
+ * nlsg_sann_minimize and nlsg_sann_time_solve answer NLSG_ERR_STATE. */
+int nlsg_sann_set_params(nlsg_sann *e, const double *params_host);
+/* Chains that share a wave at this shape: 64 / G for dim <= 8, 16, 32, 64 (G = 4, 8, 16, 32) while
+ * 4 * (64 / G) rows of n_params doubles (row stride: the least count >= n_params that is 2 mod 4) fit
+ * in 163840 bytes next to the 4096 of the kernel's table, else 1. n_params 0: an objective without
+ * parameters. 0 for dim 0 or n_params outside 0 .. NLSG_CUSTOM_MAX_PARAMS. Host only, no device. */
+uint32_t nlsg_sann_chains_per_wave(uint64_t dim, int32_t n_params);
+/* Dynamic LDS bytes of a launch at this shape: the parameter rows, one per lane group or four (one
+ * per wave); the kernel's table is static and not counted. 0 without parameters. Host only. */
+uint64_t nlsg_sann_lds_bytes(uint64_t dim, int32_t n_params);
 int nlsg_sann_destroy(nlsg_sann *e);
 /* x [batch][dim] in: starts, out: best points (:2808). One status per chain: f_value =
  * f_multiplier * f(x) as the reference returns it (:2790), iteration = max_iter,

@@ -309,6 +309,10 @@ OPTIONAL_SYMBOLS = {
     "nlsg_bfgs_lds_bytes": (u64, [u64, C.c_uint32]),
     "nlsg_bfgs_create_gradient": (C.c_int, [C.POINTER(BFGSConfig), C.POINTER(CustomObjectiveC),
                                             C.POINTER(BFGSGradientC), C.POINTER(_H)]),
+    "nlsg_sann_create_params": (C.c_int, [C.POINTER(SANNConfig), C.POINTER(CustomObjectiveC), C.POINTER(_H)]),
+    "nlsg_sann_set_params": (C.c_int, [_H, pd]),
+    "nlsg_sann_chains_per_wave": (C.c_uint32, [u64, i32]),
+    "nlsg_sann_lds_bytes": (u64, [u64, i32]),
 }
 SYMBOLS.update(OPTIONAL_SYMBOLS)
 _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
@@ -330,6 +334,10 @@ _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
                     "nlsg_bfgs_create_params": "library has no run-time objective parameters for BFGS",
                     "nlsg_bfgs_set_params": "library has no run-time objective parameters for BFGS",
                     "nlsg_bfgs_lds_bytes": "library has no run-time objective parameters for BFGS",
+                    "nlsg_sann_create_params": "library has no run-time objective parameters for simulated annealing",
+                    "nlsg_sann_set_params": "library has no run-time objective parameters for simulated annealing",
+                    "nlsg_sann_chains_per_wave": "library has no run-time objective parameters for simulated annealing",
+                    "nlsg_sann_lds_bytes": "library has no run-time objective parameters for simulated annealing",
                     "nlsg_de_batch_": "library has no resident batch DE",
                     "nlsg_pso_batch_": "library has no resident batch PSO"}
 

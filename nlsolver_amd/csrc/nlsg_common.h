@@ -433,9 +433,27 @@ struct Objective<NLSG_OBJ_RASTRIGIN> {
 // doubles are past the 64 KiB of static LDS): the macro's value is the rows' offset in doubles
 // from the start of the dynamic block (behind the reference-order xs | ts buffers, a multiple of
 // two), wave w's row follows w rows of kCustomParamsRow doubles. The wave stages its row itself
-// and publishes it with a wavefront fence and wave_barrier: no block barrier anywhere.
+// and publishes it with a wavefront fence and wave_barrier: no block barrier anywhere. The SANN
+// kernels that run a wave per chain (rtc_build_sann) take the same layout at offset 0.
+//
+// NLSG_PARAMS_PER_GROUP (beside the two; rtc_build_sann for sann_anneal_groups_kernel<OBJ, G>, value G):
+// 64 / G solves share a wave, one per group of G lanes, so a row per wave is not enough either. Every
+// group of the block has a row in the dynamic block, 4 * (64 / G) rows, group threadIdx.x / G's at
+// that many strides of kCustomParamsRow = the least count >= n_params that is 2 mod 4 (host:
+// custom_params_group_stride): even, so rows keep the 16-byte alignment, and half of it odd, so the 16
+// groups that read p(k) with one k land on 16 different pairs of the 64 banks (ds_read_b64: bank pair
+// (k + group * stride) mod 32, a bijection of group in 0..15 for such a stride; a multiple of 32 would
+// put all 16 on one pair). Each group stages the row of the solve it computes; published per wave.
 // ---------------------------------------------------------------------------
-#if defined(NLSG_N_PARAMS) && defined(NLSG_PARAMS_PER_WAVE)
+#if defined(NLSG_N_PARAMS) && defined(NLSG_PARAMS_PER_GROUP)
+constexpr uint32_t kCustomParamsRow = 4 * ((static_cast<uint32_t>(NLSG_N_PARAMS) + 1) / 4) + 2;
+constexpr size_t kCustomParamsLdsBytes = 0;  // (no static row)
+extern __shared__ __align__(16) double custom_params_dyn[];  // the kernel's dynamic block
+__device__ inline double *custom_params_group_row() {
+  return custom_params_dyn + static_cast<uint32_t>(NLSG_PARAMS_PER_WAVE) +
+         (threadIdx.x / static_cast<uint32_t>(NLSG_PARAMS_PER_GROUP)) * kCustomParamsRow;
+}
+#elif defined(NLSG_N_PARAMS) && defined(NLSG_PARAMS_PER_WAVE)
 constexpr uint32_t kCustomParamsRow = (static_cast<uint32_t>(NLSG_N_PARAMS) + 1) & ~1u;
 constexpr size_t kCustomParamsLdsBytes = 0;  // (no static row)
 extern __shared__ __align__(16) double custom_params_dyn[];  // the kernel's dynamic block
@@ -474,10 +492,28 @@ __device__ inline void stage_custom_params_one_wave(const double *params, uint64
 // One wave per solve (NLSG_PARAMS_PER_WAVE): called by the 64 lanes of the wave that owns solve b,
 // after the wave's early returns; the row is published to the wave when the call returns.
 __device__ inline void stage_custom_params_wave(const double *params, uint64_t b) {
-#if defined(NLSG_N_PARAMS) && defined(NLSG_PARAMS_PER_WAVE)
+#if defined(NLSG_N_PARAMS) && defined(NLSG_PARAMS_PER_WAVE) && !defined(NLSG_PARAMS_PER_GROUP)
   const double *__restrict__ row = params + b * static_cast<uint64_t>(NLSG_N_PARAMS);
   double *dst = custom_params_wave_row();
   for (uint32_t i = threadIdx.x & 63u; i < static_cast<uint32_t>(NLSG_N_PARAMS); i += 64) dst[i] = row[i];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+#else
+  (void)params;
+  (void)b;
+#endif
+}
+// Several solves per wave (NLSG_PARAMS_PER_GROUP): called by all 64 lanes of a wave after its early
+// return, `b` the solve of the lane's group of G lanes (an idle group passes the live solve it
+// shadows, so every row that is read has been written). The rows are published to the wave when the
+// call returns.
+template <int G>
+__device__ inline void stage_custom_params_group(const double *params, uint64_t b) {
+#if defined(NLSG_N_PARAMS) && defined(NLSG_PARAMS_PER_GROUP)
+  static_assert(G == NLSG_PARAMS_PER_GROUP, "the kernel's group is not the one the rows were laid out for");
+  const double *__restrict__ row = params + b * static_cast<uint64_t>(NLSG_N_PARAMS);
+  double *dst = custom_params_group_row();
+  for (uint32_t i = threadIdx.x & (G - 1); i < static_cast<uint32_t>(NLSG_N_PARAMS); i += G) dst[i] = row[i];
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 #else
@@ -491,6 +527,11 @@ __device__ inline void stage_custom_params_wave(const double *params, uint64_t b
 inline uint64_t custom_params_lds_bytes(int64_t n_params) {
   if (n_params <= 0 || n_params > NLSG_CUSTOM_MAX_PARAMS) return 0;
   return 8 * ((static_cast<uint64_t>(n_params) + 1) & ~1ull);
+}
+// doubles from one lane group's row to the next (NLSG_PARAMS_PER_GROUP, kCustomParamsRow there); 0 as above
+inline uint64_t custom_params_group_stride(int64_t n_params) {
+  if (n_params <= 0 || n_params > NLSG_CUSTOM_MAX_PARAMS) return 0;
+  return 4 * ((static_cast<uint64_t>(n_params) + 1) / 4) + 2;
 }
 // every engine but the two resident batch ones: among create_custom's argument checks
 inline int reject_custom_params(const nlsg_custom_objective *obj) {

@@ -80,10 +80,12 @@ static int rtc_compile_source(const std::string &src, const char *what,
 // rows live per wave in the dynamic LDS block, that many doubles from its start (NLSG_PARAMS_PER_WAVE).
 // grad_body (rtc_build_bfgs for nlsg_bfgs_create_gradient only): one more member, Objective::grad, made of it;
 // without one the source is byte for byte what it is without this argument.
+// params_group > 0 (rtc_build_sann's packed kernel, with n_params > 0 only): a row per group of that many lanes
+// (NLSG_PARAMS_PER_GROUP) instead of one per wave. keep_code: as rtc_compile_source's.
 static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_header,
                        const std::vector<std::string> &name_exprs, hipModule_t *mod_out,
                        std::vector<hipFunction_t> *fns_out, long wave_rows_offset = -1,
-                       const char *grad_body = nullptr) {
+                       const char *grad_body = nullptr, int params_group = 0, bool keep_code = false) {
   if (!obj || !obj->term_body || !obj->term_body[0])
     return fail(NLSG_ERR_INVALID_ARG, "a custom objective needs a term body");
   // n_params > 0 (resident batch engines and nlsg_nm / nmpso / lm / bfgs_create_params; every
@@ -96,11 +98,15 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
   std::string src;
   if (n_params) src += "#define NLSG_N_PARAMS " + std::to_string(n_params) + "\n";
   if (per_wave) src += "#define NLSG_PARAMS_PER_WAVE " + std::to_string(wave_rows_offset) + "\n";
+  const bool per_group = per_wave && params_group > 0;
+  if (per_group) src += "#define NLSG_PARAMS_PER_GROUP " + std::to_string(params_group) + "\n";
   src += std::string("#include \"") + kernel_header + "\"\n"
          "namespace nlsg {\n"
          "template <>\n"
          "struct Objective<NLSG_OBJ_CUSTOM> {\n";
-  if (per_wave)  // the row of wave threadIdx.x >> 6
+  if (per_group)  // the row of lane group threadIdx.x / G
+    src += "  __device__ static inline double p(uint64_t k) { return custom_params_group_row()[k]; }\n";
+  else if (per_wave)  // the row of wave threadIdx.x >> 6
     src += "  __device__ static inline double p(uint64_t k) { return custom_params_wave_row()[k]; }\n";
   else if (n_params)
     src += "  __device__ static inline double p(uint64_t k) { return custom_params_lds[k]; }\n";
@@ -149,7 +155,7 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
     }
     src += "};\n}  // namespace nlsg\n";
   }
-  return rtc_compile_source(src, "custom objective", name_exprs, mod_out, fns_out);
+  return rtc_compile_source(src, "custom objective", name_exprs, mod_out, fns_out, keep_code);
 }
 
 // A compiled code object and the lowered names of its kernels, kept by source text: a second engine
@@ -479,7 +485,11 @@ int rtc_build_sann(const nlsg_custom_objective *obj, int chunks, bool vec, int g
       : group ? "nlsg::sann_anneal_groups_kernel<" + std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) +
                   ", " + std::to_string(group) + ">"
             : "nlsg::sann_anneal_kernel<" + targs(chunks, vec) + ">";
-  const int rc = rtc_compile(obj, "nlsg_sann_kernels.h", {name}, &k.mod, &f);
+  // n_params > 0 (nlsg_sann_create_params): the rows start the dynamic block (offset 0), one per wave, or with
+  // `group` one per lane group. The code object is kept by its source: the engines of a sweep, of the drop-in's
+  // calls and of a sharded batch differ in their configuration only and load it instead of compiling.
+  const int rc = rtc_compile(obj, "nlsg_sann_kernels.h", {name}, &k.mod, &f, obj && obj->n_params > 0 ? 0 : -1,
+                             nullptr, group, true);
   if (rc) return rc;
   k.anneal = f[0];
   *out = k;

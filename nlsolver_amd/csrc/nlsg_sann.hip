@@ -17,10 +17,36 @@ struct nlsg_sann {
   int chunks = 0;
   int group = 0;  // lanes per chain when several chains share a wave (dim <= 64), else 0
   SannRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it
+  int32_t n_params = 0;          // nlsg_sann_create_params: the objective's run-time doubles per chain
+  double *params_dev = nullptr;  // [batch][n_params]
+  bool params_set = false;
+  unsigned lds = 0;              // dynamic LDS of a launch: the parameter rows (0 without parameters)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
 namespace {
+
+constexpr uint64_t kSannLdsBudget = 160ull * 1024;                      // a workgroup's LDS
+constexpr uint64_t kSannTableBytes = 8ull * kRnormTabDoubles;           // rn_tab, static, in every kernel
+int sann_group_of(uint64_t D) { return D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 0; }
+// dynamic LDS of the packed kernel with `group` lanes per chain: a row per group, 4 * (64 / group) to the block
+uint64_t sann_group_rows_bytes(int group, int64_t n_params) {
+  return 4ull * (64 / group) * 8 * custom_params_group_stride(n_params);
+}
+// Lanes per chain of the kernel a shape gets: the packing by dim, unless the group rows of a
+// parametrised objective do not fit next to rn_tab — then one chain per wave (0), whose four rows always do.
+// A chain's history does not depend on the packing, so the rule moves no bit.
+int sann_group_for(uint64_t D, int64_t n_params) {
+  const int group = sann_group_of(D);
+  if (group && n_params > 0 && kSannTableBytes + sann_group_rows_bytes(group, n_params) > kSannLdsBudget) return 0;
+  return group;
+}
+// a parametrised engine launches nothing before its first rows
+int params_ready(const nlsg_sann *e) {
+  if (e->n_params > 0 && !e->params_set)
+    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_sann_set_params first", e->n_params);
+  return NLSG_OK;
+}
 
 #define SANN_FOR_CHUNKS(OBJ, chunks, CALL) \
   switch (chunks) {                        \
@@ -72,7 +98,7 @@ void launch_anneal(nlsg_sann *e, uint64_t iter_begin, uint64_t iter_end) {
   const bool vec = e->p.D % 2 == 0;
   if (e->cfg.objective == NLSG_OBJ_CUSTOM) {
     void *args[] = {&e->p, &iter_begin, &iter_end};
-    launch_module_kernel(e->rtc.anneal, grid.x, 256, 0, e->stream, args);
+    launch_module_kernel(e->rtc.anneal, grid.x, 256, e->lds, e->stream, args);
     return;
   }
   if (e->p.D > 1024) {  // chains streamed in segments
@@ -132,7 +158,7 @@ void launch_solve(nlsg_sann *e) {
 }  // namespace
 
 static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective *custom,
-                       nlsg_sann **out);
+                       nlsg_sann **out, bool with_params = false);
 
 extern "C" {
 
@@ -151,10 +177,45 @@ int nlsg_sann_create_custom(const nlsg_sann_config *cfg, const nlsg_custom_objec
   return sann_create(cfg, obj, out);
 }
 
+int nlsg_sann_create_params(const nlsg_sann_config *cfg, const nlsg_custom_objective *obj,
+                            nlsg_sann **out) {
+  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (cfg->objective != NLSG_OBJ_CUSTOM)
+    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  return sann_create(cfg, obj, out, true);
+}
+
+// 1, or the 64 / G chains that share a wave. 0 for dim == 0 or an n_params outside 0 .. NLSG_CUSTOM_MAX_PARAMS.
+uint32_t nlsg_sann_chains_per_wave(uint64_t dim, int32_t n_params) {
+  if (dim < 1 || n_params < 0 || n_params > NLSG_CUSTOM_MAX_PARAMS) return 0;
+  const int group = sann_group_for(dim, n_params);
+  return group ? 64 / group : 1;
+}
+
+// The dynamic LDS of a launch: the parameter rows (rn_tab is static and not counted). 0 without parameters
+// and outside the ranges above.
+uint64_t nlsg_sann_lds_bytes(uint64_t dim, int32_t n_params) {
+  if (dim < 1 || n_params < 1 || n_params > NLSG_CUSTOM_MAX_PARAMS) return 0;
+  const int group = sann_group_for(dim, n_params);
+  return group ? sann_group_rows_bytes(group, n_params) : 4 * custom_params_lds_bytes(n_params);
+}
+
+int nlsg_sann_set_params(nlsg_sann *e, const double *params_host) {
+  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (e->n_params <= 0)
+    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_sann_create_params)");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
+                          hipMemcpyHostToDevice, e->stream));
+  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
+  e->params_set = true;
+  return NLSG_OK;
+}
+
 }  // extern "C"
 
 static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective *custom,
-                       nlsg_sann **out) {
+                       nlsg_sann **out, bool with_params) {
   if (!cfg || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(nlsg_sann_config))
@@ -169,6 +230,9 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
                 (unsigned long long)cfg->dim);
   if (cfg->dim > 0xffffffffull) return fail(NLSG_ERR_UNSUPPORTED, "dim beyond 2^32");
   if (cfg->batch > 0x7fffffffull) return fail(NLSG_ERR_UNSUPPORTED, "batch too large");
+  if (with_params)  // (a row per wave, four to the block, always fits; the packed kernel's rows: sann_group_for)
+    if (const int prc = check_custom_params(custom, kSannTableBytes, "nlsg_sann", "nlsg_sann_create_custom", 4))
+      return prc;
   int rc = check_device(cfg->device);
   if (rc) return rc;
   NLSG_HIP(hipSetDevice(cfg->device));
@@ -187,7 +251,9 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
   }
   const uint64_t B = cfg->batch, D = cfg->dim;
   e->chunks = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
-  e->group = D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 0;
+  e->n_params = with_params ? custom->n_params : 0;
+  e->group = sann_group_for(D, e->n_params);
+  e->lds = static_cast<unsigned>(nlsg_sann_lds_bytes(D, e->n_params));
   SannParams &p = e->p;
   std::memset(&p, 0, sizeof p);
   hipError_t he = hipSuccess;
@@ -195,6 +261,8 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.p), B * D * 8);
   if (he == hipSuccess && D > 1024) he = pool_malloc(reinterpret_cast<void **>(&p.trial), B * D * 8);
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.prob), B * sizeof(SannProblem));
+  if (he == hipSuccess && e->n_params)
+    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * 8);
   if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->zero_dev), 16);
   if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
   if (he == hipSuccess) he = hipEventCreate(&e->ev0);
@@ -210,7 +278,18 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
       nlsg_sann_destroy(e);
       return rc2;
     }
+    // (the module API's counterpart of hipFuncSetAttribute on a kernel symbol: the rows can pass the 64 KiB
+    // a launch may take without it)
+    if (e->lds > 64 * 1024) {
+      he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.anneal),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->lds));
+      if (he != hipSuccess) {
+        nlsg_sann_destroy(e);
+        return fail(NLSG_ERR_HIP, "raising the kernel's dynamic LDS limit failed: %s", hipGetErrorString(he));
+      }
+    }
   }
+  p.params = e->params_dev;
   p.zero = e->zero_dev;
   p.batch = B;
   p.D = D;
@@ -235,6 +314,7 @@ int nlsg_sann_destroy(nlsg_sann *e) {
   pool_free(e->p.trial);
   pool_free(e->p.prob);
   pool_free(e->zero_dev);
+  pool_free(e->params_dev);
   if (e->ev0) hipEventDestroy(e->ev0);
   if (e->ev1) hipEventDestroy(e->ev1);
   if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
@@ -244,6 +324,7 @@ int nlsg_sann_destroy(nlsg_sann *e) {
 
 int nlsg_sann_minimize(nlsg_sann *e, double *x_inout_host, nlsg_status *status_host) {
   if (!e || !x_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   const uint64_t B = e->p.batch, D = e->p.D;
   NLSG_HIP(hipMemcpy(e->p.x, x_inout_host, B * D * 8, hipMemcpyHostToDevice));
@@ -273,6 +354,7 @@ int nlsg_sann_minimize(nlsg_sann *e, double *x_inout_host, nlsg_status *status_h
 
 int nlsg_sann_time_solve(nlsg_sann *e, const double *x0_host, uint32_t repeats, float *ms_total) {
   if (!e || !x0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   float total = 0.f;
   for (uint32_t r = 0; r < repeats; r++) {

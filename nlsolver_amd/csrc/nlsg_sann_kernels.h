@@ -13,6 +13,12 @@
 // s = iter * (temperature_iter - 1) + (j - 1) has ks = key(kc, s); coordinate e takes draws 2e
 // (log) and 2e + 1 (cos) of ks, the acceptance test draw 2 D. oracle_sann.c's orc_sann_sync
 // executes the same chain on the CPU.
+//
+// A user objective with run-time parameters (NLSG_N_PARAMS, nlsg_common.h) keeps chain b's row in LDS
+// for the whole launch, in the dynamic block behind rn_tab: one row per wave in the two kernels that
+// run a wave per chain (the BFGS layout), one row per lane group in sann_anneal_groups_kernel. A wave
+// stages after its early return and publishes to itself: the only block barrier stays the one in
+// rnorm_table_to_lds. Every launch of a cut schedule stages again from p.params.
 #pragma once
 
 #include "nlsg_common.h"
@@ -31,6 +37,7 @@ struct SannParams {
   double *trial;      // [batch][D] trial point, D > 1024 only (sann_anneal_long_kernel)
   SannProblem *prob;  // [batch]
   const double *zero;
+  const double *params;  // [batch][n_params] of a user objective with run-time parameters, else null
   uint64_t batch, D, seed, chain_lo;
   uint64_t inner;     // trial points per temperature: temperature_iter - 1 (0 if that is 0), :2795
   double temp_max, fmul;
@@ -57,6 +64,7 @@ __global__ __launch_bounds__(256) void sann_anneal_kernel(SannParams p, uint64_t
   const uint64_t chain = static_cast<uint64_t>(blockIdx.x) * 4 +
                          __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
   if (chain >= p.batch) return;
+  stage_custom_params_wave(p.params, chain);  // (a user objective's row, into this wave's slice; else nothing)
   const int lane = lane_id();
   const uint64_t D = p.D;
   constexpr double e_minus_1 = 1.7182818;  // :2780
@@ -147,6 +155,7 @@ __global__ __launch_bounds__(256) void sann_anneal_long_kernel(SannParams p, uin
   const uint64_t chain = static_cast<uint64_t>(blockIdx.x) * 4 +
                          __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
   if (chain >= p.batch) return;
+  stage_custom_params_wave(p.params, chain);  // (a user objective's row, into this wave's slice; else nothing)
   const int lane = lane_id();
   const uint64_t D = p.D;
   constexpr double e_minus_1 = 1.7182818;  // :2780
@@ -246,6 +255,7 @@ __global__ __launch_bounds__(256) void sann_anneal_groups_kernel(SannParams p, u
   if (wave * P >= p.batch) return;
   const bool live = wave * P + gi < p.batch;
   const uint64_t chain = live ? wave * P + gi : wave * P;  // idle groups shadow a live chain
+  stage_custom_params_group<G>(p.params, chain);  // (a user objective's row per group; else nothing)
   const uint64_t D = p.D;
   constexpr double e_minus_1 = 1.7182818;  // :2780
   const uint32_t j0 = 2 * g, j1 = 2 * g + 1;

@@ -501,7 +501,10 @@ typedef enum {
   NLSG_OBJ_TANH_REGRESSION = 32,
   /* r_i(theta) = y_i - phi(sum_j A_ij theta_j), phi and phi' from an nlsg_lm_link
    * (nlsg_lm_create_link only) */
-  NLSG_OBJ_LINK_REGRESSION = 33
+  NLSG_OBJ_LINK_REGRESSION = 33,
+  /* r_i(theta) = residual(theta; t_i, y_i), residual and Jacobian row from an nlsg_lm_curve
+   * (nlsg_lm_create_curve only) */
+  NLSG_OBJ_CURVE_MODEL = 34
 } nlsg_nlls_objective;
 /* NLSG_LM_CHOLESKY_REFERENCE_ORDER: the class's own solve with the reference's literal arithmetic
  * — every probe of fin_diff / fin_diff_h sums its objective in INDEX order (the reference's
@@ -572,6 +575,38 @@ typedef struct {
  * NLSG_LM_WIDE_MFMA / NLSG_LM_WIDE256 / NLSG_LM_WIDE_CHOL switches of the built-in engine are ignored.
  * Optional symbol (NLSG_ABI_VERSION stays 1): look it up before relying on it. */
 int nlsg_lm_create_link(const nlsg_lm_config *cfg, const nlsg_lm_link *link, nlsg_lm **out);
+/* A curve model, r_i(theta) = residual(theta; t_i, y_i) with k numbers t_i per observation: the residual
+ * and its Jacobian row as ONE body of HIP source compiled at engine creation. The body sees
+ *   th(j)   parameter j                     t(k)   the observation's k-th datum      y   its target
+ *   n       the number of parameters (int)
+ *   r       to be set to the residual       J(j)   to be set to dr / dtheta_j
+ * and may call the library's deterministic device math (det_exp, det_log, det_tanh, det_sqrt, ...). The
+ * six names th, t, y, n, r and J are taken inside a body. The index of t(k) should be a constant or the
+ * counter of a loop that unrolls: the data live in registers; t(k) with k outside [0, curve.k) is 0.
+ * Exponential decay theta0 exp(-theta1 t) + theta2:
+ *   "const double e = det_exp(-th(1) * t(0));"
+ *   "r = y - (th(0) * e + th(2));"
+ *   "J(0) = -e;  J(1) = th(0) * t(0) * e;  J(2) = -1.0;"
+ * A J(j) the body does not write is 0; a J(j) with j outside [0, n) is dropped; rows past m contribute
+ * nothing whatever the body makes of their zero data (NaN and inf included). Per-problem constants can
+ * ride in extra columns of t. */
+typedef struct {
+  const char *body;
+  uint32_t k;             /* data per observation, 1 .. 16 */
+} nlsg_lm_curve;
+/* An engine of the Gauss-Newton functors (f = sum r^2, Grad = 2 J^T r, Hess = 2 J^T J, the last on the
+ * matrix cores) on the curve model `curve`; one wave per problem, n <= 64, any m. cfg->objective must be
+ * NLSG_OBJ_CURVE_MODEL. Before the device is touched, in this order: NULL arguments, the objective id, the
+ * struct size, an unknown solver, NLSG_LM_CHOLESKY_REFERENCE_ORDER (NLSG_ERR_UNSUPPORTED), m, n, batch >= 1,
+ * n > 64 (NLSG_ERR_UNSUPPORTED), k outside 1 .. 16, a NULL or empty body. A body that does not compile is
+ * NLSG_ERR_INVALID_ARG with the compiler's message, which names curve_body and the line in it. The data
+ * come by nlsg_lm_set_curve_data (nlsg_lm_set_data and nlsg_lm_set_params answer NLSG_ERR_INVALID_ARG);
+ * nlsg_lm_set_solver / _minimize / _time_* / _destroy work as on a link engine, the status counts are a
+ * tanh engine's. Optional symbols (NLSG_ABI_VERSION stays 1): look them up before relying on them. */
+int nlsg_lm_create_curve(const nlsg_lm_config *cfg, const nlsg_lm_curve *curve, nlsg_lm **out);
+/* t_host [batch][m][k] and y_host [batch][m] of a curve engine, copied and repacked on the device before
+ * the call returns; may be called again to replace them. */
+int nlsg_lm_set_curve_data(nlsg_lm *e, const double *t_host, const double *y_host);
 /* Dynamic LDS bytes of the launch that evaluates an objective of n parameters through the default
  * finite-difference functors (what a custom objective runs), solver = NLSG_LM_CHOLESKY or
  * NLSG_LM_CHOLESKY_REFERENCE_ORDER. 0 outside 1 <= n <= 1024 and for any other solver — and in tree

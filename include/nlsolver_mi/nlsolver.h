@@ -325,7 +325,32 @@ struct LinkRegression {
     throw std::logic_error("LinkRegression: the link is device source text, there is no host evaluation");
   }
 };
+// A curve model: r_i(theta) = residual(theta; t_i, y_i) with k numbers t_i per observation, nonlinear in
+// any of its n <= 64 parameters. `body` is HIP source compiled when the engine is made
+// (nlsg_lm_create_curve): it sees th(j), t(k), y and n, and writes the residual r and its Jacobian row
+// J(j) = dr / dtheta_j (an unwritten J(j) is 0); it may call det_exp / det_log / det_tanh / ...
+// Exponential decay theta0 exp(-theta1 t) + theta2:
+//   CurveModel<double>(m, 3, 1, t, y, "const double e = det_exp(-th(1) * t(0)); r = y - (th(0) * e + th(2));"
+//                                     "J(0) = -e; J(1) = th(0) * t(0) * e; J(2) = -1.0;")
+// The residual exists on the device only: operator() throws.
+template <typename T = double>
+struct CurveModel {
+  static constexpr int nlsg_nlls_objective = NLSG_OBJ_CURVE_MODEL;
+  size_t m, n, k;
+  std::vector<T> t, y;  // problems*m*k, problems*m
+  std::string curve_body;
+  CurveModel(size_t m, size_t n, size_t k, std::vector<T> t, std::vector<T> y, std::string body)
+      : m(m), n(n), k(k), t(std::move(t)), y(std::move(y)), curve_body(std::move(body)) {}
+  size_t problems() const { return y.size() / m; }
+  T operator()(const std::vector<T> &) const {
+    throw std::logic_error("CurveModel: the residual is device source text, there is no host evaluation");
+  }
+};
 struct gauss_newton {};  // Grad / Hess tag of device NLLS models
+template <typename C, typename = void>
+struct has_curve_body : std::false_type {};
+template <typename C>
+struct has_curve_body<C, std::void_t<decltype(std::declval<const C &>().curve_body)>> : std::true_type {};
 template <typename C, typename = void>
 struct has_link_bodies : std::false_type {};
 template <typename C>
@@ -426,6 +451,8 @@ class api {
   decltype(&nlsg_lm_create_params) lm_create_params = nullptr;
   decltype(&nlsg_lm_set_params) lm_set_params = nullptr;
   decltype(&nlsg_lm_create_link) lm_create_link = nullptr;
+  decltype(&nlsg_lm_create_curve) lm_create_curve = nullptr;
+  decltype(&nlsg_lm_set_curve_data) lm_set_curve_data = nullptr;
   decltype(&nlsg_bfgs_create_gradient) bfgs_create_gradient = nullptr;
   // the resident engine's LDS need with the parameter row; throws when the library cannot take
   // parameters or the shape does not fit (`shape_need` = nlsg_*_batch_lds_bytes, 0 = out of range)
@@ -511,6 +538,8 @@ class api {
     bind_optional(h, "nlsg_lm_create_params", lm_create_params);
     bind_optional(h, "nlsg_lm_set_params", lm_set_params);
     bind_optional(h, "nlsg_lm_create_link", lm_create_link);
+    bind_optional(h, "nlsg_lm_create_curve", lm_create_curve);
+    bind_optional(h, "nlsg_lm_set_curve_data", lm_set_curve_data);
     bind_optional(h, "nlsg_bfgs_create_gradient", bfgs_create_gradient);
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
@@ -2388,13 +2417,25 @@ class LevenbergMarquardt {
       api.check(api.lm_create_link(&cfg, &link, &eng));
       made = true;
     }
+    if constexpr (device::has_nlls_objective<Callable>::value && device::has_curve_body<Callable>::value) {
+      if (!api.lm_create_curve || !api.lm_set_curve_data)
+        throw device_error("the loaded library has no nlsg_lm_create_curve (curve models)");
+      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
+      const nlsg_lm_curve curve{f.curve_body.c_str(), static_cast<uint32_t>(f.k)};
+      api.check(api.lm_create_curve(&cfg, &curve, &eng));
+      made = true;
+    }
     if (!made) api.check(api.lm_create(&cfg, &eng));
     std::vector<scalar_t> flat(B * n), lam(B);
     for (size_t p = 0; p < B; p++) std::copy(thetas[p].begin(), thetas[p].end(), flat.begin() + p * n);
     std::vector<nlsg_status> st(B);
     int rc = 0;
-    if constexpr (device::has_nlls_objective<Callable>::value)
-      rc = api.lm_set_data(eng, f.A.data(), f.y.data());
+    if constexpr (device::has_nlls_objective<Callable>::value) {
+      if constexpr (device::has_curve_body<Callable>::value)
+        rc = api.lm_set_curve_data(eng, f.t.data(), f.y.data());
+      else
+        rc = api.lm_set_data(eng, f.A.data(), f.y.data());
+    }
     if (!rc) rc = api.lm_minimize(eng, flat.data(), st.data(), lam.data());
     const std::string msg = rc ? api.last_error() : "";
     api.lm_destroy(eng);

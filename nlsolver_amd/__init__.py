@@ -20,7 +20,7 @@ from .de import DE, CustomObjective, DEBatchEngine, DEEngine, DERefEngine, DESol
 from .rng import XorShift  # noqa: F401
 from .pso import PSO, PSOBatchEngine, PSOEngine, PSOSolver  # noqa: F401
 from .bfgs import BFGS, BFGSEngine, QuadDiagRank1  # noqa: F401
-from .lm import LevenbergMarquardt, LinkRegression, LMEngine, TanhRegression  # noqa: F401
+from .lm import CurveModel, LevenbergMarquardt, LinkRegression, LMEngine, TanhRegression  # noqa: F401
 from .nm import NelderMead, NMEngine  # noqa: F401
 from .sann import SANN, SANNEngine  # noqa: F401
 from .nmpso import NelderMeadPSO, NMPSOEngine  # noqa: F401

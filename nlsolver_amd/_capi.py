@@ -108,6 +108,7 @@ BFGS_REFERENCE_ORDER = 2  # NLSG_BFGS_REFERENCE_ORDER
 
 OBJ_TANH_REGRESSION = 32
 OBJ_LINK_REGRESSION = 33  # NLSG_OBJ_LINK_REGRESSION: nlsg_lm_create_link
+OBJ_CURVE_MODEL = 34  # NLSG_OBJ_CURVE_MODEL: nlsg_lm_create_curve
 LM_CHOLESKY, LM_QR, LM_CHOLESKY_REFERENCE_ORDER = 0, 1, 2
 
 
@@ -119,6 +120,10 @@ class LMConfig(C.Structure):
 
 class LMLinkC(C.Structure):  # nlsg_lm_link
     _fields_ = [("value_body", C.c_char_p), ("slope_body", C.c_char_p)]
+
+
+class LMCurveC(C.Structure):  # nlsg_lm_curve
+    _fields_ = [("body", C.c_char_p), ("k", C.c_uint32)]
 
 
 NM_REFERENCE_ORDER = 1  # NLSG_NM_REFERENCE_ORDER
@@ -304,6 +309,8 @@ OPTIONAL_SYMBOLS = {
     "nlsg_lm_set_params": (C.c_int, [_H, pd]),
     "nlsg_lm_lds_bytes": (u64, [u64, C.c_int32]),
     "nlsg_lm_create_link": (C.c_int, [C.POINTER(LMConfig), C.POINTER(LMLinkC), C.POINTER(_H)]),
+    "nlsg_lm_create_curve": (C.c_int, [C.POINTER(LMConfig), C.POINTER(LMCurveC), C.POINTER(_H)]),
+    "nlsg_lm_set_curve_data": (C.c_int, [_H, pd, pd]),
     "nlsg_bfgs_create_params": (C.c_int, [C.POINTER(BFGSConfig), C.POINTER(CustomObjectiveC), C.POINTER(_H)]),
     "nlsg_bfgs_set_params": (C.c_int, [_H, pd]),
     "nlsg_bfgs_lds_bytes": (u64, [u64, C.c_uint32]),
@@ -330,6 +337,8 @@ _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
                     "nlsg_lm_set_params": "library has no run-time objective parameters for Levenberg-Marquardt",
                     "nlsg_lm_lds_bytes": "library has no run-time objective parameters for Levenberg-Marquardt",
                     "nlsg_lm_create_link": "library has no user-supplied link functions for Levenberg-Marquardt",
+                    "nlsg_lm_create_curve": "library has no curve models for Levenberg-Marquardt",
+                    "nlsg_lm_set_curve_data": "library has no curve models for Levenberg-Marquardt",
                     "nlsg_bfgs_create_gradient": "library has no analytic gradients of compiled objectives for BFGS",
                     "nlsg_bfgs_create_params": "library has no run-time objective parameters for BFGS",
                     "nlsg_bfgs_set_params": "library has no run-time objective parameters for BFGS",

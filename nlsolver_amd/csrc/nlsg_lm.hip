@@ -29,6 +29,8 @@ struct nlsg_lm {
   LmRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it;
                      // NLSG_OBJ_LINK_REGRESSION: the Gauss-Newton evaluation kernel on the user's link
   bool link = false;  // nlsg_lm_create_link
+  uint32_t curve_k = 0;  // nlsg_lm_create_curve: data per observation (0: no curve engine); rtc.iter is
+                         // lm_curve_iter_kernel, A_dev the repacked (t, y) of nlsg_lm_set_curve_data
   int32_t n_params = 0;          // nlsg_lm_create_params: the objective's run-time doubles per problem
   double *params_dev = nullptr;  // [batch][n_params]
   bool params_set = false;
@@ -74,6 +76,9 @@ int params_ready(const nlsg_lm *e) {
   return NLSG_OK;
 }
 
+// the call that hands the engine its data
+const char *data_call(const nlsg_lm *e) { return e->curve_k ? "nlsg_lm_set_curve_data" : "nlsg_lm_set_data"; }
+
 // finite-difference model: step k + evaluation k + 1 (first: the evaluation at x0 only)
 void launch_fd_iter(nlsg_lm *e, int first) {
   const dim3 grid(static_cast<unsigned>(e->p.batch));
@@ -116,7 +121,7 @@ void launch_fd_iter(nlsg_lm *e, int first) {
 // Gauss-Newton model up to 64 parameters: step k (with_step) + evaluation k + 1, one wave per problem
 void launch_gn_iter(nlsg_lm *e, int first, int with_step) {
   const unsigned grid = static_cast<unsigned>(e->p.batch);
-  if (e->link) {
+  if (e->link || e->curve_k) {  // (a curve engine's kernel takes the same arguments)
     void *args[] = {&e->p, &first, &with_step};
     launch_module_kernel(e->rtc.iter, grid, 64, 0, e->stream, args);
     return;
@@ -249,7 +254,8 @@ int launch_solve(nlsg_lm *e) {
 }  // namespace
 
 static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *custom, nlsg_lm **out,
-                     bool with_params = false, const nlsg_lm_link *link = nullptr);
+                     bool with_params = false, const nlsg_lm_link *link = nullptr,
+                     const nlsg_lm_curve *curve = nullptr);
 
 extern "C" {
 
@@ -258,6 +264,8 @@ int nlsg_lm_create(const nlsg_lm_config *cfg, nlsg_lm **out) {
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_lm_create_custom");
   if (cfg && cfg->objective == NLSG_OBJ_LINK_REGRESSION)
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_LINK_REGRESSION engines are made by nlsg_lm_create_link");
+  if (cfg && cfg->objective == NLSG_OBJ_CURVE_MODEL)
+    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CURVE_MODEL engines are made by nlsg_lm_create_curve");
   PhaseClock clk;
   const int rc = lm_create(cfg, nullptr, out);
   call_timing().create_ms = clk.lap();
@@ -295,6 +303,16 @@ int nlsg_lm_create_link(const nlsg_lm_config *cfg, const nlsg_lm_link *link, nls
   return rc;
 }
 
+int nlsg_lm_create_curve(const nlsg_lm_config *cfg, const nlsg_lm_curve *curve, nlsg_lm **out) {
+  if (!cfg || !curve || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (cfg->objective != NLSG_OBJ_CURVE_MODEL)
+    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CURVE_MODEL");
+  PhaseClock clk;
+  const int rc = lm_create(cfg, nullptr, out, false, nullptr, curve);
+  call_timing().create_ms = clk.lap();
+  return rc;
+}
+
 // The dynamic LDS of the launch that evaluates an objective (the finite-difference model, which is what a
 // custom objective runs): 0 for a shape that model rejects (n outside 1 .. 1024, the QR solver, an
 // unknown solver) — and for tree order past 64 parameters, whose evaluation kernel takes none.
@@ -306,6 +324,9 @@ uint64_t nlsg_lm_lds_bytes(uint64_t n, int32_t solver) {
 
 int nlsg_lm_set_params(nlsg_lm *e, const double *params_host) {
   if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (e->curve_k)
+    return fail(NLSG_ERR_INVALID_ARG, "a curve model has no p(k): per-problem constants ride in columns of t "
+                                      "(nlsg_lm_set_curve_data)");
   if (e->n_params <= 0)
     return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_lm_create_params)");
   NLSG_HIP(hipSetDevice(e->cfg.device));
@@ -319,14 +340,15 @@ int nlsg_lm_set_params(nlsg_lm *e, const double *params_host) {
 }  // extern "C"
 
 static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *custom, nlsg_lm **out,
-                     bool with_params, const nlsg_lm_link *link) {
+                     bool with_params, const nlsg_lm_link *link, const nlsg_lm_curve *curve) {
   if (!cfg || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   *out = nullptr;
   if (cfg->struct_size != sizeof(nlsg_lm_config))
     return fail(NLSG_ERR_INVALID_ARG, "nlsg_lm_config size mismatch (%u vs %zu)", cfg->struct_size,
                 sizeof(nlsg_lm_config));
   const bool fd = lm_fd_objective(cfg->objective);
-  if (cfg->objective != NLSG_OBJ_TANH_REGRESSION && !(link && cfg->objective == NLSG_OBJ_LINK_REGRESSION) && !fd)
+  if (cfg->objective != NLSG_OBJ_TANH_REGRESSION && !(link && cfg->objective == NLSG_OBJ_LINK_REGRESSION) &&
+      !(curve && cfg->objective == NLSG_OBJ_CURVE_MODEL) && !fd)
     return fail(NLSG_ERR_INVALID_ARG, "unknown objective %d", cfg->objective);
   const bool ref_order = cfg->solver == NLSG_LM_CHOLESKY_REFERENCE_ORDER;
   if (cfg->solver != NLSG_LM_CHOLESKY && cfg->solver != NLSG_LM_QR && !ref_order)
@@ -342,6 +364,9 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
                 "cosine is the device's own, a whole-vector body's x.sum() adds in the lane-tree order");
   if (cfg->n < 1 || (!fd && cfg->m < 1) || cfg->batch < 1)
     return fail(NLSG_ERR_INVALID_ARG, "need n >= 1, m >= 1, batch >= 1");
+  if (curve && cfg->n > kLmN)
+    return fail(NLSG_ERR_UNSUPPORTED, "curve models run one wave per problem: n = %llu > %d",
+                (unsigned long long)cfg->n, kLmN);
   const bool wide = cfg->n > kLmN;
   if (cfg->n > kLmWideMaxN)
     return fail(NLSG_ERR_UNSUPPORTED, "n = %llu > %d (a thread of the step follows at most four rows)",
@@ -356,6 +381,10 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
       return prc;
   if (link && (!link->value_body || !link->value_body[0] || !link->slope_body || !link->slope_body[0]))
     return fail(NLSG_ERR_INVALID_ARG, "a link needs a value body and a slope body (nlsg_lm_link)");
+  if (curve && (curve->k < 1 || curve->k > 16))
+    return fail(NLSG_ERR_INVALID_ARG, "a curve model takes 1 .. 16 data per observation: k = %u", curve->k);
+  if (curve && (!curve->body || !curve->body[0]))
+    return fail(NLSG_ERR_INVALID_ARG, "a curve model needs a body (nlsg_lm_curve)");
   int rc = check_device(cfg->device);
   if (rc) return rc;
   NLSG_HIP(hipSetDevice(cfg->device));
@@ -365,6 +394,7 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   e->wide = wide;
   e->n_params = with_params ? custom->n_params : 0;
   e->link = link != nullptr;
+  e->curve_k = curve ? curve->k : 0;
   if (!e->link) {  // (a link engine has one evaluation kernel per shape, and the blocked step: no A/B forms)
     const char *sw = std::getenv("NLSG_LM_WIDE_MFMA");
     e->wide_valu = sw && sw[0] == '0';
@@ -388,11 +418,14 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   std::memset(&p, 0, sizeof p);
   const uint64_t B = cfg->batch, m = fd ? 0 : cfg->m;  // no design matrix behind an objective
   hipError_t he = hipSuccess;
-  const uint64_t nstep = wide ? 0 : (m + 15) / 16;
+  // row groups of 16 (design matrices), or super-steps of 64 observations (curve data)
+  const uint64_t nstep = wide ? 0 : curve ? (m + 63) / 64 : (m + 15) / 16;
   p.nstep = nstep;
-  if (he == hipSuccess && nstep)
+  if (he == hipSuccess && curve)  // [super-step][batch][k + 1][64], y in the last row
+    he = pool_malloc(reinterpret_cast<void **>(&e->A_dev), nstep * B * (curve->k + 1) * 64 * 8);
+  if (he == hipSuccess && nstep && !curve)
     he = pool_malloc(reinterpret_cast<void **>(&e->A_dev), nstep * B * 16 * kLmN * 8);
-  if (he == hipSuccess && nstep)
+  if (he == hipSuccess && nstep && !curve)
     he = pool_malloc(reinterpret_cast<void **>(&e->y_dev), nstep * B * 16 * 8);
   if (he == hipSuccess && wide && m) {  // the caller's layout, [batch][m][n]
     he = pool_malloc(reinterpret_cast<void **>(&e->A_dev), B * m * cfg->n * 8);
@@ -457,6 +490,13 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
       return rc2;
     }
   }
+  if (curve) {
+    const int rc2 = rtc_build_lm_curve(curve, cfg->n, &e->rtc);
+    if (rc2) {
+      nlsg_lm_destroy(e);
+      return rc2;
+    }
+  }
   p.A = e->A_dev;
   p.y = e->y_dev;
   p.Aw = e->A_dev;
@@ -510,6 +550,8 @@ int nlsg_lm_destroy(nlsg_lm *e) {
 int nlsg_lm_set_data(nlsg_lm *e, const double *a_host, const double *y_host) {
   if (!e || !a_host || !y_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (e->p.fd) return fail(NLSG_ERR_STATE, "this engine minimises a built-in objective: no data");
+  if (e->curve_k)
+    return fail(NLSG_ERR_INVALID_ARG, "a curve model's data are t and y: nlsg_lm_set_curve_data");
   NLSG_HIP(hipSetDevice(e->cfg.device));
   PhaseClock clk;
   const uint64_t B = e->p.batch, m = e->p.m, n = e->p.n;
@@ -572,6 +614,35 @@ int nlsg_lm_set_data(nlsg_lm *e, const double *a_host, const double *y_host) {
   return NLSG_OK;
 }
 
+// host layout t [problem][m][k], y [problem][m] -> device layout [super-step][problem][k + 1][64] (zero
+// padded past m, y in row k): a lane per observation reads its data coalesced (lm_curve_repack_kernel)
+int nlsg_lm_set_curve_data(nlsg_lm *e, const double *t_host, const double *y_host) {
+  if (!e || !t_host || !y_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (!e->curve_k)
+    return fail(NLSG_ERR_INVALID_ARG, "not a curve engine (nlsg_lm_create_curve): its data go by nlsg_lm_set_data");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  PhaseClock clk;
+  const uint64_t B = e->p.batch, m = e->p.m, K = e->curve_k;
+  double *t_raw = nullptr, *y_raw = nullptr;
+  hipError_t he = pool_malloc(reinterpret_cast<void **>(&t_raw), B * m * K * 8);
+  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&y_raw), B * m * 8);
+  if (he == hipSuccess) he = hipMemcpyAsync(t_raw, t_host, B * m * K * 8, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) he = hipMemcpyAsync(y_raw, y_host, B * m * 8, hipMemcpyHostToDevice, e->stream);
+  if (he == hipSuccess) {
+    const uint64_t total = e->p.nstep * B * (K + 1) * 64;
+    hipLaunchKernelGGL(lm_curve_repack_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0,
+                       e->stream, e->p, e->curve_k, t_raw, y_raw, e->A_dev);
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = hipStreamSynchronize(e->stream);  // the host buffers are borrowed for this call only
+  pool_free(t_raw);
+  pool_free(y_raw);
+  NLSG_HIP(he);
+  e->has_data = true;
+  call_timing().upload_ms = clk.lap();
+  return NLSG_OK;
+}
+
 // Page-locked host memory for buffers that cross PCIe at the boundary (design matrices, start
 // points): what lives there is copied by DMA at the link's rate instead of being staged.
 int nlsg_host_alloc(void **out, uint64_t bytes) {
@@ -606,7 +677,7 @@ int nlsg_lm_set_solver(nlsg_lm *e, int32_t solver) {
 int nlsg_lm_minimize(nlsg_lm *e, double *theta_inout_host, nlsg_status *status_host,
                      double *lambda_out_host) {
   if (!e || !theta_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (!e->has_data) return fail(NLSG_ERR_STATE, "nlsg_lm_set_data has not been called");
+  if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));
   if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   PhaseClock clk;
@@ -654,7 +725,7 @@ int nlsg_lm_minimize(nlsg_lm *e, double *theta_inout_host, nlsg_status *status_h
 int nlsg_lm_time_solve(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total) {
   if (!e || !theta0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (const int prc = params_ready(e)) return prc;
-  if (!e->has_data) return fail(NLSG_ERR_STATE, "nlsg_lm_set_data has not been called");
+  if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));
   NLSG_HIP(hipSetDevice(e->cfg.device));
   float total = 0.f;
   for (uint32_t r = 0; r < repeats; r++) {
@@ -680,7 +751,7 @@ int nlsg_lm_time_eval_kernel(nlsg_lm *e, const double *theta0_host, uint32_t rep
   if (!e || !theta0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (const int prc = params_ready(e)) return prc;  // (before anything that could launch an evaluation)
   if (e->p.fd) return fail(NLSG_ERR_UNSUPPORTED, "Gauss-Newton model only");
-  if (!e->has_data) return fail(NLSG_ERR_STATE, "nlsg_lm_set_data has not been called");
+  if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));
   NLSG_HIP(hipSetDevice(e->cfg.device));
   int rc = upload_theta(e, theta0_host);
   if (rc) return rc;
@@ -709,7 +780,7 @@ int nlsg_lm_time_qr_kernel(nlsg_lm *e, const double *theta0_host, uint32_t repea
   if (const int prc = params_ready(e)) return prc;  // (before anything that could launch an evaluation)
   if (e->p.fd) return fail(NLSG_ERR_UNSUPPORTED, "Gauss-Newton model only");
   if (e->wide) return fail(NLSG_ERR_UNSUPPORTED, "the tinyqr step kernel: n <= 64 only");
-  if (!e->has_data) return fail(NLSG_ERR_STATE, "nlsg_lm_set_data has not been called");
+  if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));
   NLSG_HIP(hipSetDevice(e->cfg.device));
   int rc = upload_theta(e, theta0_host);
   if (rc) return rc;

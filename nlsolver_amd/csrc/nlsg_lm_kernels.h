@@ -771,6 +771,185 @@ __global__ __launch_bounds__(64, 2) void lm_iter_kernel(LmParams p, int first, i
   lm_eval_wave<Link>(p, first, pid, LmWaveShared{smem, smem + 16 * kLmJStride}, theta_lds);
 }
 
+// ---- The curve model r_i(theta) = residual(theta; t_i, y_i): the residual and its Jacobian row come
+// from one body of source (nlsg_lm_create_curve, rtc_build_lm_curve), Model::eval(th, t, y, n, r, J) with
+// Model::kK data per observation. Everything after the evaluation is the regression models': Hg, gg and
+// LmProblem are published in lm_eval_wave's layout, both steps run unchanged.
+//
+// One wave per problem; per super-step the wave takes 64 observations, a lane each. Device layout of the
+// data (lm_curve_repack_kernel): [super-step][problem][kK + 1][64], row kK holding y, zeros past m — the
+// lanes of a wave read 512 contiguous bytes per datum. The lane runs the body once and leaves its Jacobian
+// row and, behind it, r in row `lane` of an LDS tile of 64 rows x (NPAD + 1) doubles. J^T J then comes
+// from the tile on the matrix cores (v_mfma_f64_16x16x4, 16 k-steps per super-step, the lower 16 x 16
+// blocks, a diagonal block with operand A = operand B), J^T r on the VALU from the same operands.
+//
+// Row stride S = NPAD + 1, odd, and k-step q takes the rows q, q + 16, q + 32, q + 48:
+//   - the body's store of column j: ds_write_b64 is served in four groups of 16 contiguous lanes over
+//     32 banks of 4 bytes, 16 doubles; lane l writes double l S + j, and l S mod 16 takes sixteen values
+//     over sixteen consecutive l exactly when S is odd;
+//   - the operand read of k-step q: ds_read_b64 is served in two groups of 32 lanes over 64 banks,
+//     32 doubles; the lane (kk, cc) = (lane >> 4, lane & 15) reads double (q + 16 kk) S + 16 b + cc, and
+//     within a group (kk = 0, 1 or 2, 3) 16 S kk + cc mod 32 takes 32 values exactly when S is odd.
+//   (Four consecutive rows per k-step would need S = 16 mod 32 for the reads, which is 16-way on the stores.)
+// So the rows of the sums are taken in the order q, q + 16, q + 32, q + 48 within a super-step: a fixed
+// order, the same for every problem and batch size.
+template <int NPAD>
+struct LmCurveJ {  // J(j) = v: the store into the lane's row, dropped for j outside [0, n), 0.0 on a row >= m
+  double *row;
+  int n;
+  bool in;
+  struct Ref {
+    double *row;
+    int j;
+    bool ok, in;  // ok: j is inside [0, n)
+    __device__ inline const Ref &operator=(double v) const {
+      if (ok) row[j] = in ? v : 0.0;
+      return *this;
+    }
+  };
+  __device__ inline Ref operator()(int j) const {
+    return Ref{row, j, static_cast<unsigned>(j) < static_cast<unsigned>(n), in};
+  }
+};
+template <int K>
+struct LmCurveT {  // t(k): the observation's k-th datum, 0.0 for k outside [0, K); k is meant to be a constant
+  double v[K];   // (or the counter of a loop that unrolls): a run-time k can move the array out of registers
+  __device__ inline double operator()(int k) const {
+    return static_cast<unsigned>(k) < static_cast<unsigned>(K) ? v[static_cast<unsigned>(k) % K] : 0.0;
+  }
+};
+struct LmCurveTh {  // th(j): parameter j, a broadcast read of the wave's LDS copy
+  const double *theta;
+  __device__ inline double operator()(int j) const { return theta[j & 63]; }  // (never outside the copy)
+};
+
+// theta: the parameters in LDS (64 doubles); tile: [64][NPAD + 1]
+template <typename Model, int NPAD>
+__device__ inline void lm_curve_eval_wave(const LmParams &p, int first, uint64_t pid, double *tile,
+                                          const double *theta) {
+  static_assert(NPAD == 16 || NPAD == 32 || NPAD == 64, "padded column count");
+  constexpr int K = Model::kK, S = NPAD + 1, NB = NPAD / 16, NACC = NB * (NB + 1) / 2;
+  LmProblem *pr = p.prob + pid;
+  const int lane = threadIdx.x, kk = lane >> 4, cc = lane & 15, n = static_cast<int>(p.n);
+  const double *dp = p.A + pid * ((K + 1) * 64) + lane;
+  const uint64_t stride = p.batch * ((K + 1) * 64), nstep = p.nstep;
+  v4d acc[NACC];
+#pragma unroll
+  for (int i = 0; i < NACC; i++) acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
+  double gacc[NB], facc = 0.0;
+#pragma unroll
+  for (int b = 0; b < NB; b++) gacc[b] = 0.0;
+  double d[K + 1];
+  auto fetch = [&](uint64_t s) {
+#pragma unroll
+    for (int k = 0; k <= K; k++)  // read once per evaluation: streamed (nt)
+      d[k] = __builtin_nontemporal_load(dp + s * stride + k * 64);
+  };
+  double *myrow = tile + lane * S;
+  fetch(0);
+  for (uint64_t s = 0; s < nstep; s++) {
+    const bool in = 64 * s + static_cast<uint64_t>(lane) < p.m;
+#pragma unroll
+    for (int j = 0; j < NPAD; j++) myrow[j] = 0.0;  // a J(j) the body does not write is 0
+    LmCurveT<K> t;
+#pragma unroll
+    for (int k = 0; k < K; k++) t.v[k] = d[k];
+    double r = 0.0;
+    Model::eval(LmCurveTh{theta}, t, d[K], n, r, LmCurveJ<NPAD>{myrow, n, in});
+    r = in ? r : 0.0;  // a select: whatever the body made of a padded row's zeros, NaN and inf included
+    myrow[NPAD] = r;
+    facc = __builtin_fma(r, r, facc);
+    // the next 64 observations travel from HBM while these are on the matrix cores
+    if (s + 1 < nstep) fetch(s + 1);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 4
+    for (int q = 0; q < 16; q++) {
+      const double *row = tile + (q + 16 * kk) * S;
+      const double rv = row[NPAD];
+      double op[NB];
+#pragma unroll
+      for (int b = 0; b < NB; b++) op[b] = row[16 * b + cc];
+#pragma unroll
+      for (int b = 0; b < NB; b++) gacc[b] = __builtin_fma(op[b], rv, gacc[b]);
+#pragma unroll
+      for (int rb = 0; rb < NB; rb++)
+#pragma unroll
+        for (int cb = 0; cb <= rb; cb++)
+          acc[rb * (rb + 1) / 2 + cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(
+              op[rb], op[cb], acc[rb * (rb + 1) / 2 + cb], 0, 0, 0);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  // ---- publish the lower triangle of H = 2 J^T J (rows below n only: the rest of Hg stays zero),
+  // g = 2 J^T r (zeros from n on), f
+#pragma unroll
+  for (int rb = 0; rb < NB; rb++)
+#pragma unroll
+    for (int cb = 0; cb <= rb; cb++)
+#pragma unroll
+      for (int rg = 0; rg < 4; rg++) {
+        const int row = 16 * rb + kk + 4 * rg, col = 16 * cb + cc;
+        if (col <= row && row < n)
+          p.Hg[pid * kLmTri + lm_tri_row(row) + col] = 2 * acc[rb * (rb + 1) / 2 + cb][rg];
+      }
+#pragma unroll
+  for (int b = 0; b < 4; b++) {
+    double gv = 0.0;  // (the step reads all 64)
+    if (b < NB) {
+      const double gb = gacc[b < NB ? b : 0];
+      const double g0 = __shfl(gb, cc, 64), g1 = __shfl(gb, cc + 16, 64);
+      const double g2 = __shfl(gb, cc + 32, 64), g3 = __shfl(gb, cc + 48, 64);
+      gv = 2 * (((g0 + g1) + g2) + g3);
+    }
+    if (kk == 0) p.gg[pid * kLmN + 16 * b + cc] = gv;
+  }
+  const double f = wave_sum(facc);
+  if (lane == 0) lm_publish_state(p, pr, first, f);
+}
+
+// lm_iter_kernel for a curve model. LDS of the wave: the step's packed triangle | g, overlaid by the
+// evaluation's tile; the parameters wait in `upd` behind whichever is longer.
+template <int NPAD>
+constexpr int lm_curve_upd_offset() {
+  return 64 * (NPAD + 1) > kLmTri + 64 ? 64 * (NPAD + 1) : kLmTri + 64;
+}
+template <typename Model, int NPAD>
+__global__ __launch_bounds__(64) void lm_curve_iter_kernel(LmParams p, int first, int with_step) {
+  constexpr int kUpd = lm_curve_upd_offset<NPAD>();
+  __shared__ __align__(16) double smem[kUpd + 64];
+  static_assert(64 * (NPAD + 1) <= kUpd && kLmTri + 64 <= kUpd, "neither the tile nor g may reach upd");
+  const uint64_t pid = blockIdx.x;
+  bool have = false;
+  if (!first) {
+    if (p.prob[pid].done) return;
+    if (with_step) {
+      if (!lm_step_wave<false>(p, pid, LmStepShared{smem, smem + kLmTri, smem + kUpd})) return;
+      have = true;
+    }
+  }
+  if (!have) {  // the first launch, and every launch of the QR pipeline: the parameters from global
+    smem[kUpd + threadIdx.x] = p.theta[pid * kLmN + threadIdx.x];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  lm_curve_eval_wave<Model, NPAD>(p, first, pid, smem, smem + kUpd);
+}
+
+// host layout t [problem][m][K], y [problem][m] -> [super-step][problem][K + 1][64], zeros past m
+__global__ void lm_curve_repack_kernel(LmParams p, uint32_t K, const double *t_raw, const double *y_raw,
+                                       double *out) {
+  const uint64_t per = (static_cast<uint64_t>(K) + 1) * 64, total = p.nstep * p.batch * per;
+  const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const uint64_t lane = i & 63, k = (i >> 6) % (K + 1), b = (i / per) % p.batch, s = i / (per * p.batch);
+  const uint64_t row = 64 * s + lane;
+  double v = 0.0;
+  if (row < p.m) v = k < K ? t_raw[(b * p.m + row) * K + k] : y_raw[b * p.m + row];
+  out[i] = v;
+}
+
 // ---- The reference's default functors on a built-in objective: when the
 // caller gives LevenbergMarquardt no Grad / Hess, solve() builds them from finite differences
 // (nlsolver.h:3494-3511 -> fin_diff :1385-1413 and fin_diff_h :1446-1515, both at accuracy 1):

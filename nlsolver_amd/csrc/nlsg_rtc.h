@@ -70,6 +70,9 @@ int rtc_build_lm(const nlsg_custom_objective *obj, int wide_chunks, bool referen
 // the Gauss-Newton evaluation kernel of n parameters (lm_iter_kernel to 64, the one-pass kernels to 128
 // and 256, the super-block kernel beyond) on the link `value_body` / `slope_body` describe; k->iter
 int rtc_build_lm_link(const nlsg_lm_link *link, uint64_t n, LmRtcKernels *out);
+// the curve model's iteration kernel (lm_curve_iter_kernel) of n <= 64 parameters and curve->k data per
+// observation, around the residual-and-Jacobian body; k->iter
+int rtc_build_lm_curve(const nlsg_lm_curve *curve, uint64_t n, LmRtcKernels *out);
 void rtc_release(LmRtcKernels *k);
 struct HybRtcKernels {
   hipModule_t mod = nullptr;

@@ -544,6 +544,33 @@ int rtc_build_lm_link(const nlsg_lm_link *link, uint64_t n, LmRtcKernels *out) {
   *out = k;
   return NLSG_OK;
 }
+// lm_curve_iter_kernel on a model made of the body (nlsg_lm_kernels.h): K data per observation, the
+// padded column count chosen from n. The body sees th(j), t(k), y, n, r and J(j).
+int rtc_build_lm_curve(const nlsg_lm_curve *curve, uint64_t n, LmRtcKernels *out) {
+  if (!curve || !curve->body || !curve->body[0])
+    return fail(NLSG_ERR_INVALID_ARG, "a curve model needs a body (nlsg_lm_curve)");
+  std::string src =
+      "#include \"nlsg_lm_kernels.h\"\n"
+      "namespace nlsg {\n"
+      "struct LmUserCurve {\n"
+      "  static constexpr int kK = " + std::to_string(curve->k) + ";\n"
+      "  template <typename Th, typename T, typename Jt>\n"
+      "  __device__ static inline void eval(const Th &th, const T &t, const double y, const int n, double &r,\n"
+      "                                     const Jt &J) {\n"
+      "    (void)th;\n    (void)t;\n    (void)y;\n    (void)n;\n    (void)J;\n#line 1 \"curve_body\"\n";
+  src += curve->body;
+  src += "\n  }\n};\n}  // namespace nlsg\n";
+  const int npad = n <= 16 ? 16 : n <= 32 ? 32 : 64;
+  std::vector<hipFunction_t> f;
+  LmRtcKernels k;
+  const int rc = rtc_compile_source(
+      src, "curve model", {"nlsg::lm_curve_iter_kernel<nlsg::LmUserCurve, " + std::to_string(npad) + ">"},
+      &k.mod, &f, true);
+  if (rc) return rc;
+  k.iter = f[0];
+  *out = k;
+  return NLSG_OK;
+}
 void rtc_release(LmRtcKernels *k) {
   if (k && k->mod) hipModuleUnload(k->mod);
   if (k) *k = LmRtcKernels();

@@ -5,8 +5,9 @@ reference's default functors (finite-difference gradient and Hessian, nlsolver.h
 Reference interface (nlsolver.h:3428-3463):
     LevenbergMarquardt<Callable, scalar_t, Grad, Hess>(f, lambda = 10, upward_mult = 10,
         downward_mult = 10, max_iter = 100, f_delta = 1e-12, g, h).minimize(x)
-Here `f` is a TanhRegression model, or a LinkRegression (the same model with another link function,
-given as source text) (f = sum r^2, Grad = 2 J^T r, Hess = 2 J^T J evaluated by the
+Here `f` is a TanhRegression model, a LinkRegression (the same model with another link function,
+given as source text) or a CurveModel (any residual r(theta; t_i, y_i), given with its Jacobian row as
+source text) (f = sum r^2, Grad = 2 J^T r, Hess = 2 J^T J evaluated by the
 kernels); minimize() takes one start (n,) or a batch (batch, n) — BASELINE config 4.
 """
 import ctypes as C
@@ -84,8 +85,85 @@ class LinkRegression:
         return cls(A, y, "return z;", "return 1.0;", host=lambda z: z)
 
 
+class CurveModel:
+    """r_i(theta) = residual(theta; t_i, y_i): a model nonlinear in several parameters, fitted to each of
+    `batch` series with their own (t_i, y_i). t: (batch, m, K) — K numbers per observation, 1 <= K <= 16 —
+    or (batch, m) for K = 1, or one problem without the batch axis; y: (batch, m) or (m,); n parameters,
+    1 <= n <= 64.
+
+    body: HIP source compiled when an engine is made, the residual and its Jacobian row in one. It sees
+    th(j) (parameter j), t(k) (the observation's k-th datum; k a constant or an unrolled loop's counter),
+    y (its target) and n, and writes r (the residual) and J(j) = dr/dtheta_j — six names taken inside
+    it; it may call the library's deterministic device math (det_exp, det_log, det_tanh, ...). A J(j) it does not write is 0, a J(j) with j outside [0, n) is dropped, and
+    rows past m contribute nothing whatever the body makes of zero data. Per-problem constants can ride
+    in extra columns of t. The engine runs the Gauss-Newton functors of TanhRegression (f = sum r^2,
+    2 J^T r, 2 J^T J on the matrix cores) with either step.
+
+    host: an optional numpy callable (theta, t, y) -> r, with t (m, K) and y (m,), for __call__ (f at a
+    point, on the CPU); the device never uses it."""
+    nlsg_nlls_objective = _capi.OBJ_CURVE_MODEL
+
+    def __init__(self, t, y, body, n, host=None):
+        self.t = np.ascontiguousarray(t, dtype=np.float64)
+        self.y = np.ascontiguousarray(y, dtype=np.float64)
+        if self.y.ndim == 1 and self.t.ndim in (1, 2):  # one problem
+            self.t, self.y = self.t[None], self.y[None]
+        if self.t.ndim == 2:  # K = 1
+            self.t = self.t[:, :, None]
+        if self.t.ndim != 3 or self.y.ndim != 2 or self.y.shape != self.t.shape[:2] or 0 in self.t.shape:
+            raise ValueError(f"t must be (batch, m, K), (batch, m), (m, K) or (m,) and y its (batch, m) or "
+                             f"(m,): got {np.shape(t)} and {np.shape(y)}")
+        if not 1 <= self.t.shape[2] <= 16:
+            raise ValueError(f"a curve model takes 1 .. 16 data per observation: K = {self.t.shape[2]}")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"n is the number of parameters, an integer >= 1: got {n!r}")
+        if not isinstance(body, str) or not body.strip():
+            raise TypeError("body is the source text of the residual and its Jacobian row")
+        self.n, self.body, self.host = int(n), body, host
+
+    def __call__(self, theta, problem=0):
+        if self.host is None:
+            raise TypeError("this CurveModel has no host= residual: its body exists as device source only")
+        r = np.asarray(self.host(np.asarray(theta, dtype=np.float64), self.t[problem], self.y[problem]),
+                       dtype=np.float64)
+        return float(r @ r)
+
+    @classmethod
+    def exp_decay(cls, t, y):
+        """theta0 exp(-theta1 t) + theta2"""
+        body = ("const double e = det_exp(-th(1) * t(0));\n"
+                "r = y - (th(0) * e + th(2));\n"
+                "J(0) = -e;  J(1) = th(0) * t(0) * e;  J(2) = -1.0;")
+        return cls(t, y, body, 3, host=lambda th, t, y: y - (th[0] * np.exp(-th[1] * t[:, 0]) + th[2]))
+
+    @classmethod
+    def gaussian_peak(cls, t, y):
+        """theta = (amplitude, centre, width, offset): a exp(-(t - c)^2 / (2 w^2)) + d"""
+        body = ("const double u = (t(0) - th(1)) / th(2);\n"
+                "const double e = det_exp(-0.5 * (u * u));\n"
+                "r = y - (th(0) * e + th(3));\n"
+                "const double ae = th(0) * e;\n"
+                "J(0) = -e;  J(1) = -(ae * u / th(2));  J(2) = -(ae * (u * u) / th(2));  J(3) = -1.0;")
+        return cls(t, y, body, 4, host=lambda th, t, y: y - (
+            th[0] * np.exp(-0.5 * ((t[:, 0] - th[1]) / th[2]) ** 2) + th[3]))
+
+    @classmethod
+    def logistic4(cls, t, y):
+        """the four-parameter dose-response curve, theta = (a, b, c, d): d + (a - d) / (1 + (t / c)^b) for
+        t > 0 — a the response at t -> 0, d at t -> inf, c the inflection point, b the slope there"""
+        body = ("const double L = det_log(t(0)) - det_log(th(2));\n"
+                "const double u = det_exp(th(1) * L);\n"
+                "const double s = 1.0 / (1.0 + u);\n"
+                "const double ad = th(0) - th(3);\n"
+                "r = y - (th(3) + ad * s);\n"
+                "const double w = ad * (s * s) * u;\n"
+                "J(0) = -s;  J(1) = w * L;  J(2) = -(w * th(1) / th(2));  J(3) = -(1.0 - s);")
+        return cls(t, y, body, 4, host=lambda th, t, y: y - (
+            th[3] + (th[0] - th[3]) / (1.0 + (t[:, 0] / th[2]) ** th[1])))
+
+
 class LMEngine:
-    """model: a TanhRegression or a LinkRegression, or the name / id of a built-in objective ("rosenbrock", "sphere",
+    """model: a TanhRegression, a LinkRegression or a CurveModel, or the name / id of a built-in objective ("rosenbrock", "sphere",
     "styblinski_tang") or a CustomObjective, with batch= and n= (default functors: fin_diff +
     fin_diff_h).
 
@@ -121,6 +199,9 @@ class LMEngine:
             B, m = batch, 0
             objective = (_capi.OBJ_CUSTOM if custom else
                          _capi.OBJECTIVES[model] if isinstance(model, str) else model)
+        elif isinstance(model, CurveModel):
+            (B, m), n = model.y.shape, model.n
+            objective = model.nlsg_nlls_objective
         else:
             B, m, n = model.A.shape
             objective = model.nlsg_nlls_objective
@@ -148,9 +229,15 @@ class LMEngine:
             check(lib().nlsg_rtc_load(rtc_library_path().encode()))
             link = _capi.LMLinkC(model.value_body.encode(), model.slope_body.encode())
             check(create(C.byref(cfg), C.byref(link), C.byref(self._h)))
+        elif isinstance(model, CurveModel):
+            create, set_data = require("nlsg_lm_create_curve"), require("nlsg_lm_set_curve_data")
+            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
+            curve = _capi.LMCurveC(model.body.encode(), model.t.shape[2])
+            check(create(C.byref(cfg), C.byref(curve), C.byref(self._h)))
+            check(set_data(self._h, model.t.ctypes.data_as(_capi.pd), model.y.ctypes.data_as(_capi.pd)))
         else:
             check(lib().nlsg_lm_create(C.byref(cfg), C.byref(self._h)))
-        if not fd:
+        if not fd and not isinstance(model, CurveModel):
             check(lib().nlsg_lm_set_data(self._h, model.A.ctypes.data_as(_capi.pd),
                                          model.y.ctypes.data_as(_capi.pd)))
 
@@ -248,7 +335,8 @@ class LevenbergMarquardt:
         if not isinstance(x, np.ndarray) or x.dtype != np.float64 or x.ndim not in (1, 2):
             raise TypeError("x must be a float64 numpy array of shape (n,) or (batch, n)")
         xb = x.reshape(1, -1) if x.ndim == 1 else x
-        shape = {} if hasattr(self.f, "A") else dict(batch=xb.shape[0], n=xb.shape[1])
+        has_data = hasattr(self.f, "A") or isinstance(self.f, CurveModel)
+        shape = {} if has_data else dict(batch=xb.shape[0], n=xb.shape[1])
         args = dict(self.args)
         if args["solver"] is None:
             from .de import CustomObjective

@@ -384,6 +384,20 @@ typedef enum {
  * 9.4e6 against 2.6e6 iteration-problems/s at Rosenbrock-128D x 4096; with a gradient functor the H
  * passes (a lane per row) cost 1.5 x the tree kernels' time at dim = 1024. */
 #define NLSG_BFGS_REFERENCE_ORDER 2
+/* NLSG_BFGS_RESIDENT: the whole while(true) loop of 3238-3284 in ONE kernel, for batches of small
+ * problems (1 <= dim <= 64): a 64-lane workgroup owns a problem, keeps its inverse Hessian in LDS and
+ * runs up to `iters` turns per launch of nlsg_bfgs_step — no launches between iterations, no H traffic,
+ * no waiting for the batch's slowest line search. The turn is the lock-step engine's own code and the H
+ * passes make its additions in its order, in either summation order: every call returns what the engine
+ * without the flag returns, bit for bit, nlsg_bfgs_download_state included. nlsg_bfgs_step cuts at 256
+ * turns per launch; nlsg_bfgs_time_steps is NLSG_ERR_UNSUPPORTED (there are no separate H kernels to
+ * bracket). Checks, before the device is touched and behind the older ones: with NLSG_BFGS_SYMMETRIC
+ * NLSG_ERR_INVALID_ARG; dim > 64 NLSG_ERR_UNSUPPORTED. The workgroup holds ONE parameter row: the budget of
+ * nlsg_bfgs_create_params is nlsg_bfgs_lds_bytes(dim, flags) + nlsg_custom_params_lds_bytes(n_params),
+ * which 4096 parameters meet at every dim <= 64. No new symbol, NLSG_ABI_VERSION stays 1: a caller asks
+ * whether a library has the mode with nlsg_bfgs_lds_bytes(2, NLSG_BFGS_RESIDENT) != 0 — a library older
+ * than the flag answers 0 to it. */
+#define NLSG_BFGS_RESIDENT 4
 
 typedef struct {
   uint32_t struct_size;
@@ -393,7 +407,8 @@ typedef struct {
                        /* NLSG_OBJ_ROSENBROCK / SPHERE / STYBLINSKI_TANG / RASTRIGIN:  */
                        /* reference's default gradient fin_diff (nlsolver.h:         */
                        /* 1385-1413, 2849-2855), evaluated on the device              */
-  int32_t flags;       /* 0, NLSG_BFGS_SYMMETRIC or NLSG_BFGS_REFERENCE_ORDER     */
+  int32_t flags;       /* 0, NLSG_BFGS_SYMMETRIC or NLSG_BFGS_REFERENCE_ORDER,    */
+                       /* the latter or 0 also with NLSG_BFGS_RESIDENT            */
   uint64_t batch;      /* independent problems                                    */
   uint64_t dim;        /* x.size() of each problem (<= 1024)                      */
   uint64_t max_iter;   /* ctor args of nlsolver.h:3181-3185                       */
@@ -460,7 +475,8 @@ int nlsg_bfgs_create_gradient(const nlsg_bfgs_config *cfg, const nlsg_custom_obj
 int nlsg_bfgs_set_params(nlsg_bfgs *e, const double *params_host);
 /* Dynamic LDS bytes of a search / init launch before any parameter rows: the four waves' buffers with
  * NLSG_BFGS_REFERENCE_ORDER, none without. 0 also outside 1 <= dim <= 1024, for unknown flags and for a
- * combination of flags the engine rejects. Host only, no device. */
+ * combination of flags the engine rejects. With NLSG_BFGS_RESIDENT: the resident workgroup's block
+ * without its parameter row, never 0 for a shape the engine takes, 0 for dim > 64. Host only, no device. */
 uint64_t nlsg_bfgs_lds_bytes(uint64_t dim, uint32_t flags);
 int nlsg_bfgs_destroy(nlsg_bfgs *e);
 /* x0_host: batch*dim start points (row-major). H = I, g = grad(x0) (3212, 3234). */

@@ -454,6 +454,10 @@ class api {
   decltype(&nlsg_lm_create_curve) lm_create_curve = nullptr;
   decltype(&nlsg_lm_set_curve_data) lm_set_curve_data = nullptr;
   decltype(&nlsg_bfgs_create_gradient) bfgs_create_gradient = nullptr;
+  // optional; with it, whether the library has the resident BFGS mode: one older than NLSG_BFGS_RESIDENT
+  // answers 0 to the flag it does not know
+  decltype(&nlsg_bfgs_lds_bytes) bfgs_lds_bytes = nullptr;
+  bool has_bfgs_resident() const { return bfgs_lds_bytes && bfgs_lds_bytes(2, NLSG_BFGS_RESIDENT) != 0; }
   // the resident engine's LDS need with the parameter row; throws when the library cannot take
   // parameters or the shape does not fit (`shape_need` = nlsg_*_batch_lds_bytes, 0 = out of range)
   void require_params_fit(bool has_engine, bool has_set, uint64_t shape_need, int32_t n_params,
@@ -541,6 +545,7 @@ class api {
     bind_optional(h, "nlsg_lm_create_curve", lm_create_curve);
     bind_optional(h, "nlsg_lm_set_curve_data", lm_set_curve_data);
     bind_optional(h, "nlsg_bfgs_create_gradient", bfgs_create_gradient);
+    bind_optional(h, "nlsg_bfgs_lds_bytes", bfgs_lds_bytes);
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
   }
@@ -674,6 +679,26 @@ inline pso_driver &pso_driver_mode() {
   return mode;
 }
 constexpr uint64_t pso_resident_lds_budget = 160 * 1024;
+// How BFGS<...>::minimize / minimize_batch run a device solve of at most 64 coordinates:
+//   turns     the lock-step engine: three or four launches per iteration, H streamed from memory (default)
+//   resident  the whole loop in one kernel, a workgroup per start with its inverse Hessian in LDS
+//             (NLSG_BFGS_RESIDENT): the same x and status bit for bit. Taken when dim <= 64 and the library
+//             has the mode (nlsg_bfgs_lds_bytes(dim, flags | NLSG_BFGS_RESIDENT) != 0); the lock-step engine
+//             solves everything else.
+// Set before the solves it should govern: `nlsolver::device::bfgs_driver_mode() = bfgs_driver::resident`,
+// or the environment variable NLSG_BFGS_DRIVER = turns | resident (read at first use).
+enum class bfgs_driver { turns, resident };
+inline bfgs_driver &bfgs_driver_mode() {
+  static bfgs_driver mode = [] {
+    const char *e = std::getenv("NLSG_BFGS_DRIVER");
+    const std::string v = e ? e : "";
+    if (v == "resident") return bfgs_driver::resident;
+    if (!v.empty() && v != "turns")
+      throw device_error("NLSG_BFGS_DRIVER must be turns or resident, not '" + v + "'");
+    return bfgs_driver::turns;
+  }();
+  return mode;
+}
 }  // namespace device
 
 // ---------------------------------------------------------------------------
@@ -1480,6 +1505,11 @@ class BFGS {
     cfg.struct_size = sizeof(cfg);
     if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
     if (use_reference_order()) cfg.flags |= NLSG_BFGS_REFERENCE_ORDER;
+    // device::bfgs_driver::resident: the same solve in the resident kernel, where it is taken (the header
+    // never asks for the symmetric restatement)
+    if (device::bfgs_driver_mode() == device::bfgs_driver::resident && n <= 64 && api.bfgs_lds_bytes &&
+        api.has_bfgs_resident() && api.bfgs_lds_bytes(n, cfg.flags | NLSG_BFGS_RESIDENT) != 0)
+      cfg.flags |= NLSG_BFGS_RESIDENT;
     cfg.batch = B;
     cfg.dim = n;
     cfg.max_iter = max_iter;

@@ -104,6 +104,7 @@ class BFGSGradientC(C.Structure):  # nlsg_bfgs_gradient
 
 BFGS_SYMMETRIC = 1  # NLSG_BFGS_SYMMETRIC
 BFGS_REFERENCE_ORDER = 2  # NLSG_BFGS_REFERENCE_ORDER
+BFGS_RESIDENT = 4  # NLSG_BFGS_RESIDENT
 
 
 OBJ_TANH_REGRESSION = 32

@@ -53,16 +53,51 @@ class BFGSEngine:
     objective's own path; "finite_difference" forces the default gradient whatever the objective
     carries; "analytic" insists and raises ValueError when there is no gradient to evaluate.
     gradient_used says which ran: "analytic" or "finite_difference". In reference order a gradient of the
-    terms form costs one index-order sum of the D terms (the body's `s`) beside the body, read or not."""
+    terms form costs one index-order sum of the D terms (the body's `s`) beside the body, read or not.
+
+    resident=True (NLSG_BFGS_RESIDENT, dim <= 64, not with symmetric): the whole loop of a solve in one
+    kernel, a 64-lane workgroup per problem with its inverse Hessian in LDS; step(k) is one launch per 256
+    turns instead of three or four per turn, and a problem neither waits for the batch's slowest line
+    search nor keeps its wave once it has stopped. Every call returns what the lock-step engine returns,
+    bit for bit, download_state() included; time_steps() is NlsgError code 2. fits_resident() says
+    whether a shape is taken."""
 
     GRADIENTS = (None, "analytic", "finite_difference")
 
     @staticmethod
-    def lds_bytes(dim, reference_order=False, n_params=0):
+    def lds_bytes(dim, reference_order=False, n_params=0, resident=False):
         """LDS bytes of a search / init launch: the reference-order buffers of its four waves (none in
-        tree order) and four rows of n_params objective parameters (host only)"""
-        need = int(require("nlsg_bfgs_lds_bytes")(dim, _capi.BFGS_REFERENCE_ORDER if reference_order else 0))
+        tree order) and four rows of n_params objective parameters (host only). resident=True: the
+        resident workgroup's block — H, its vectors, one wave's buffers — and ONE row; 0 where the library
+        or the shape has no resident mode."""
+        flags = _capi.BFGS_REFERENCE_ORDER if reference_order else 0
+        if resident:
+            need = int(require("nlsg_bfgs_lds_bytes")(dim, flags | _capi.BFGS_RESIDENT))
+            if need == 0:
+                return 0
+            return need + (int(require("nlsg_custom_params_lds_bytes")(n_params)) if n_params else 0)
+        need = int(require("nlsg_bfgs_lds_bytes")(dim, flags))
         return need + (4 * int(require("nlsg_custom_params_lds_bytes")(n_params)) if n_params else 0)
+
+    @staticmethod
+    def has_resident():
+        """whether the loaded library has the resident mode (one older than the flag answers 0 to it)"""
+        try:
+            return int(require("nlsg_bfgs_lds_bytes")(2, _capi.BFGS_RESIDENT)) != 0
+        except NlsgError:
+            return False
+
+    @staticmethod
+    def fits_resident(dim, symmetric=False, n_params=0):
+        """whether an engine with resident=True takes the shape: 1 <= dim <= 64, the literal update,
+        0 <= n_params <= 4096 (either summation order: the workgroup's block stays below 75 KiB)"""
+        from .de import LDS_BUDGET
+        if symmetric or not (1 <= dim <= 64 and 0 <= n_params <= _capi.CUSTOM_MAX_PARAMS):
+            return False
+        if not BFGSEngine.has_resident():
+            return False
+        need = BFGSEngine.lds_bytes(dim, True, n_params, resident=True)
+        return 0 < need <= LDS_BUDGET
 
     @staticmethod
     def fits(dim, reference_order=False, n_params=0):
@@ -74,7 +109,8 @@ class BFGSEngine:
         return BFGSEngine.lds_bytes(dim, reference_order, n_params) <= LDS_BUDGET
 
     def __init__(self, objective, batch, *, dim=None, max_iter=100, grad_eps=5e-3, alpha=1.0,
-                 device=0, stream=None, symmetric=False, reference_order=False, gradient=None):
+                 device=0, stream=None, symmetric=False, reference_order=False, gradient=None,
+                 resident=False):
         from .de import CustomObjective, rtc_library_path
         if gradient not in self.GRADIENTS:
             raise ValueError(f"gradient must be one of {self.GRADIENTS}, not {gradient!r}")
@@ -88,8 +124,10 @@ class BFGSEngine:
         self.gradient_used = "analytic" if has_analytic and gradient != "finite_difference" else "finite_difference"
         cfg = BFGSConfig()
         cfg.flags = (_capi.BFGS_SYMMETRIC if symmetric else 0) | \
-            (_capi.BFGS_REFERENCE_ORDER if reference_order else 0)
+            (_capi.BFGS_REFERENCE_ORDER if reference_order else 0) | \
+            (_capi.BFGS_RESIDENT if resident else 0)
         self.symmetric = bool(symmetric)
+        self.resident = bool(resident)
         cfg.struct_size = C.sizeof(BFGSConfig)
         cfg.device = device
         cfg.stream = None if stream is None else (stream or 1)
@@ -228,11 +266,19 @@ class BFGS:
 
     A CustomObjective that carries grad_body is minimised with that gradient (BFGSEngine gradient=None);
     gradient_used says which path the last minimize() took. g stays None: the gradient of a device
-    objective is part of the objective."""
+    objective is part of the objective.
+
+    driver="resident": the solve runs in the resident kernel (BFGSEngine resident=True) whenever
+    BFGSEngine.fits_resident holds — dim <= 64, not symmetric, a library that has the mode — and through
+    the lock-step engine otherwise: the same x and status bit for bit either way. `driver_used` says
+    which engine the last minimize() ran on. Default "turns": the lock-step engine."""
 
     def __init__(self, f, g=None, max_iter=100, grad_eps=5e-3, alpha=1.0, *, device=0,
-                 symmetric=False, reference_order=None, params=None):
+                 symmetric=False, reference_order=None, params=None, driver="turns"):
         from .nm import _drop_in_rows
+        if driver not in ("turns", "resident"):
+            raise ValueError(f"driver must be 'turns' or 'resident', not {driver!r}")
+        self.driver, self.driver_used = driver, None
         self.n_params = getattr(f, "n_params", 0)
         if (params is not None) != bool(self.n_params):
             raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
@@ -262,6 +308,11 @@ class BFGS:
             args["reference_order"] = (fd or quad) and not args["symmetric"]
         from .nm import _rows_for_batch
         rows = _rows_for_batch(self.params, xb.shape[0])
+        resident = self.driver == "resident" and \
+            BFGSEngine.fits_resident(xb.shape[1], bool(args["symmetric"]), self.n_params)
+        if resident:
+            args["resident"] = True
+        self.driver_used = "resident" if resident else "turns"
         with BFGSEngine(self.f, xb.shape[0], **extra, **args) as eng:
             self.gradient_used = eng.gradient_used
             out, st = eng.minimize(xb, params=rows)

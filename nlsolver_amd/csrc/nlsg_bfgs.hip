@@ -27,6 +27,8 @@ struct nlsg_bfgs {
   bool params_set = false;
   unsigned fd_lds = 0;  // dynamic LDS of the module's search / init launches: the reference-order buffers,
                         // and behind them a parameter row per wave
+  bool resident = false;   // NLSG_BFGS_RESIDENT: the whole loop in bfgs_resident_kernel, H in LDS
+  BfgsResidentLayout res{};  // its dynamic LDS block (doubles)
 };
 
 namespace {
@@ -86,6 +88,33 @@ namespace {
       default: break;                                                    \
     }                                                                    \
   } while (0)
+
+// the resident kernel: CHUNKS = 1 only, a 64-lane workgroup per problem
+#define BFGS_RESIDENT_CASE(V, M)                                                                                \
+  hipLaunchKernelGGL((bfgs_resident_kernel<1, V, M>), dim3(static_cast<unsigned>(e->p.batch)), dim3(64), lds_, \
+                     e->stream, e->p, iters, e->res.h_at, e->res.vec_at)
+#define BFGS_RESIDENT_MODELS(V)                                                       \
+  switch (e->p.model) {                                                               \
+    case kBfgsQuad: BFGS_RESIDENT_CASE(V, kBfgsQuad); break;                          \
+    case NLSG_OBJ_ROSENBROCK: BFGS_RESIDENT_CASE(V, NLSG_OBJ_ROSENBROCK); break;      \
+    case NLSG_OBJ_SPHERE: BFGS_RESIDENT_CASE(V, NLSG_OBJ_SPHERE); break;              \
+    case NLSG_OBJ_STYBLINSKI_TANG: BFGS_RESIDENT_CASE(V, NLSG_OBJ_STYBLINSKI_TANG); break; \
+    case NLSG_OBJ_RASTRIGIN: BFGS_RESIDENT_CASE(V, NLSG_OBJ_RASTRIGIN); break;        \
+    default: break;                                                                   \
+  }
+
+// one resident launch: every unfinished problem makes up to `iters` turns
+void launch_resident(nlsg_bfgs *e, uint32_t iters) {
+  const unsigned lds_ = e->res.total * static_cast<unsigned>(sizeof(double));
+  if (e->p.model == NLSG_OBJ_CUSTOM) {
+    void *args[] = {&e->p, &iters, &e->res.h_at, &e->res.vec_at};
+    launch_module_kernel(e->rtc.resident, static_cast<unsigned>(e->p.batch), 64, lds_, e->stream, args);
+  } else if (e->vec) {
+    BFGS_RESIDENT_MODELS(true)
+  } else {
+    BFGS_RESIDENT_MODELS(false)
+  }
+}
 
 void launch_iteration(nlsg_bfgs *e, bool timed) {
   const unsigned wave_grid = static_cast<unsigned>((e->p.batch + 3) / 4);
@@ -197,8 +226,17 @@ int nlsg_bfgs_create_gradient(const nlsg_bfgs_config *cfg, const nlsg_custom_obj
 // The dynamic LDS of a search / init launch without parameter rows: the four waves' reference-order
 // buffers, or nothing. 0 also outside 1 <= dim <= 1024, for unknown flags and for reference order with
 // the symmetric restatement (which the engine rejects).
+// With NLSG_BFGS_RESIDENT: the resident workgroup's block without its parameter row — never 0 for a shape the
+// engine takes, 0 for dim > 64 and with the symmetric restatement (a library older than the mode answers 0 to
+// the flag it does not know: the probe for the mode is nlsg_bfgs_lds_bytes(2, NLSG_BFGS_RESIDENT) != 0).
 uint64_t nlsg_bfgs_lds_bytes(uint64_t dim, uint32_t flags) {
-  if (dim < 1 || dim > 1024 || (flags & ~(NLSG_BFGS_SYMMETRIC | NLSG_BFGS_REFERENCE_ORDER))) return 0;
+  if (dim < 1 || dim > 1024 ||
+      (flags & ~(NLSG_BFGS_SYMMETRIC | NLSG_BFGS_REFERENCE_ORDER | NLSG_BFGS_RESIDENT)))
+    return 0;
+  if (flags & NLSG_BFGS_RESIDENT) {
+    if (dim > kBfgsResidentMaxDim || (flags & NLSG_BFGS_SYMMETRIC)) return 0;
+    return bfgs_resident_layout(dim, (flags & NLSG_BFGS_REFERENCE_ORDER) ? 1 : 0, 0).total * sizeof(double);
+  }
   if (!(flags & NLSG_BFGS_REFERENCE_ORDER) || (flags & NLSG_BFGS_SYMMETRIC)) return 0;
   return bfgs_fd_seq_lds_bytes(bfgs_chunks(dim));
 }
@@ -235,8 +273,9 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
     return fail(NLSG_ERR_UNSUPPORTED, "dim %llu > 1024 is not covered by the device path",
                 (unsigned long long)cfg->dim);
   const bool seq = (cfg->flags & NLSG_BFGS_REFERENCE_ORDER) != 0;
-  if (cfg->flags & ~(NLSG_BFGS_SYMMETRIC | NLSG_BFGS_REFERENCE_ORDER))
+  if (cfg->flags & ~(NLSG_BFGS_SYMMETRIC | NLSG_BFGS_REFERENCE_ORDER | NLSG_BFGS_RESIDENT))
     return fail(NLSG_ERR_INVALID_ARG, "unknown flags 0x%x", cfg->flags);
+  const bool resident = (cfg->flags & NLSG_BFGS_RESIDENT) != 0;
   if (seq && (cfg->flags & NLSG_BFGS_SYMMETRIC))
     return fail(NLSG_ERR_INVALID_ARG,
                 "NLSG_BFGS_REFERENCE_ORDER reproduces the reference's literal arithmetic; the symmetric "
@@ -249,12 +288,20 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
     return fail(NLSG_ERR_UNSUPPORTED,
                 "NLSG_BFGS_REFERENCE_ORDER: Rastrigin's cosine is the device's deterministic one, not "
                 "libm's — there is no reference arithmetic to reproduce");
+  if (resident && (cfg->flags & NLSG_BFGS_SYMMETRIC))
+    return fail(NLSG_ERR_INVALID_ARG,
+                "NLSG_BFGS_RESIDENT keeps the literal update's whole matrix in LDS; the symmetric restatement "
+                "is the streaming engine's");
+  if (resident && cfg->dim > kBfgsResidentMaxDim)
+    return fail(NLSG_ERR_UNSUPPORTED, "NLSG_BFGS_RESIDENT holds a problem of at most %d coordinates in LDS, not %llu",
+                kBfgsResidentMaxDim, (unsigned long long)cfg->dim);
   if (grad_body && custom->n_params < 0)  // (zero is an objective without parameters: no row, no check)
     return fail(NLSG_ERR_INVALID_ARG, "n_params = %d: nlsg_bfgs_create_gradient takes 0 .. %d parameters",
                 custom->n_params, NLSG_CUSTOM_MAX_PARAMS);
-  if (with_params)  // (a row per wave, four to the block, behind the reference-order buffers)
+  if (with_params)  // (a row per wave, four to the block, behind the reference-order buffers; the resident
+                    // workgroup is one wave with one row)
     if (const int prc = check_custom_params(custom, nlsg_bfgs_lds_bytes(cfg->dim, cfg->flags), "nlsg_bfgs",
-                                            "nlsg_bfgs_create_custom", 4))
+                                            "nlsg_bfgs_create_custom", resident ? 1 : 4))
       return prc;
   int rc = check_device(cfg->device);
   if (rc) return rc;
@@ -269,6 +316,9 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   // launch size and the offset the kernels are compiled with (NLSG_PARAMS_PER_WAVE) are taken
   const size_t rows_at = seq ? bfgs_fd_seq_lds_bytes(e->chunks) : 0;
   e->fd_lds = static_cast<unsigned>(rows_at + 4 * custom_params_lds_bytes(e->n_params));
+  // (the resident kernel's row sits where the init kernel's first wave has its own: bfgs_resident_layout)
+  e->resident = resident;
+  e->res = bfgs_resident_layout(n, seq ? 1 : 0, custom_params_lds_bytes(e->n_params) / sizeof(double));
   e->vec = n % 2 == 0;
   e->bpp = static_cast<uint32_t>((n + 4 * kBfgsRowsPerWave - 1) / (4 * kBfgsRowsPerWave));
   e->symmetric = (cfg->flags & NLSG_BFGS_SYMMETRIC) != 0;
@@ -345,7 +395,7 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   p.nstored = nstored;
   if (custom) {
     const int rc2 = rtc_build_bfgs(custom, e->chunks, e->vec, static_cast<long>(rows_at / sizeof(double)), &e->rtc,
-                                   grad_body);
+                                   grad_body, resident);
     if (rc2) {
       nlsg_bfgs_destroy(e);
       return rc2;
@@ -361,6 +411,16 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
       if (he != hipSuccess) {
         nlsg_bfgs_destroy(e);
         return fail(NLSG_ERR_HIP, "raising the kernels' dynamic LDS limit failed: %s", hipGetErrorString(he));
+      }
+    }
+    // (only a module kernel has a parameter row: the built-in resident kernels stay below 64 KiB)
+    if (resident && e->res.total * sizeof(double) > 64 * 1024) {
+      he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.resident),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(e->res.total * sizeof(double)));
+      if (he != hipSuccess) {
+        nlsg_bfgs_destroy(e);
+        return fail(NLSG_ERR_HIP, "raising the resident kernel's dynamic LDS limit failed: %s", hipGetErrorString(he));
       }
     }
   }
@@ -421,7 +481,15 @@ int nlsg_bfgs_step(nlsg_bfgs *e, uint64_t iters) {
   if (const int prc = params_ready(e)) return prc;
   if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_bfgs_init has not been called");
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  for (uint64_t k = 0; k < iters; k++) launch_iteration(e, false);
+  if (e->resident) {  // the host cuts at a constant number of turns per launch
+    for (uint64_t left = iters; left > 0;) {
+      const uint32_t cut = static_cast<uint32_t>(std::min<uint64_t>(left, kBfgsResidentCut));
+      launch_resident(e, cut);
+      left -= cut;
+    }
+  } else {
+    for (uint64_t k = 0; k < iters; k++) launch_iteration(e, false);
+  }
   NLSG_HIP(launches_status());
   return NLSG_OK;
 }
@@ -521,7 +589,7 @@ int nlsg_bfgs_minimize(nlsg_bfgs *e, double *x_inout_host, nlsg_status *status_h
   // every problem stops after at most max_iter + 1 turns (the last one only fires the stop test)
   uint64_t left = e->cfg.max_iter + 1;
   for (;;) {
-    const uint64_t chunk = std::min<uint64_t>(left ? left : 1, 8);
+    const uint64_t chunk = std::min<uint64_t>(left ? left : 1, e->resident ? kBfgsResidentCut : 8);
     rc = nlsg_bfgs_step(e, chunk);
     if (rc) return rc;
     left = left > chunk ? left - chunk : 0;
@@ -540,6 +608,8 @@ int nlsg_bfgs_time_steps(nlsg_bfgs *e, uint64_t iters, float *ms_total, float *m
   if (!e || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (const int prc = params_ready(e)) return prc;
   if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_bfgs_init has not been called");
+  if (e->resident)
+    return fail(NLSG_ERR_UNSUPPORTED, "a resident engine has no separate H kernels to bracket: time nlsg_bfgs_step");
   NLSG_HIP(hipSetDevice(e->cfg.device));
   float hess = 0.f;
   NLSG_HIP(hipEventRecord(e->ev0, e->stream));

@@ -13,6 +13,8 @@
 //                        direction d = -H' g (reads H, writes H)      — HBM bound
 // A freshly reset H (identity, 3212 / 3253-3260) is never materialised: a per-problem
 // flag makes the two streaming kernels treat H as I (no read).
+// Small problems (n <= 64, NLSG_BFGS_RESIDENT) have a second shape, bfgs_resident_kernel: a workgroup per
+// problem, H in LDS, the whole loop in one launch — the same turn (nlsg_bfgs_turn.h) and the same additions.
 // Every reduction is the lane tree of DESIGN.md (element e -> lane (e%128)/2, in-lane
 // sequential, 64-lane xor butterfly), mirrored by oracle/oracle_bfgs.c (tree = 1).
 #pragma once
@@ -611,6 +613,26 @@ __device__ inline void load_vec(const double *p, uint64_t n, const double *zero,
   load_row<CHUNKS, VEC>(p, n, zero, v);
 }
 
+// A turn of BFGS::solve's loop up to the two H passes (nlsg_bfgs_turn.h) as a function: stopped(fv) when a stop
+// test fired, advanced(s, y, rho, identity) at the end of a turn that ran. bfgs_resident_kernel calls it.
+// bfgs_search_kernel includes the same statements in place instead: through a function — any function, even
+// one that merely wraps its old body — this compiler hands the kernel's argument block over as a copy and
+// allocates 2 to 6 vector registers differently, and the lock-step kernels are to stay what they were.
+template <int CHUNKS, int MODEL, typename Stopped, typename Advanced>
+__device__ inline void bfgs_search_turn(const BfgsParams &p, const BfgsModel<MODEL, CHUNKS> &model,
+                                        double (&x)[CHUNKS][2], double (&g)[CHUNKS][2], double (&dir)[CHUNKS][2],
+                                        uint64_t iter, uint64_t &fcalls, uint64_t &gcalls, double &prev_norm,
+                                        double &cur_norm, Stopped &&stopped, Advanced &&advanced) {
+  const uint64_t n = p.n;
+#define NLSG_BFGS_TURN_STOPPED(fv) \
+  stopped(fv);                     \
+  return;
+#define NLSG_BFGS_TURN_ADVANCED advanced(s, y, rho, identity);
+#include "nlsg_bfgs_turn.h"
+#undef NLSG_BFGS_TURN_STOPPED
+#undef NLSG_BFGS_TURN_ADVANCED
+}
+
 // One wave per problem: everything of an iteration except the two H passes.
 // Long vectors (CHUNKS >= 4) want the whole register file of a SIMD for one wave; short ones
 // (every finite-difference model) leave room for four, which is what hides the latency of the
@@ -636,140 +658,18 @@ bfgs_search_kernel(BfgsParams p) {
   uint64_t iter = pr->iter, fcalls = pr->fcalls, gcalls = pr->gcalls;
   double prev_norm = pr->prev_norm, cur_norm = pr->cur_norm;
 
-  // stop tests, nlsolver.h:3239-3246
-  if (iter >= p.max_iter || cur_norm < p.grad_eps || fabs(cur_norm - prev_norm) < p.grad_eps ||
-      isinf(cur_norm)) {
-    const double fv = model.f(x, fcalls);
-    if (lane == 0) {
-      pr->fval = fv;
-      pr->fcalls = fcalls;
-      pr->done = 1;
-    }
-    return;
-  }
-  // direction: d = -H g, computed by the previous update pass (or -g while H = I)
-  // H in memory is valid after the previous update pass; only the very first
-  // iteration (H = I, :3212) and the reset guard below use the identity shortcut
-  int identity = (iter == 0) ? 1 : 0;
-  if (identity) {
-#pragma unroll
-    for (int c = 0; c < CHUNKS; c++) {
-      dir[c][0] = -g[c][0];
-      dir[c][1] = -g[c][1];
-    }
-  }
-  const double phi = bfgs_dot<CHUNKS>(g, dir, n, p.seq, model.lds);
-  if ((phi > 0) || isnan(phi) || cur_norm > prev_norm) {  // reset guard, :3253-3260
-    identity = 1;
-#pragma unroll
-    for (int c = 0; c < CHUNKS; c++) {
-      dir[c][0] = -g[c][0];
-      dir[c][1] = -g[c][1];
-    }
-  }
-  double pg[CHUNKS][2];
-#pragma unroll
-  for (int c = 0; c < CHUNKS; c++) {
-    pg[c][0] = g[c][0];
-    pg[c][1] = g[c][1];
-  }
-  // more_thuente_search (1880-1891) -> cvsrch (1673-1793)
-  const double f0 = model.f(x, fcalls);
-  double stp = p.alpha;
-  {
-    int info = 0, infoc = 1;
-    const double xtol = 1e-15, ftol = 1e-4, gtol = 1e-2, stpmin = 1e-15, stpmax = 1e15, xtrapf = 4;
-    const int maxfev = 20;
-    int nfev = 0;
-    const double dginit = bfgs_dot<CHUNKS>(g, dir, n, p.seq, model.lds);
-    if (!(dginit >= 0.0)) {
-      int brackt = 0, stage1 = 1;
-      const double finit = f0, dgtest = ftol * dginit;
-      double width = stpmax - stpmin, width1 = 2 * width;
-      double stx = 0.0, fx = finit, dgx = dginit, sty = 0.0, fy = finit, dgy = dginit;
-      double stmin, stmax;
-      for (;;) {
-        if (brackt) {
-          stmin = mt_min(stx, sty);
-          stmax = mt_max(stx, sty);
-        } else {
-          stmin = stx;
-          stmax = stp + xtrapf * (stp - stx);
-        }
-        stp = mt_clamp(stp, stpmin, stpmax);
-        if ((brackt && ((stp <= stmin) || (stp >= stmax))) || (nfev >= maxfev - 1) ||
-            (infoc == 0) || (brackt && ((stmax - stmin) <= (xtol * stmax))))
-          stp = stx;
-        double tmp[CHUNKS][2];
-#pragma unroll
-        for (int c = 0; c < CHUNKS; c++) {
-          tmp[c][0] = x[c][0] + stp * dir[c][0];
-          tmp[c][1] = x[c][1] + stp * dir[c][1];
-        }
-        const double fcur = model.f(tmp, fcalls);
-        model.grad(tmp, g, fcalls, gcalls);
-        nfev++;
-        const double dg = bfgs_dot<CHUNKS>(g, dir, n, p.seq, model.lds);
-        const double ftest1 = finit + stp * dgtest;
-        if ((brackt & ((stp <= stmin) | (stp >= stmax))) | (infoc == 0)) info = 6;
-        if ((stp == stpmax) & (fcur <= ftest1) & (dg <= dgtest)) info = 5;
-        if ((stp == stpmin) & ((fcur > ftest1) | (dg >= dgtest))) info = 4;
-        if (nfev >= maxfev) info = 3;
-        if (brackt & (stmax - stmin <= xtol * stmax)) info = 2;
-        if ((fcur <= ftest1) & (fabs(dg) <= gtol * (-dginit))) info = 1;
-        if (info != 0) break;
-        if (stage1 & (fcur <= ftest1) & (dg >= mt_min(ftol, gtol) * dginit)) stage1 = 0;
-        // ONE call site, on copies chosen by value: with two calls on different references the compiler
-        // merges them into one call on a selected address, and the bracket then lives in scratch memory
-        const bool modified = stage1 & (fcur <= fx) & (fcur > ftest1);  // the modified function of stage 1
-        double fxm = fx, fym = fy, dgxm = dgx, dgym = dgy, fm = fcur, dgm = dg;
-        if (modified) {
-          fm = fcur - stp * dgtest;
-          fxm = fx - stx * dgtest;
-          fym = fy - sty * dgtest;
-          dgm = dg - dgtest;
-          dgxm = dgx - dgtest;
-          dgym = dgy - dgtest;
-        }
-        mt_cstep(stx, fxm, dgxm, sty, fym, dgym, stp, fm, dgm, brackt, stmin, stmax, infoc);
-        fx = fxm;
-        fy = fym;
-        dgx = dgxm;
-        dgy = dgym;
-        if (modified) {
-          fx = fxm + stx * dgtest;
-          fy = fym + sty * dgtest;
-          dgx = dgxm + dgtest;
-          dgy = dgym + dgtest;
-        }
-        if (brackt) {
-          if (fabs(sty - stx) >= 0.66 * width1) stp = stx + 0.5 * (sty - stx);
-          width1 = width;
-          width = fabs(sty - stx);
-        }
-      }
-    }
-  }
-  // s = rate d; x += s; g = grad(x); norms; y; rho  (3266-3278)
-  double s[CHUNKS][2], y[CHUNKS][2];
-#pragma unroll
-  for (int c = 0; c < CHUNKS; c++) {
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      s[c][h] = dir[c][h] * stp;
-      x[c][h] = x[c][h] + s[c][h];
-    }
-  }
-  model.grad(x, g, fcalls, gcalls);
-  prev_norm = cur_norm;
-  cur_norm = sqrt(bfgs_dot<CHUNKS>(g, g, n, p.seq, model.lds));
-#pragma unroll
-  for (int c = 0; c < CHUNKS; c++) {
-    y[c][0] = g[c][0] - pg[c][0];
-    y[c][1] = g[c][1] - pg[c][1];
-  }
-  double rho = bfgs_dot<CHUNKS>(y, s, n, p.seq, model.lds);
-  rho = 1 / rho;
+  // (the turn's statements in place, not through bfgs_search_turn: see there)
+#define NLSG_BFGS_TURN_STOPPED(fv) \
+  if (lane == 0) {                 \
+    pr->fval = fv;                 \
+    pr->fcalls = fcalls;           \
+    pr->done = 1;                  \
+  }                                \
+  return;
+#define NLSG_BFGS_TURN_ADVANCED
+#include "nlsg_bfgs_turn.h"
+#undef NLSG_BFGS_TURN_STOPPED
+#undef NLSG_BFGS_TURN_ADVANCED
   store_row<CHUNKS, VEC>(p.x + pid * n, n, x);
   store_row<CHUNKS, VEC>(p.g + pid * n, n, g);
   store_row<CHUNKS, VEC>(p.s + pid * n, n, s);
@@ -1149,6 +1049,242 @@ __global__ __launch_bounds__(256) void bfgs_update_seq_kernel(BfgsParams p, uint
     load(B, c0 + 3 * TC);
   }
   if (row0 + lane < n) p.dir[pid * n + row0 + lane] = -acc;  // :3249-3250 with the updated row
+}
+
+// ---- the resident whole-solve kernel (NLSG_BFGS_RESIDENT), 1 <= n <= 64 ---------------------------
+// One 64-lane workgroup — a single wave, so no block barrier anywhere — owns a problem for a whole launch:
+// it loads BfgsProblem, x, g, dir and H once, runs up to `iters` turns of BFGS::solve's loop (3238-3284)
+// with H in LDS, and writes the state back in the lock-step engine's layout. A turn is bfgs_search_turn —
+// the lock-step engine's own code — followed by the two H passes on the LDS matrix:
+//   tree order       the additions of bfgs_hy_kernel / bfgs_update_kernel: a row in the lane layout of
+//                    load_row (element e in lane e / 2, one aligned 16-byte read per lane: EVEN row stride),
+//                    its dot wave_dot<1>. The n row dots of a pass are independent, so four rows go through
+//                    the cross-lane steps together (wave_sum4: every addition the pair wave_sum adds).
+//   reference order  the additions of bfgs_hy_seq_kernel / bfgs_denom_seq_kernel / bfgs_update_seq_kernel:
+//                    a lane per row, the other factor read at a wave-uniform address. The 32 lanes of a
+//                    ds_read_b64 group read addresses one row stride apart: an ODD stride puts them on 32
+//                    different bank pairs.
+// The dynamic LDS block, in doubles (bfgs_resident_layout; the host passes h_at and vec_at):
+//   reference order  [0, 256) the wave's xs | ts buffers of BfgsModel; [256, 640) six vectors of 64;
+//                    [1024, ..) the parameter row, where the lock-step kernels of the same module have their
+//                    first wave's (NLSG_PARAMS_PER_WAVE is one number per module); then H, n rows of n | 1
+//   tree order       the parameter row; H, n rows of n rounded up to even; six vectors of 64
+constexpr int kBfgsResidentMaxDim = 64;
+constexpr uint32_t kBfgsResidentCut = 256;  // turns per launch: bounds a launch, tunes nothing
+struct BfgsResidentLayout {
+  uint32_t rows_at, h_at, vec_at, total;  // doubles
+};
+__host__ __device__ constexpr uint32_t bfgs_resident_stride(uint64_t n, int seq) {
+  return static_cast<uint32_t>(seq ? (n | 1) : ((n + 1) & ~1ull));
+}
+__host__ __device__ constexpr BfgsResidentLayout bfgs_resident_layout(uint64_t n, int seq, uint64_t row_doubles) {
+  BfgsResidentLayout l{};
+  const uint32_t hsz = static_cast<uint32_t>(n) * bfgs_resident_stride(n, seq), vsz = 6 * 64;
+  if (seq) {
+    l.rows_at = static_cast<uint32_t>(bfgs_fd_seq_lds_bytes(1) / sizeof(double));
+    l.vec_at = 2 * 128;
+    l.h_at = l.rows_at + static_cast<uint32_t>(row_doubles);
+    l.total = l.h_at + hsz;
+  } else {
+    l.rows_at = 0;
+    l.h_at = static_cast<uint32_t>(row_doubles);
+    l.vec_at = l.h_at + hsz;
+    l.total = l.vec_at + vsz;
+  }
+  return l;
+}
+
+// a vector of <= 64 entries: LDS (index order) -> the lane layout, zeros in the lanes past it
+__device__ inline void bfgs_res_gather(const double *v, double (&out)[1][2]) {
+  const int lane = lane_id();
+  double2 t = make_double2(0.0, 0.0);
+  if (lane < 32) t = *reinterpret_cast<const double2 *>(v + 2 * lane);
+  out[0][0] = t.x;
+  out[0][1] = t.y;
+}
+__device__ inline void bfgs_res_scatter(double *v, const double (&in)[1][2]) {
+  const int lane = lane_id();
+  if (lane < 32) *reinterpret_cast<double2 *>(v + 2 * lane) = make_double2(in[0][0], in[0][1]);
+}
+__device__ inline void bfgs_res_publish() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <int CHUNKS, bool VEC, int MODEL>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 4))) void
+bfgs_resident_kernel(BfgsParams p, uint32_t iters, uint32_t h_at, uint32_t vec_at) {
+  static_assert(CHUNKS == 1, "the resident kernel holds a problem of at most 64 coordinates");
+  extern __shared__ __align__(16) double bfgs_smem[];
+  const uint64_t pid = blockIdx.x;
+  BfgsProblem *pr = p.prob + pid;
+  if (pr->done) return;
+  const int lane = lane_id();
+  const uint64_t n = p.n;
+  const int N = static_cast<int>(n), seq = p.seq;
+  const int S = static_cast<int>(bfgs_resident_stride(n, seq));
+  double *Hs = bfgs_smem + h_at, *vs = bfgs_smem + vec_at;
+  double *ys = vs, *gs = vs + 64, *ss = vs + 128, *ts = vs + 192, *ds = vs + 256;
+  double x[1][2], g[1][2], dir[1][2], s[1][2], y[1][2];
+  BfgsModel<MODEL, 1> model;
+  model.template load<VEC>(p);
+  stage_custom_params_wave(p.params, pid);
+  load_vec<1, VEC>(p.x + pid * n, n, p.zero, x);
+  load_vec<1, VEC>(p.g + pid * n, n, p.zero, g);
+  load_vec<1, VEC>(p.dir + pid * n, n, p.zero, dir);
+  uint64_t iter = pr->iter, fcalls = pr->fcalls, gcalls = pr->gcalls;
+  double prev_norm = pr->prev_norm, cur_norm = pr->cur_norm, rho = pr->rho, fval = pr->fval;
+  int identity = pr->identity, done = 0;
+#pragma unroll
+  for (int k = 0; k < 6; k++) vs[64 * k + lane] = 0.0;
+  double *Hg = p.H + pid * n * p.ldh;
+  const int ld = static_cast<int>(p.ldh);
+  // H in memory exists from the first update on (iter > 0); before that it is the identity, synthesised
+  if (iter > 0)
+    for (int idx = lane; idx < N * N; idx += 64) {
+      const int r = idx / N, c = idx - r * N;
+      Hs[r * S + c] = Hg[r * ld + c];
+    }
+  if (S > N && lane < N) Hs[lane * S + N] = 0.0;  // (the pair of the last coordinate of an odd row: zeros past n)
+  bfgs_res_publish();
+  bool h_written = false;
+  const int jc = lane < N ? lane : N - 1;  // reference order: this lane's row
+  for (uint32_t turn = 0; turn < iters; turn++) {
+    bfgs_search_turn<1, MODEL>(
+        p, model, x, g, dir, iter, fcalls, gcalls, prev_norm, cur_norm,
+        [&](double fv) {
+          fval = fv;
+          done = 1;
+        },
+        [&](const double (&s_)[1][2], const double (&y_)[1][2], double rho_, int identity_) {
+          s[0][0] = s_[0][0];
+          s[0][1] = s_[0][1];
+          y[0][0] = y_[0][0];
+          y[0][1] = y_[0][1];
+          rho = rho_;
+          identity = identity_;
+          iter = iter + 1;
+        });
+    if (done) break;
+    h_written = true;
+    double t[1][2];
+    if (seq) {
+      bfgs_res_scatter(ys, y);
+      bfgs_res_scatter(gs, g);
+      bfgs_res_scatter(ss, s);
+      bfgs_res_publish();
+      // t = H y (3139-3142): row `lane`, index order
+      double tj = ys[jc];  // H = I: t = y exactly
+      if (!identity) {
+        double acc = 0.0;
+#pragma unroll 4
+        for (int i = 0; i < N; i++) acc = acc + ys[i] * Hs[jc * S + i];
+        tj = acc;
+      }
+      if (lane < N) ts[lane] = tj;
+      bfgs_res_publish();
+      bfgs_res_gather(ts, t);
+      // denom = rho y^T t + 1 (3143-3145), the sum in index order
+      double prod[1][2];
+      prod[0][0] = y[0][0] * t[0][0];
+      prod[0][1] = y[0][1] * t[0][1];
+      const double dsum = wave_sum_seq_buf<1>(prod, n, model.lds);
+      const double denom = (dsum * rho) + 1.0;
+      // rank-2 update (3151-3164) fused with d = -H' g (3248-3251)
+      const double sj = ss[jc];
+      double acc = 0.0;
+#pragma unroll 4
+      for (int i = 0; i < N; i++) {
+        const double si = ss[i], ti = ts[i];
+        const double hij = identity ? (i == lane ? 1.0 : 0.0) : Hs[jc * S + i];
+        const double w = hij - rho * (si * tj + ti * sj + denom * si * sj);
+        if (lane < N) Hs[lane * S + i] = w;
+        acc = acc + w * gs[i];
+      }
+      if (lane < N) ds[lane] = -acc;
+      bfgs_res_publish();
+      bfgs_res_gather(ds, dir);
+    } else {
+      const bool in_row = 2 * lane < N;
+      bfgs_res_scatter(ss, s);
+      // t = H y: four rows' dots through the butterfly together; row j0 + q ends in lanes 16 q .. 16 q + 15
+      if (identity) {
+        t[0][0] = y[0][0];
+        t[0][1] = y[0][1];
+        bfgs_res_scatter(ts, t);
+        bfgs_res_publish();
+      } else {
+        for (int j0 = 0; j0 < N; j0 += 4) {
+          double a[4];
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            const int j = j0 + q < N ? j0 + q : N - 1;
+            double2 h = make_double2(0.0, 0.0);
+            if (in_row) h = *reinterpret_cast<const double2 *>(Hs + j * S + 2 * lane);
+            double acc = 0.0;  // wave_dot<1>(y, h)
+            acc = acc + y[0][0] * h.x;
+            acc = acc + y[0][1] * h.y;
+            a[q] = acc;
+          }
+          const double v = wave_sum4(a[0], a[1], a[2], a[3]);
+          const int j = j0 + (lane >> 4);
+          if ((lane & 15) == 0 && j < N) ts[j] = v;
+        }
+        bfgs_res_publish();
+        bfgs_res_gather(ts, t);
+      }
+      double denom = wave_dot<1>(y, t);  // :3143-3145
+      denom = (denom * rho) + 1.0;
+      for (int j0 = 0; j0 < N; j0 += 4) {
+        double a[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          const bool live = j0 + q < N;  // wave-uniform
+          const int j = live ? j0 + q : N - 1;
+          const double sj = ss[j], tj = ts[j];
+          double2 hl = make_double2(0.0, 0.0);
+          if (in_row && !identity) hl = *reinterpret_cast<const double2 *>(Hs + j * S + 2 * lane);
+          double h[2] = {hl.x, hl.y};
+#pragma unroll
+          for (int k = 0; k < 2; k++) {
+            const int i = 2 * lane + k;
+            const double hij = identity ? (i == j ? 1.0 : 0.0) : h[k];
+            const double v = hij - rho * (s[0][k] * tj + t[0][k] * sj + denom * s[0][k] * sj);  // :3156-3163
+            h[k] = (i < N) ? v : 0.0;
+          }
+          if (live && 2 * lane < S) *reinterpret_cast<double2 *>(Hs + j * S + 2 * lane) = make_double2(h[0], h[1]);
+          double acc = 0.0;  // wave_dot<1>(h, g), :3249-3250 with the updated row
+          acc = acc + h[0] * g[0][0];
+          acc = acc + h[1] * g[0][1];
+          a[q] = acc;
+        }
+        const double v = wave_sum4(a[0], a[1], a[2], a[3]);
+        const int j = j0 + (lane >> 4);
+        if ((lane & 15) == 0 && j < N) ds[j] = -v;
+      }
+      bfgs_res_publish();
+      bfgs_res_gather(ds, dir);
+    }
+  }
+  store_row<1, VEC>(p.x + pid * n, n, x);
+  store_row<1, VEC>(p.g + pid * n, n, g);
+  store_row<1, VEC>(p.dir + pid * n, n, dir);
+  if (h_written)
+    for (int idx = lane; idx < N * N; idx += 64) {
+      const int r = idx / N, c = idx - r * N;
+      Hg[r * ld + c] = Hs[r * S + c];
+    }
+  if (lane == 0) {
+    pr->prev_norm = prev_norm;
+    pr->cur_norm = cur_norm;
+    pr->rho = rho;
+    pr->fval = fval;
+    pr->iter = iter;
+    pr->fcalls = fcalls;
+    pr->gcalls = gcalls;
+    pr->identity = identity;
+    if (done) pr->done = 1;
+  }
 }
 
 // ---- symmetric restatement of the rank-2 update (NLSG_BFGS_SYMMETRIC) ----------------------------

@@ -25,6 +25,7 @@ void rtc_release(DeRtcKernels *k);
 struct BfgsRtcKernels {  // finite-difference model around the user's objective, or the one on its gradient body
   hipModule_t mod = nullptr;
   hipFunction_t init = nullptr, search = nullptr;
+  hipFunction_t resident = nullptr;  // bfgs_resident_kernel, for an engine made with NLSG_BFGS_RESIDENT only
 };
 // wave_rows_offset: where the per-wave parameter rows (obj->n_params > 0) start in the kernels' dynamic
 // LDS block, in doubles — the caller's own launch layout (behind bfgs_fd_seq_lds_bytes(chunks) in
@@ -32,7 +33,7 @@ struct BfgsRtcKernels {  // finite-difference model around the user's objective,
 // grad_body != nullptr (nlsg_bfgs_create_gradient): the kernels are instantiated on kBfgsCustomGrad, whose
 // gradient is that body (Objective<NLSG_OBJ_CUSTOM>::grad) instead of finite differences
 int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long wave_rows_offset,
-                   BfgsRtcKernels *out, const char *grad_body = nullptr);
+                   BfgsRtcKernels *out, const char *grad_body = nullptr, bool resident = false);
 void rtc_release(BfgsRtcKernels *k);
 struct NmRtcKernels {
   hipModule_t mod = nullptr;

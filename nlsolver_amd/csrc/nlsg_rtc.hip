@@ -400,7 +400,7 @@ int rtc_build_pso(const nlsg_custom_objective *obj, int chunks, bool vec, int ty
 }
 
 int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long wave_rows_offset,
-                   BfgsRtcKernels *out, const char *grad_body) {
+                   BfgsRtcKernels *out, const char *grad_body, bool resident) {
   // <CHUNKS, VEC, MODEL>: MODEL = the objective id selects the finite-difference BfgsModel, kBfgsCustomGrad
   // (-2, nlsg_bfgs_kernels.h) the one that evaluates the objective's own gradient body
   const std::string t = std::to_string(chunks) + ", " + (vec ? "true" : "false") + ", " +
@@ -408,10 +408,14 @@ int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long 
                                    : std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)));
   std::vector<hipFunction_t> f;
   BfgsRtcKernels k;
-  const int rc = rtc_compile(obj, "nlsg_bfgs_kernels.h",
-                             {"nlsg::bfgs_init_kernel<" + t + ">", "nlsg::bfgs_search_kernel<" + t + ">"},
+  // (the resident kernel is instantiated for an engine that asks for it only: a lock-step engine compiles
+  // what it always did)
+  std::vector<std::string> names = {"nlsg::bfgs_init_kernel<" + t + ">", "nlsg::bfgs_search_kernel<" + t + ">"};
+  if (resident) names.push_back("nlsg::bfgs_resident_kernel<" + t + ">");
+  const int rc = rtc_compile(obj, "nlsg_bfgs_kernels.h", names,
                              &k.mod, &f, wave_rows_offset, grad_body);  // (a row per wave in the dynamic block)
   if (rc) return rc;
+  if (resident) k.resident = f[2];
   k.init = f[0];
   k.search = f[1];
   *out = k;

@@ -371,6 +371,41 @@ struct is_device_objective : std::false_type {};
 template <typename C>
 struct is_device_objective<C, std::void_t<decltype(C::nlsg_objective)>> : std::true_type {};
 
+// Every entry point of libnlsolver_hip.so that this header calls, named once: X(name, required) is the
+// symbol nlsg_<name>, kept in api::<name>. A required one that is missing is an error; an optional one is
+// null when the library was built without, or predates, what it belongs to.
+#define NLSOLVER_MI_ENTRY_POINTS(X)                                                                       \
+  X(last_error, true) X(abi_version, true)                                                                \
+  X(de_create, true) X(de_create_custom, true) X(rtc_load, true) X(de_destroy, true) X(de_minimize, true) \
+  X(pso_create, true) X(pso_create_custom, true) X(pso_destroy, true) X(pso_minimize, true)               \
+  X(bfgs_create, true) X(bfgs_create_custom, true) X(bfgs_destroy, true) X(bfgs_minimize, true)           \
+  X(lm_create, true) X(lm_create_custom, true) X(lm_destroy, true) X(lm_set_data, true)                   \
+  X(lm_minimize, true)                                                                                    \
+  X(nm_create, true) X(nm_create_custom, true) X(nm_destroy, true) X(nm_minimize, true)                   \
+  X(nmpso_create, true) X(nmpso_create_custom, true) X(nmpso_destroy, true) X(nmpso_minimize, true)       \
+  X(sann_create, true) X(sann_create_custom, true) X(sann_destroy, true) X(sann_minimize, true)           \
+  /* reference-order DE */                                                                                \
+  X(de_ref_create, false) X(de_ref_create_custom, false) X(de_ref_destroy, false)                         \
+  X(de_ref_minimize, false)                                                                               \
+  /* the resident batch DE */                                                                             \
+  X(de_batch_lds_bytes, false) X(de_batch_create, false) X(de_batch_create_custom, false)                 \
+  X(de_batch_destroy, false) X(de_batch_minimize, false)                                                  \
+  /* the resident batch PSO */                                                                            \
+  X(pso_batch_lds_bytes, false) X(pso_batch_create, false) X(pso_batch_create_custom, false)              \
+  X(pso_batch_destroy, false) X(pso_batch_minimize, false)                                                \
+  /* run-time objective parameters (Custom::params): the resident engines, Nelder-Mead and the NM/PSO */  \
+  /* hybrid, BFGS and Levenberg-Marquardt */                                                              \
+  X(custom_params_lds_bytes, false) X(de_batch_set_params, false) X(pso_batch_set_params, false)          \
+  X(nm_create_params, false) X(nm_set_params, false)                                                      \
+  X(nmpso_create_params, false) X(nmpso_set_params, false)                                                \
+  X(bfgs_create_params, false) X(bfgs_set_params, false)                                                  \
+  X(lm_create_params, false) X(lm_set_params, false)                                                      \
+  /* link and curve models, gradient bodies */                                                            \
+  X(lm_create_link, false) X(lm_create_curve, false) X(lm_set_curve_data, false)                          \
+  X(bfgs_create_gradient, false)                                                                          \
+  /* with it, whether the library has the resident BFGS mode (has_bfgs_resident) */                       \
+  X(bfgs_lds_bytes, false)
+
 // Lazily bound entry points of libnlsolver_hip.so. Search order: $NLSG_LIBRARY,
 // then the default loader path.
 class api {
@@ -379,84 +414,18 @@ class api {
     static const api instance;
     return instance;
   }
-  decltype(&nlsg_last_error) last_error;
-  decltype(&nlsg_abi_version) abi_version;
-  decltype(&nlsg_de_create) de_create;
-  decltype(&nlsg_de_create_custom) de_create_custom;
-  decltype(&nlsg_rtc_load) rtc_load;
-  decltype(&nlsg_de_destroy) de_destroy;
-  decltype(&nlsg_de_minimize) de_minimize;
-  decltype(&nlsg_pso_create) pso_create;
-  decltype(&nlsg_pso_create_custom) pso_create_custom;
-  decltype(&nlsg_pso_destroy) pso_destroy;
-  decltype(&nlsg_pso_minimize) pso_minimize;
-  decltype(&nlsg_bfgs_create) bfgs_create;
-  decltype(&nlsg_bfgs_create_custom) bfgs_create_custom;
-  decltype(&nlsg_bfgs_destroy) bfgs_destroy;
-  decltype(&nlsg_bfgs_minimize) bfgs_minimize;
-  decltype(&nlsg_lm_create) lm_create;
-  decltype(&nlsg_lm_create_custom) lm_create_custom;
-  decltype(&nlsg_lm_destroy) lm_destroy;
-  decltype(&nlsg_lm_set_data) lm_set_data;
-  decltype(&nlsg_lm_minimize) lm_minimize;
-  decltype(&nlsg_nm_create) nm_create;
-  decltype(&nlsg_nm_create_custom) nm_create_custom;
-  decltype(&nlsg_nm_destroy) nm_destroy;
-  decltype(&nlsg_nm_minimize) nm_minimize;
-  decltype(&nlsg_nmpso_create) nmpso_create;
-  decltype(&nlsg_nmpso_create_custom) nmpso_create_custom;
-  decltype(&nlsg_nmpso_destroy) nmpso_destroy;
-  decltype(&nlsg_nmpso_minimize) nmpso_minimize;
-  decltype(&nlsg_sann_create) sann_create;
-  decltype(&nlsg_sann_create_custom) sann_create_custom;
-  decltype(&nlsg_sann_destroy) sann_destroy;
-  decltype(&nlsg_sann_minimize) sann_minimize;
-  // optional: null when the library was built without reference-order DE
-  decltype(&nlsg_de_ref_create) de_ref_create = nullptr;
-  decltype(&nlsg_de_ref_create_custom) de_ref_create_custom = nullptr;
-  decltype(&nlsg_de_ref_destroy) de_ref_destroy = nullptr;
-  decltype(&nlsg_de_ref_minimize) de_ref_minimize = nullptr;
+#define NLSOLVER_MI_MEMBER(name, required) decltype(&nlsg_##name) name = nullptr;
+  NLSOLVER_MI_ENTRY_POINTS(NLSOLVER_MI_MEMBER)
+#undef NLSOLVER_MI_MEMBER
   bool has_de_ref() const { return de_ref_create && de_ref_create_custom && de_ref_destroy && de_ref_minimize; }
-  // optional: null when the library was built without the resident batch DE
-  decltype(&nlsg_de_batch_lds_bytes) de_batch_lds_bytes = nullptr;
-  decltype(&nlsg_de_batch_create) de_batch_create = nullptr;
-  decltype(&nlsg_de_batch_create_custom) de_batch_create_custom = nullptr;
-  decltype(&nlsg_de_batch_destroy) de_batch_destroy = nullptr;
-  decltype(&nlsg_de_batch_minimize) de_batch_minimize = nullptr;
   bool has_de_batch() const {
     return de_batch_lds_bytes && de_batch_create && de_batch_create_custom && de_batch_destroy && de_batch_minimize;
   }
-  // optional: null when the library was built without the resident batch PSO
-  decltype(&nlsg_pso_batch_lds_bytes) pso_batch_lds_bytes = nullptr;
-  decltype(&nlsg_pso_batch_create) pso_batch_create = nullptr;
-  decltype(&nlsg_pso_batch_create_custom) pso_batch_create_custom = nullptr;
-  decltype(&nlsg_pso_batch_destroy) pso_batch_destroy = nullptr;
-  decltype(&nlsg_pso_batch_minimize) pso_batch_minimize = nullptr;
   bool has_pso_batch() const {
     return pso_batch_lds_bytes && pso_batch_create && pso_batch_create_custom && pso_batch_destroy &&
            pso_batch_minimize;
   }
-  // optional: null when the library predates run-time objective parameters (Custom::params)
-  decltype(&nlsg_custom_params_lds_bytes) custom_params_lds_bytes = nullptr;
-  decltype(&nlsg_de_batch_set_params) de_batch_set_params = nullptr;
-  decltype(&nlsg_pso_batch_set_params) pso_batch_set_params = nullptr;
-  // optional: null when the library predates parameters for Nelder-Mead and the NM/PSO hybrid
-  decltype(&nlsg_nm_create_params) nm_create_params = nullptr;
-  decltype(&nlsg_nm_set_params) nm_set_params = nullptr;
-  decltype(&nlsg_nmpso_create_params) nmpso_create_params = nullptr;
-  decltype(&nlsg_nmpso_set_params) nmpso_set_params = nullptr;
-  // optional: null when the library predates parameters for BFGS and Levenberg-Marquardt
-  decltype(&nlsg_bfgs_create_params) bfgs_create_params = nullptr;
-  decltype(&nlsg_bfgs_set_params) bfgs_set_params = nullptr;
-  decltype(&nlsg_lm_create_params) lm_create_params = nullptr;
-  decltype(&nlsg_lm_set_params) lm_set_params = nullptr;
-  decltype(&nlsg_lm_create_link) lm_create_link = nullptr;
-  decltype(&nlsg_lm_create_curve) lm_create_curve = nullptr;
-  decltype(&nlsg_lm_set_curve_data) lm_set_curve_data = nullptr;
-  decltype(&nlsg_bfgs_create_gradient) bfgs_create_gradient = nullptr;
-  // optional; with it, whether the library has the resident BFGS mode: one older than NLSG_BFGS_RESIDENT
-  // answers 0 to the flag it does not know
-  decltype(&nlsg_bfgs_lds_bytes) bfgs_lds_bytes = nullptr;
+  // a library older than NLSG_BFGS_RESIDENT answers 0 to the flag it does not know
   bool has_bfgs_resident() const { return bfgs_lds_bytes && bfgs_lds_bytes(2, NLSG_BFGS_RESIDENT) != 0; }
   // the resident engine's LDS need with the parameter row; throws when the library cannot take
   // parameters or the shape does not fit (`shape_need` = nlsg_*_batch_lds_bytes, 0 = out of range)
@@ -478,87 +447,125 @@ class api {
 
  private:
   api() {
-    const char *env = std::getenv("NLSG_LIBRARY");
-    const char *name = (env && *env) ? env : "libnlsolver_hip.so";
-    void *h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-    if (!h)
-      throw device_error(std::string("cannot load ") + name + " (" + dlerror() +
-                         "); device objectives have no CPU fallback");
-    bind(h, "nlsg_last_error", last_error);
-    bind(h, "nlsg_abi_version", abi_version);
-    bind(h, "nlsg_de_create", de_create);
-    bind(h, "nlsg_de_create_custom", de_create_custom);
-    bind(h, "nlsg_rtc_load", rtc_load);
-    bind(h, "nlsg_de_destroy", de_destroy);
-    bind(h, "nlsg_de_minimize", de_minimize);
-    bind(h, "nlsg_pso_create", pso_create);
-    bind(h, "nlsg_pso_create_custom", pso_create_custom);
-    bind(h, "nlsg_pso_destroy", pso_destroy);
-    bind(h, "nlsg_pso_minimize", pso_minimize);
-    bind(h, "nlsg_bfgs_create", bfgs_create);
-    bind(h, "nlsg_bfgs_create_custom", bfgs_create_custom);
-    bind(h, "nlsg_bfgs_destroy", bfgs_destroy);
-    bind(h, "nlsg_bfgs_minimize", bfgs_minimize);
-    bind(h, "nlsg_lm_create", lm_create);
-    bind(h, "nlsg_lm_create_custom", lm_create_custom);
-    bind(h, "nlsg_lm_destroy", lm_destroy);
-    bind(h, "nlsg_lm_set_data", lm_set_data);
-    bind(h, "nlsg_lm_minimize", lm_minimize);
-    bind(h, "nlsg_nm_create", nm_create);
-    bind(h, "nlsg_nm_create_custom", nm_create_custom);
-    bind(h, "nlsg_nm_destroy", nm_destroy);
-    bind(h, "nlsg_nm_minimize", nm_minimize);
-    bind(h, "nlsg_nmpso_create", nmpso_create);
-    bind(h, "nlsg_nmpso_create_custom", nmpso_create_custom);
-    bind(h, "nlsg_nmpso_destroy", nmpso_destroy);
-    bind(h, "nlsg_nmpso_minimize", nmpso_minimize);
-    bind(h, "nlsg_sann_create", sann_create);
-    bind(h, "nlsg_sann_create_custom", sann_create_custom);
-    bind(h, "nlsg_sann_destroy", sann_destroy);
-    bind(h, "nlsg_sann_minimize", sann_minimize);
-    bind_optional(h, "nlsg_de_ref_create", de_ref_create);
-    bind_optional(h, "nlsg_de_ref_create_custom", de_ref_create_custom);
-    bind_optional(h, "nlsg_de_ref_destroy", de_ref_destroy);
-    bind_optional(h, "nlsg_de_ref_minimize", de_ref_minimize);
-    bind_optional(h, "nlsg_de_batch_lds_bytes", de_batch_lds_bytes);
-    bind_optional(h, "nlsg_de_batch_create", de_batch_create);
-    bind_optional(h, "nlsg_de_batch_create_custom", de_batch_create_custom);
-    bind_optional(h, "nlsg_de_batch_destroy", de_batch_destroy);
-    bind_optional(h, "nlsg_de_batch_minimize", de_batch_minimize);
-    bind_optional(h, "nlsg_pso_batch_lds_bytes", pso_batch_lds_bytes);
-    bind_optional(h, "nlsg_pso_batch_create", pso_batch_create);
-    bind_optional(h, "nlsg_pso_batch_create_custom", pso_batch_create_custom);
-    bind_optional(h, "nlsg_pso_batch_destroy", pso_batch_destroy);
-    bind_optional(h, "nlsg_pso_batch_minimize", pso_batch_minimize);
-    bind_optional(h, "nlsg_custom_params_lds_bytes", custom_params_lds_bytes);
-    bind_optional(h, "nlsg_de_batch_set_params", de_batch_set_params);
-    bind_optional(h, "nlsg_pso_batch_set_params", pso_batch_set_params);
-    bind_optional(h, "nlsg_nm_create_params", nm_create_params);
-    bind_optional(h, "nlsg_nm_set_params", nm_set_params);
-    bind_optional(h, "nlsg_nmpso_create_params", nmpso_create_params);
-    bind_optional(h, "nlsg_nmpso_set_params", nmpso_set_params);
-    bind_optional(h, "nlsg_bfgs_create_params", bfgs_create_params);
-    bind_optional(h, "nlsg_bfgs_set_params", bfgs_set_params);
-    bind_optional(h, "nlsg_lm_create_params", lm_create_params);
-    bind_optional(h, "nlsg_lm_set_params", lm_set_params);
-    bind_optional(h, "nlsg_lm_create_link", lm_create_link);
-    bind_optional(h, "nlsg_lm_create_curve", lm_create_curve);
-    bind_optional(h, "nlsg_lm_set_curve_data", lm_set_curve_data);
-    bind_optional(h, "nlsg_bfgs_create_gradient", bfgs_create_gradient);
-    bind_optional(h, "nlsg_bfgs_lds_bytes", bfgs_lds_bytes);
+    std::string why;
+    void *h = tinyqr::device::detail::open_library(why);
+    if (!h) throw device_error(why + "; device objectives have no CPU fallback");
+#define NLSOLVER_MI_BIND(name, required)                            \
+  name = reinterpret_cast<decltype(name)>(dlsym(h, "nlsg_" #name)); \
+  if (required && !name) throw device_error("missing symbol nlsg_" #name);
+    NLSOLVER_MI_ENTRY_POINTS(NLSOLVER_MI_BIND)
+#undef NLSOLVER_MI_BIND
     if (abi_version() != NLSG_ABI_VERSION)
       throw device_error("libnlsolver_hip.so ABI version mismatch");
   }
-  template <typename F>
-  static void bind(void *h, const char *sym, F &fn) {
-    fn = reinterpret_cast<F>(dlsym(h, sym));
-    if (!fn) throw device_error(std::string("missing symbol ") + sym);
-  }
-  template <typename F>
-  static void bind_optional(void *h, const char *sym, F &fn) {
-    fn = reinterpret_cast<F>(dlsym(h, sym));
-  }
 };
+#undef NLSOLVER_MI_ENTRY_POINTS
+
+// ---------------------------------------------------------------------------
+// What every device path is made of. A path reads: a config from make_config with its fields set in
+// order; an engine<E>; create(); eng.check(api.*_minimize(...)); to_status().
+// ---------------------------------------------------------------------------
+// Owns an engine handle: destroyed on every way out of the solve, an exception from an allocation
+// between create and minimize included.
+template <typename E>
+class engine {
+ public:
+  explicit engine(int (*destroy)(E *)) : destroy_(destroy) {}
+  engine(engine &&other) noexcept : ptr_(std::exchange(other.ptr_, nullptr)), destroy_(other.destroy_) {}
+  engine(const engine &) = delete;
+  engine &operator=(const engine &) = delete;
+  ~engine() {
+    if (ptr_) destroy_(ptr_);
+  }
+  E **out() { return &ptr_; }  // where *_create puts the handle
+  operator E *() const { return ptr_; }
+  // a nonzero return code is device_error("nlsg error N: " + last_error()); the message is read here, where
+  // the exception is made, which is before the unwinding destroys the engine (a destroy may overwrite it)
+  void check(int rc) const { api::get().check(rc); }
+
+ private:
+  E *ptr_ = nullptr;
+  int (*destroy_)(E *);
+};
+
+// a zeroed config of type Cfg with struct_size set and the device of $NLSG_DEVICE (default 0)
+template <typename Cfg>
+inline Cfg make_config() {
+  Cfg cfg{};
+  cfg.struct_size = sizeof(cfg);
+  if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+  return cfg;
+}
+
+// the run-time compiler, before anything is made from source text: $NLSG_HIPRTC names the hiprtc of the
+// HIP runtime in use (default: libhiprtc.so)
+inline void load_rtc() {
+  const api &lib = api::get();
+  lib.check(lib.rtc_load(std::getenv("NLSG_HIPRTC")));
+}
+// the nlsg_custom_objective view of a Custom (valid while f is)
+template <typename C>
+inline nlsg_custom_objective custom_objective(const C &f) {
+  return nlsg_custom_objective{f.term_body.c_str(), f.finish_body.c_str(), f.chain, custom_n_params(f)};
+}
+
+// f.params, replicated into `rows` rows (the functor's one row, shown to every start), sent to the engine
+template <typename E, typename C>
+inline void send_params(const engine<E> &eng, const C &f, size_t rows, int (*set_params)(E *, const double *)) {
+  std::vector<double> flat;
+  for (size_t r = 0; r < rows; r++) flat.insert(flat.end(), f.params.begin(), f.params.end());
+  eng.check(set_params(eng, flat.data()));
+}
+
+// Makes the engine of one family for the objective f. A built-in objective: `plain`. A Custom: the
+// run-time compiler is loaded, then
+//   * with f.params and a library that has both `create_params` and `set_params`: create_params, then
+//     set_params with f.params in `rows` rows;
+//   * otherwise create_custom — with parameters, that is a family or a library that does not take them,
+//     whose "unsupported" error is the answer.
+// (The resident DE and PSO engines take parameters through their custom creator: they pass it as
+// create_params too, after api::require_params_fit.) `plain` may be nullptr where F is always a Custom.
+template <typename E, typename Cfg, typename F, typename Plain>
+inline void create(engine<E> &eng, const Cfg &cfg, const F &f, Plain plain,
+                   int (*create_custom)(const Cfg *, const nlsg_custom_objective *, E **),
+                   int (*create_params)(const Cfg *, const nlsg_custom_objective *, E **) = nullptr,
+                   int (*set_params)(E *, const double *) = nullptr, size_t rows = 1) {
+  if constexpr (F::nlsg_objective == NLSG_OBJ_CUSTOM) {
+    load_rtc();
+    const nlsg_custom_objective obj = custom_objective(f);
+    if (!f.params.empty() && create_params && set_params) {
+      eng.check(create_params(&cfg, &obj, eng.out()));
+      send_params(eng, f, rows, set_params);
+    } else {
+      eng.check(create_custom(&cfg, &obj, eng.out()));
+    }
+  } else {
+    eng.check(plain(&cfg, eng.out()));
+  }
+}
+
+// the solver_status of an engine's answer. `counters`: how many evaluation counters the solver reports
+// (1: function calls; 2: and gradients; 3: and Hessians) — the others stay 0, as in the reference
+inline solver_status<double> to_status(const nlsg_status &st, int counters = 1) {
+  return solver_status<double>(st.f_value, st.iteration, st.function_calls_used,
+                               counters > 1 ? st.gradient_evals_used : 0, counters > 2 ? st.hessian_evals_used : 0);
+}
+// the starts of a batch back to back, [B][n], as the batch engines take them ...
+inline std::vector<double> flatten(const std::vector<std::vector<double>> &xs, size_t n) {
+  std::vector<double> flat(xs.size() * n);
+  for (size_t b = 0; b < xs.size(); b++) std::copy(xs[b].begin(), xs[b].end(), flat.begin() + b * n);
+  return flat;
+}
+// ... and the engine's answer back into them, with one solver_status per start
+inline std::vector<solver_status<double>> scatter(const std::vector<double> &flat, const std::vector<nlsg_status> &st,
+                                                  std::vector<std::vector<double>> &xs, size_t n, int counters = 1) {
+  std::vector<solver_status<double>> out;
+  for (size_t b = 0; b < xs.size(); b++) {
+    std::copy(flat.begin() + b * n, flat.begin() + (b + 1) * n, xs[b].begin());
+    out.push_back(to_status(st[b], counters));
+  }
+  return out;
+}
 
 // 64-bit key for the device's counter-based generator from a reference-style
 // generator (T operator()() in [0,1], held by reference: it advances by exactly
@@ -572,6 +579,17 @@ inline uint64_t seed_from(RNG &generator) {
   const uint64_t hi = half();
   const uint64_t lo = half();
   return (hi << 32) | lo;
+}
+
+// A two-valued mode read from the environment: false for `first` (also when the variable is unset or
+// empty), true for `second`; anything else is an error, not a default.
+inline bool env_mode(const char *variable, const char *first, const char *second) {
+  const char *e = std::getenv(variable);
+  const std::string v = e ? e : "";
+  if (v == second) return true;
+  if (!v.empty() && v != first)
+    throw device_error(std::string(variable) + " must be " + first + " or " + second + ", not '" + v + "'");
+  return false;
 }
 
 // Summation order of the device solves whose results turn on the last bit of a sum: BFGS (dots,
@@ -596,14 +614,7 @@ inline uint64_t seed_from(RNG &generator) {
 // environment variable NLSG_SUMMATION = reference | tree (read at first use).
 enum class sum_order { reference, tree };
 inline sum_order &summation() {
-  static sum_order order = [] {
-    const char *e = std::getenv("NLSG_SUMMATION");
-    const std::string v = e ? e : "";
-    if (v == "tree") return sum_order::tree;
-    if (!v.empty() && v != "reference")
-      throw device_error("NLSG_SUMMATION must be reference or tree, not '" + v + "'");
-    return sum_order::reference;
-  }();
+  static sum_order order = env_mode("NLSG_SUMMATION", "reference", "tree") ? sum_order::tree : sum_order::reference;
   return order;
 }
 inline bool reference_order() { return summation() == sum_order::reference; }
@@ -623,14 +634,7 @@ inline bool reference_order() { return summation() == sum_order::reference; }
 // (read at first use).
 enum class de_generation { keyed, reference };
 inline de_generation &de_generation_mode() {
-  static de_generation mode = [] {
-    const char *e = std::getenv("NLSG_DE_GENERATION");
-    const std::string v = e ? e : "";
-    if (v == "reference") return de_generation::reference;
-    if (!v.empty() && v != "keyed")
-      throw device_error("NLSG_DE_GENERATION must be keyed or reference, not '" + v + "'");
-    return de_generation::keyed;
-  }();
+  static de_generation mode = env_mode("NLSG_DE_GENERATION", "keyed", "reference") ? de_generation::reference : de_generation::keyed;
   return mode;
 }
 
@@ -645,14 +649,7 @@ inline de_generation &de_generation_mode() {
 // or the environment variable NLSG_DE_DRIVER = turns | resident (read at first use).
 enum class de_driver { turns, resident };
 inline de_driver &de_driver_mode() {
-  static de_driver mode = [] {
-    const char *e = std::getenv("NLSG_DE_DRIVER");
-    const std::string v = e ? e : "";
-    if (v == "resident") return de_driver::resident;
-    if (!v.empty() && v != "turns")
-      throw device_error("NLSG_DE_DRIVER must be turns or resident, not '" + v + "'");
-    return de_driver::turns;
-  }();
+  static de_driver mode = env_mode("NLSG_DE_DRIVER", "turns", "resident") ? de_driver::resident : de_driver::turns;
   return mode;
 }
 constexpr uint64_t de_resident_lds_budget = 160 * 1024;  // bytes of LDS one gfx950 workgroup can take
@@ -668,14 +665,7 @@ constexpr uint64_t de_resident_lds_budget = 160 * 1024;  // bytes of LDS one gfx
 // or the environment variable NLSG_PSO_DRIVER = turns | resident (read at first use).
 enum class pso_driver { turns, resident };
 inline pso_driver &pso_driver_mode() {
-  static pso_driver mode = [] {
-    const char *e = std::getenv("NLSG_PSO_DRIVER");
-    const std::string v = e ? e : "";
-    if (v == "resident") return pso_driver::resident;
-    if (!v.empty() && v != "turns")
-      throw device_error("NLSG_PSO_DRIVER must be turns or resident, not '" + v + "'");
-    return pso_driver::turns;
-  }();
+  static pso_driver mode = env_mode("NLSG_PSO_DRIVER", "turns", "resident") ? pso_driver::resident : pso_driver::turns;
   return mode;
 }
 constexpr uint64_t pso_resident_lds_budget = 160 * 1024;
@@ -689,14 +679,7 @@ constexpr uint64_t pso_resident_lds_budget = 160 * 1024;
 // or the environment variable NLSG_BFGS_DRIVER = turns | resident (read at first use).
 enum class bfgs_driver { turns, resident };
 inline bfgs_driver &bfgs_driver_mode() {
-  static bfgs_driver mode = [] {
-    const char *e = std::getenv("NLSG_BFGS_DRIVER");
-    const std::string v = e ? e : "";
-    if (v == "resident") return bfgs_driver::resident;
-    if (!v.empty() && v != "turns")
-      throw device_error("NLSG_BFGS_DRIVER must be turns or resident, not '" + v + "'");
-    return bfgs_driver::turns;
-  }();
+  static bfgs_driver mode = env_mode("NLSG_BFGS_DRIVER", "turns", "resident") ? bfgs_driver::resident : bfgs_driver::turns;
   return mode;
 }
 }  // namespace device
@@ -759,9 +742,7 @@ class DE {
       const uint64_t need = api.de_batch_lds_bytes(pop_size, x.size());
       if (need != 0 && need <= device::de_resident_lds_budget) return solve_resident<minimize>(x);
     }
-    nlsg_de_config cfg{};
-    cfg.struct_size = sizeof(cfg);
-    if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+    auto cfg = device::make_config<nlsg_de_config>();
     cfg.objective = Callable::nlsg_objective;
     cfg.minimize = minimize ? 1 : 0;
     cfg.strategy = RecombinationType == best ? NLSG_DE_BEST : NLSG_DE_RANDOM;
@@ -773,31 +754,18 @@ class DE {
     cfg.max_iter = max_iter;
     cfg.best_val_no_change = best_value_no_change;
     cfg.seed = device::seed_from(generator);
-    nlsg_de *eng = nullptr;
-    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-      // $NLSG_HIPRTC names the hiprtc of the HIP runtime in use (default: libhiprtc.so)
-      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-      api.check(api.de_create_custom(&cfg, &obj, &eng));
-    } else {
-      api.check(api.de_create(&cfg, &eng));
-    }
+    device::engine<nlsg_de> eng(api.de_destroy);
+    device::create(eng, cfg, f, api.de_create, api.de_create_custom);
     nlsg_status st{};
-    const int rc = api.de_minimize(eng, x.data(), 0, &st);
-    const std::string msg = rc ? api.last_error() : "";
-    api.de_destroy(eng);
-    if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
-    return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
+    eng.check(api.de_minimize(eng, x.data(), 0, &st));
+    return device::to_status(st);
   }
 
   // device::de_driver::resident: the same keyed solve through the resident batch engine (one solve)
   template <bool minimize>
   solver_status<scalar_t> solve_resident(std::vector<scalar_t> &x) {
     const device::api &api = device::api::get();
-    nlsg_de_batch_config cfg{};
-    cfg.struct_size = sizeof(cfg);
-    if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+    auto cfg = device::make_config<nlsg_de_batch_config>();
     cfg.objective = Callable::nlsg_objective;
     cfg.minimize = minimize ? 1 : 0;
     cfg.strategy = RecombinationType == best ? NLSG_DE_BEST : NLSG_DE_RANDOM;
@@ -810,28 +778,12 @@ class DE {
     cfg.max_iter = max_iter;
     cfg.best_val_no_change = best_value_no_change;
     const uint64_t seed = device::seed_from(generator);
-    nlsg_de_batch *eng = nullptr;
-    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-      api.check(api.de_batch_create_custom(&cfg, &obj, &eng));
-    } else {
-      api.check(api.de_batch_create(&cfg, &eng));
-    }
+    device::engine<nlsg_de_batch> eng(api.de_batch_destroy);
+    device::create(eng, cfg, f, api.de_batch_create, api.de_batch_create_custom, api.de_batch_create_custom,
+                   api.de_batch_set_params);
     nlsg_status st{};
-    int rc = NLSG_OK;
-    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-      if (!f.params.empty()) {
-        const std::vector<double> row(f.params.begin(), f.params.end());
-        rc = api.de_batch_set_params(eng, row.data());
-      }
-    }
-    if (!rc) rc = api.de_batch_minimize(eng, x.data(), &seed, &st);
-    const std::string msg = rc ? api.last_error() : "";
-    api.de_batch_destroy(eng);
-    if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
-    return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
+    eng.check(api.de_batch_minimize(eng, x.data(), &seed, &st));
+    return device::to_status(st);
   }
 
   // device::de_generation::reference: the reference's own generation on the caller's xorshift
@@ -852,9 +804,7 @@ class DE {
                              "lane-tree order, not the reference's");
       const device::api &api = device::api::get();
       if (!api.has_de_ref()) throw device_error("library has no reference-order DE");
-      nlsg_de_ref_config cfg{};
-      cfg.struct_size = sizeof(cfg);
-      if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+      auto cfg = device::make_config<nlsg_de_ref_config>();
       cfg.objective = Callable::nlsg_objective;
       cfg.minimize = minimize ? 1 : 0;
       cfg.strategy = RecombinationType == best ? NLSG_DE_BEST : NLSG_DE_RANDOM;
@@ -866,23 +816,13 @@ class DE {
       cfg.eps = eps;
       cfg.max_iter = max_iter;
       cfg.best_val_no_change = best_value_no_change;
-      nlsg_de_ref *eng = nullptr;
-      if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-        api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-        api.check(api.de_ref_create_custom(&cfg, &obj, &eng));
-      } else {
-        api.check(api.de_ref_create(&cfg, &eng));
-      }
+      device::engine<nlsg_de_ref> eng(api.de_ref_destroy);
+      device::create(eng, cfg, f, api.de_ref_create, api.de_ref_create_custom);
       std::array<uint64_t, 2> state = generator.raw_state();
       nlsg_status st{};
-      const int rc = api.de_ref_minimize(eng, x.data(), state.data(), &st);
-      const std::string msg = rc ? api.last_error() : "";
-      api.de_ref_destroy(eng);
-      if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
+      eng.check(api.de_ref_minimize(eng, x.data(), state.data(), &st));
       generator.set_state(state[0], state[1]);
-      return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
+      return device::to_status(st);
     }
   }
 
@@ -1038,9 +978,7 @@ class PSO {
         if (need != 0 && need <= device::pso_resident_lds_budget)
           return solve_resident<minimize, constrained>(x, lower, upper);
       }
-      nlsg_pso_config cfg{};
-      cfg.struct_size = sizeof(cfg);
-      if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+      auto cfg = device::make_config<nlsg_pso_config>();
       cfg.objective = Callable::nlsg_objective;
       cfg.minimize = minimize ? 1 : 0;
       cfg.type = Type == Accelerated ? NLSG_PSO_ACCELERATED : NLSG_PSO_VANILLA;
@@ -1054,21 +992,11 @@ class PSO {
       cfg.max_iter = max_iter;
       cfg.best_val_no_change = best_val_no_change;
       cfg.seed = device::seed_from(generator);
-      nlsg_pso *eng = nullptr;
-      if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-        api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-        api.check(api.pso_create_custom(&cfg, &obj, &eng));
-      } else {
-        api.check(api.pso_create(&cfg, &eng));
-      }
+      device::engine<nlsg_pso> eng(api.pso_destroy);
+      device::create(eng, cfg, f, api.pso_create, api.pso_create_custom);
       nlsg_status st{};
-      const int rc = api.pso_minimize(eng, x.data(), lower.data(), upper.data(), 0, &st);
-      const std::string msg = rc ? api.last_error() : "";
-      api.pso_destroy(eng);
-      if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
-      return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
+      eng.check(api.pso_minimize(eng, x.data(), lower.data(), upper.data(), 0, &st));
+      return device::to_status(st);
     } else {
       return solve_host<minimize, constrained>(x, lower, upper);
     }
@@ -1079,9 +1007,7 @@ class PSO {
   solver_status<scalar_t> solve_resident(std::vector<scalar_t> &x, const std::vector<scalar_t> &lower,
                                          const std::vector<scalar_t> &upper) {
     const device::api &api = device::api::get();
-    nlsg_pso_batch_config cfg{};
-    cfg.struct_size = sizeof(cfg);
-    if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+    auto cfg = device::make_config<nlsg_pso_batch_config>();
     cfg.objective = Callable::nlsg_objective;
     cfg.minimize = minimize ? 1 : 0;
     cfg.type = Type == Accelerated ? NLSG_PSO_ACCELERATED : NLSG_PSO_VANILLA;
@@ -1096,28 +1022,12 @@ class PSO {
     cfg.max_iter = max_iter;
     cfg.best_val_no_change = best_val_no_change;
     const uint64_t seed = device::seed_from(generator);
-    nlsg_pso_batch *eng = nullptr;
-    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-      api.check(api.pso_batch_create_custom(&cfg, &obj, &eng));
-    } else {
-      api.check(api.pso_batch_create(&cfg, &eng));
-    }
+    device::engine<nlsg_pso_batch> eng(api.pso_batch_destroy);
+    device::create(eng, cfg, f, api.pso_batch_create, api.pso_batch_create_custom, api.pso_batch_create_custom,
+                   api.pso_batch_set_params);
     nlsg_status st{};
-    int rc = NLSG_OK;
-    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-      if (!f.params.empty()) {
-        const std::vector<double> row(f.params.begin(), f.params.end());
-        rc = api.pso_batch_set_params(eng, row.data());
-      }
-    }
-    if (!rc) rc = api.pso_batch_minimize(eng, x.data(), lower.data(), upper.data(), &seed, &st);
-    const std::string msg = rc ? api.last_error() : "";
-    api.pso_batch_destroy(eng);
-    if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
-    return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
+    eng.check(api.pso_batch_minimize(eng, x.data(), lower.data(), upper.data(), &seed, &st));
+    return device::to_status(st);
   }
 
   // Host path for arbitrary callables: the reference's serial algorithm
@@ -1501,9 +1411,7 @@ class BFGS {
     static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
     const device::api &api = device::api::get();
     const size_t B = xs.size(), n = B ? xs[0].size() : 0;
-    nlsg_bfgs_config cfg{};
-    cfg.struct_size = sizeof(cfg);
-    if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+    auto cfg = device::make_config<nlsg_bfgs_config>();
     if (use_reference_order()) cfg.flags |= NLSG_BFGS_REFERENCE_ORDER;
     // device::bfgs_driver::resident: the same solve in the resident kernel, where it is taken (the header
     // never asks for the symmetric restatement)
@@ -1515,11 +1423,11 @@ class BFGS {
     cfg.max_iter = max_iter;
     cfg.grad_eps = grad_eps;
     cfg.alpha = alpha;
-    nlsg_bfgs *eng = nullptr;
+    device::engine<nlsg_bfgs> eng(api.bfgs_destroy);
     if constexpr (device::has_grad_objective<Callable>::value) {
       cfg.objective = Callable::nlsg_grad_objective;
       cfg.quad_c = f.c;
-      api.check(api.bfgs_create(&cfg, f.d.data(), f.b.data(), &eng));
+      eng.check(api.bfgs_create(&cfg, f.d.data(), f.b.data(), eng.out()));
     } else if constexpr (device_custom_grad()) {  // the objective's own gradient body
       if (f.grad_body.empty())
         throw device_error("BFGS<Custom, scalar_t, device::analytic_grad> needs Custom::grad_body (the default "
@@ -1530,57 +1438,22 @@ class BFGS {
       if (!f.params.empty() && !api.bfgs_set_params)
         throw device_error("library has no run-time objective parameters for BFGS");
       cfg.objective = Callable::nlsg_objective;
-      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain, device::custom_n_params(f)};
+      device::load_rtc();
+      const nlsg_custom_objective obj = device::custom_objective(f);
       const nlsg_bfgs_gradient grad{sizeof(nlsg_bfgs_gradient), 0, f.grad_body.c_str()};
-      api.check(api.bfgs_create_gradient(&cfg, &obj, &grad, &eng));
-      if (!f.params.empty()) {
-        std::vector<double> rows;  // the functor's one row, shown to every start
-        for (size_t b = 0; b < B; b++) rows.insert(rows.end(), f.params.begin(), f.params.end());
-        const int prc = api.bfgs_set_params(eng, rows.data());
-        if (prc) {
-          const std::string pmsg = api.last_error();
-          api.bfgs_destroy(eng);
-          throw device_error("nlsg error " + std::to_string(prc) + ": " + pmsg);
-        }
-      }
+      eng.check(api.bfgs_create_gradient(&cfg, &obj, &grad, eng.out()));
+      if (!f.params.empty()) device::send_params(eng, f, B, api.bfgs_set_params);
     } else {  // fin_diff (nlsolver.h:2849-2855) evaluated on the device
       cfg.objective = Callable::nlsg_objective;
-      if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-        api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-        if (!f.params.empty() && api.bfgs_create_params && api.bfgs_set_params) {
-          api.check(api.bfgs_create_params(&cfg, &obj, &eng));
-          std::vector<double> rows;  // the functor's one row, shown to every start
-          for (size_t b = 0; b < B; b++) rows.insert(rows.end(), f.params.begin(), f.params.end());
-          const int prc = api.bfgs_set_params(eng, rows.data());
-          if (prc) {
-            const std::string pmsg = api.last_error();
-            api.bfgs_destroy(eng);
-            throw device_error("nlsg error " + std::to_string(prc) + ": " + pmsg);
-          }
-        } else {  // (with parameters and a library that predates them: its "unsupported" error)
-          api.check(api.bfgs_create_custom(&cfg, &obj, &eng));
-        }
-      } else {
-        api.check(api.bfgs_create(&cfg, nullptr, nullptr, &eng));
-      }
+      if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM)
+        device::create(eng, cfg, f, nullptr, api.bfgs_create_custom, api.bfgs_create_params, api.bfgs_set_params, B);
+      else
+        eng.check(api.bfgs_create(&cfg, nullptr, nullptr, eng.out()));
     }
-    std::vector<scalar_t> flat(B * n);
-    for (size_t p = 0; p < B; p++) std::copy(xs[p].begin(), xs[p].end(), flat.begin() + p * n);
+    std::vector<scalar_t> flat = device::flatten(xs, n);
     std::vector<nlsg_status> st(B);
-    const int rc = api.bfgs_minimize(eng, flat.data(), st.data());
-    const std::string msg = rc ? api.last_error() : "";
-    api.bfgs_destroy(eng);
-    if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
-    std::vector<solver_status<scalar_t>> out;
-    for (size_t p = 0; p < B; p++) {
-      std::copy(flat.begin() + p * n, flat.begin() + (p + 1) * n, xs[p].begin());
-      out.emplace_back(st[p].f_value, st[p].iteration, st[p].function_calls_used,
-                       st[p].gradient_evals_used);
-    }
-    return out;
+    eng.check(api.bfgs_minimize(eng, flat.data(), st.data()));
+    return device::scatter(flat, st, xs, n, 2);
   }
 
   // Host path for arbitrary callables: BFGS::solve (nlsolver.h:3196-3285) incl. the
@@ -1690,9 +1563,7 @@ class SANN {
     static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
     const device::api &api = device::api::get();
     const size_t B = xs.size(), n = B ? xs[0].size() : 0;
-    nlsg_sann_config cfg{};
-    cfg.struct_size = sizeof(cfg);
-    if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+    auto cfg = device::make_config<nlsg_sann_config>();
     cfg.objective = Callable::nlsg_objective;
     cfg.minimize = minimize ? 1 : 0;
     cfg.batch = B;
@@ -1701,29 +1572,13 @@ class SANN {
     cfg.temperature_iter = temperature_iter;
     cfg.temperature_max = temperature_max;
     cfg.seed = device::seed_from(generator);
-    nlsg_sann *eng = nullptr;
-    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-      api.check(api.sann_create_custom(&cfg, &obj, &eng));
-    } else {
-      api.check(api.sann_create(&cfg, &eng));
-    }
-    std::vector<scalar_t> flat(B * n);
-    for (size_t b = 0; b < B; b++) std::copy(xs[b].begin(), xs[b].end(), flat.begin() + b * n);
+    device::engine<nlsg_sann> eng(api.sann_destroy);
+    device::create(eng, cfg, f, api.sann_create, api.sann_create_custom);
+    std::vector<scalar_t> flat = device::flatten(xs, n);
     std::vector<nlsg_status> st(B);
-    const int rc = api.sann_minimize(eng, flat.data(), st.data());
-    const std::string msg = rc ? api.last_error() : "";
-    api.sann_destroy(eng);
-    if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
-    std::vector<solver_status<scalar_t>> out;
-    for (size_t b = 0; b < B; b++) {
-      std::copy(flat.begin() + b * n, flat.begin() + (b + 1) * n, xs[b].begin());
-      f_evals += st[b].function_calls_used;
-      out.emplace_back(st[b].f_value, st[b].iteration, st[b].function_calls_used);
-    }
-    return out;
+    eng.check(api.sann_minimize(eng, flat.data(), st.data()));
+    for (size_t b = 0; b < B; b++) f_evals += st[b].function_calls_used;
+    return device::scatter(flat, st, xs, n);
   }
 
   // Host path for arbitrary callables: SANN::solve (nlsolver.h:2777-2814). Trial points are
@@ -1836,9 +1691,7 @@ class NelderMeadPSO {
     static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
     const device::api &api = device::api::get();
     const size_t B = xs.size(), n = B ? xs[0].size() : 0;
-    nlsg_nmpso_config cfg{};
-    cfg.struct_size = sizeof(cfg);
-    if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+    auto cfg = device::make_config<nlsg_nmpso_config>();
     cfg.objective = Callable::nlsg_objective;
     cfg.minimize = minimize ? 1 : 0;
     cfg.bounded = bound ? 1 : 0;
@@ -1855,41 +1708,14 @@ class NelderMeadPSO {
     cfg.max_iter = max_iter;
     cfg.no_change_best_iter = no_change_best_iter;
     cfg.seed = device::seed_from(generator);
-    nlsg_nmpso *eng = nullptr;
-    if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-      nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-      if (!f.params.empty() && api.nmpso_create_params && api.nmpso_set_params) {
-        api.check(api.nmpso_create_params(&cfg, &obj, &eng));
-        std::vector<double> rows;  // the functor's one row, shown to every instance
-        for (size_t b = 0; b < B; b++) rows.insert(rows.end(), f.params.begin(), f.params.end());
-        const int prc = api.nmpso_set_params(eng, rows.data());
-        if (prc) {
-          const std::string pmsg = api.last_error();
-          api.nmpso_destroy(eng);
-          throw device_error("nlsg error " + std::to_string(prc) + ": " + pmsg);
-        }
-      } else {  // (with parameters and a library that predates them: its "unsupported" error)
-        api.check(api.nmpso_create_custom(&cfg, &obj, &eng));
-      }
-    } else {
-      api.check(api.nmpso_create(&cfg, &eng));
-    }
-    std::vector<scalar_t> flat(B * n);
-    for (size_t b = 0; b < B; b++) std::copy(xs[b].begin(), xs[b].end(), flat.begin() + b * n);
+    device::engine<nlsg_nmpso> eng(api.nmpso_destroy);
+    device::create(eng, cfg, f, api.nmpso_create, api.nmpso_create_custom, api.nmpso_create_params,
+                   api.nmpso_set_params, B);
+    std::vector<scalar_t> flat = device::flatten(xs, n);
     std::vector<nlsg_status> st(B);
-    const int rc = api.nmpso_minimize(eng, flat.data(), bound ? lower.data() : nullptr,
-                                      bound ? upper.data() : nullptr, st.data());
-    const std::string msg = rc ? api.last_error() : "";
-    api.nmpso_destroy(eng);
-    if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
-    std::vector<solver_status<scalar_t>> out;
-    for (size_t b = 0; b < B; b++) {
-      std::copy(flat.begin() + b * n, flat.begin() + (b + 1) * n, xs[b].begin());
-      out.emplace_back(st[b].f_value, st[b].iteration, st[b].function_calls_used);
-    }
-    return out;
+    eng.check(api.nmpso_minimize(eng, flat.data(), bound ? lower.data() : nullptr, bound ? upper.data() : nullptr,
+                                 st.data()));
+    return device::scatter(flat, st, xs, n);
   }
 
   // Host path for arbitrary callables: NelderMeadPSO::solve (nlsolver.h:3623-3685) with
@@ -2059,9 +1885,7 @@ class NelderMead {
     if constexpr (device::is_device_objective<Callable>::value) {
       static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
       const device::api &api = device::api::get();
-      nlsg_nm_config cfg{};
-      cfg.struct_size = sizeof(cfg);
-      if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+      auto cfg = device::make_config<nlsg_nm_config>();
       cfg.objective = Callable::nlsg_objective;
       cfg.minimize = minimize ? 1 : 0;
       cfg.bounded = bound ? 1 : 0;
@@ -2083,35 +1907,14 @@ class NelderMead {
       cfg.max_iter = max_iter;
       cfg.no_change_best_tol = no_change_best_tol;
       cfg.restarts = restarts;
-      nlsg_nm *eng = nullptr;
-      if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-        api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-        if (!f.params.empty() && api.nm_create_params && api.nm_set_params) {
-          api.check(api.nm_create_params(&cfg, &obj, &eng));
-          const std::vector<double> row(f.params.begin(), f.params.end());
-          const int prc = api.nm_set_params(eng, row.data());
-          if (prc) {
-            const std::string pmsg = api.last_error();
-            api.nm_destroy(eng);
-            throw device_error("nlsg error " + std::to_string(prc) + ": " + pmsg);
-          }
-        } else {  // (with parameters and a library that predates them: its "unsupported" error)
-          api.check(api.nm_create_custom(&cfg, &obj, &eng));
-        }
-      } else {
-        api.check(api.nm_create(&cfg, &eng));
-      }
+      device::engine<nlsg_nm> eng(api.nm_destroy);
+      device::create(eng, cfg, f, api.nm_create, api.nm_create_custom, api.nm_create_params, api.nm_set_params);
       nlsg_status st{};
       double eps_after = eps;
-      const int rc = api.nm_minimize(eng, x.data(), bound ? upper.data() : nullptr,
-                                     bound ? lower.data() : nullptr, &st, &eps_after);
-      const std::string msg = rc ? api.last_error() : "";
-      api.nm_destroy(eng);
-      if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
+      eng.check(api.nm_minimize(eng, x.data(), bound ? upper.data() : nullptr, bound ? lower.data() : nullptr, &st,
+                                &eps_after));
       eps = eps_after;
-      return solver_status<scalar_t>(st.f_value, st.iteration, st.function_calls_used);
+      return device::to_status(st);
     } else {
       auto res = solve_host<minimize, bound>(x, upper, lower);
       for (size_t i = 0; i < restarts; i++) res.add(solve_host<minimize, bound>(x, upper, lower));
@@ -2386,9 +2189,7 @@ class LevenbergMarquardt {
     static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
     const device::api &api = device::api::get();
     const size_t B = thetas.size();
-    nlsg_lm_config cfg{};
-    cfg.struct_size = sizeof(cfg);
-    if (const char *d = std::getenv("NLSG_DEVICE")) cfg.device = std::atoi(d);
+    auto cfg = device::make_config<nlsg_lm_config>();
     cfg.batch = B;
     size_t n = 0;
     if constexpr (device::has_nlls_objective<Callable>::value) {
@@ -2416,68 +2217,35 @@ class LevenbergMarquardt {
     cfg.down = downward_mult;
     cfg.max_iter = max_iter;
     cfg.f_delta = f_delta;
-    nlsg_lm *eng = nullptr;
-    bool made = false;
-    if constexpr (device::is_device_objective<Callable>::value) {
-      if constexpr (Callable::nlsg_objective == NLSG_OBJ_CUSTOM) {
-        api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
-        nlsg_custom_objective obj{f.term_body.c_str(), f.finish_body.c_str(), f.chain,
-                                  device::custom_n_params(f)};
-        if (!f.params.empty() && api.lm_create_params && api.lm_set_params) {
-          api.check(api.lm_create_params(&cfg, &obj, &eng));
-          std::vector<double> rows;  // the functor's one row, shown to every start
-          for (size_t b = 0; b < B; b++) rows.insert(rows.end(), f.params.begin(), f.params.end());
-          const int prc = api.lm_set_params(eng, rows.data());
-          if (prc) {
-            const std::string pmsg = api.last_error();
-            api.lm_destroy(eng);
-            throw device_error("nlsg error " + std::to_string(prc) + ": " + pmsg);
-          }
-        } else {  // (with parameters and a library that predates them: its "unsupported" error)
-          api.check(api.lm_create_custom(&cfg, &obj, &eng));
-        }
-        made = true;
-      }
-    }
-    if constexpr (device::has_nlls_objective<Callable>::value && device::has_link_bodies<Callable>::value) {
+    device::engine<nlsg_lm> eng(api.lm_destroy);
+    if constexpr (!device::has_nlls_objective<Callable>::value) {  // the objective itself, a Custom included
+      device::create(eng, cfg, f, api.lm_create, api.lm_create_custom, api.lm_create_params, api.lm_set_params, B);
+    } else if constexpr (device::has_link_bodies<Callable>::value) {
       if (!api.lm_create_link)
         throw device_error("the loaded library has no nlsg_lm_create_link (user-supplied link functions)");
-      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
+      device::load_rtc();
       const nlsg_lm_link link{f.value_body.c_str(), f.slope_body.c_str()};
-      api.check(api.lm_create_link(&cfg, &link, &eng));
-      made = true;
-    }
-    if constexpr (device::has_nlls_objective<Callable>::value && device::has_curve_body<Callable>::value) {
+      eng.check(api.lm_create_link(&cfg, &link, eng.out()));
+    } else if constexpr (device::has_curve_body<Callable>::value) {
       if (!api.lm_create_curve || !api.lm_set_curve_data)
         throw device_error("the loaded library has no nlsg_lm_create_curve (curve models)");
-      api.check(api.rtc_load(std::getenv("NLSG_HIPRTC")));
+      device::load_rtc();
       const nlsg_lm_curve curve{f.curve_body.c_str(), static_cast<uint32_t>(f.k)};
-      api.check(api.lm_create_curve(&cfg, &curve, &eng));
-      made = true;
+      eng.check(api.lm_create_curve(&cfg, &curve, eng.out()));
+    } else {
+      eng.check(api.lm_create(&cfg, eng.out()));
     }
-    if (!made) api.check(api.lm_create(&cfg, &eng));
-    std::vector<scalar_t> flat(B * n), lam(B);
-    for (size_t p = 0; p < B; p++) std::copy(thetas[p].begin(), thetas[p].end(), flat.begin() + p * n);
+    std::vector<scalar_t> flat = device::flatten(thetas, n), lam(B);
     std::vector<nlsg_status> st(B);
-    int rc = 0;
     if constexpr (device::has_nlls_objective<Callable>::value) {
       if constexpr (device::has_curve_body<Callable>::value)
-        rc = api.lm_set_curve_data(eng, f.t.data(), f.y.data());
+        eng.check(api.lm_set_curve_data(eng, f.t.data(), f.y.data()));
       else
-        rc = api.lm_set_data(eng, f.A.data(), f.y.data());
+        eng.check(api.lm_set_data(eng, f.A.data(), f.y.data()));
     }
-    if (!rc) rc = api.lm_minimize(eng, flat.data(), st.data(), lam.data());
-    const std::string msg = rc ? api.last_error() : "";
-    api.lm_destroy(eng);
-    if (rc) throw device_error("nlsg error " + std::to_string(rc) + ": " + msg);
-    std::vector<solver_status<scalar_t>> out;
-    for (size_t p = 0; p < B; p++) {
-      std::copy(flat.begin() + p * n, flat.begin() + (p + 1) * n, thetas[p].begin());
-      out.emplace_back(st[p].f_value, st[p].iteration, st[p].function_calls_used,
-                       st[p].gradient_evals_used, st[p].hessian_evals_used);
-    }
+    eng.check(api.lm_minimize(eng, flat.data(), st.data(), lam.data()));
     if (B == 1) lambda = lam[0];
-    return out;
+    return device::scatter(flat, st, thetas, n, 3);
   }
 
   // Host path: LevenbergMarquardt::solve (nlsolver.h:3465-3544): damped Newton, the step is

@@ -137,16 +137,22 @@ struct device_error : std::runtime_error {
 };
 
 namespace detail {
+// libnlsolver_hip.so: $NLSG_LIBRARY, else the default loader path. Null on failure, with the reason in
+// `why` (nlsolver.h loads its entry points through this too).
+inline void *open_library(std::string &why) {
+  const char *env = std::getenv("NLSG_LIBRARY");
+  const char *name = (env && *env) ? env : "libnlsolver_hip.so";
+  void *h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
+  if (!h) why = std::string("cannot load ") + name + " (" + dlerror() + ")";
+  return h;
+}
 struct entry_points {
   decltype(&nlsg_tinyqr_lm) lm = nullptr;
   decltype(&nlsg_last_error) last_error = nullptr;
   entry_points() {
-    const char *env = std::getenv("NLSG_LIBRARY");
-    const char *name = (env && *env) ? env : "libnlsolver_hip.so";
-    void *h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-    if (!h)
-      throw device_error(std::string("cannot load ") + name + " (" + dlerror() +
-                         "); tinyqr::device has no CPU fallback");
+    std::string why;
+    void *h = open_library(why);
+    if (!h) throw device_error(why + "; tinyqr::device has no CPU fallback");
     lm = reinterpret_cast<decltype(lm)>(dlsym(h, "nlsg_tinyqr_lm"));
     last_error = reinterpret_cast<decltype(last_error)>(dlsym(h, "nlsg_last_error"));
     if (!lm || !last_error) throw device_error("libnlsolver_hip.so lacks nlsg_tinyqr_lm");

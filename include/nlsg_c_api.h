@@ -651,6 +651,25 @@ int nlsg_lm_time_solve(nlsg_lm *e, const double *theta0_host, uint32_t repeats, 
 int nlsg_lm_time_eval_kernel(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total);
 /* the same for the QR step kernel alone (after one evaluation at theta0) */
 int nlsg_lm_time_qr_kernel(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total);
+/* Parameter covariance of every problem's fit at theta [batch][n] (usually what nlsg_lm_minimize
+ * returned): cov_b = c (J^T J)^-1 with J^T J exactly half of what the engine's evaluation launch leaves
+ * at theta_b, and c = s2_b = f_b / (m - n), the residual variance (NLSG_LM_COV_RESIDUAL,
+ * scipy.optimize.curve_fit's default), or c = 1 (NLSG_LM_COV_ABSOLUTE: the residuals are already divided
+ * by their sigma — weights ride in a column of t or in the rows of A). cov_out_host [batch][n][n]
+ * row-major, bitwise symmetric; s2_out_host [batch] (f / (m - n) in either mode, NaN where m <= n) and
+ * ok_out_host [batch] may be NULL. ok_b = 1 when every Cholesky pivot of J^T J is > 0 and, in residual
+ * mode, f_b is finite; otherwise 0 and all n * n entries of cov_b are NaN (collinear or all-zero
+ * columns, NaN or inf in J or f). Near-singularity is NOT diagnosed: a matrix that factors gets its
+ * inverse, however ill-conditioned. A problem's bits depend neither on the batch around it nor on the
+ * engine's solver, and a later nlsg_lm_minimize returns what it would have without this call.
+ * Gauss-Newton models (tanh, link, curve) with n <= 64 only: n > 64 and default-functor engines (whose
+ * matrix is a finite-difference Hessian of an arbitrary objective) are NLSG_ERR_UNSUPPORTED; an unknown
+ * scale, and residual mode with m <= n, NLSG_ERR_INVALID_ARG; NLSG_ERR_STATE before the data are set.
+ * Fills nlsg_call_timing's init / iterate / read-back like nlsg_lm_minimize.
+ * Optional symbol (NLSG_ABI_VERSION stays 1): look it up before relying on it. */
+typedef enum { NLSG_LM_COV_RESIDUAL = 0, NLSG_LM_COV_ABSOLUTE = 1 } nlsg_lm_cov_scale;
+int nlsg_lm_covariance(nlsg_lm *e, const double *theta_host, int32_t scale, double *cov_out_host,
+                       double *s2_out_host, int32_t *ok_out_host);
 
 /* ========================================================================== */
 /* Batched Nelder-Mead — replaces NelderMead::solve (nlsolver.h:2166-2299), the  */

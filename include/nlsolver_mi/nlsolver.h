@@ -347,6 +347,9 @@ struct CurveModel {
   }
 };
 struct gauss_newton {};  // Grad / Hess tag of device NLLS models
+// LevenbergMarquardt::covariance: cov = s2 (J^T J)^-1 with s2 = f / (m - n), the residual variance
+// (scipy's curve_fit default), or (J^T J)^-1 itself, the residuals being divided by their sigma already
+enum class cov_scale : int32_t { residual = NLSG_LM_COV_RESIDUAL, absolute = NLSG_LM_COV_ABSOLUTE };
 template <typename C, typename = void>
 struct has_curve_body : std::false_type {};
 template <typename C>
@@ -403,6 +406,8 @@ struct is_device_objective<C, std::void_t<decltype(C::nlsg_objective)>> : std::t
   /* link and curve models, gradient bodies */                                                            \
   X(lm_create_link, false) X(lm_create_curve, false) X(lm_set_curve_data, false)                          \
   X(bfgs_create_gradient, false)                                                                          \
+  /* parameter covariance of a Gauss-Newton fit */                                                        \
+  X(lm_covariance, false)                                                                                 \
   /* with it, whether the library has the resident BFGS mode (has_bfgs_resident) */                       \
   X(bfgs_lds_bytes, false)
 
@@ -2171,6 +2176,38 @@ class LevenbergMarquardt {
   std::vector<solver_status<scalar_t>> minimize_batch(std::vector<std::vector<scalar_t>> &thetas) {
     return solve_device(thetas);
   }
+  // Extension: the parameter covariance of a fit at x (usually what minimize left there), row-major
+  // n x n: scale (J^T J)^-1 from the model's own device Jacobian (nlsg_lm_covariance). All NaN where
+  // J^T J has no Cholesky factor; near-singularity is not diagnosed. NLLS models with n <= 64.
+  std::vector<double> covariance(const std::vector<double> &x,
+                                 device::cov_scale scale = device::cov_scale::residual) {
+    return std::move(covariance_batch({x}, scale).first[0]);
+  }
+  // ... of every problem of the model at its own point, and whether its J^T J factored
+  std::pair<std::vector<std::vector<double>>, std::vector<bool>> covariance_batch(
+      const std::vector<std::vector<double>> &thetas, device::cov_scale scale = device::cov_scale::residual) {
+    static_assert(device::has_nlls_objective<Callable>::value,
+                  "covariance needs a device NLLS model (TanhRegression, a link or a curve model): behind the "
+                  "default functors the engine's matrix is a finite-difference Hessian, not J^T J");
+    static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
+    const device::api &api = device::api::get();
+    if (!api.lm_covariance)
+      throw device_error("the loaded library has no nlsg_lm_covariance (parameter covariance of a fit)");
+    const size_t B = thetas.size();
+    size_t n = 0;
+    device::engine<nlsg_lm> eng = make_engine(thetas, n);
+    const std::vector<double> flat = device::flatten(thetas, n);
+    std::vector<double> cov(B * n * n);
+    std::vector<int32_t> ok(B);
+    upload_data(eng);
+    eng.check(api.lm_covariance(eng, flat.data(), static_cast<int32_t>(scale), cov.data(), nullptr, ok.data()));
+    std::pair<std::vector<std::vector<double>>, std::vector<bool>> out;
+    for (size_t b = 0; b < B; b++) {
+      out.first.emplace_back(cov.begin() + b * n * n, cov.begin() + (b + 1) * n * n);
+      out.second.push_back(ok[b] != 0);
+    }
+    return out;
+  }
   // The reference's arithmetic exists on the device for the default functors on the objectives
   // given by their terms (not Rastrigin: its device cosine is not libm's; not Custom; not the
   // TanhRegression model, whose tanh is the device's).
@@ -2182,16 +2219,14 @@ class LevenbergMarquardt {
   }
 
  private:
-  std::vector<solver_status<scalar_t>> solve_device(std::vector<std::vector<scalar_t>> &thetas) {
-    static_assert(device::has_nlls_objective<Callable>::value || device_fd(),
-                  "minimize_batch needs a device NLLS model, or Rosenbrock / Sphere / "
-                  "StyblinskiTang with the default finite-difference functors");
-    static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
+  // the engine of a batch of B starts (the model's problems, or B x n of the objective itself): created,
+  // its data not yet handed over (upload_data)
+  device::engine<nlsg_lm> make_engine(const std::vector<std::vector<scalar_t>> &thetas, size_t &n) {
     const device::api &api = device::api::get();
     const size_t B = thetas.size();
     auto cfg = device::make_config<nlsg_lm_config>();
     cfg.batch = B;
-    size_t n = 0;
+    n = 0;
     if constexpr (device::has_nlls_objective<Callable>::value) {
       if (B != f.problems()) throw device_error("one start per problem of the model is required");
       cfg.objective = Callable::nlsg_nlls_objective;
@@ -2235,14 +2270,31 @@ class LevenbergMarquardt {
     } else {
       eng.check(api.lm_create(&cfg, eng.out()));
     }
-    std::vector<scalar_t> flat = device::flatten(thetas, n), lam(B);
-    std::vector<nlsg_status> st(B);
+    return eng;
+  }
+  // a model's data, to its engine
+  void upload_data(const device::engine<nlsg_lm> &eng) {
+    const device::api &api = device::api::get();
     if constexpr (device::has_nlls_objective<Callable>::value) {
       if constexpr (device::has_curve_body<Callable>::value)
         eng.check(api.lm_set_curve_data(eng, f.t.data(), f.y.data()));
       else
         eng.check(api.lm_set_data(eng, f.A.data(), f.y.data()));
     }
+  }
+
+  std::vector<solver_status<scalar_t>> solve_device(std::vector<std::vector<scalar_t>> &thetas) {
+    static_assert(device::has_nlls_objective<Callable>::value || device_fd(),
+                  "minimize_batch needs a device NLLS model, or Rosenbrock / Sphere / "
+                  "StyblinskiTang with the default finite-difference functors");
+    static_assert(std::is_same_v<scalar_t, double>, "the device path computes in fp64");
+    const device::api &api = device::api::get();
+    const size_t B = thetas.size();
+    size_t n = 0;
+    device::engine<nlsg_lm> eng = make_engine(thetas, n);
+    std::vector<scalar_t> flat = device::flatten(thetas, n), lam(B);
+    std::vector<nlsg_status> st(B);
+    upload_data(eng);
     eng.check(api.lm_minimize(eng, flat.data(), st.data(), lam.data()));
     if (B == 1) lambda = lam[0];
     return device::scatter(flat, st, thetas, n, 3);

@@ -111,6 +111,7 @@ OBJ_TANH_REGRESSION = 32
 OBJ_LINK_REGRESSION = 33  # NLSG_OBJ_LINK_REGRESSION: nlsg_lm_create_link
 OBJ_CURVE_MODEL = 34  # NLSG_OBJ_CURVE_MODEL: nlsg_lm_create_curve
 LM_CHOLESKY, LM_QR, LM_CHOLESKY_REFERENCE_ORDER = 0, 1, 2
+LM_COV_RESIDUAL, LM_COV_ABSOLUTE = 0, 1  # nlsg_lm_cov_scale: cov = s2 (J^T J)^-1, or (J^T J)^-1
 
 
 class LMConfig(C.Structure):
@@ -312,6 +313,7 @@ OPTIONAL_SYMBOLS = {
     "nlsg_lm_create_link": (C.c_int, [C.POINTER(LMConfig), C.POINTER(LMLinkC), C.POINTER(_H)]),
     "nlsg_lm_create_curve": (C.c_int, [C.POINTER(LMConfig), C.POINTER(LMCurveC), C.POINTER(_H)]),
     "nlsg_lm_set_curve_data": (C.c_int, [_H, pd, pd]),
+    "nlsg_lm_covariance": (C.c_int, [_H, pd, i32, pd, pd, C.POINTER(C.c_int32)]),
     "nlsg_bfgs_create_params": (C.c_int, [C.POINTER(BFGSConfig), C.POINTER(CustomObjectiveC), C.POINTER(_H)]),
     "nlsg_bfgs_set_params": (C.c_int, [_H, pd]),
     "nlsg_bfgs_lds_bytes": (u64, [u64, C.c_uint32]),
@@ -340,6 +342,7 @@ _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
                     "nlsg_lm_create_link": "library has no user-supplied link functions for Levenberg-Marquardt",
                     "nlsg_lm_create_curve": "library has no curve models for Levenberg-Marquardt",
                     "nlsg_lm_set_curve_data": "library has no curve models for Levenberg-Marquardt",
+                    "nlsg_lm_covariance": "library has no parameter covariance for Levenberg-Marquardt",
                     "nlsg_bfgs_create_gradient": "library has no analytic gradients of compiled objectives for BFGS",
                     "nlsg_bfgs_create_params": "library has no run-time objective parameters for BFGS",
                     "nlsg_bfgs_set_params": "library has no run-time objective parameters for BFGS",

@@ -722,6 +722,61 @@ int nlsg_lm_minimize(nlsg_lm *e, double *theta_inout_host, nlsg_status *status_h
   return NLSG_OK;
 }
 
+// cov = c (J^T J)^-1 at theta: the solve's own first launch (evaluation at theta, which also resets
+// LmProblem), then lm_cov_kernel on the Hg and f it left. The output block is the pool's: it goes back
+// only after the stream has drained, whatever failed in between.
+int nlsg_lm_covariance(nlsg_lm *e, const double *theta_host, int32_t scale, double *cov_out_host,
+                       double *s2_out_host, int32_t *ok_out_host) {
+  if (!e || !theta_host || !cov_out_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));
+  if (e->wide)
+    return fail(NLSG_ERR_UNSUPPORTED, "the covariance kernel runs one wave per problem: n = %llu > %d",
+                (unsigned long long)e->p.n, kLmN);
+  if (e->p.fd)
+    return fail(NLSG_ERR_UNSUPPORTED, "Gauss-Newton models only: behind the default functors the engine's "
+                                      "matrix is a finite-difference Hessian, not J^T J");
+  if (scale != NLSG_LM_COV_RESIDUAL && scale != NLSG_LM_COV_ABSOLUTE)
+    return fail(NLSG_ERR_INVALID_ARG, "unknown scale %d", scale);
+  if (scale == NLSG_LM_COV_RESIDUAL && e->p.m <= e->p.n)
+    return fail(NLSG_ERR_INVALID_ARG, "the residual variance f / (m - n) needs m > n: m = %llu, n = %llu "
+                                      "(NLSG_LM_COV_ABSOLUTE takes m <= n)",
+                (unsigned long long)e->p.m, (unsigned long long)e->p.n);
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  PhaseClock clk;
+  const uint64_t B = e->p.batch, n = e->p.n;
+  // cov [B][n][n] | s2 [B] | ok [B]
+  const uint64_t cov_bytes = B * n * n * 8;
+  unsigned char *block = nullptr;
+  NLSG_HIP(pool_malloc(reinterpret_cast<void **>(&block), cov_bytes + B * 8 + B * 4));
+  double *cov_dev = reinterpret_cast<double *>(block);
+  double *s2_dev = reinterpret_cast<double *>(block + cov_bytes);
+  int32_t *ok_dev = reinterpret_cast<int32_t *>(block + cov_bytes + B * 8);
+  int rc = upload_theta(e, theta_host);  // (synchronous copies: nothing in flight if it fails)
+  if (rc) {
+    pool_free(block);
+    return rc;
+  }
+  call_timing().init_ms = clk.lap();
+  launch_gn_iter(e, 1, 0);
+  if (scale == NLSG_LM_COV_RESIDUAL)
+    hipLaunchKernelGGL(lm_cov_kernel<true>, dim3(static_cast<unsigned>(B)), dim3(64), 0, e->stream, e->p,
+                       cov_dev, s2_dev, ok_dev);
+  else
+    hipLaunchKernelGGL(lm_cov_kernel<false>, dim3(static_cast<unsigned>(B)), dim3(64), 0, e->stream, e->p,
+                       cov_dev, s2_dev, ok_dev);
+  hipError_t he = launches_status();
+  const hipError_t se = hipStreamSynchronize(e->stream);  // before the block can go back, on every path
+  if (he == hipSuccess) he = se;
+  call_timing().iterate_ms = clk.lap();
+  if (he == hipSuccess) he = hipMemcpy(cov_out_host, cov_dev, cov_bytes, hipMemcpyDeviceToHost);
+  if (he == hipSuccess && s2_out_host) he = hipMemcpy(s2_out_host, s2_dev, B * 8, hipMemcpyDeviceToHost);
+  if (he == hipSuccess && ok_out_host) he = hipMemcpy(ok_out_host, ok_dev, B * 4, hipMemcpyDeviceToHost);
+  pool_free(block);
+  NLSG_HIP(he);
+  call_timing().readback_ms = clk.lap();
+  return NLSG_OK;
+}
+
 int nlsg_lm_time_solve(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total) {
   if (!e || !theta0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (const int prc = params_ready(e)) return prc;

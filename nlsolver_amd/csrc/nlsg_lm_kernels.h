@@ -1353,6 +1353,122 @@ __global__ __launch_bounds__(THREADS) void lm_qr_step_kernel(LmParams p) {
   if (t < n) p.theta[pid * kLmN + t] = p.theta[pid * kLmN + t] - qs.upd[t];  // :3534
 }
 
+// ---- Parameter covariance of a Gauss-Newton fit (nlsg_lm_covariance): cov = c (J^T J)^-1 at the point
+// the evaluation launch before it left its Hg and f for, c = f / (m - n) (RESIDUAL) or 1. One wave per
+// problem, nothing of the model in it. G = Hg / 2 on load (exact), G = L L^T by the left-looking
+// four-column panel of lm_solve_cholesky_wave (lane t owns row t; no is_diagonal shortcut: that is the
+// reference's step rule, not linear algebra), X = L^-1 by rows with lane c owning column c,
+// cov = X^T X, one triangle, mirrored on the store.
+// LDS: two packed triangles (lm_tri_row), 33 KiB: `tri` holds G, then L, then the lower triangle of
+// cov; `xs` holds X. Every loop has the same trip count in every lane: what a lane reads above its
+// diagonal lies inside the buffers and is replaced by zero (inversion) or never stored (products).
+// ok = every pivot > 0 (and f finite, RESIDUAL); a failed problem computes on, with whatever NaN or
+// inf that gives, and stores NaN through a select: every byte of its output block is written.
+template <bool RESIDUAL>
+__global__ __launch_bounds__(64) void lm_cov_kernel(LmParams p, double *cov, double *s2_out, int32_t *ok_out) {
+  __shared__ __align__(16) double tri[kLmTri];
+  __shared__ __align__(16) double xs[kLmTri];
+  const uint64_t pid = blockIdx.x;
+  const int t = threadIdx.x, n = static_cast<int>(p.n);
+  const bool row = t < n;
+  {  // rows >= n of Hg are zeros, not data: the image ends with row n - 1, zeros behind it
+    const double *src = p.Hg + pid * kLmTri;
+    const int used = lm_tri_row(n);
+    double h[33];
+#pragma unroll
+    for (int q = 0; q < 33; q++) h[q] = 64 * q + t < used ? src[64 * q + t] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 33; q++) tri[64 * q + t] = 0.5 * h[q];  // J^T J itself
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const LmRowsTri H{tri};
+  bool bad = false;  // lane j: pivot j is not positive
+  for (int j0 = 0; j0 < n; j0 += 4) {
+    double s4[4] = {0.0, 0.0, 0.0, 0.0};
+    const bool act = row && t >= j0;
+    if (t >= (j0 & ~15))  // (finished groups of sixteen rows sit the sums out, as in the step)
+      for (int k = 0; k < j0; k += 4) {
+        const double2 xa = H.pair(t, k), xb = H.pair(t, k + 2);  // lanes t < j0: in-buffer, unused
+        const double x[4] = {xa.x, xa.y, xb.x, xb.y};
+#pragma unroll
+        for (int c = 0; c < 4; c++) {  // L[j0+c][k..k+3]: a wave-uniform address, a broadcast
+          const double2 la = H.pair(min(j0 + c, 63), k), lb = H.pair(min(j0 + c, 63), k + 2);
+          const double l[4] = {la.x, la.y, lb.x, lb.y};
+#pragma unroll
+          for (int q = 0; q < 4; q++) s4[c] = __builtin_fma(x[q], l[q], s4[c]);
+        }
+      }
+    double hd[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) hd[c] = H(t, min(j0 + c, 63));
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const int j = j0 + c;
+      if (j < n) {  // wave-uniform
+        const double d = hd[c] - s4[c];
+        double v = 0.0, rinv = 0.0;
+        if (t == j) {
+          bad = !(d > 0.0);  // (NaN included)
+          v = sqrt(d);
+          rinv = 1.0 / v;
+        }
+        const double ri = lane_broadcast(rinv, j);
+        if (act && t > j) v = ri * d;
+        if (act && t >= j) H(t, j) = v;
+#pragma unroll
+        for (int c2 = c + 1; c2 < 4; c2++)
+          s4[c2] = __builtin_fma(v, lane_broadcast(v, min(j0 + c2, 63)), s4[c2]);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  const double f = p.prob[pid].f;
+  const double s2 = p.m > p.n ? f / static_cast<double>(p.m - p.n) : __builtin_nan("");
+  bool ok = __ballot(bad) == 0ull;
+  if (RESIDUAL) ok = ok && isfinite(f);
+  // X = L^-1, row i at a time: X[i][c] = ((i == c) - sum_{k < i} L[i][k] X[k][c]) / L[i][i]. L[i][k] is a
+  // broadcast (pairs of columns as one 128-bit read), X[k][c] a read by consecutive lanes.
+  const int c = t;
+  for (int i = 0; i < n; i++) {
+    double s = 0.0;
+    for (int k = 0; k < i; k += 2) {  // (k + 1 == i: the pair's second half is the diagonal, masked)
+      const double2 l = H.pair(i, k);
+      const double x0 = xs[lm_tri_row(k) + c], x1 = xs[lm_tri_row(k + 1) + c];
+      s = __builtin_fma(l.x, k >= c ? x0 : 0.0, s);
+      s = __builtin_fma(l.y, (k + 1 >= c && k + 1 < i) ? x1 : 0.0, s);
+    }
+    const double x = ((i == c ? 1.0 : 0.0) - s) / H(i, i);
+    if (c <= i) xs[lm_tri_row(i) + c] = x;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  // cov[i][c] = scale * sum_{k >= i} X[k][i] X[k][c] for c <= i: X[k][i] is a broadcast, X[k][c] a read
+  // by consecutive lanes. It replaces L, which is dead.
+  const double scale = RESIDUAL ? s2 : 1.0;
+  for (int i = 0; i < n; i++) {
+    double s = 0.0;
+    for (int k = i; k < n; k++) s = __builtin_fma(xs[lm_tri_row(k) + i], xs[lm_tri_row(k) + c], s);
+    if (c <= i) tri[lm_tri_row(i) + c] = scale * s;  // (lanes c > i summed rows' neighbours: dropped)
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  // [n][n] row-major, lane c the column: contiguous across lanes; the upper triangle is the lower one's
+  // element read again (a column read of the packed triangle: not conflict-free, n^2 / 2 of them)
+  double *out = cov + pid * p.n * p.n;
+  const double nan = __builtin_nan("");
+  if (row)
+    for (int i = 0; i < n; i++) {
+      const double v = tri[c <= i ? lm_tri_row(i) + c : lm_tri_row(c) + i];
+      out[static_cast<uint64_t>(i) * n + c] = ok ? v : nan;
+    }
+  if (t == 0) {
+    s2_out[pid] = s2;
+    ok_out[pid] = ok ? 1 : 0;
+  }
+}
+
 // host layout -> device layout of A and y (see nlsg_lm_set_data), for the problems [b0, b0 + nb):
 // a_raw holds those problems' matrices only ([nb][m][n]), y_raw all of y ([batch][m])
 __global__ void lm_repack_kernel(LmParams p, const double *a_raw, const double *y_raw, double *A,

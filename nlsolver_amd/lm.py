@@ -162,6 +162,16 @@ class CurveModel:
             th[3] + (th[0] - th[3]) / (1.0 + (t[:, 0] / th[2]) ** th[1])))
 
 
+def _cov_scale(scale):
+    """"residual" / "absolute" or LM_COV_RESIDUAL / LM_COV_ABSOLUTE -> the constant (no library call)"""
+    names = {"residual": _capi.LM_COV_RESIDUAL, "absolute": _capi.LM_COV_ABSOLUTE}
+    if isinstance(scale, str) and scale in names:
+        return names[scale]
+    if not isinstance(scale, (bool, str)) and isinstance(scale, (int, np.integer)) and int(scale) in names.values():
+        return int(scale)
+    raise ValueError(f'scale is "residual" or "absolute" (LM_COV_RESIDUAL / LM_COV_ABSOLUTE): got {scale!r}')
+
+
 class LMEngine:
     """model: a TanhRegression, a LinkRegression or a CurveModel, or the name / id of a built-in objective ("rosenbrock", "sphere",
     "styblinski_tang") or a CustomObjective, with batch= and n= (default functors: fin_diff +
@@ -280,6 +290,29 @@ class LMEngine:
                                      lam.ctypes.data_as(_capi.pd)))
         return theta, list(st), lam
 
+    def covariance(self, theta, scale="residual"):
+        """Parameter covariance of every problem's fit at theta (batch, n), usually minimize()'s result:
+        cov = c (J^T J)^-1 with c = s2 = f / (m - n) (scale="residual", scipy's curve_fit default) or
+        c = 1 (scale="absolute": the residuals are already divided by their sigma). Returns
+        (cov (batch, n, n), s2 (batch,), ok (batch,) bool); where J^T J has a Cholesky pivot <= 0 — or,
+        in residual mode, f is not finite — ok is False and the problem's cov is all NaN.
+        Near-singularity is not diagnosed. Gauss-Newton models with n <= 64 only."""
+        scale = _cov_scale(scale)
+        theta = np.ascontiguousarray(theta, dtype=np.float64)
+        B, n = self.cfg.batch, self.cfg.n
+        if theta.shape != (B, n):
+            raise ValueError(f"theta must be (batch, n) = ({B}, {n}): got {theta.shape}")
+        fn = require("nlsg_lm_covariance")
+        cov, s2, ok = np.empty((B, n, n)), np.empty(B), np.empty(B, dtype=np.int32)
+        check(fn(self._h, theta.ctypes.data_as(_capi.pd), scale, cov.ctypes.data_as(_capi.pd),
+                 s2.ctypes.data_as(_capi.pd), ok.ctypes.data_as(C.POINTER(C.c_int32))))
+        return cov, s2, ok.astype(bool)
+
+    def stderr(self, theta, scale="residual"):
+        """Standard errors (batch, n): the square roots of covariance()'s diagonal, NaN rows where not ok"""
+        cov, _, _ = self.covariance(theta, scale)
+        return np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
+
     def time_solve(self, theta0, repeats=1, params=None):
         if params is not None:
             self.set_params(params)
@@ -331,7 +364,8 @@ class LevenbergMarquardt:
         self.args = dict(lam=lam, up=upward_mult, down=downward_mult, max_iter=max_iter,
                          f_delta=f_delta, solver=solver, device=device)
 
-    def minimize(self, x):
+    def _engine(self, x):
+        """x as (batch, n), the engine minimize() runs it on, and the parameter rows of that batch"""
         if not isinstance(x, np.ndarray) or x.dtype != np.float64 or x.ndim not in (1, 2):
             raise TypeError("x must be a float64 numpy array of shape (n,) or (batch, n)")
         xb = x.reshape(1, -1) if x.ndim == 1 else x
@@ -346,11 +380,29 @@ class LevenbergMarquardt:
             args["solver"] = _capi.LM_CHOLESKY_REFERENCE_ORDER if ref else _capi.LM_CHOLESKY
         from .nm import _rows_for_batch
         rows = _rows_for_batch(self.params, xb.shape[0])
-        with LMEngine(self.f, **args, **shape) as eng:
+        return xb, LMEngine(self.f, **args, **shape), rows
+
+    def minimize(self, x):
+        xb, engine, rows = self._engine(x)
+        with engine as eng:
             out, st, lam = eng.minimize(xb, params=rows)
         xb[...] = out
         self.lambdas = lam  # the reference keeps lambda as a member across calls (:3436)
         return st[0] if x.ndim == 1 else st
+
+    def covariance(self, x, scale="residual"):
+        """LMEngine.covariance at x, (n,) or (batch, n) as in minimize (usually the x it left): the
+        covariance (n, n) or (batch, n, n). A problem whose J^T J does not factor is all NaN."""
+        scale = _cov_scale(scale)
+        xb, engine, _ = self._engine(x)
+        with engine as eng:
+            cov, _, _ = eng.covariance(xb, scale)
+        return cov[0] if x.ndim == 1 else cov
+
+    def stderr(self, x, scale="residual"):
+        """the square roots of covariance()'s diagonal: (n,) or (batch, n)"""
+        cov = self.covariance(x, scale)
+        return np.sqrt(np.diagonal(cov, axis1=-2, axis2=-1))
 
     def maximize(self, x):  # nlsolver.h:3468 static_assert(minimize, ...)
         raise NotImplementedError("LevenbergMarquardt currently only supports minimization")

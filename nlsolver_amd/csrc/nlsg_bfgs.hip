@@ -1,30 +1,25 @@
 // nlsolver_amd/csrc/nlsg_bfgs.hip — host side of the batched BFGS engine + C-ABI.
 #include <algorithm>
-#include <new>
 #include <vector>
 
 #include "nlsg_bfgs_kernels.h"
+#include "nlsg_engine.h"
 #include "nlsg_rtc.h"
 
 using namespace nlsg;
 
-struct nlsg_bfgs {
+struct nlsg_bfgs : EngineBase {  // (n_params: nlsg_bfgs_create_params, a row per problem)
   BfgsRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernels hiprtc built (finite differences, or the
                        // objective's gradient body: nlsg_bfgs_create_gradient)
   nlsg_bfgs_config cfg;
   BfgsParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   double *qd_dev = nullptr, *qb_dev = nullptr, *zero_dev = nullptr;
   unsigned long long *count_dev = nullptr;
   int chunks = 0;
   bool vec = false, initialised = false;
   uint32_t bpp = 0;  // blocks per problem in the H-streaming kernels
   bool symmetric = false;  // NLSG_BFGS_SYMMETRIC: upper blocks of H only
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-  int32_t n_params = 0;          // nlsg_bfgs_create_params: the objective's run-time doubles per problem
-  double *params_dev = nullptr;  // [batch][n_params]
-  bool params_set = false;
+  hipEvent_t ev2 = nullptr, ev3 = nullptr;  // around the H kernels of a timed iteration
   unsigned fd_lds = 0;  // dynamic LDS of the module's search / init launches: the reference-order buffers,
                         // and behind them a parameter row per wave
   bool resident = false;   // NLSG_BFGS_RESIDENT: the whole loop in bfgs_resident_kernel, H in LDS
@@ -156,9 +151,7 @@ void launch_iteration(nlsg_bfgs *e, bool timed) {
 
 // a parametrised engine launches no evaluation before its first rows
 int params_ready(const nlsg_bfgs *e) {
-  if (e->n_params > 0 && !e->params_set)
-    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_bfgs_set_params first", e->n_params);
-  return NLSG_OK;
+  return e->params_ready("the objective has %d parameters: call nlsg_bfgs_set_params first");
 }
 
 constexpr int bfgs_chunks(uint64_t n) { return n <= 128 ? 1 : n <= 256 ? 2 : n <= 512 ? 4 : 8; }
@@ -175,10 +168,7 @@ int nlsg_bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const
                      nlsg_bfgs **out) {
   if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_bfgs_create_custom");
-  PhaseClock clk;
-  const int rc = bfgs_create(cfg, diag_host, lin_host, nullptr, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return bfgs_create(cfg, diag_host, lin_host, nullptr, out); });
 }
 
 int nlsg_bfgs_create_custom(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
@@ -187,10 +177,7 @@ int nlsg_bfgs_create_custom(const nlsg_bfgs_config *cfg, const nlsg_custom_objec
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
   if (const int prc = reject_custom_params(obj)) return prc;
-  PhaseClock clk;
-  const int rc = bfgs_create(cfg, nullptr, nullptr, obj, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return bfgs_create(cfg, nullptr, nullptr, obj, out); });
 }
 
 int nlsg_bfgs_create_params(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
@@ -198,10 +185,7 @@ int nlsg_bfgs_create_params(const nlsg_bfgs_config *cfg, const nlsg_custom_objec
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  PhaseClock clk;
-  const int rc = bfgs_create(cfg, nullptr, nullptr, obj, out, true);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return bfgs_create(cfg, nullptr, nullptr, obj, out, true); });
 }
 
 // The objective with its gradient as a second body: the kernels evaluate it instead of finite differences.
@@ -217,10 +201,7 @@ int nlsg_bfgs_create_gradient(const nlsg_bfgs_config *cfg, const nlsg_custom_obj
   if (!grad->grad_body || !grad->grad_body[0])
     return fail(NLSG_ERR_INVALID_ARG, "nlsg_bfgs_create_gradient needs a gradient body (finite differences are "
                 "nlsg_bfgs_create_custom's)");
-  PhaseClock clk;
-  const int rc = bfgs_create(cfg, nullptr, nullptr, obj, out, obj->n_params != 0, grad->grad_body);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return bfgs_create(cfg, nullptr, nullptr, obj, out, obj->n_params != 0, grad->grad_body); });
 }
 
 // The dynamic LDS of a search / init launch without parameter rows: the four waves' reference-order
@@ -243,14 +224,7 @@ uint64_t nlsg_bfgs_lds_bytes(uint64_t dim, uint32_t flags) {
 
 int nlsg_bfgs_set_params(nlsg_bfgs *e, const double *params_host) {
   if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (e->n_params <= 0)
-    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_bfgs_create_params)");
-  NLSG_HIP(hipSetDevice(e->cfg.device));
-  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
-                          hipMemcpyHostToDevice, e->stream));
-  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
-  e->params_set = true;
-  return NLSG_OK;
+  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (nlsg_bfgs_create_params)");
 }
 
 static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const double *lin_host,
@@ -303,11 +277,8 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
     if (const int prc = check_custom_params(custom, nlsg_bfgs_lds_bytes(cfg->dim, cfg->flags), "nlsg_bfgs",
                                             "nlsg_bfgs_create_custom", resident ? 1 : 4))
       return prc;
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-  nlsg_bfgs *e = new (std::nothrow) nlsg_bfgs();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_bfgs *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
   const uint64_t n = cfg->dim, B = cfg->batch;
   e->chunks = bfgs_chunks(n);
@@ -324,60 +295,44 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   e->symmetric = (cfg->flags & NLSG_BFGS_SYMMETRIC) != 0;
   const uint32_t nb = static_cast<uint32_t>((n + kBfgsSymB - 1) / kBfgsSymB), nstored = nb * (nb + 1) / 2;
   if (B * e->bpp > 0x7fffffffull || B * nstored > 0x7fffffffull) {
-    delete e;
+    delete e;  // (its stream goes back with it)
     return fail(NLSG_ERR_UNSUPPORTED, "batch * dim too large for one launch grid");
-  }
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
   }
   BfgsParams &p = e->p;
   std::memset(&p, 0, sizeof p);
   p.ldh = seq && (n * sizeof(double)) % 4096 == 0 ? n + 16 : n;  // (BfgsParams::ldh)
-  auto alloc = [&](void **ptr, size_t bytes) { return pool_malloc(ptr, bytes ? bytes : 8); };
-  hipError_t he = hipSuccess;
+  DeviceOwner &own = e->own;
+  hipError_t &he = own.err;
+  auto alloc = [&](auto **ptr, size_t bytes) { own.alloc(ptr, bytes ? bytes : 8); };
   const size_t vec_bytes = B * n * sizeof(double);
-  if (he == hipSuccess && !e->symmetric)
-    he = alloc(reinterpret_cast<void **>(&p.H), B * n * p.ldh * sizeof(double));
-  if (he == hipSuccess && e->symmetric)
-    he = alloc(reinterpret_cast<void **>(&p.Hs), B * nstored * kBfgsSymB * kBfgsSymB * sizeof(double));
-  if (he == hipSuccess && e->symmetric)
-    he = alloc(reinterpret_cast<void **>(&p.part), B * nb * nb * kBfgsSymB * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.x), vec_bytes);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.g), vec_bytes);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.dir), vec_bytes);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.s), vec_bytes);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.y), vec_bytes);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.t), vec_bytes);
+  if (!e->symmetric) alloc(&p.H, B * n * p.ldh * sizeof(double));
+  if (e->symmetric) alloc(&p.Hs, B * nstored * kBfgsSymB * kBfgsSymB * sizeof(double));
+  if (e->symmetric) alloc(&p.part, B * nb * nb * kBfgsSymB * sizeof(double));
+  alloc(&p.x, vec_bytes);
+  alloc(&p.g, vec_bytes);
+  alloc(&p.dir, vec_bytes);
+  alloc(&p.s, vec_bytes);
+  alloc(&p.y, vec_bytes);
+  alloc(&p.t, vec_bytes);
   if (he == hipSuccess) he = hipMemset(p.dir, 0, vec_bytes);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.prob), B * sizeof(BfgsProblem));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->qd_dev), n * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->qb_dev), n * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->zero_dev), 16);
-  if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->count_dev), 8);
-  if (he == hipSuccess && e->n_params)
-    he = alloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * sizeof(double));
+  alloc(&p.prob, B * sizeof(BfgsProblem));
+  alloc(&e->qd_dev, n * sizeof(double));
+  alloc(&e->qb_dev, n * sizeof(double));
+  own.zeroed(&e->zero_dev, 16);
+  alloc(&e->count_dev, 8);
+  e->alloc_params(B, e->n_params);
   if (he == hipSuccess)
     he = quad ? hipMemcpy(e->qd_dev, diag_host, n * sizeof(double), hipMemcpyHostToDevice)
               : hipMemset(e->qd_dev, 0, n * sizeof(double));
   if (he == hipSuccess)
     he = quad ? hipMemcpy(e->qb_dev, lin_host, n * sizeof(double), hipMemcpyHostToDevice)
               : hipMemset(e->qb_dev, 0, n * sizeof(double));
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev2);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev3);
-  if (he != hipSuccess) {
+  e->timing_events();
+  own.event(&e->ev2);
+  own.event(&e->ev3);
+  if (const int rc = e->setup_status("device allocation failed: %s")) {
     nlsg_bfgs_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP,
-                "device allocation failed: %s", hipGetErrorString(he));
+    return rc;
   }
   p.qd = e->qd_dev;
   p.qb = e->qb_dev;
@@ -403,24 +358,24 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
     // the module API's counterpart of hipFuncSetAttribute on a kernel symbol: four rows of parameters go
     // past the 64 KiB a launch may take without it
     if (e->fd_lds > 64 * 1024) {
-      he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.search),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->fd_lds));
-      if (he == hipSuccess)
-        he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.init),
+      hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.search),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->fd_lds));
+      if (ae == hipSuccess)
+        ae = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.init),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->fd_lds));
-      if (he != hipSuccess) {
+      if (ae != hipSuccess) {
         nlsg_bfgs_destroy(e);
-        return fail(NLSG_ERR_HIP, "raising the kernels' dynamic LDS limit failed: %s", hipGetErrorString(he));
+        return fail(NLSG_ERR_HIP, "raising the kernels' dynamic LDS limit failed: %s", hipGetErrorString(ae));
       }
     }
     // (only a module kernel has a parameter row: the built-in resident kernels stay below 64 KiB)
     if (resident && e->res.total * sizeof(double) > 64 * 1024) {
-      he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.resident),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               static_cast<int>(e->res.total * sizeof(double)));
-      if (he != hipSuccess) {
+      const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.resident),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                static_cast<int>(e->res.total * sizeof(double)));
+      if (ae != hipSuccess) {
         nlsg_bfgs_destroy(e);
-        return fail(NLSG_ERR_HIP, "raising the resident kernel's dynamic LDS limit failed: %s", hipGetErrorString(he));
+        return fail(NLSG_ERR_HIP, "raising the resident kernel's dynamic LDS limit failed: %s", hipGetErrorString(ae));
       }
     }
   }
@@ -431,27 +386,9 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
 int nlsg_bfgs_destroy(nlsg_bfgs *e) {
   if (!e) return NLSG_OK;
   PhaseClock clk;
-  hipSetDevice(e->cfg.device);
-  if (e->stream) hipStreamSynchronize(e->stream);
-  pool_free(e->p.H);
-  pool_free(e->p.Hs);
-  pool_free(e->p.part);
-  pool_free(e->p.x);
-  pool_free(e->p.g);
-  pool_free(e->p.dir);
-  pool_free(e->p.s);
-  pool_free(e->p.y);
-  pool_free(e->p.t);
-  pool_free(e->p.prob);
+  e->drain();
   rtc_release(&e->rtc);
-  pool_free(e->qd_dev);
-  pool_free(e->qb_dev);
-  pool_free(e->zero_dev);
-  pool_free(e->count_dev);
-  pool_free(e->params_dev);
-  for (hipEvent_t ev : {e->ev0, e->ev1, e->ev2, e->ev3})
-    if (ev) hipEventDestroy(ev);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   call_timing().destroy_ms = clk.lap();
   return NLSG_OK;
@@ -612,19 +549,18 @@ int nlsg_bfgs_time_steps(nlsg_bfgs *e, uint64_t iters, float *ms_total, float *m
     return fail(NLSG_ERR_UNSUPPORTED, "a resident engine has no separate H kernels to bracket: time nlsg_bfgs_step");
   NLSG_HIP(hipSetDevice(e->cfg.device));
   float hess = 0.f;
-  NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-  for (uint64_t k = 0; k < iters; k++) {
-    // one timed iteration per sync: the two inner events are reused
-    launch_iteration(e, true);
-    NLSG_HIP(hipEventSynchronize(e->ev3));
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev2, e->ev3));
-    hess += ms;
-  }
-  NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-  NLSG_HIP(hipEventSynchronize(e->ev1));
-  NLSG_HIP(launches_status());
-  NLSG_HIP(hipEventElapsedTime(ms_total, e->ev0, e->ev1));
+  const int rc = time_repeats(e->stream, e->ev0, e->ev1, 1, ms_total, [&]() -> int {
+    for (uint64_t k = 0; k < iters; k++) {
+      // one timed iteration per sync: the two inner events are reused
+      launch_iteration(e, true);
+      NLSG_HIP(hipEventSynchronize(e->ev3));
+      float ms = 0.f;
+      NLSG_HIP(hipEventElapsedTime(&ms, e->ev2, e->ev3));
+      hess += ms;
+    }
+    return NLSG_OK;
+  });
+  if (rc) return rc;
   if (ms_hessian) *ms_hessian = hess;
   return NLSG_OK;
 }

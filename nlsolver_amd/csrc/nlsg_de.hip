@@ -5,20 +5,17 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
-#include <new>
-#include <vector>
 
 #include "nlsg_comm.h"
 #include "nlsg_de_kernels.h"
+#include "nlsg_engine.h"
 #include "nlsg_rtc.h"
 
 using namespace nlsg;
 
-struct nlsg_de {
+struct nlsg_de : EngineBase {
   nlsg_de_config cfg;
   DeParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   double *x0_dev = nullptr;
   double *zero_dev = nullptr;
   double *rec = nullptr;  // local record (single-GPU finaliser input)
@@ -37,7 +34,6 @@ struct nlsg_de {
   DeRtcKernels rtc;           // objective == NLSG_OBJ_CUSTOM: the kernels hiprtc built for it
   bool overlap = false;
   bool fused = false;   // head k and generation k+1 share one launch (strategy random, one GPU)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
 namespace {
@@ -341,10 +337,7 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
 int nlsg_de_create(const nlsg_de_config *cfg, nlsg_de **out) {
   if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_de_create_custom");
-  PhaseClock clk;
-  const int rc = de_create(cfg, nullptr, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return de_create(cfg, nullptr, out); });
 }
 
 int nlsg_de_create_custom(const nlsg_de_config *cfg, const nlsg_custom_objective *obj, nlsg_de **out) {
@@ -352,10 +345,7 @@ int nlsg_de_create_custom(const nlsg_de_config *cfg, const nlsg_custom_objective
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
   if (const int prc = reject_custom_params(obj)) return prc;
-  PhaseClock clk;
-  const int rc = de_create(cfg, obj, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return de_create(cfg, obj, out); });
 }
 
 static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *custom, nlsg_de **out) {
@@ -382,12 +372,8 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
                 (unsigned long long)cfg->pop);
   if (cfg->shard_n > 0xffffffffull)  // donor indices are drawn as 32-bit values inside a shard
     return fail(NLSG_ERR_UNSUPPORTED, "shard_n >= 2^32 agents per engine");
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-
-  nlsg_de *e = new (std::nothrow) nlsg_de();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_de *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
   const uint64_t D = cfg->dim, n = cfg->shard_n;
   e->chunks = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
@@ -395,46 +381,29 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   e->group = D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 0;
   if (const char *g = std::getenv("NLSG_DE_GROUPS"))  // A/B switch: 0 = one agent per wave at any D
     if (g[0] == '0') e->group = 0;
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
-  }
   DeParams &p = e->p;
   std::memset(&p, 0, sizeof p);
-  auto alloc = [&](void **ptr, size_t bytes) { return pool_malloc(ptr, bytes ? bytes : 8); };
-  hipError_t he = hipSuccess;
+  DeviceOwner &own = e->own;
+  auto alloc = [&](auto **ptr, size_t bytes) { own.alloc(ptr, bytes ? bytes : 8); };
   const size_t rows = n * D * sizeof(double);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.buf[0]), rows);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.buf[1]), rows);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.scores[0]), n * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.scores[1]), n * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.home[0]), n);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.home[1]), n);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.best_x), D * sizeof(double));
-  if (he == hipSuccess && cfg->trace)
-    he = alloc(reinterpret_cast<void **>(&p.trace), n * kTraceWords * sizeof(uint64_t));
-  if (he == hipSuccess && cfg->trace)  // the bound's path counters (cleared by init)
-    he = alloc(reinterpret_cast<void **>(&p.counts), 3 * sizeof(uint64_t));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.state), sizeof(DeState));
+  alloc(&p.buf[0], rows);
+  alloc(&p.buf[1], rows);
+  alloc(&p.scores[0], n * sizeof(double));
+  alloc(&p.scores[1], n * sizeof(double));
+  alloc(&p.home[0], n);
+  alloc(&p.home[1], n);
+  alloc(&p.best_x, D * sizeof(double));
+  if (cfg->trace) alloc(&p.trace, n * kTraceWords * sizeof(uint64_t));
+  if (cfg->trace) alloc(&p.counts, 3 * sizeof(uint64_t));  // the bound's path counters (cleared by init)
+  alloc(&p.state, sizeof(DeState));
   p.ntiles = static_cast<uint32_t>((n + kTile - 1) / kTile);
-  if (he == hipSuccess)
-    he = alloc(reinterpret_cast<void **>(&p.part), p.ntiles * sizeof(TilePartial));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.ticket), 8);
-  if (he == hipSuccess) he = hipMemset(p.ticket, 0, 8);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->zero_dev), 16);
-  if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
+  alloc(&p.part, p.ntiles * sizeof(TilePartial));
+  own.zeroed(&p.ticket, 8);
+  own.zeroed(&e->zero_dev, 16);
   p.zero = e->zero_dev;
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->x0_dev), D * sizeof(double));
-  if (he == hipSuccess)
-    he = alloc(reinterpret_cast<void **>(&e->rec), (kRecHeader + D) * sizeof(double));
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
+  alloc(&e->x0_dev, D * sizeof(double));
+  alloc(&e->rec, (kRecHeader + D) * sizeof(double));
+  e->timing_events();
   // Overlapped turns (one GPU, strategy random) are opt-in (NLSG_DE_OVERLAP=1): on MI355X /
   // ROCm 7.2 the two cross-stream event waits per turn cost more (~+3 us) than the 10 us
   // head they hide, measured at pop = 65536 (61.7 vs 58.7 us per turn).
@@ -443,17 +412,16 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   const char *fu = std::getenv("NLSG_DE_FUSED_TURN");
   e->fused = cfg->strategy == NLSG_DE_RANDOM && cfg->shard_n == cfg->pop && !e->long_rows &&
              !e->overlap && !cfg->trace && !(fu && fu[0] == '0');  // the trace buffer is not double-buffered
-  if (e->overlap) {
-    if (he == hipSuccess) he = pool_stream_get(&e->side);
+  if (e->overlap) {  // (the owner drains the side stream with the engine's own before any block goes back)
+    own.stream(&e->side);
     for (int i = 0; i < 4; i++) {
-      if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_gen[i], hipEventDisableTiming);
-      if (he == hipSuccess) he = hipEventCreateWithFlags(&e->ev_head[i], hipEventDisableTiming);
+      own.event(&e->ev_gen[i], hipEventDisableTiming);
+      own.event(&e->ev_head[i], hipEventDisableTiming);
     }
   }
-  if (he != hipSuccess) {
+  if (const int rc = e->setup_status("device allocation failed: %s")) {
     nlsg_de_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP,
-                "device allocation failed: %s", hipGetErrorString(he));
+    return rc;
   }
   p.pop = cfg->pop;
   p.D = D;
@@ -506,36 +474,10 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
 int nlsg_de_destroy(nlsg_de *e) {
   if (!e) return NLSG_OK;
   PhaseClock clk;
-  hipSetDevice(e->cfg.device);
-  // every stream the engine queues work on is drained before its blocks go back to the pool
-  // (pool_free does not synchronise the device the way hipFree does)
-  if (e->stream) hipStreamSynchronize(e->stream);
-  if (e->side) hipStreamSynchronize(e->side);
-  pool_free(e->p.buf[0]);
-  pool_free(e->p.buf[1]);
-  pool_free(e->p.scores[0]);
-  pool_free(e->p.scores[1]);
-  pool_free(e->p.home[0]);
-  pool_free(e->p.home[1]);
-  if (e->side) pool_stream_put(e->cfg.device, e->side);
-  for (int i = 0; i < 4; i++) {
-    if (e->ev_gen[i]) hipEventDestroy(e->ev_gen[i]);
-    if (e->ev_head[i]) hipEventDestroy(e->ev_head[i]);
-  }
-  pool_free(e->p.best_x);
-  pool_free(e->p.trace);
-  pool_free(e->p.counts);
-  pool_free(e->p.state);
-  pool_free(e->p.part);
-  pool_free(e->p.ticket);
+  e->drain();  // the engine's stream and the side stream
   comm_detach(e->comm);
   rtc_release(&e->rtc);
-  pool_free(e->x0_dev);
-  pool_free(e->zero_dev);
-  pool_free(e->rec);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   call_timing().destroy_ms = clk.lap();
   return NLSG_OK;
@@ -609,20 +551,17 @@ int nlsg_de_download(nlsg_de *e, double *pop_host, double *scores_host, uint64_t
   if (rc) return rc;
   const uint64_t n = e->p.shard_n, D = e->p.D;
   if (pop_host) {  // rows are spread over both buffers (DeParams.home): gathered, then one copy
+    DeviceOwner tmp(e->cfg.device);  // (drains the stream before the block goes back: a failed copy may still be queued)
+    tmp.watch(e->stream);
     double *stage = nullptr;
-    NLSG_HIP(pool_malloc(reinterpret_cast<void **>(&stage), n * D * sizeof(double)));
+    NLSG_HIP(tmp.take(&stage, n * D * sizeof(double)));
     const unsigned grid = static_cast<unsigned>(std::min<uint64_t>(n, 65536));
     hipLaunchKernelGGL(de_gather_kernel, dim3(grid), dim3(256), 0, e->stream, e->p, s.parity, stage);
     hipError_t he = hipMemcpyAsync(pop_host, stage, n * D * sizeof(double), hipMemcpyDeviceToHost,
                                    e->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = launches_status();
-    if (he != hipSuccess) {  // the copy may still be queued: the block is released, not parked
-      hipStreamSynchronize(e->stream);
-      pool_free(stage);
-      return fail(NLSG_ERR_HIP, "population download failed: %s", hipGetErrorString(he));
-    }
-    pool_free(stage);
+    if (he != hipSuccess) return fail(NLSG_ERR_HIP, "population download failed: %s", hipGetErrorString(he));
   }
   if (scores_host)
     NLSG_HIP(hipMemcpy(scores_host, e->p.scores[s.parity], n * sizeof(double),
@@ -705,13 +644,12 @@ int nlsg_de_time_generation_kernel(nlsg_de *e, uint32_t launches, float *ms_tota
   DeState s;
   int rc = read_state(e, &s);
   if (rc) return rc;
-  NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-  for (uint32_t k = 0; k < launches; k++)
-    launch_generation(e, (s.parity + static_cast<int>(k)) & 1, s.iter + 1 + k, 1);
-  NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-  NLSG_HIP(hipEventSynchronize(e->ev1));
-  NLSG_HIP(launches_status());
-  NLSG_HIP(hipEventElapsedTime(ms_total, e->ev0, e->ev1));
+  rc = time_repeats(e->stream, e->ev0, e->ev1, 1, ms_total, [&]() -> int {
+    for (uint32_t k = 0; k < launches; k++)
+      launch_generation(e, (s.parity + static_cast<int>(k)) & 1, s.iter + 1 + k, 1);
+    return NLSG_OK;
+  });
+  if (rc) return rc;
   // The population advanced `launches` generations without best scans; the
   // engine must be re-initialised before it is used for a solve again.
   e->initialised = false;
@@ -725,18 +663,13 @@ int nlsg_de_time_turns(nlsg_de *e, uint64_t turns, float *ms_total) {
   NLSG_HIP(hipSetDevice(e->cfg.device));
   int rcj = join_side(e);
   if (rcj) return rcj;
-  NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-  for (uint64_t t = 0; t < turns; t++) {
-    int rc = launch_turn_single(e);
-    if (rc) return rc;
-  }
-  rcj = join_side(e);
-  if (rcj) return rcj;
-  NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-  NLSG_HIP(hipEventSynchronize(e->ev1));
-  NLSG_HIP(launches_status());
-  NLSG_HIP(hipEventElapsedTime(ms_total, e->ev0, e->ev1));
-  return NLSG_OK;
+  return time_repeats(e->stream, e->ev0, e->ev1, 1, ms_total, [&]() -> int {
+    for (uint64_t t = 0; t < turns; t++) {
+      int rc = launch_turn_single(e);
+      if (rc) return rc;
+    }
+    return join_side(e);
+  });
 }
 
 uint64_t nlsg_de_record_doubles(const nlsg_de *e) {

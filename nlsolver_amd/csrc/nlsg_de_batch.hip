@@ -4,19 +4,17 @@
 // (nlsg_de_*) with seed seeds[b] bit for bit. No global-memory fallback: a shape whose population
 // does not fit a workgroup's LDS is NLSG_ERR_UNSUPPORTED.
 #include <algorithm>
-#include <new>
 #include <vector>
 
 #include "nlsg_de_batch_kernels.h"
+#include "nlsg_engine.h"
 #include "nlsg_rtc.h"
 
 using namespace nlsg;
 
-struct nlsg_de_batch {
+struct nlsg_de_batch : EngineBase {  // (n_params: a row per solve, nlsg_de_batch_set_params)
   nlsg_de_batch_config cfg;
   DeBatchParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   size_t lds = 0;
   int group = 0;                 // lanes per agent: 4 / 8 / 16 / 32, or 64 = one wave per agent
   const void *init_fn = nullptr, *turn_fn = nullptr;  // built-in objectives
@@ -24,11 +22,7 @@ struct nlsg_de_batch {
   uint64_t turns_per_launch = 0;
   uint64_t *seeds_dev = nullptr;
   double *x0_dev = nullptr;
-  int32_t n_params = 0;          // run-time parameters per solve (custom objectives), 0 = none
-  double *params_dev = nullptr;  // [batch][n_params], filled by nlsg_de_batch_set_params
-  bool params_set = false;
   bool initialised = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
 namespace {
@@ -92,10 +86,7 @@ void launch_turns(nlsg_de_batch *e, uint64_t turns) {
 }
 
 int params_ready(const nlsg_de_batch *e) {
-  if (e->n_params > 0 && !e->params_set)
-    return fail(NLSG_ERR_STATE, "the objective has %d parameters: nlsg_de_batch_set_params has not been called",
-                e->n_params);
-  return NLSG_OK;
+  return e->params_ready("the objective has %d parameters: nlsg_de_batch_set_params has not been called");
 }
 
 // x0 and the seeds in, state reset, generation 0 scored. Asynchronous after the copies.
@@ -193,41 +184,27 @@ int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective
     return fail(NLSG_ERR_INVALID_ARG, "unknown objective %d", cfg->objective);
   if (cfg->strategy != NLSG_DE_BEST && cfg->strategy != NLSG_DE_RANDOM)
     return fail(NLSG_ERR_INVALID_ARG, "unknown strategy %d", cfg->strategy);
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-
-  nlsg_de_batch *e = new (std::nothrow) nlsg_de_batch();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_de_batch *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
   const uint64_t B = cfg->batch, n = cfg->pop, D = cfg->dim;
   e->lds = lds;
   e->n_params = n_params;
   e->group = D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 64;  // the turn engine's mappings
   e->turns_per_launch = cfg->turns_per_launch ? cfg->turns_per_launch : kDeBatchTurnsPerLaunch;
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
-  }
   DeBatchParams &p = e->p;
   std::memset(&p, 0, sizeof p);
-  hipError_t he = pool_malloc(reinterpret_cast<void **>(&p.rows), B * n * D * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.scores), B * n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.best_x), B * D * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.state), B * sizeof(DeState));
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.n_done), 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->seeds_dev), B * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->x0_dev), B * D * 8);
-  if (he == hipSuccess && n_params)
-    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(n_params) * 8);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
+  DeviceOwner &own = e->own;
+  hipError_t &he = own.err;
+  own.alloc(&p.rows, B * n * D * 8);
+  own.alloc(&p.scores, B * n * 8);
+  own.alloc(&p.best_x, B * D * 8);
+  own.alloc(&p.state, B * sizeof(DeState));
+  own.alloc(&p.n_done, 8);
+  own.alloc(&e->seeds_dev, B * 8);
+  own.alloc(&e->x0_dev, B * D * 8);
+  e->alloc_params(B, n_params);
+  e->timing_events();
   p.seeds = e->seeds_dev;
   p.params = e->params_dev;
   p.x0 = e->x0_dev;
@@ -261,10 +238,9 @@ int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective
                              hipFuncAttributeMaxDynamicSharedMemorySize,
                              static_cast<int>(kDeBatchLdsBudget - params_lds));
   }
-  if (he != hipSuccess) {
+  if (const int rc = e->setup_status()) {
     nlsg_de_batch_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP, "device setup failed: %s",
-                hipGetErrorString(he));
+    return rc;
   }
   *out = e;
   return NLSG_OK;
@@ -279,10 +255,7 @@ uint64_t nlsg_de_batch_lds_bytes(uint64_t pop, uint64_t dim) { return de_batch_l
 int nlsg_de_batch_create(const nlsg_de_batch_config *cfg, nlsg_de_batch **out) {
   if (cfg && out && cfg->struct_size == sizeof(nlsg_de_batch_config) && cfg->objective == NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_de_batch_create_custom");
-  PhaseClock clk;
-  const int rc = de_batch_create(cfg, nullptr, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return de_batch_create(cfg, nullptr, out); });
 }
 
 int nlsg_de_batch_create_custom(const nlsg_de_batch_config *cfg, const nlsg_custom_objective *obj,
@@ -290,29 +263,15 @@ int nlsg_de_batch_create_custom(const nlsg_de_batch_config *cfg, const nlsg_cust
   if (!cfg || !obj || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->struct_size == sizeof(nlsg_de_batch_config) && cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  PhaseClock clk;
-  const int rc = de_batch_create(cfg, obj, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return de_batch_create(cfg, obj, out); });
 }
 
 int nlsg_de_batch_destroy(nlsg_de_batch *e) {
   if (!e) return NLSG_OK;
   PhaseClock clk;
-  hipSetDevice(e->cfg.device);
-  if (e->stream) hipStreamSynchronize(e->stream);  // before the first pool_free: nothing in flight
+  e->drain();
   rtc_release(&e->rtc);
-  pool_free(e->p.rows);
-  pool_free(e->p.scores);
-  pool_free(e->p.best_x);
-  pool_free(e->p.state);
-  pool_free(e->p.n_done);
-  pool_free(e->seeds_dev);
-  pool_free(e->x0_dev);
-  pool_free(e->params_dev);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   call_timing().destroy_ms = clk.lap();
   return NLSG_OK;
@@ -320,14 +279,7 @@ int nlsg_de_batch_destroy(nlsg_de_batch *e) {
 
 int nlsg_de_batch_set_params(nlsg_de_batch *e, const double *params_host) {
   if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (e->n_params <= 0)
-    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (n_params == 0)");
-  NLSG_HIP(hipSetDevice(e->cfg.device));
-  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
-                          hipMemcpyHostToDevice, e->stream));
-  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
-  e->params_set = true;
-  return NLSG_OK;
+  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (n_params == 0)");
 }
 
 int nlsg_de_batch_init(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host) {
@@ -436,23 +388,18 @@ int nlsg_de_batch_time_solve(nlsg_de_batch *e, const double *x0_host, const uint
   NLSG_HIP(hipMemcpyAsync(e->x0_dev, x0_host, B * D * 8, hipMemcpyHostToDevice, e->stream));
   NLSG_HIP(hipMemcpyAsync(e->seeds_dev, seeds_host, B * 8, hipMemcpyHostToDevice, e->stream));
   NLSG_HIP(hipStreamSynchronize(e->stream));
-  float total = 0.f;
-  for (uint32_t r = 0; r < repeats; r++) {
-    NLSG_HIP(hipMemsetAsync(e->p.n_done, 0, sizeof(uint32_t), e->stream));
-    NLSG_HIP(hipMemsetAsync(e->p.best_x, 0, B * D * 8, e->stream));
-    NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-    launch_init(e);
-    e->initialised = true;
-    int rc = run_to_done(e);
-    if (rc) return rc;
-    NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-    NLSG_HIP(hipEventSynchronize(e->ev1));
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    total += ms;
-  }
-  *ms_total = total;
-  return NLSG_OK;
+  return time_repeats(
+      e->stream, e->ev0, e->ev1, repeats, ms_total,
+      [&]() -> int {
+        launch_init(e);
+        e->initialised = true;
+        return run_to_done(e);
+      },
+      [&]() -> int {  // the state reset, outside the interval
+        NLSG_HIP(hipMemsetAsync(e->p.n_done, 0, sizeof(uint32_t), e->stream));
+        NLSG_HIP(hipMemsetAsync(e->p.best_x, 0, B * D * 8, e->stream));
+        return NLSG_OK;
+      });
 }
 
 }  // extern "C"

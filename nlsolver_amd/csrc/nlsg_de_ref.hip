@@ -1,22 +1,19 @@
 // nlsolver_amd/csrc/nlsg_de_ref.hip — host side of the reference-order DE engine + C-ABI.
 // Batched solves of the reference's own DE (nlsolver.h:2414-2476) on the caller's xorshift states.
-#include <new>
 #include <vector>
 
 #include "nlsg_de_ref_kernels.h"
+#include "nlsg_engine.h"
 #include "nlsg_rtc.h"
 
 using namespace nlsg;
 
-struct nlsg_de_ref {
+struct nlsg_de_ref : EngineBase {
   DeRefRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it
   nlsg_de_ref_config cfg;
   DeRefParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   size_t lds = 0;
   uint64_t *jump_dev = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
 namespace {
@@ -150,39 +147,27 @@ static int de_ref_create(const nlsg_de_ref_config *cfg, const nlsg_custom_object
   if (cfg->dim < 1 || cfg->batch < 1) return fail(NLSG_ERR_INVALID_ARG, "dim and batch must be >= 1");
   if (cfg->batch > 0x7fffffffull || cfg->pop > 0x7fffffffull)
     return fail(NLSG_ERR_UNSUPPORTED, "batch and pop must be < 2^31");
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-  nlsg_de_ref *e = new (std::nothrow) nlsg_de_ref();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_de_ref *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
-  }
   DeRefParams &p = e->p;
   std::memset(&p, 0, sizeof p);
   const uint64_t B = cfg->batch, pop = cfg->pop, D = cfg->dim, L = cfg->log_capacity;
   p.lds_pop = de_ref_lds_bytes(pop, D, true, true) <= kDeRefLdsBudget;
   p.lds_scores = p.lds_pop || de_ref_lds_bytes(pop, D, false, true) <= kDeRefLdsBudget;
   e->lds = de_ref_lds_bytes(pop, D, p.lds_pop, p.lds_scores);
-  hipError_t he = pool_malloc(reinterpret_cast<void **>(&p.x), B * D * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.ctl), B * sizeof(DeRefCtl));
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.agents), B * pop * D * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.scores), B * (pop + 8) * 8);
-  if (he == hipSuccess && !p.lds_pop) he = pool_malloc(reinterpret_cast<void **>(&p.trial), B * (D + 8) * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.n_done), sizeof(uint32_t));
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->jump_dev), kDeRefJumpEntries * 16);
-  if (he == hipSuccess && L) he = pool_malloc(reinterpret_cast<void **>(&p.log_x), B * L * D * 8);
-  if (he == hipSuccess && L) he = pool_malloc(reinterpret_cast<void **>(&p.log_f), B * L * 8);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
+  DeviceOwner &own = e->own;
+  hipError_t &he = own.err;
+  own.alloc(&p.x, B * D * 8);
+  own.alloc(&p.ctl, B * sizeof(DeRefCtl));
+  own.alloc(&p.agents, B * pop * D * 8);
+  own.alloc(&p.scores, B * (pop + 8) * 8);
+  if (!p.lds_pop) own.alloc(&p.trial, B * (D + 8) * 8);
+  own.alloc(&p.n_done, sizeof(uint32_t));
+  own.alloc(&e->jump_dev, kDeRefJumpEntries * 16);
+  if (L) own.alloc(&p.log_x, B * L * D * 8);
+  if (L) own.alloc(&p.log_f, B * L * 8);
+  e->timing_events();
   if (he == hipSuccess) {
     std::vector<uint64_t> jt(2 * kDeRefJumpEntries);
     build_jump_table(jt.data());
@@ -200,10 +185,9 @@ static int de_ref_create(const nlsg_de_ref_config *cfg, const nlsg_custom_object
     he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.solve),
                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->lds));
   }
-  if (he != hipSuccess) {
+  if (const int rc = e->setup_status()) {
     nlsg_de_ref_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP, "device setup failed: %s",
-                hipGetErrorString(he));
+    return rc;
   }
   p.jump = e->jump_dev;
   p.batch = B;
@@ -225,21 +209,9 @@ static int de_ref_create(const nlsg_de_ref_config *cfg, const nlsg_custom_object
 
 int nlsg_de_ref_destroy(nlsg_de_ref *e) {
   if (!e) return NLSG_OK;
-  hipSetDevice(e->cfg.device);
-  if (e->stream) hipStreamSynchronize(e->stream);  // before the first pool_free: nothing in flight
+  e->drain();
   rtc_release(&e->rtc);
-  pool_free(e->p.x);
-  pool_free(e->p.ctl);
-  pool_free(e->p.agents);
-  pool_free(e->p.scores);
-  pool_free(e->p.trial);
-  pool_free(e->p.n_done);
-  pool_free(e->jump_dev);
-  pool_free(e->p.log_x);
-  pool_free(e->p.log_f);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   return NLSG_OK;
 }
@@ -308,21 +280,9 @@ int nlsg_de_ref_time_solve(nlsg_de_ref *e, const double *x0_host, const uint64_t
                            uint32_t repeats, float *ms_total) {
   if (!e || !x0_host || !rng_state0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  float total = 0.f;
-  for (uint32_t r = 0; r < repeats; r++) {
-    int rc = upload(e, x0_host, rng_state0_host);
-    if (rc) return rc;
-    NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-    rc = run(e);
-    if (rc) return rc;
-    NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-    NLSG_HIP(hipEventSynchronize(e->ev1));
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    total += ms;
-  }
-  *ms_total = total;
-  return NLSG_OK;
+  return time_repeats(
+      e->stream, e->ev0, e->ev1, repeats, ms_total, [&]() -> int { return run(e); },
+      [&]() -> int { return upload(e, x0_host, rng_state0_host); });  // outside the interval
 }
 
 int nlsg_de_ref_jump_table(uint64_t *table_host) {

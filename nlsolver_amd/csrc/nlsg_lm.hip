@@ -3,19 +3,17 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
-#include <new>
 #include <vector>
 
+#include "nlsg_engine.h"
 #include "nlsg_lm_kernels.h"
 #include "nlsg_rtc.h"
 
 using namespace nlsg;
 
-struct nlsg_lm {
+struct nlsg_lm : EngineBase {  // (n_params: nlsg_lm_create_params, a row per problem)
   nlsg_lm_config cfg;
   LmParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   double *A_dev = nullptr, *y_dev = nullptr, *zero_dev = nullptr;
   unsigned long long *count_dev = nullptr;
   bool has_data = false;
@@ -25,15 +23,11 @@ struct nlsg_lm {
   bool wide_chol = true;   // NLSG_LM_WIDE_CHOL=0: the steps before the blocked one — LDS-resident at
                            // n <= 128, column by column beyond (A/B switch)
   uint64_t ldt = kLmN; // row stride of theta / gg on the device: 64, or n when wide
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   LmRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it;
                      // NLSG_OBJ_LINK_REGRESSION: the Gauss-Newton evaluation kernel on the user's link
   bool link = false;  // nlsg_lm_create_link
   uint32_t curve_k = 0;  // nlsg_lm_create_curve: data per observation (0: no curve engine); rtc.iter is
                          // lm_curve_iter_kernel, A_dev the repacked (t, y) of nlsg_lm_set_curve_data
-  int32_t n_params = 0;          // nlsg_lm_create_params: the objective's run-time doubles per problem
-  double *params_dev = nullptr;  // [batch][n_params]
-  bool params_set = false;
 };
 
 namespace {
@@ -71,9 +65,7 @@ size_t lm_fd_launch_lds_bytes(uint64_t n, bool ref_order) {
 
 // a parametrised engine solves nothing before its first rows
 int params_ready(const nlsg_lm *e) {
-  if (e->n_params > 0 && !e->params_set)
-    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_lm_set_params first", e->n_params);
-  return NLSG_OK;
+  return e->params_ready("the objective has %d parameters: call nlsg_lm_set_params first");
 }
 
 // the call that hands the engine its data
@@ -266,10 +258,7 @@ int nlsg_lm_create(const nlsg_lm_config *cfg, nlsg_lm **out) {
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_LINK_REGRESSION engines are made by nlsg_lm_create_link");
   if (cfg && cfg->objective == NLSG_OBJ_CURVE_MODEL)
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CURVE_MODEL engines are made by nlsg_lm_create_curve");
-  PhaseClock clk;
-  const int rc = lm_create(cfg, nullptr, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return lm_create(cfg, nullptr, out); });
 }
 
 int nlsg_lm_create_custom(const nlsg_lm_config *cfg, const nlsg_custom_objective *obj, nlsg_lm **out) {
@@ -277,40 +266,28 @@ int nlsg_lm_create_custom(const nlsg_lm_config *cfg, const nlsg_custom_objective
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
   if (const int prc = reject_custom_params(obj)) return prc;
-  PhaseClock clk;
-  const int rc = lm_create(cfg, obj, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return lm_create(cfg, obj, out); });
 }
 
 int nlsg_lm_create_params(const nlsg_lm_config *cfg, const nlsg_custom_objective *obj, nlsg_lm **out) {
   if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  PhaseClock clk;
-  const int rc = lm_create(cfg, obj, out, true);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return lm_create(cfg, obj, out, true); });
 }
 
 int nlsg_lm_create_link(const nlsg_lm_config *cfg, const nlsg_lm_link *link, nlsg_lm **out) {
   if (!cfg || !link) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_LINK_REGRESSION)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_LINK_REGRESSION");
-  PhaseClock clk;
-  const int rc = lm_create(cfg, nullptr, out, false, link);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return lm_create(cfg, nullptr, out, false, link); });
 }
 
 int nlsg_lm_create_curve(const nlsg_lm_config *cfg, const nlsg_lm_curve *curve, nlsg_lm **out) {
   if (!cfg || !curve || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->objective != NLSG_OBJ_CURVE_MODEL)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CURVE_MODEL");
-  PhaseClock clk;
-  const int rc = lm_create(cfg, nullptr, out, false, nullptr, curve);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return lm_create(cfg, nullptr, out, false, nullptr, curve); });
 }
 
 // The dynamic LDS of the launch that evaluates an objective (the finite-difference model, which is what a
@@ -327,14 +304,7 @@ int nlsg_lm_set_params(nlsg_lm *e, const double *params_host) {
   if (e->curve_k)
     return fail(NLSG_ERR_INVALID_ARG, "a curve model has no p(k): per-problem constants ride in columns of t "
                                       "(nlsg_lm_set_curve_data)");
-  if (e->n_params <= 0)
-    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_lm_create_params)");
-  NLSG_HIP(hipSetDevice(e->cfg.device));
-  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
-                          hipMemcpyHostToDevice, e->stream));
-  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
-  e->params_set = true;
-  return NLSG_OK;
+  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (nlsg_lm_create_params)");
 }
 
 }  // extern "C"
@@ -385,11 +355,8 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
     return fail(NLSG_ERR_INVALID_ARG, "a curve model takes 1 .. 16 data per observation: k = %u", curve->k);
   if (curve && (!curve->body || !curve->body[0]))
     return fail(NLSG_ERR_INVALID_ARG, "a curve model needs a body (nlsg_lm_curve)");
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-  nlsg_lm *e = new (std::nothrow) nlsg_lm();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_lm *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
   e->wide = wide;
   e->n_params = with_params ? custom->n_params : 0;
@@ -404,48 +371,31 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
     e->wide_chol = !(wc && wc[0] == '0');
   }
   e->ldt = wide ? cfg->n : kLmN;
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
-  }
   LmParams &p = e->p;
   std::memset(&p, 0, sizeof p);
   const uint64_t B = cfg->batch, m = fd ? 0 : cfg->m;  // no design matrix behind an objective
-  hipError_t he = hipSuccess;
+  DeviceOwner &own = e->own;
+  hipError_t &he = own.err;
   // row groups of 16 (design matrices), or super-steps of 64 observations (curve data)
   const uint64_t nstep = wide ? 0 : curve ? (m + 63) / 64 : (m + 15) / 16;
   p.nstep = nstep;
-  if (he == hipSuccess && curve)  // [super-step][batch][k + 1][64], y in the last row
-    he = pool_malloc(reinterpret_cast<void **>(&e->A_dev), nstep * B * (curve->k + 1) * 64 * 8);
-  if (he == hipSuccess && nstep && !curve)
-    he = pool_malloc(reinterpret_cast<void **>(&e->A_dev), nstep * B * 16 * kLmN * 8);
-  if (he == hipSuccess && nstep && !curve)
-    he = pool_malloc(reinterpret_cast<void **>(&e->y_dev), nstep * B * 16 * 8);
-  if (he == hipSuccess && wide && m) {  // the caller's layout, [batch][m][n]
-    he = pool_malloc(reinterpret_cast<void **>(&e->A_dev), B * m * cfg->n * 8);
-    if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->y_dev), B * m * 8);
-    if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.rw), B * 2 * m * 8);
+  if (curve) own.alloc(&e->A_dev, nstep * B * (curve->k + 1) * 64 * 8);  // [super-step][batch][k + 1][64], y in the last row
+  if (nstep && !curve) own.alloc(&e->A_dev, nstep * B * 16 * kLmN * 8);
+  if (nstep && !curve) own.alloc(&e->y_dev, nstep * B * 16 * 8);
+  if (wide && m) {  // the caller's layout, [batch][m][n]
+    own.alloc(&e->A_dev, B * m * cfg->n * 8);
+    own.alloc(&e->y_dev, B * m * 8);
+    own.alloc(&p.rw, B * 2 * m * 8);
   }
-  if (he == hipSuccess && wide)
-    he = pool_malloc(reinterpret_cast<void **>(&p.Hw), B * cfg->n * cfg->n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.theta), B * e->ldt * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.prob), B * sizeof(LmProblem));
-  if (he == hipSuccess && !wide) he = pool_malloc(reinterpret_cast<void **>(&p.Hg), B * kLmTri * 8);
-  if (he == hipSuccess && !wide) he = hipMemset(p.Hg, 0, B * kLmTri * 8);  // rows past n are never written
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.gg), B * e->ldt * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->count_dev), 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->zero_dev), 16);
-  if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
-  if (he == hipSuccess && e->n_params)
-    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * 8);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
+  if (wide) own.alloc(&p.Hw, B * cfg->n * cfg->n * 8);
+  own.alloc(&p.theta, B * e->ldt * 8);
+  own.alloc(&p.prob, B * sizeof(LmProblem));
+  if (!wide) own.zeroed(&p.Hg, B * kLmTri * 8);  // rows past n are never written
+  own.alloc(&p.gg, B * e->ldt * 8);
+  own.alloc(&e->count_dev, 8);
+  own.zeroed(&e->zero_dev, 16);
+  e->alloc_params(B, e->n_params);
+  e->timing_events();
   if (he == hipSuccess)
     he = hipFuncSetAttribute(reinterpret_cast<const void *>(lm_qr_step_kernel<kLmQrThreads>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(LmQrShared));
@@ -464,10 +414,9 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
                                   : reinterpret_cast<const void *>(lm_wide_chol_step_kernel<512, false>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, lm_wchol_lds_bytes(512));
   }
-  if (he != hipSuccess) {
+  if (const int rc = e->setup_status()) {
     nlsg_lm_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP,
-                "device setup failed: %s", hipGetErrorString(he));
+    return rc;
   }
   if (custom) {
     const uint64_t n = cfg->n;
@@ -525,23 +474,9 @@ extern "C" {
 int nlsg_lm_destroy(nlsg_lm *e) {
   if (!e) return NLSG_OK;
   PhaseClock clk;
-  hipSetDevice(e->cfg.device);
-  if (e->stream) hipStreamSynchronize(e->stream);
-  pool_free(e->A_dev);
-  pool_free(e->y_dev);
-  pool_free(e->p.theta);
-  pool_free(e->p.prob);
-  pool_free(e->p.Hg);
-  pool_free(e->p.Hw);
-  pool_free(e->p.rw);
-  pool_free(e->p.gg);
-  pool_free(e->count_dev);
-  pool_free(e->zero_dev);
-  pool_free(e->params_dev);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
+  e->drain();
   rtc_release(&e->rtc);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   call_timing().destroy_ms = clk.lap();
   return NLSG_OK;
@@ -574,13 +509,16 @@ int nlsg_lm_set_data(nlsg_lm *e, const double *a_host, const double *y_host) {
   double *raw[2] = {nullptr, nullptr}, *y_raw = nullptr;
   hipStream_t copy = nullptr;
   hipEvent_t landed[2] = {nullptr, nullptr}, packed[2] = {nullptr, nullptr};
-  hipError_t he = pool_stream_get(&copy);
-  for (int k = 0; k < 2 && he == hipSuccess; k++) {
-    he = pool_malloc(reinterpret_cast<void **>(&raw[k]), chunk * per);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&landed[k], hipEventDisableTiming);
-    if (he == hipSuccess) he = hipEventCreateWithFlags(&packed[k], hipEventDisableTiming);
+  DeviceOwner tmp(e->cfg.device);  // the staging buffers, the copy stream and its events: this call's only
+  hipError_t &he = tmp.err;
+  tmp.watch(e->stream);
+  tmp.stream(&copy);
+  for (int k = 0; k < 2; k++) {
+    tmp.alloc(&raw[k], chunk * per);
+    tmp.event(&landed[k], hipEventDisableTiming);
+    tmp.event(&packed[k], hipEventDisableTiming);
   }
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&y_raw), B * m * 8);
+  tmp.alloc(&y_raw, B * m * 8);
   if (he == hipSuccess) he = hipMemcpyAsync(y_raw, y_host, B * m * 8, hipMemcpyHostToDevice, copy);
   uint64_t k = 0;
   for (uint64_t b0 = 0; b0 < B && he == hipSuccess; b0 += chunk, k++) {
@@ -600,14 +538,7 @@ int nlsg_lm_set_data(nlsg_lm *e, const double *a_host, const double *y_host) {
     if (he == hipSuccess) he = hipEventRecord(packed[slot], e->stream);
   }
   if (he == hipSuccess) he = hipStreamSynchronize(e->stream);  // the host buffers are borrowed for this call only
-  if (copy) hipStreamSynchronize(copy);
-  for (int q = 0; q < 2; q++) {
-    pool_free(raw[q]);
-    if (landed[q]) hipEventDestroy(landed[q]);
-    if (packed[q]) hipEventDestroy(packed[q]);
-  }
-  pool_free(y_raw);
-  if (copy) pool_stream_put(e->cfg.device, copy);
+  tmp.release();  // (drains the copy stream, and the engine's on a failed path, before the buffers go back)
   NLSG_HIP(he);
   e->has_data = true;
   call_timing().upload_ms = clk.lap();
@@ -624,8 +555,11 @@ int nlsg_lm_set_curve_data(nlsg_lm *e, const double *t_host, const double *y_hos
   PhaseClock clk;
   const uint64_t B = e->p.batch, m = e->p.m, K = e->curve_k;
   double *t_raw = nullptr, *y_raw = nullptr;
-  hipError_t he = pool_malloc(reinterpret_cast<void **>(&t_raw), B * m * K * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&y_raw), B * m * 8);
+  DeviceOwner tmp(e->cfg.device);
+  hipError_t &he = tmp.err;
+  tmp.watch(e->stream);
+  tmp.alloc(&t_raw, B * m * K * 8);
+  tmp.alloc(&y_raw, B * m * 8);
   if (he == hipSuccess) he = hipMemcpyAsync(t_raw, t_host, B * m * K * 8, hipMemcpyHostToDevice, e->stream);
   if (he == hipSuccess) he = hipMemcpyAsync(y_raw, y_host, B * m * 8, hipMemcpyHostToDevice, e->stream);
   if (he == hipSuccess) {
@@ -635,8 +569,7 @@ int nlsg_lm_set_curve_data(nlsg_lm *e, const double *t_host, const double *y_hos
     he = hipGetLastError();
   }
   if (he == hipSuccess) he = hipStreamSynchronize(e->stream);  // the host buffers are borrowed for this call only
-  pool_free(t_raw);
-  pool_free(y_raw);
+  tmp.release();
   NLSG_HIP(he);
   e->has_data = true;
   call_timing().upload_ms = clk.lap();
@@ -747,15 +680,14 @@ int nlsg_lm_covariance(nlsg_lm *e, const double *theta_host, int32_t scale, doub
   // cov [B][n][n] | s2 [B] | ok [B]
   const uint64_t cov_bytes = B * n * n * 8;
   unsigned char *block = nullptr;
-  NLSG_HIP(pool_malloc(reinterpret_cast<void **>(&block), cov_bytes + B * 8 + B * 4));
+  DeviceOwner tmp(e->cfg.device);  // drains the engine's stream before the block goes back, on every path
+  tmp.watch(e->stream);
+  NLSG_HIP(tmp.take(&block, cov_bytes + B * 8 + B * 4));
   double *cov_dev = reinterpret_cast<double *>(block);
   double *s2_dev = reinterpret_cast<double *>(block + cov_bytes);
   int32_t *ok_dev = reinterpret_cast<int32_t *>(block + cov_bytes + B * 8);
-  int rc = upload_theta(e, theta_host);  // (synchronous copies: nothing in flight if it fails)
-  if (rc) {
-    pool_free(block);
-    return rc;
-  }
+  int rc = upload_theta(e, theta_host);
+  if (rc) return rc;
   call_timing().init_ms = clk.lap();
   launch_gn_iter(e, 1, 0);
   if (scale == NLSG_LM_COV_RESIDUAL)
@@ -765,13 +697,13 @@ int nlsg_lm_covariance(nlsg_lm *e, const double *theta_host, int32_t scale, doub
     hipLaunchKernelGGL(lm_cov_kernel<false>, dim3(static_cast<unsigned>(B)), dim3(64), 0, e->stream, e->p,
                        cov_dev, s2_dev, ok_dev);
   hipError_t he = launches_status();
-  const hipError_t se = hipStreamSynchronize(e->stream);  // before the block can go back, on every path
+  const hipError_t se = hipStreamSynchronize(e->stream);
   if (he == hipSuccess) he = se;
   call_timing().iterate_ms = clk.lap();
   if (he == hipSuccess) he = hipMemcpy(cov_out_host, cov_dev, cov_bytes, hipMemcpyDeviceToHost);
   if (he == hipSuccess && s2_out_host) he = hipMemcpy(s2_out_host, s2_dev, B * 8, hipMemcpyDeviceToHost);
   if (he == hipSuccess && ok_out_host) he = hipMemcpy(ok_out_host, ok_dev, B * 4, hipMemcpyDeviceToHost);
-  pool_free(block);
+  tmp.release();
   NLSG_HIP(he);
   call_timing().readback_ms = clk.lap();
   return NLSG_OK;
@@ -782,22 +714,9 @@ int nlsg_lm_time_solve(nlsg_lm *e, const double *theta0_host, uint32_t repeats, 
   if (const int prc = params_ready(e)) return prc;
   if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  float total = 0.f;
-  for (uint32_t r = 0; r < repeats; r++) {
-    int rc = upload_theta(e, theta0_host);
-    if (rc) return rc;
-    NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-    rc = launch_solve(e);
-    if (rc) return rc;
-    NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-    NLSG_HIP(hipEventSynchronize(e->ev1));
-    NLSG_HIP(launches_status());
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    total += ms;
-  }
-  *ms_total = total;
-  return NLSG_OK;
+  return time_repeats(
+      e->stream, e->ev0, e->ev1, repeats, ms_total, [&]() -> int { return launch_solve(e); },
+      [&]() -> int { return upload_theta(e, theta0_host); });  // the start point again, outside the interval
 }
 
 // Times `repeats` launches of the dominant kernel of the Cholesky pipeline (f, g, H at theta0
@@ -810,22 +729,13 @@ int nlsg_lm_time_eval_kernel(nlsg_lm *e, const double *theta0_host, uint32_t rep
   NLSG_HIP(hipSetDevice(e->cfg.device));
   int rc = upload_theta(e, theta0_host);
   if (rc) return rc;
-  float total = 0.f;
-  for (uint32_t r = 0; r < repeats; r++) {
-    NLSG_HIP(hipEventRecord(e->ev0, e->stream));
+  return time_repeats(e->stream, e->ev0, e->ev1, repeats, ms_total, [&]() -> int {
     if (e->wide)
       launch_wide_eval(e, 1);
     else
       launch_gn_iter(e, 1, 0);
-    NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-    NLSG_HIP(hipEventSynchronize(e->ev1));
-    NLSG_HIP(launches_status());
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    total += ms;
-  }
-  *ms_total = total;
-  return NLSG_OK;
+    return NLSG_OK;
+  });
 }
 
 // Times `repeats` launches of the QR step kernel alone (stop tests, damped matrix, Givens QR,
@@ -841,20 +751,11 @@ int nlsg_lm_time_qr_kernel(nlsg_lm *e, const double *theta0_host, uint32_t repea
   if (rc) return rc;
   const dim3 grid(static_cast<unsigned>(e->p.batch));
   launch_gn_iter(e, 1, 0);
-  float total = 0.f;
-  for (uint32_t r = 0; r < repeats; r++) {
-    NLSG_HIP(hipEventRecord(e->ev0, e->stream));
+  return time_repeats(e->stream, e->ev0, e->ev1, repeats, ms_total, [&]() -> int {
     hipLaunchKernelGGL(lm_qr_step_kernel<kLmQrThreads>, grid, dim3(kLmQrThreads), sizeof(LmQrShared),
                        e->stream, e->p);
-    NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-    NLSG_HIP(hipEventSynchronize(e->ev1));
-    NLSG_HIP(launches_status());
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    total += ms;
-  }
-  *ms_total = total;
-  return NLSG_OK;
+    return NLSG_OK;
+  });
 }
 
 }  // extern "C"

@@ -1,27 +1,21 @@
 // nlsolver_amd/csrc/nlsg_nm.hip — host side of the batched Nelder-Mead engine + C-ABI.
 #include <cstdlib>
-#include <new>
 #include <vector>
 
+#include "nlsg_engine.h"
 #include "nlsg_nm_kernels.h"
 #include "nlsg_rtc.h"
 
 using namespace nlsg;
 
-struct nlsg_nm {
+struct nlsg_nm : EngineBase {  // (n_params: nlsg_nm_create_params, a row per start)
   NmRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it
   nlsg_nm_config cfg;
   NmParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   double *upper_dev = nullptr, *lower_dev = nullptr;
   size_t lds = 0;
   bool driver = false;  // n <= 128: nm_solve_driver_kernel (NLSG_NM_DRIVER=0: the phase-per-barrier kernel)
-  unsigned long long *phase_dev = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int32_t n_params = 0;          // nlsg_nm_create_params: the objective's run-time doubles per start
-  double *params_dev = nullptr;  // [batch][n_params]
-  bool params_set = false;
+  unsigned long long *phase_dev = nullptr;  // from the first nlsg_nm_phase_cycles on
 };
 
 namespace {
@@ -91,9 +85,7 @@ void launch(nlsg_nm *e) {
 
 // a parametrised engine solves nothing before its first rows
 int params_ready(const nlsg_nm *e) {
-  if (e->n_params > 0 && !e->params_set)
-    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_nm_set_params first", e->n_params);
-  return NLSG_OK;
+  return e->params_ready("the objective has %d parameters: call nlsg_nm_set_params first");
 }
 
 int upload_bounds(nlsg_nm *e, const double *upper_host, const double *lower_host) {
@@ -141,14 +133,8 @@ uint64_t nlsg_nm_lds_bytes(uint64_t dim, uint32_t flags) {
 
 int nlsg_nm_set_params(nlsg_nm *e, const double *params_host) {
   if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (e->n_params <= 0)
-    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_nm_create_params)");
-  NLSG_HIP(hipSetDevice(e->cfg.device));
-  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
-                          hipMemcpyHostToDevice, e->stream));
-  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
-  e->params_set = true;
-  return NLSG_OK;
+  return e->set_params(e->p.batch, params_host,
+                       "the engine's objective declares no parameters (nlsg_nm_create_params)");
 }
 
 static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *custom, nlsg_nm **out,
@@ -175,22 +161,9 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
     if (const int prc = check_custom_params(custom, nlsg_nm_lds_bytes(cfg->dim, cfg->flags), "nlsg_nm",
                                             "nlsg_nm_create_custom"))
       return prc;
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-  nlsg_nm *e = new (std::nothrow) nlsg_nm();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_nm *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
-  }
   NmParams &p = e->p;
   std::memset(&p, 0, sizeof p);
   const uint64_t B = cfg->batch, n = cfg->dim;
@@ -198,18 +171,16 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
   // (the parameter row is static LDS of the run-time compiled module, in front of this dynamic block)
   e->n_params = with_params ? custom->n_params : 0;
   e->lds = nm_launch_lds_bytes(n, nm_block_threads(n) / 64, seq, custom_params_lds_bytes(e->n_params));
-  hipError_t he = hipSuccess;
+  DeviceOwner &own = e->own;
+  hipError_t &he = own.err;
   const int chunks = nm_chunks(n);
-  if (he == hipSuccess && chunks > 1)  // the simplexes themselves: past what LDS holds
-    he = pool_malloc(reinterpret_cast<void **>(&p.simplex), B * (n + 1) * n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.x), B * n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.prob), B * sizeof(NmProblem));
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->upper_dev), n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->lower_dev), n * 8);
-  if (he == hipSuccess && e->n_params)
-    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * 8);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
+  if (chunks > 1) own.alloc(&p.simplex, B * (n + 1) * n * 8);  // the simplexes themselves: past what LDS holds
+  own.alloc(&p.x, B * n * 8);
+  own.alloc(&p.prob, B * sizeof(NmProblem));
+  own.alloc(&e->upper_dev, n * 8);
+  own.alloc(&e->lower_dev, n * 8);
+  e->alloc_params(B, e->n_params);
+  e->timing_events();
   {
     const char *sw = std::getenv("NLSG_NM_DRIVER");
     e->driver = chunks == 1 && !(sw && sw[0] == '0');
@@ -232,10 +203,9 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
     he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.solve),
                              hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->lds));
   }
-  if (he != hipSuccess) {
+  if (const int rc = e->setup_status()) {
     nlsg_nm_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP,
-                "device setup failed: %s", hipGetErrorString(he));
+    return rc;
   }
   p.upper = e->upper_dev;
   p.lower = e->lower_dev;
@@ -265,19 +235,9 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
 
 int nlsg_nm_destroy(nlsg_nm *e) {
   if (!e) return NLSG_OK;
-  hipSetDevice(e->cfg.device);
-  if (e->stream) hipStreamSynchronize(e->stream);
+  e->drain();
   rtc_release(&e->rtc);
-  pool_free(e->p.simplex);
-  pool_free(e->p.x);
-  pool_free(e->p.prob);
-  pool_free(e->upper_dev);
-  pool_free(e->lower_dev);
-  pool_free(e->phase_dev);
-  pool_free(e->params_dev);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   return NLSG_OK;
 }
@@ -324,7 +284,7 @@ int nlsg_nm_phase_cycles(nlsg_nm *e, const double *x0_host, uint64_t *cycles_hos
   // a measurement aid: its buffer exists from its first use on, and it profiles the unbounded
   // solve only (a bounded engine would run on whatever bounds its last minimize left behind)
   if (e->cfg.bounded) return fail(NLSG_ERR_UNSUPPORTED, "nlsg_nm_phase_cycles profiles unbounded engines");
-  if (!e->phase_dev) NLSG_HIP(pool_malloc(reinterpret_cast<void **>(&e->phase_dev), B * kNmPhases * 8));
+  if (!e->phase_dev) NLSG_HIP(e->own.take(&e->phase_dev, B * kNmPhases * 8));
   NLSG_HIP(hipMemcpy(e->p.x, x0_host, B * e->p.n * 8, hipMemcpyHostToDevice));
   NLSG_HIP(hipMemset(e->phase_dev, 0, B * kNmPhases * 8));
   e->p.phase = e->phase_dev;
@@ -340,20 +300,16 @@ int nlsg_nm_time_solve(nlsg_nm *e, const double *x0_host, uint32_t repeats, floa
   if (!e || !x0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  float total = 0.f;
-  for (uint32_t r = 0; r < repeats; r++) {
-    NLSG_HIP(hipMemcpy(e->p.x, x0_host, e->p.batch * e->p.n * 8, hipMemcpyHostToDevice));
-    NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-    launch(e);
-    NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-    NLSG_HIP(hipEventSynchronize(e->ev1));
-    NLSG_HIP(launches_status());
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    total += ms;
-  }
-  *ms_total = total;
-  return NLSG_OK;
+  return time_repeats(
+      e->stream, e->ev0, e->ev1, repeats, ms_total,
+      [&]() -> int {
+        launch(e);
+        return NLSG_OK;
+      },
+      [&]() -> int {  // the start point again, outside the interval
+        NLSG_HIP(hipMemcpy(e->p.x, x0_host, e->p.batch * e->p.n * 8, hipMemcpyHostToDevice));
+        return NLSG_OK;
+      });
 }
 
 }  // extern "C"

@@ -1,24 +1,17 @@
 // nlsolver_amd/csrc/nlsg_nmpso.hip — host side of the batched Nelder-Mead / PSO hybrid + C-ABI.
-#include <cstdlib>
-#include <new>
 #include <vector>
 
+#include "nlsg_engine.h"
 #include "nlsg_nmpso_kernels.h"
 #include "nlsg_rtc.h"
 
 using namespace nlsg;
 
-struct nlsg_nmpso {
+struct nlsg_nmpso : EngineBase {  // (n_params: nlsg_nmpso_create_params, a row per instance)
   nlsg_nmpso_config cfg;
   HybParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   double *upper_dev = nullptr, *lower_dev = nullptr, *zero_dev = nullptr;
   HybRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int32_t n_params = 0;          // nlsg_nmpso_create_params: the objective's run-time doubles per instance
-  double *params_dev = nullptr;  // [batch][n_params]
-  bool params_set = false;
 };
 
 namespace {
@@ -83,10 +76,7 @@ void launch(nlsg_nmpso *e) {
 
 // a parametrised engine solves nothing before its first rows
 int params_ready(const nlsg_nmpso *e) {
-  if (e->n_params > 0 && !e->params_set)
-    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_nmpso_set_params first",
-                e->n_params);
-  return NLSG_OK;
+  return e->params_ready("the objective has %d parameters: call nlsg_nmpso_set_params first");
 }
 
 int upload_bounds(nlsg_nmpso *e, const double *lower_host, const double *upper_host) {
@@ -136,14 +126,7 @@ uint64_t nlsg_nmpso_lds_bytes(uint64_t dim) {
 
 int nlsg_nmpso_set_params(nlsg_nmpso *e, const double *params_host) {
   if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (e->n_params <= 0)
-    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_nmpso_create_params)");
-  NLSG_HIP(hipSetDevice(e->cfg.device));
-  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
-                          hipMemcpyHostToDevice, e->stream));
-  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
-  e->params_set = true;
-  return NLSG_OK;
+  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (nlsg_nmpso_create_params)");
 }
 
 }  // extern "C"
@@ -169,39 +152,24 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
     if (const int prc = check_custom_params(custom, nlsg_nmpso_lds_bytes(cfg->dim), "nlsg_nmpso",
                                             "nlsg_nmpso_create_custom"))
       return prc;
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-  nlsg_nmpso *e = new (std::nothrow) nlsg_nmpso();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_nmpso *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
   e->n_params = with_params ? custom->n_params : 0;
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
-  }
   HybParams &p = e->p;
   std::memset(&p, 0, sizeof p);
   const uint64_t B = cfg->batch, n = cfg->dim, rows = B * (3 * n + 1);
-  hipError_t he = hipSuccess;
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.x), B * n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.pos), rows * n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.vel), rows * n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.prob), B * sizeof(HybProblem));
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->upper_dev), n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->lower_dev), n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->zero_dev), 16);
-  if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
-  if (he == hipSuccess && e->n_params)
-    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * 8);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
+  DeviceOwner &own = e->own;
+  hipError_t &he = own.err;
+  own.alloc(&p.x, B * n * 8);
+  own.alloc(&p.pos, rows * n * 8);
+  own.alloc(&p.vel, rows * n * 8);
+  own.alloc(&p.prob, B * sizeof(HybProblem));
+  own.alloc(&e->upper_dev, n * 8);
+  own.alloc(&e->lower_dev, n * 8);
+  own.zeroed(&e->zero_dev, 16);
+  e->alloc_params(B, e->n_params);
+  e->timing_events();
   if (he == hipSuccess && n > kHybMaxN && !custom) {
     switch (cfg->objective) {
       case NLSG_OBJ_ROSENBROCK: he = allow_wide_lds<NLSG_OBJ_ROSENBROCK>(n); break;
@@ -210,10 +178,9 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
       default: he = allow_wide_lds<NLSG_OBJ_RASTRIGIN>(n); break;
     }
   }
-  if (he != hipSuccess) {
+  if (const int rc = e->setup_status()) {
     nlsg_nmpso_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP,
-                "device setup failed: %s", hipGetErrorString(he));
+    return rc;
   }
   if (custom) {
     const int rc2 = rtc_build_nmpso(custom, wide_chunks(n), &e->rtc);
@@ -250,20 +217,9 @@ extern "C" {
 
 int nlsg_nmpso_destroy(nlsg_nmpso *e) {
   if (!e) return NLSG_OK;
-  hipSetDevice(e->cfg.device);
-  if (e->stream) hipStreamSynchronize(e->stream);
+  e->drain();
   rtc_release(&e->rtc);
-  pool_free(e->p.x);
-  pool_free(e->p.pos);
-  pool_free(e->p.vel);
-  pool_free(e->p.prob);
-  pool_free(e->upper_dev);
-  pool_free(e->lower_dev);
-  pool_free(e->zero_dev);
-  pool_free(e->params_dev);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   return NLSG_OK;
 }
@@ -306,20 +262,16 @@ int nlsg_nmpso_time_solve(nlsg_nmpso *e, const double *x0_host, uint32_t repeats
   if (const int prc = params_ready(e)) return prc;
   if (e->p.bounded) return fail(NLSG_ERR_UNSUPPORTED, "timing aid of the unbounded overloads");
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  float total = 0.f;
-  for (uint32_t r = 0; r < repeats; r++) {
-    NLSG_HIP(hipMemcpy(e->p.x, x0_host, e->p.batch * e->p.n * 8, hipMemcpyHostToDevice));
-    NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-    launch(e);
-    NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-    NLSG_HIP(hipEventSynchronize(e->ev1));
-    NLSG_HIP(launches_status());
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    total += ms;
-  }
-  *ms_total = total;
-  return NLSG_OK;
+  return time_repeats(
+      e->stream, e->ev0, e->ev1, repeats, ms_total,
+      [&]() -> int {
+        launch(e);
+        return NLSG_OK;
+      },
+      [&]() -> int {  // the start point again, outside the interval
+        NLSG_HIP(hipMemcpy(e->p.x, x0_host, e->p.batch * e->p.n * 8, hipMemcpyHostToDevice));
+        return NLSG_OK;
+      });
 }
 
 }  // extern "C"

@@ -2,20 +2,18 @@
 // (include/nlsg_c_api.h). Same structure as nlsg_de.hip. No CPU fallback.
 #include <algorithm>
 #include <cmath>
-#include <new>
 #include <vector>
 
 #include "nlsg_comm.h"
+#include "nlsg_engine.h"
 #include "nlsg_pso_kernels.h"
 #include "nlsg_rtc.h"
 
 using namespace nlsg;
 
-struct nlsg_pso {
+struct nlsg_pso : EngineBase {
   nlsg_pso_config cfg;
   PsoParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   double *lower_dev = nullptr, *upper_dev = nullptr, *zero_dev = nullptr, *tab_dev = nullptr;
   ShardLocal *loc = nullptr;
   ShardComm *comm = nullptr;  // set by nlsg_pso_comm_attach
@@ -26,7 +24,6 @@ struct nlsg_pso {
   bool long_rows = false;  // D > 1024: rows streamed in segments (pso_*_long_kernel)
   unsigned move_grid_cap = 2048;  // workgroups of the striding move kernel: 8 per CU (move_blocks_per_cu)
   bool initialised = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
 namespace {
@@ -247,10 +244,7 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
 int nlsg_pso_create(const nlsg_pso_config *cfg, nlsg_pso **out) {
   if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_pso_create_custom");
-  PhaseClock clk;
-  const int rc = pso_create(cfg, nullptr, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return pso_create(cfg, nullptr, out); });
 }
 
 int nlsg_pso_create_custom(const nlsg_pso_config *cfg, const nlsg_custom_objective *obj,
@@ -259,10 +253,7 @@ int nlsg_pso_create_custom(const nlsg_pso_config *cfg, const nlsg_custom_objecti
   if (cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
   if (const int prc = reject_custom_params(obj)) return prc;
-  PhaseClock clk;
-  const int rc = pso_create(cfg, obj, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return pso_create(cfg, obj, out); });
 }
 
 static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *custom, nlsg_pso **out) {
@@ -287,12 +278,8 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
                 (unsigned long long)cfg->n_particles);
   if (cfg->shard_n > (1ull << 32))
     return fail(NLSG_ERR_UNSUPPORTED, "shard_n > 2^32 particles per engine");
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-
-  nlsg_pso *e = new (std::nothrow) nlsg_pso();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_pso *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
   const uint64_t D = cfg->dim, n = cfg->shard_n;
   e->chunks = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
@@ -300,42 +287,28 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
   e->group = D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 0;
   if (const char *g = std::getenv("NLSG_PSO_GROUPS"))  // A/B switch: 0 = one particle per wave at any D
     if (g[0] == '0') e->group = 0;
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
-  }
   PsoParams &p = e->p;
   std::memset(&p, 0, sizeof p);
-  auto alloc = [&](void **ptr, size_t bytes) { return pool_malloc(ptr, bytes ? bytes : 8); };
+  DeviceOwner &own = e->own;
+  hipError_t &he = own.err;
+  auto alloc = [&](auto **ptr, size_t bytes) { own.alloc(ptr, bytes ? bytes : 8); };
   const bool vanilla = cfg->type == NLSG_PSO_VANILLA;
   const size_t rows = n * D * sizeof(double);
-  hipError_t he = hipSuccess;
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.pos), rows);
-  if (he == hipSuccess && vanilla) he = alloc(reinterpret_cast<void **>(&p.vel), rows);
-  if (he == hipSuccess && vanilla) he = alloc(reinterpret_cast<void **>(&p.pbest_pos), rows);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.pbest_val), n * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.cur_val), n * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.gbest_x), D * sizeof(double));
-  if (he == hipSuccess) he = hipMemset(p.gbest_x, 0, D * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->lower_dev), D * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->upper_dev), D * sizeof(double));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->zero_dev), 16);
-  if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.state), sizeof(PsoState));
+  alloc(&p.pos, rows);
+  if (vanilla) alloc(&p.vel, rows);
+  if (vanilla) alloc(&p.pbest_pos, rows);
+  alloc(&p.pbest_val, n * sizeof(double));
+  alloc(&p.cur_val, n * sizeof(double));
+  own.zeroed(&p.gbest_x, D * sizeof(double));
+  alloc(&e->lower_dev, D * sizeof(double));
+  alloc(&e->upper_dev, D * sizeof(double));
+  own.zeroed(&e->zero_dev, 16);
+  alloc(&p.state, sizeof(PsoState));
   p.ntiles = static_cast<uint32_t>((n + kTile - 1) / kTile);
-  if (he == hipSuccess)
-    he = alloc(reinterpret_cast<void **>(&p.part), p.ntiles * sizeof(TilePartial));
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&p.ticket), 8);
-  if (he == hipSuccess) he = hipMemset(p.ticket, 0, 8);
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->loc), sizeof(ShardLocal));
-  if (he == hipSuccess)
-    he = alloc(reinterpret_cast<void **>(&e->rec), (kRecHeader + D) * sizeof(double));
+  alloc(&p.part, p.ntiles * sizeof(TilePartial));
+  own.zeroed(&p.ticket, 8);
+  alloc(&e->loc, sizeof(ShardLocal));
+  alloc(&e->rec, (kRecHeader + D) * sizeof(double));
   // inertia schedule pow(inertia, iter) (:2613) computed with the host libm, as the
   // reference does, so the device uses bit-identical values
   // (max_iter + 1 entries — guarded against wrapping — or up to the first fixed point of the
@@ -354,15 +327,13 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
     }
   }
   p.tab_len = tab.size();
-  if (he == hipSuccess) he = alloc(reinterpret_cast<void **>(&e->tab_dev), p.tab_len * sizeof(double));
+  alloc(&e->tab_dev, p.tab_len * sizeof(double));
   if (he == hipSuccess)
     he = hipMemcpy(e->tab_dev, tab.data(), p.tab_len * sizeof(double), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
-  if (he != hipSuccess) {
+  e->timing_events();
+  if (const int rc = e->setup_status("device allocation failed: %s")) {
     nlsg_pso_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP,
-                "device allocation failed: %s", hipGetErrorString(he));
+    return rc;
   }
   p.lower = e->lower_dev;
   p.upper = e->upper_dev;
@@ -401,28 +372,10 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
 int nlsg_pso_destroy(nlsg_pso *e) {
   if (!e) return NLSG_OK;
   PhaseClock clk;
-  hipSetDevice(e->cfg.device);
-  if (e->stream) hipStreamSynchronize(e->stream);
-  pool_free(e->p.pos);
-  pool_free(e->p.vel);
-  pool_free(e->p.pbest_pos);
-  pool_free(e->p.pbest_val);
-  pool_free(e->p.cur_val);
-  pool_free(e->p.gbest_x);
-  pool_free(e->p.state);
-  pool_free(e->p.part);
-  pool_free(e->p.ticket);
-  pool_free(e->lower_dev);
-  pool_free(e->upper_dev);
-  pool_free(e->zero_dev);
-  pool_free(e->tab_dev);
-  pool_free(e->loc);
+  e->drain();
   comm_detach(e->comm);
   rtc_release(&e->rtc);
-  pool_free(e->rec);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   call_timing().destroy_ms = clk.lap();
   return NLSG_OK;
@@ -529,12 +482,11 @@ int nlsg_pso_time_move_kernel(nlsg_pso *e, uint32_t launches, float *ms_total) {
   PsoState s;
   int rc = read_state(e, &s);
   if (rc) return rc;
-  NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-  for (uint32_t k = 0; k < launches; k++) launch_move(e, 1, s.iter + k);
-  NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-  NLSG_HIP(hipEventSynchronize(e->ev1));
-  NLSG_HIP(launches_status());
-  NLSG_HIP(hipEventElapsedTime(ms_total, e->ev0, e->ev1));
+  rc = time_repeats(e->stream, e->ev0, e->ev1, 1, ms_total, [&]() -> int {
+    for (uint32_t k = 0; k < launches; k++) launch_move(e, 1, s.iter + k);
+    return NLSG_OK;
+  });
+  if (rc) return rc;
   e->initialised = false;  // the swarm moved without best bookkeeping: re-init before solving
   return NLSG_OK;
 }

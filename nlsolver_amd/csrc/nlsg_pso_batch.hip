@@ -5,10 +5,9 @@
 // fallback: a shape whose swarm does not fit a workgroup's LDS is NLSG_ERR_UNSUPPORTED.
 #include <algorithm>
 #include <cmath>
-#include <new>
 #include <vector>
 
-#include "nlsg_common.h"
+#include "nlsg_engine.h"
 // nlsg_pso_kernels.h defines the turn engine's non-template kernels with external linkage, and
 // nlsg_pso.hip owns them. This file needs the header's types and device functions only
 // (PsoState, PsoParams, pso_apply_pending, pso_finish_turn, pso_inertia_at), so here its kernels
@@ -23,11 +22,9 @@
 
 using namespace nlsg;
 
-struct nlsg_pso_batch {
+struct nlsg_pso_batch : EngineBase {  // (n_params: a row per solve, nlsg_pso_batch_set_params)
   nlsg_pso_batch_config cfg;
   PsoBatchParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   size_t lds = 0;
   int group = 0;  // lanes per particle: 4 / 8 / 16 / 32, or 64 = one wave per particle
   const void *init_fn = nullptr, *turn_fn = nullptr;  // built-in objectives
@@ -35,11 +32,7 @@ struct nlsg_pso_batch {
   uint64_t turns_per_launch = 0;
   uint64_t *seeds_dev = nullptr;
   double *lower_dev = nullptr, *upper_dev = nullptr, *tab_dev = nullptr;
-  int32_t n_params = 0;          // run-time parameters per solve (custom objectives), 0 = none
-  double *params_dev = nullptr;  // [batch][n_params], filled by nlsg_pso_batch_set_params
-  bool params_set = false;
   bool initialised = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
 namespace {
@@ -95,10 +88,7 @@ void launch_turns(nlsg_pso_batch *e, uint64_t turns) {
 }
 
 int params_ready(const nlsg_pso_batch *e) {
-  if (e->n_params > 0 && !e->params_set)
-    return fail(NLSG_ERR_STATE, "the objective has %d parameters: nlsg_pso_batch_set_params has not been called",
-                e->n_params);
-  return NLSG_OK;
+  return e->params_ready("the objective has %d parameters: nlsg_pso_batch_set_params has not been called");
 }
 
 int upload_inputs(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
@@ -202,12 +192,8 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
   if (cfg->batch >= (1ull << 23)) return fail(NLSG_ERR_UNSUPPORTED, "batch must be < 2^23 solves");
   if (!custom && (cfg->objective < 0 || cfg->objective > NLSG_OBJ_RASTRIGIN))
     return fail(NLSG_ERR_INVALID_ARG, "unknown objective %d", cfg->objective);
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-
-  nlsg_pso_batch *e = new (std::nothrow) nlsg_pso_batch();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_pso_batch *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
   const uint64_t B = cfg->batch, n = cfg->n_particles, D = cfg->dim;
   const bool vanilla = cfg->type == NLSG_PSO_VANILLA;
@@ -215,32 +201,23 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
   e->n_params = n_params;
   e->group = D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 64;  // the turn engine's mappings
   e->turns_per_launch = cfg->turns_per_launch ? cfg->turns_per_launch : kPsoBatchTurnsPerLaunch;
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
-  }
   PsoBatchParams &p = e->p;
   std::memset(&p, 0, sizeof p);
   PsoParams &q = p.q;
-  hipError_t he = pool_malloc(reinterpret_cast<void **>(&q.pos), B * n * D * 8);
-  if (he == hipSuccess && vanilla) he = pool_malloc(reinterpret_cast<void **>(&q.vel), B * n * D * 8);
-  if (he == hipSuccess && vanilla) he = pool_malloc(reinterpret_cast<void **>(&q.pbest_pos), B * n * D * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&q.pbest_val), B * n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&q.cur_val), B * n * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&q.gbest_x), B * D * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&q.state), B * sizeof(PsoState));
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.n_done), 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->seeds_dev), B * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->lower_dev), B * D * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->upper_dev), B * D * 8);
-  if (he == hipSuccess && n_params)
-    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(n_params) * 8);
+  DeviceOwner &own = e->own;
+  hipError_t &he = own.err;
+  own.alloc(&q.pos, B * n * D * 8);
+  if (vanilla) own.alloc(&q.vel, B * n * D * 8);
+  if (vanilla) own.alloc(&q.pbest_pos, B * n * D * 8);
+  own.alloc(&q.pbest_val, B * n * 8);
+  own.alloc(&q.cur_val, B * n * 8);
+  own.alloc(&q.gbest_x, B * D * 8);
+  own.alloc(&q.state, B * sizeof(PsoState));
+  own.alloc(&p.n_done, 8);
+  own.alloc(&e->seeds_dev, B * 8);
+  own.alloc(&e->lower_dev, B * D * 8);
+  own.alloc(&e->upper_dev, B * D * 8);
+  e->alloc_params(B, n_params);
   // the inertia schedule pow(inertia, iter) (:2613) from the host libm, exactly as nlsg_pso_create
   // builds it (max_iter + 1 entries, or up to the first fixed point; at most 2^22)
   const uint64_t want = cfg->max_iter == ~0ull ? ~0ull : cfg->max_iter + 1;
@@ -257,10 +234,9 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
     }
   }
   q.tab_len = tab.size();
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->tab_dev), q.tab_len * 8);
+  own.alloc(&e->tab_dev, q.tab_len * 8);
   if (he == hipSuccess) he = hipMemcpy(e->tab_dev, tab.data(), q.tab_len * 8, hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
+  e->timing_events();
   p.seeds = e->seeds_dev;
   p.params = e->params_dev;
   p.batch = B;
@@ -300,10 +276,9 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
                              hipFuncAttributeMaxDynamicSharedMemorySize,
                              static_cast<int>(kPsoBatchLdsBudget - params_lds));
   }
-  if (he != hipSuccess) {
+  if (const int rc = e->setup_status()) {
     nlsg_pso_batch_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP, "device setup failed: %s",
-                hipGetErrorString(he));
+    return rc;
   }
   *out = e;
   return NLSG_OK;
@@ -320,10 +295,7 @@ uint64_t nlsg_pso_batch_lds_bytes(uint64_t n_particles, uint64_t dim, int32_t ty
 int nlsg_pso_batch_create(const nlsg_pso_batch_config *cfg, nlsg_pso_batch **out) {
   if (cfg && out && cfg->struct_size == sizeof(nlsg_pso_batch_config) && cfg->objective == NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_pso_batch_create_custom");
-  PhaseClock clk;
-  const int rc = pso_batch_create(cfg, nullptr, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return pso_batch_create(cfg, nullptr, out); });
 }
 
 int nlsg_pso_batch_create_custom(const nlsg_pso_batch_config *cfg, const nlsg_custom_objective *obj,
@@ -331,34 +303,15 @@ int nlsg_pso_batch_create_custom(const nlsg_pso_batch_config *cfg, const nlsg_cu
   if (!cfg || !obj || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (cfg->struct_size == sizeof(nlsg_pso_batch_config) && cfg->objective != NLSG_OBJ_CUSTOM)
     return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  PhaseClock clk;
-  const int rc = pso_batch_create(cfg, obj, out);
-  call_timing().create_ms = clk.lap();
-  return rc;
+  return timed_create([&] { return pso_batch_create(cfg, obj, out); });
 }
 
 int nlsg_pso_batch_destroy(nlsg_pso_batch *e) {
   if (!e) return NLSG_OK;
   PhaseClock clk;
-  hipSetDevice(e->cfg.device);
-  if (e->stream) hipStreamSynchronize(e->stream);  // before the first pool_free: nothing in flight
+  e->drain();
   rtc_release(&e->rtc);
-  pool_free(e->p.q.pos);
-  pool_free(e->p.q.vel);
-  pool_free(e->p.q.pbest_pos);
-  pool_free(e->p.q.pbest_val);
-  pool_free(e->p.q.cur_val);
-  pool_free(e->p.q.gbest_x);
-  pool_free(e->p.q.state);
-  pool_free(e->p.n_done);
-  pool_free(e->seeds_dev);
-  pool_free(e->lower_dev);
-  pool_free(e->upper_dev);
-  pool_free(e->params_dev);
-  pool_free(e->tab_dev);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   call_timing().destroy_ms = clk.lap();
   return NLSG_OK;
@@ -366,14 +319,7 @@ int nlsg_pso_batch_destroy(nlsg_pso_batch *e) {
 
 int nlsg_pso_batch_set_params(nlsg_pso_batch *e, const double *params_host) {
   if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (e->n_params <= 0)
-    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (n_params == 0)");
-  NLSG_HIP(hipSetDevice(e->cfg.device));
-  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
-                          hipMemcpyHostToDevice, e->stream));
-  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
-  e->params_set = true;
-  return NLSG_OK;
+  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (n_params == 0)");
 }
 
 int nlsg_pso_batch_init(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
@@ -486,23 +432,18 @@ int nlsg_pso_batch_time_solve(nlsg_pso_batch *e, const double *lower_host, const
   int rc = upload_inputs(e, lower_host, upper_host, seeds_host);
   if (rc) return rc;
   const uint64_t B = e->p.batch, D = e->p.q.D;
-  float total = 0.f;
-  for (uint32_t r = 0; r < repeats; r++) {
-    NLSG_HIP(hipMemsetAsync(e->p.n_done, 0, sizeof(uint32_t), e->stream));
-    NLSG_HIP(hipMemsetAsync(e->p.q.gbest_x, 0, B * D * 8, e->stream));
-    NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-    launch_init(e);
-    e->initialised = true;
-    rc = run_to_done(e);
-    if (rc) return rc;
-    NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-    NLSG_HIP(hipEventSynchronize(e->ev1));
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    total += ms;
-  }
-  *ms_total = total;
-  return NLSG_OK;
+  return time_repeats(
+      e->stream, e->ev0, e->ev1, repeats, ms_total,
+      [&]() -> int {
+        launch_init(e);
+        e->initialised = true;
+        return run_to_done(e);
+      },
+      [&]() -> int {  // the state reset, outside the interval
+        NLSG_HIP(hipMemsetAsync(e->p.n_done, 0, sizeof(uint32_t), e->stream));
+        NLSG_HIP(hipMemsetAsync(e->p.q.gbest_x, 0, B * D * 8, e->stream));
+        return NLSG_OK;
+      });
 }
 
 }  // extern "C"

@@ -1,27 +1,20 @@
 // nlsolver_amd/csrc/nlsg_sann.hip — host side of the batched simulated-annealing engine + C-ABI.
-#include <cstdlib>
-#include <new>
 #include <vector>
 
+#include "nlsg_engine.h"
 #include "nlsg_rtc.h"
 #include "nlsg_sann_kernels.h"
 
 using namespace nlsg;
 
-struct nlsg_sann {
+struct nlsg_sann : EngineBase {  // (n_params: nlsg_sann_create_params, a row per chain)
   nlsg_sann_config cfg;
   SannParams p;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
   double *zero_dev = nullptr;
   int chunks = 0;
   int group = 0;  // lanes per chain when several chains share a wave (dim <= 64), else 0
   SannRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it
-  int32_t n_params = 0;          // nlsg_sann_create_params: the objective's run-time doubles per chain
-  double *params_dev = nullptr;  // [batch][n_params]
-  bool params_set = false;
-  unsigned lds = 0;              // dynamic LDS of a launch: the parameter rows (0 without parameters)
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  unsigned lds = 0;  // dynamic LDS of a launch: the parameter rows (0 without parameters)
 };
 
 namespace {
@@ -43,9 +36,7 @@ int sann_group_for(uint64_t D, int64_t n_params) {
 }
 // a parametrised engine launches nothing before its first rows
 int params_ready(const nlsg_sann *e) {
-  if (e->n_params > 0 && !e->params_set)
-    return fail(NLSG_ERR_STATE, "the objective has %d parameters: call nlsg_sann_set_params first", e->n_params);
-  return NLSG_OK;
+  return e->params_ready("the objective has %d parameters: call nlsg_sann_set_params first");
 }
 
 #define SANN_FOR_CHUNKS(OBJ, chunks, CALL) \
@@ -202,14 +193,7 @@ uint64_t nlsg_sann_lds_bytes(uint64_t dim, int32_t n_params) {
 
 int nlsg_sann_set_params(nlsg_sann *e, const double *params_host) {
   if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (e->n_params <= 0)
-    return fail(NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters (nlsg_sann_create_params)");
-  NLSG_HIP(hipSetDevice(e->cfg.device));
-  NLSG_HIP(hipMemcpyAsync(e->params_dev, params_host, e->p.batch * static_cast<uint64_t>(e->n_params) * 8,
-                          hipMemcpyHostToDevice, e->stream));
-  NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffer is borrowed for this call only
-  e->params_set = true;
-  return NLSG_OK;
+  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (nlsg_sann_create_params)");
 }
 
 }  // extern "C"
@@ -233,22 +217,9 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
   if (with_params)  // (a row per wave, four to the block, always fits; the packed kernel's rows: sann_group_for)
     if (const int prc = check_custom_params(custom, kSannTableBytes, "nlsg_sann", "nlsg_sann_create_custom", 4))
       return prc;
-  int rc = check_device(cfg->device);
-  if (rc) return rc;
-  NLSG_HIP(hipSetDevice(cfg->device));
-  nlsg_sann *e = new (std::nothrow) nlsg_sann();
-  if (!e) return fail(NLSG_ERR_OOM, "host allocation failed");
+  nlsg_sann *e = nullptr;
+  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
   e->cfg = *cfg;
-  if (cfg->stream) {
-    e->stream = borrowed_stream(cfg->stream);
-  } else {
-    hipError_t he = pool_stream_get(&e->stream);
-    if (he != hipSuccess) {
-      delete e;
-      return fail(NLSG_ERR_HIP, "hipStreamCreate failed: %s", hipGetErrorString(he));
-    }
-    e->own_stream = true;
-  }
   const uint64_t B = cfg->batch, D = cfg->dim;
   e->chunks = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
   e->n_params = with_params ? custom->n_params : 0;
@@ -256,21 +227,17 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
   e->lds = static_cast<unsigned>(nlsg_sann_lds_bytes(D, e->n_params));
   SannParams &p = e->p;
   std::memset(&p, 0, sizeof p);
-  hipError_t he = hipSuccess;
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.x), B * D * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.p), B * D * 8);
-  if (he == hipSuccess && D > 1024) he = pool_malloc(reinterpret_cast<void **>(&p.trial), B * D * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&p.prob), B * sizeof(SannProblem));
-  if (he == hipSuccess && e->n_params)
-    he = pool_malloc(reinterpret_cast<void **>(&e->params_dev), B * static_cast<uint64_t>(e->n_params) * 8);
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&e->zero_dev), 16);
-  if (he == hipSuccess) he = hipMemset(e->zero_dev, 0, 16);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev0);
-  if (he == hipSuccess) he = hipEventCreate(&e->ev1);
-  if (he != hipSuccess) {
+  DeviceOwner &own = e->own;
+  own.alloc(&p.x, B * D * 8);
+  own.alloc(&p.p, B * D * 8);
+  if (D > 1024) own.alloc(&p.trial, B * D * 8);
+  own.alloc(&p.prob, B * sizeof(SannProblem));
+  e->alloc_params(B, e->n_params);
+  own.zeroed(&e->zero_dev, 16);
+  e->timing_events();
+  if (const int rc = e->setup_status()) {
     nlsg_sann_destroy(e);
-    return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP,
-                "device setup failed: %s", hipGetErrorString(he));
+    return rc;
   }
   if (custom) {
     const int rc2 = rtc_build_sann(custom, D > 1024 ? 0 : e->chunks, D % 2 == 0, e->group, &e->rtc);
@@ -281,8 +248,8 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
     // (the module API's counterpart of hipFuncSetAttribute on a kernel symbol: the rows can pass the 64 KiB
     // a launch may take without it)
     if (e->lds > 64 * 1024) {
-      he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.anneal),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->lds));
+      const hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.anneal),
+                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->lds));
       if (he != hipSuccess) {
         nlsg_sann_destroy(e);
         return fail(NLSG_ERR_HIP, "raising the kernel's dynamic LDS limit failed: %s", hipGetErrorString(he));
@@ -306,18 +273,9 @@ extern "C" {
 
 int nlsg_sann_destroy(nlsg_sann *e) {
   if (!e) return NLSG_OK;
-  hipSetDevice(e->cfg.device);
-  if (e->stream) hipStreamSynchronize(e->stream);
+  e->drain();
   rtc_release(&e->rtc);
-  pool_free(e->p.x);
-  pool_free(e->p.p);
-  pool_free(e->p.trial);
-  pool_free(e->p.prob);
-  pool_free(e->zero_dev);
-  pool_free(e->params_dev);
-  if (e->ev0) hipEventDestroy(e->ev0);
-  if (e->ev1) hipEventDestroy(e->ev1);
-  if (e->own_stream && e->stream) pool_stream_put(e->cfg.device, e->stream);
+  e->close();
   delete e;
   return NLSG_OK;
 }
@@ -356,20 +314,16 @@ int nlsg_sann_time_solve(nlsg_sann *e, const double *x0_host, uint32_t repeats, 
   if (!e || !x0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (const int prc = params_ready(e)) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  float total = 0.f;
-  for (uint32_t r = 0; r < repeats; r++) {
-    NLSG_HIP(hipMemcpy(e->p.x, x0_host, e->p.batch * e->p.D * 8, hipMemcpyHostToDevice));
-    NLSG_HIP(hipEventRecord(e->ev0, e->stream));
-    launch_solve(e);
-    NLSG_HIP(hipEventRecord(e->ev1, e->stream));
-    NLSG_HIP(hipEventSynchronize(e->ev1));
-    NLSG_HIP(launches_status());
-    float ms = 0.f;
-    NLSG_HIP(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    total += ms;
-  }
-  *ms_total = total;
-  return NLSG_OK;
+  return time_repeats(
+      e->stream, e->ev0, e->ev1, repeats, ms_total,
+      [&]() -> int {
+        launch_solve(e);
+        return NLSG_OK;
+      },
+      [&]() -> int {  // the start point again, outside the interval
+        NLSG_HIP(hipMemcpy(e->p.x, x0_host, e->p.batch * e->p.D * 8, hipMemcpyHostToDevice));
+        return NLSG_OK;
+      });
 }
 
 }  // extern "C"

@@ -3,6 +3,8 @@
 
 #include <algorithm>
 
+#include "nlsg_engine.h"
+
 using namespace nlsg;
 
 namespace {
@@ -83,27 +85,26 @@ int nlsg_tinyqr_lm(const double *X_host, const double *y_host, uint64_t batch, u
   if (rc) return rc;
   double *X = nullptr, *y = nullptr, *beta = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t he = pool_malloc(reinterpret_cast<void **>(&X), batch * n * p * sizeof(double));
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&y), batch * n * sizeof(double));
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&beta), batch * p * sizeof(double));
-  if (he == hipSuccess) he = hipEventCreate(&e0);
-  if (he == hipSuccess) he = hipEventCreate(&e1);
+  DeviceOwner tmp(device);  // this call's blocks and events; the null stream is what it launches on
+  hipError_t &he = tmp.err;
+  tmp.watch(nullptr);
+  tmp.alloc(&X, batch * n * p * sizeof(double));
+  tmp.alloc(&y, batch * n * sizeof(double));
+  tmp.alloc(&beta, batch * p * sizeof(double));
+  tmp.event(&e0);
+  tmp.event(&e1);
   if (he == hipSuccess) he = hipMemcpy(X, X_host, batch * n * p * sizeof(double), hipMemcpyHostToDevice);
   if (he == hipSuccess) he = hipMemcpy(y, y_host, batch * n * sizeof(double), hipMemcpyHostToDevice);
-  if (he == hipSuccess) he = hipEventRecord(e0, nullptr);
   if (he == hipSuccess) {
-    launch(X, y, beta, batch, n, p, tol, nullptr);
-    he = launches_status();
+    float ms = 0.f;
+    rc = time_repeats(nullptr, e0, e1, 1, &ms, [&]() -> int {
+      launch(X, y, beta, batch, n, p, tol, nullptr);
+      return NLSG_OK;
+    });
+    if (rc) return rc;
+    if (ms_kernel) *ms_kernel = ms;
+    he = hipMemcpy(beta_host, beta, batch * p * sizeof(double), hipMemcpyDeviceToHost);
   }
-  if (he == hipSuccess) he = hipEventRecord(e1, nullptr);
-  if (he == hipSuccess) he = hipEventSynchronize(e1);
-  if (he == hipSuccess && ms_kernel) he = hipEventElapsedTime(ms_kernel, e0, e1);
-  if (he == hipSuccess) he = hipMemcpy(beta_host, beta, batch * p * sizeof(double), hipMemcpyDeviceToHost);
-  pool_free(X);
-  pool_free(y);
-  pool_free(beta);
-  if (e0) hipEventDestroy(e0);
-  if (e1) hipEventDestroy(e1);
   if (he != hipSuccess)
     return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP, "nlsg_tinyqr_lm failed: %s",
                 hipGetErrorString(he));
@@ -130,12 +131,15 @@ int nlsg_tinyqr_qr(const double *X_host, const double *y_host, uint64_t batch, u
   const uint64_t W = n + p, per = n * W * sizeof(double);
   const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(batch, (2ull << 30) / per));
   double *X = nullptr, *y = nullptr, *work = nullptr, *Q = nullptr, *R = nullptr, *beta = nullptr;
-  hipError_t he = pool_malloc(reinterpret_cast<void **>(&X), batch * n * p * sizeof(double));
-  if (he == hipSuccess && y_host) he = pool_malloc(reinterpret_cast<void **>(&y), batch * n * sizeof(double));
-  if (he == hipSuccess) he = pool_malloc(reinterpret_cast<void **>(&work), chunk * per);
-  if (he == hipSuccess && Q_host) he = pool_malloc(reinterpret_cast<void **>(&Q), batch * n * p * sizeof(double));
-  if (he == hipSuccess && R_host) he = pool_malloc(reinterpret_cast<void **>(&R), batch * p * p * sizeof(double));
-  if (he == hipSuccess && beta_host) he = pool_malloc(reinterpret_cast<void **>(&beta), batch * p * sizeof(double));
+  DeviceOwner tmp(device);
+  hipError_t &he = tmp.err;
+  tmp.watch(nullptr);
+  tmp.alloc(&X, batch * n * p * sizeof(double));
+  if (y_host) tmp.alloc(&y, batch * n * sizeof(double));
+  tmp.alloc(&work, chunk * per);
+  if (Q_host) tmp.alloc(&Q, batch * n * p * sizeof(double));
+  if (R_host) tmp.alloc(&R, batch * p * p * sizeof(double));
+  if (beta_host) tmp.alloc(&beta, batch * p * sizeof(double));
   if (he == hipSuccess) he = hipMemcpy(X, X_host, batch * n * p * sizeof(double), hipMemcpyHostToDevice);
   if (he == hipSuccess && y_host) he = hipMemcpy(y, y_host, batch * n * sizeof(double), hipMemcpyHostToDevice);
   for (uint64_t s0 = 0; he == hipSuccess && s0 < batch; s0 += chunk) {
@@ -164,12 +168,6 @@ int nlsg_tinyqr_qr(const double *X_host, const double *y_host, uint64_t batch, u
   if (he == hipSuccess && Q_host) he = hipMemcpy(Q_host, Q, batch * n * p * sizeof(double), hipMemcpyDeviceToHost);
   if (he == hipSuccess && R_host) he = hipMemcpy(R_host, R, batch * p * p * sizeof(double), hipMemcpyDeviceToHost);
   if (he == hipSuccess && beta_host) he = hipMemcpy(beta_host, beta, batch * p * sizeof(double), hipMemcpyDeviceToHost);
-  pool_free(X);
-  pool_free(y);
-  pool_free(work);
-  pool_free(Q);
-  pool_free(R);
-  pool_free(beta);
   if (he != hipSuccess)
     return fail(he == hipErrorOutOfMemory ? NLSG_ERR_OOM : NLSG_ERR_HIP, "nlsg_tinyqr_qr failed: %s",
                 hipGetErrorString(he));

@@ -412,8 +412,10 @@ int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long 
   // what it always did)
   std::vector<std::string> names = {"nlsg::bfgs_init_kernel<" + t + ">", "nlsg::bfgs_search_kernel<" + t + ">"};
   if (resident) names.push_back("nlsg::bfgs_resident_kernel<" + t + ">");
-  const int rc = rtc_compile(obj, "nlsg_bfgs_kernels.h", names,
-                             &k.mod, &f, wave_rows_offset, grad_body);  // (a row per wave in the dynamic block)
+  // (a row per wave in the dynamic block.) The code object is kept by its source, as the annealer's: engines
+  // that differ in alpha, max_iter or grad_eps only — a sweep of step lengths, the drop-in's engine per call —
+  // load it instead of compiling.
+  const int rc = rtc_compile(obj, "nlsg_bfgs_kernels.h", names, &k.mod, &f, wave_rows_offset, grad_body, 0, true);
   if (rc) return rc;
   if (resident) k.resident = f[2];
   k.init = f[0];

@@ -214,6 +214,56 @@ orc_status orc_bfgs_fd(int obj, double *x, size_t n, size_t max_iter, double gra
                        int tree, orc_bfgs_counters *cnt);
 void orc_update_inverse_hessian(double *H, const double *s, const double *y, double *t, double rho,
                                 size_t n, int tree);
+/* The branches of the More-Thuente search (cstep 1527-1671, cvsrch 1673-1793), one bit each, set where the
+ * branch is taken. OPEN = not bracketed. tests/_oracle.py MT_BRANCHES names them in this order. */
+enum {
+  ORC_MT_C1_OPEN = 0,     /* case 1 (fp > fx), interval not bracketed yet */
+  ORC_MT_C1_BRACKETED,    /* case 1 inside a bracket */
+  ORC_MT_C1_LEFT,         /* case 1 with stp < stx: gamma negated */
+  ORC_MT_C1_CUBIC,        /* case 1 takes the cubic step */
+  ORC_MT_C1_AVERAGE,      /* case 1 takes the mean of cubic and quadratic step */
+  ORC_MT_C2_OPEN,         /* case 2 (derivatives of opposite sign) */
+  ORC_MT_C2_BRACKETED,
+  ORC_MT_C2_LEFT,         /* case 2 with stp < stx: gamma not negated */
+  ORC_MT_C2_CUBIC,
+  ORC_MT_C2_SECANT,
+  ORC_MT_C3_OPEN,         /* case 3 (same sign, derivative decreases) */
+  ORC_MT_C3_BRACKETED,
+  ORC_MT_C3_LEFT,         /* case 3 with stp < stx */
+  ORC_MT_C3_R_NEGATIVE,   /* case 3: r < 0 and gamma != 0, the cubic's own minimiser */
+  ORC_MT_C3_STPMAX,       /* case 3: stpmax stands in for the cubic step */
+  ORC_MT_C3_STPMIN,       /* case 3: stpmin stands in for the cubic step */
+  ORC_MT_C3_ROOT_CLAMPED, /* case 3: the radicand is negative, max(0, .) acts */
+  ORC_MT_C3_B_CUBIC,      /* case 3 bracketed picks the cubic step */
+  ORC_MT_C3_B_SECANT,
+  ORC_MT_C3_O_CUBIC,      /* case 3 not bracketed picks the cubic step */
+  ORC_MT_C3_O_SECANT,
+  ORC_MT_C4_BRACKETED,    /* case 4 (same sign, derivative does not decrease): cubic through stp and sty */
+  ORC_MT_C4_RIGHT,        /* case 4 with stp > sty: gamma negated */
+  ORC_MT_C4_OPEN_STPMAX,  /* case 4 not bracketed, stp > stx */
+  ORC_MT_C4_OPEN_STPMIN,  /* case 4 not bracketed, stp <= stx */
+  ORC_MT_SAFEGUARD_UP,    /* the 0.66 safeguard replaced the step, sty > stx */
+  ORC_MT_SAFEGUARD_DOWN,  /* the same, sty <= stx */
+  ORC_MT_CSTEP_REJECT,    /* cstep returns at once: infoc = 0 */
+  ORC_MT_NOT_DESCENT,     /* dginit >= 0: no search, the step stays alpha */
+  ORC_MT_FALLBACK_STX,    /* stp = stx before an evaluation (:1728-1734) */
+  ORC_MT_STAGE_2,         /* stage 1 left */
+  ORC_MT_MODIFIED,        /* cstep on the modified function of stage 1 */
+  ORC_MT_BISECTION,       /* the forced bisection (:1784-1790) */
+  ORC_MT_EXIT_1,          /* exits: info = 1 .. 6, consecutive */
+  ORC_MT_EXIT_2,
+  ORC_MT_EXIT_3,
+  ORC_MT_EXIT_4,
+  ORC_MT_EXIT_5,
+  ORC_MT_EXIT_6,
+  ORC_MT_BRANCHES
+};
+/* BFGS on the line-search family of tests/golden/bfgs_mt.json (oracle_bfgs.c fam_f / fam_g; analytic
+ * gradient, counted as a Grad functor): n = 1 or 2, params = 5 n doubles. At n = 1 the first turn is exactly
+ * one search on phi(t) = f(x0 - t g(x0)) from stp = alpha. *mask (optional): the branches taken by every
+ * search of the solve; g_out (optional, n): the gradient the solve ended with. */
+orc_status orc_bfgs_mt(const double *params, double *x, size_t n, size_t max_iter, double grad_eps,
+                       double alpha, int tree, orc_bfgs_counters *cnt, uint64_t *mask, double *g_out);
 
 /* --------------------------------------------------------------------- LM --- */
 double orc_exp(double x);  /* deterministic (no libm), shared with the HIP kernels */

@@ -42,7 +42,12 @@ typedef struct {
   size_t n;
   int tree;
   double *scratch; /* n */
+  uint64_t *mask;  /* optional: the More-Thuente branches taken (ORC_MT_*), or-ed in where they are taken */
 } ctx_t;
+
+static void hit(uint64_t *mask, int bit) {
+  if (mask) *mask |= (uint64_t)1 << bit;
+}
 
 static double dot_(const ctx_t *c, const double *a, const double *b) { /* math::dot :58-67 */
   for (size_t i = 0; i < c->n; i++) c->scratch[i] = a[i] * b[i];
@@ -68,9 +73,26 @@ static void quad_g_raw(const ctx_t *c, const orc_quad *q, const double *x, doubl
  * finite_difference_gradient<Callable, scalar_t, 1> (nlsolver.h:1385-1413, 2849-2855). The
  * probes go through the counting wrapper f_lam (3218-3224), so they count as function calls. */
 typedef struct {
-  const orc_quad *q; /* NULL: built-in objective `obj` + finite differences */
+  const orc_quad *q; /* NULL: built-in objective `obj` + finite differences, unless `fam` */
   int obj;
+  const double *fam; /* the line-search family below: 5 parameters per coordinate, n <= 2 */
 } model_t;
+
+/* ---- the line-search family (tests/golden/bfgs_mt.json): per coordinate, with (a, b, c, d, e) = p[0..4],
+ *   q = x x, w = 1 + q;  f = ((a q + b x + c) x + d) x + e (q / w)
+ *                        g = ((4 a x + 3 b) x + 2 c) x + d + e ((2 x) / (w w))
+ * no transcendental function, one expression tree — restated operation for operation by the reference
+ * driver's functors (ref_driver_more.inc MtFamily) and by the device bodies of
+ * tests/test_bfgs_linesearch_gpu.py. One coordinate: f = 0.0 + f_0; two: f = 0.0 + (f_0 + f_1), coordinate 1
+ * under p[5..9] — a sum of ONE term in every summation order. Analytic gradient, counted as a Grad functor. */
+static double fam_f(double x, const double *p) {
+  const double q = x * x, w = 1 + q;
+  return ((p[0] * q + p[1] * x + p[2]) * x + p[3]) * x + p[4] * (q / w);
+}
+static double fam_g(double x, const double *p) {
+  const double q = x * x, w = 1 + q;
+  return ((4 * p[0] * x + 3 * p[1]) * x + 2 * p[2]) * x + p[3] + p[4] * ((2 * x) / (w * w));
+}
 
 static void log_f(orc_bfgs_counters *cnt, double v) {
   cnt->f_calls++;
@@ -78,14 +100,21 @@ static void log_f(orc_bfgs_counters *cnt, double v) {
   cnt->f_count++;
 }
 static double model_f(const ctx_t *c, const model_t *m, const double *x, orc_bfgs_counters *cnt) {
-  const double v = m->q ? quad_f_raw(c, m->q, x)
-                        : (c->tree ? orc_objective_tree(m->obj, x, c->n)
-                                   : orc_objective_seq(m->obj, x, c->n));
+  double v;
+  if (m->fam)
+    v = c->n == 1 ? 0.0 + fam_f(x[0], m->fam) : 0.0 + (fam_f(x[0], m->fam) + fam_f(x[1], m->fam + 5));
+  else
+    v = m->q ? quad_f_raw(c, m->q, x)
+             : (c->tree ? orc_objective_tree(m->obj, x, c->n) : orc_objective_seq(m->obj, x, c->n));
   log_f(cnt, v);
   return v;
 }
 static void model_g(const ctx_t *c, const model_t *m, double *x, double *g, orc_bfgs_counters *cnt) {
   cnt->g_calls++;
+  if (m->fam) {
+    for (size_t i = 0; i < c->n; i++) g[i] = fam_g(x[i], m->fam + 5 * i);
+    return;
+  }
   if (m->q) {
     quad_g_raw(c, m->q, x, g);
     return;
@@ -118,34 +147,45 @@ static double dclamp(double v, double lo, double hi) {             /* std::clamp
 
 static int cstep(double *stx, double *fx, double *dx, double *sty, double *fy, double *dy,
                  double *stp, double fp, double dp, int *brackt, double stpmin, double stpmax,
-                 int *info) {
+                 int *info, uint64_t *m) {
   *info = 0;
   int bound;
   if ((*brackt & ((*stp <= dmin(*stx, *sty)) || (*stp >= dmax(*stx, *sty)))) ||
-      (*dx * (*stp - *stx) >= 0.0) || (stpmax < stpmin))
+      (*dx * (*stp - *stx) >= 0.0) || (stpmax < stpmin)) {
+    hit(m, ORC_MT_CSTEP_REJECT);
     return -1;
+  }
   const double sgnd = dp * (*dx / fabs(*dx));
   double stpf = 0, stpc, stpq;
   if (fp > *fx) { /* case 1 */
     *info = 1;
     bound = 1;
+    hit(m, *brackt ? ORC_MT_C1_BRACKETED : ORC_MT_C1_OPEN);
     const double theta = 3. * (*fx - fp) / (*stp - *stx) + *dx + dp;
     const double s = max_abs3(theta, *dx, dp);
     double gamma = s * sqrt((theta / s) * (theta / s) - (*dx / s) * (dp / s));
-    if (*stp < *stx) gamma = -gamma;
+    if (*stp < *stx) {
+      gamma = -gamma;
+      hit(m, ORC_MT_C1_LEFT);
+    }
     const double p = (gamma - *dx) + theta;
     const double q = ((gamma - *dx) + gamma) + dp;
     const double r = p / q;
     stpc = *stx + r * (*stp - *stx);
     stpq = *stx + ((*dx / ((*fx - fp) / (*stp - *stx) + *dx)) / 2.) * (*stp - *stx);
-    if (fabs(stpc - *stx) < fabs(stpq - *stx))
+    if (fabs(stpc - *stx) < fabs(stpq - *stx)) {
       stpf = stpc;
-    else
+      hit(m, ORC_MT_C1_CUBIC);
+    } else {
       stpf = stpc + (stpq - stpc) / 2;
+      hit(m, ORC_MT_C1_AVERAGE);
+    }
     *brackt = 1;
   } else if (sgnd < 0.0) { /* case 2 */
     *info = 2;
     bound = 0;
+    hit(m, *brackt ? ORC_MT_C2_BRACKETED : ORC_MT_C2_OPEN);
+    if (!(*stp > *stx)) hit(m, ORC_MT_C2_LEFT);
     const double theta = 3 * (*fx - fp) / (*stp - *stx) + *dx + dp;
     const double s = max_abs3(theta, *dx, dp);
     double gamma = s * sqrt((theta / s) * (theta / s) - (*dx / s) * (dp / s));
@@ -155,32 +195,44 @@ static int cstep(double *stx, double *fx, double *dx, double *sty, double *fy, d
     const double r = p / q;
     stpc = *stp + r * (*stx - *stp);
     stpq = *stp + (dp / (dp - *dx)) * (*stx - *stp);
-    if (fabs(stpc - *stp) > fabs(stpq - *stp))
+    if (fabs(stpc - *stp) > fabs(stpq - *stp)) {
       stpf = stpc;
-    else
+      hit(m, ORC_MT_C2_CUBIC);
+    } else {
       stpf = stpq;
+      hit(m, ORC_MT_C2_SECANT);
+    }
     *brackt = 1;
   } else if (fabs(dp) < fabs(*dx)) { /* case 3 */
     *info = 3;
     bound = 1;
+    hit(m, *brackt ? ORC_MT_C3_BRACKETED : ORC_MT_C3_OPEN);
+    if (!(*stp > *stx)) hit(m, ORC_MT_C3_LEFT);
     const double theta = 3 * (*fx - fp) / (*stp - *stx) + *dx + dp;
     const double s = max_abs3(theta, *dx, dp);
+    if ((theta / s) * (theta / s) - (*dx / s) * (dp / s) < 0.0) hit(m, ORC_MT_C3_ROOT_CLAMPED);
     double gamma = s * sqrt(dmax(0., (theta / s) * (theta / s) - (*dx / s) * (dp / s)));
     if (*stp > *stx) gamma = -gamma;
     const double p = (gamma - dp) + theta;
     const double q = (gamma + (*dx - dp)) + gamma;
     const double r = p / q;
-    if ((r < 0.0) & (gamma != 0.0))
+    if ((r < 0.0) & (gamma != 0.0)) {
       stpc = *stp + r * (*stx - *stp);
-    else if (*stp > *stx)
+      hit(m, ORC_MT_C3_R_NEGATIVE);
+    } else if (*stp > *stx) {
       stpc = stpmax;
-    else
+      hit(m, ORC_MT_C3_STPMAX);
+    } else {
       stpc = stpmin;
+      hit(m, ORC_MT_C3_STPMIN);
+    }
     stpq = *stp + (dp / (dp - *dx)) * (*stx - *stp);
     if (*brackt) {
       stpf = (fabs(*stp - stpc) < fabs(*stp - stpq)) ? stpc : stpq;
+      hit(m, stpf == stpc ? ORC_MT_C3_B_CUBIC : ORC_MT_C3_B_SECANT);
     } else {
       stpf = (fabs(*stp - stpc) > fabs(*stp - stpq)) ? stpc : stpq;
+      hit(m, stpf == stpc ? ORC_MT_C3_O_CUBIC : ORC_MT_C3_O_SECANT);
     }
   } else { /* case 4 */
     *info = 4;
@@ -189,7 +241,11 @@ static int cstep(double *stx, double *fx, double *dx, double *sty, double *fy, d
       const double theta = 3 * (fp - *fy) / (*sty - *stp) + *dy + dp;
       const double s = max_abs3(theta, *dy, dp);
       double gamma = s * sqrt((theta / s) * (theta / s) - (*dy / s) * (dp / s));
-      if (*stp > *sty) gamma = -gamma;
+      hit(m, ORC_MT_C4_BRACKETED);
+      if (*stp > *sty) {
+        gamma = -gamma;
+        hit(m, ORC_MT_C4_RIGHT);
+      }
       const double p = (gamma - dp) + theta;
       const double q = ((gamma - dp) + gamma) + *dy;
       const double r = p / q;
@@ -197,8 +253,10 @@ static int cstep(double *stx, double *fx, double *dx, double *sty, double *fy, d
       stpf = stpc;
     } else if (*stp > *stx) {
       stpf = stpmax;
+      hit(m, ORC_MT_C4_OPEN_STPMAX);
     } else {
       stpf = stpmin;
+      hit(m, ORC_MT_C4_OPEN_STPMIN);
     }
   }
   if (fp > *fx) { /* :1644-1658 */
@@ -218,10 +276,13 @@ static int cstep(double *stx, double *fx, double *dx, double *sty, double *fy, d
   stpf = dclamp(stpf, stpmin, stpmax);
   *stp = stpf;
   if (*brackt & bound) { /* :1663-1670 */
+    const double lim = *stx + 0.66 * (*sty - *stx), before = *stp;
     if (*sty > *stx)
-      *stp = dmin(*stx + 0.66 * (*sty - *stx), *stp);
+      *stp = dmin(lim, *stp);
     else
-      *stp = dmax(*stx + 0.66 * (*sty - *stx), *stp);
+      *stp = dmax(lim, *stp);
+    /* the safeguard bound: it replaced the step (a NaN step included) */
+    if (memcmp(&before, stp, sizeof before)) hit(m, *sty > *stx ? ORC_MT_SAFEGUARD_UP : ORC_MT_SAFEGUARD_DOWN);
   }
   return 0;
 }
@@ -235,7 +296,10 @@ static void cvsrch(const ctx_t *c, const model_t *q, const double *x, double f0,
   const int maxfev = 20;
   int nfev = 0;
   const double dginit = dot_(c, gradient, dir);
-  if (dginit >= 0.0) return; /* :1692-1694 */
+  if (dginit >= 0.0) { /* :1692-1694 */
+    hit(c->mask, ORC_MT_NOT_DESCENT);
+    return;
+  }
   int brackt = 0, stage1 = 1;
   const double finit = f0, dgtest = ftol * dginit;
   double width = stpmax - stpmin, width1 = 2 * width;
@@ -251,8 +315,10 @@ static void cvsrch(const ctx_t *c, const model_t *q, const double *x, double f0,
     }
     *stp = dclamp(*stp, stpmin, stpmax);
     if ((brackt && ((*stp <= stmin) || (*stp >= stmax))) || (nfev >= maxfev - 1) ||
-        (infoc == 0) || (brackt && ((stmax - stmin) <= (xtol * stmax))))
+        (infoc == 0) || (brackt && ((stmax - stmin) <= (xtol * stmax)))) {
       *stp = stx; /* :1728-1734 */
+      hit(c->mask, ORC_MT_FALLBACK_STX);
+    }
     for (size_t i = 0; i < c->n; i++) tmp[i] = x[i] + *stp * dir[i]; /* :1737 */
     const double fcur = model_f(c, q, tmp, cnt);
     model_g(c, q, tmp, gradient, cnt);
@@ -265,23 +331,33 @@ static void cvsrch(const ctx_t *c, const model_t *q, const double *x, double f0,
     if (nfev >= maxfev) info = 3;
     if (brackt & (stmax - stmin <= xtol * stmax)) info = 2;
     if ((fcur <= ftest1) & (fabs(dg) <= gtol * (-dginit))) info = 1;
-    if (info != 0) return;
-    if (stage1 & (fcur <= ftest1) & (dg >= dmin(ftol, gtol) * dginit)) stage1 = 0;
+    if (info != 0) {
+      hit(c->mask, ORC_MT_EXIT_1 + info - 1);
+      return;
+    }
+    if (stage1 & (fcur <= ftest1) & (dg >= dmin(ftol, gtol) * dginit)) {
+      stage1 = 0;
+      hit(c->mask, ORC_MT_STAGE_2);
+    }
     if (stage1 & (fcur <= fx) & (fcur > ftest1)) { /* :1762-1778 */
+      hit(c->mask, ORC_MT_MODIFIED);
       const double fm = fcur - *stp * dgtest;
       double fxm = fx - stx * dgtest, fym = fy - sty * dgtest;
       const double dgm = dg - dgtest;
       double dgxm = dgx - dgtest, dgym = dgy - dgtest;
-      cstep(&stx, &fxm, &dgxm, &sty, &fym, &dgym, stp, fm, dgm, &brackt, stmin, stmax, &infoc);
+      cstep(&stx, &fxm, &dgxm, &sty, &fym, &dgym, stp, fm, dgm, &brackt, stmin, stmax, &infoc, c->mask);
       fx = fxm + stx * dgtest;
       fy = fym + sty * dgtest;
       dgx = dgxm + dgtest;
       dgy = dgym + dgtest;
     } else {
-      cstep(&stx, &fx, &dgx, &sty, &fy, &dgy, stp, fcur, dg, &brackt, stmin, stmax, &infoc);
+      cstep(&stx, &fx, &dgx, &sty, &fy, &dgy, stp, fcur, dg, &brackt, stmin, stmax, &infoc, c->mask);
     }
     if (brackt) { /* :1784-1790 */
-      if (fabs(sty - stx) >= 0.66 * width1) *stp = stx + 0.5 * (sty - stx);
+      if (fabs(sty - stx) >= 0.66 * width1) {
+        *stp = stx + 0.5 * (sty - stx);
+        hit(c->mask, ORC_MT_BISECTION);
+      }
       width1 = width;
       width = fabs(sty - stx);
     }
@@ -343,7 +419,7 @@ static void sym_matvec(const double *H, const double *u, double *out, size_t n) 
 void orc_update_inverse_hessian(double *H, const double *s, const double *y, double *t, double rho,
                                 size_t n, int tree) {
   double *scratch = (double *)malloc(n * sizeof(double));
-  ctx_t c = {n, tree, scratch};
+  ctx_t c = {n, tree, scratch, NULL};
   for (size_t i = 0; i < n; i++) t[i] = dot_(&c, y, H + i * n);
   double denom = dot_(&c, y, t);
   denom = (denom * rho) + 1.0;
@@ -355,13 +431,13 @@ void orc_update_inverse_hessian(double *H, const double *s, const double *y, dou
 
 /* BFGS::solve<true>, nlsolver.h:3196-3285. x is in/out. */
 static orc_status bfgs_solve(const model_t *q, double *x, size_t n, size_t max_iter, double grad_eps,
-                             double alpha, int tree, orc_bfgs_counters *cnt) {
+                             double alpha, int tree, orc_bfgs_counters *cnt, uint64_t *mask, double *g_out) {
   double *H = (double *)calloc(n * n, sizeof(double));
   double *dir = (double *)calloc(n, sizeof(double)), *g = (double *)calloc(n, sizeof(double));
   double *pg = (double *)calloc(n, sizeof(double)), *y = (double *)calloc(n, sizeof(double));
   double *s = (double *)calloc(n, sizeof(double)), *tmp = (double *)calloc(n, sizeof(double));
   double *t = (double *)calloc(n, sizeof(double)), *scratch = (double *)calloc(n, sizeof(double));
-  ctx_t c = {n, tree, scratch};
+  ctx_t c = {n, tree, scratch, mask};
   orc_bfgs_counters local = {0};
   if (!cnt) cnt = &local;
   for (size_t i = 0; i < n; i++) H[i + i * n] = 1.0; /* :3212 */
@@ -418,6 +494,7 @@ static orc_status bfgs_solve(const model_t *q, double *x, size_t n, size_t max_i
     iter++;
   }
   orc_status st = {fval, iter, cnt->f_calls, cnt->g_calls, 0};
+  if (g_out) memcpy(g_out, g, n * sizeof(double)); /* tests: the gradient the solve ended with */
   free(H);
   free(dir);
   free(g);
@@ -433,13 +510,26 @@ static orc_status bfgs_solve(const model_t *q, double *x, size_t n, size_t max_i
 /* the G6 quadratic with its analytic gradient functor */
 orc_status orc_bfgs_quad(const orc_quad *q, double *x, size_t n, size_t max_iter, double grad_eps,
                          double alpha, int tree, orc_bfgs_counters *cnt) {
-  const model_t m = {q, 0};
-  return bfgs_solve(&m, x, n, max_iter, grad_eps, alpha, tree, cnt);
+  const model_t m = {q, 0, NULL};
+  return bfgs_solve(&m, x, n, max_iter, grad_eps, alpha, tree, cnt, NULL, NULL);
 }
 
 /* a built-in objective (ORC_OBJ_*) with the default finite-difference gradient */
 orc_status orc_bfgs_fd(int obj, double *x, size_t n, size_t max_iter, double grad_eps, double alpha,
                        int tree, orc_bfgs_counters *cnt) {
-  const model_t m = {NULL, obj};
-  return bfgs_solve(&m, x, n, max_iter, grad_eps, alpha, tree, cnt);
+  const model_t m = {NULL, obj, NULL};
+  return bfgs_solve(&m, x, n, max_iter, grad_eps, alpha, tree, cnt, NULL, NULL);
+}
+
+/* the line-search family (fam_f / fam_g above), n = 1 or 2, params = 5 n doubles; *mask (optional) collects
+ * the More-Thuente branches of every search of the solve, g_out (optional, n) its last gradient */
+orc_status orc_bfgs_mt(const double *params, double *x, size_t n, size_t max_iter, double grad_eps,
+                       double alpha, int tree, orc_bfgs_counters *cnt, uint64_t *mask, double *g_out) {
+  if (mask) *mask = 0;
+  if (n < 1 || n > 2) {
+    const orc_status bad = {NAN, 0, 0, 0, 0};
+    return bad;
+  }
+  const model_t m = {NULL, 0, params};
+  return bfgs_solve(&m, x, n, max_iter, grad_eps, alpha, tree, cnt, mask, g_out);
 }

@@ -157,6 +157,80 @@ static int run_bfgs(size_t n, size_t max_iter, double grad_eps, double alpha, do
   return 0;
 }
 
+// BFGS on the line-search family (oracle/oracle_bfgs.c fam_f / fam_g say the same operation for operation):
+// per coordinate, (a, b, c, d, e) = p[0..4],
+//   q = x x, w = 1 + q;  f = ((a q + b x + c) x + d) x + e (q / w)
+//                        g = ((4 a x + 3 b) x + 2 c) x + d + e ((2 x) / (w w))
+// n = 1: f = 0.0 + f_0; n = 2: f = 0.0 + (f_0 + f_1), coordinate 1 under p[5..9]. At n = 1 the first turn of
+// BFGS::solve (H = I, d = -g) is exactly one More-Thuente search on phi(t) = f(x0 - t g(x0)) from stp = alpha,
+// so the members of this family pin the branches of cstep / cvsrch (tests/golden/bfgs_mt.json).
+struct MtFamily {
+  std::vector<double> p;  // 5 n
+  std::vector<double> f_vals;
+  size_t g_calls = 0;
+  static double f1(double x, const double *p) {
+    const double q = x * x, w = 1 + q;
+    return ((p[0] * q + p[1] * x + p[2]) * x + p[3]) * x + p[4] * (q / w);
+  }
+  static double g1(double x, const double *p) {
+    const double q = x * x, w = 1 + q;
+    return ((4 * p[0] * x + 3 * p[1]) * x + 2 * p[2]) * x + p[3] + p[4] * ((2 * x) / (w * w));
+  }
+  double operator()(std::vector<double> &x) {
+    const double v = x.size() == 1 ? 0.0 + f1(x[0], p.data())
+                                   : 0.0 + (f1(x[0], p.data()) + f1(x[1], p.data() + 5));
+    f_vals.push_back(v);
+    return v;
+  }
+};
+struct MtFamilyGrad {
+  void operator()(MtFamily &f, std::vector<double> &x, std::vector<double> &g) {
+    for (size_t i = 0; i < x.size(); i++) g[i] = MtFamily::g1(x[i], f.p.data() + 5 * i);
+    f.g_calls++;
+  }
+};
+static std::vector<double> parse_list(const char *s) {
+  std::vector<double> out;
+  std::stringstream ss(s);
+  std::string tok;
+  while (std::getline(ss, tok, ',')) out.push_back(std::strtod(tok.c_str(), nullptr));
+  return out;
+}
+
+static int run_bfgs_mt(size_t n, const char *params, const char *x0, double alpha, size_t max_iter,
+                       double grad_eps) {
+  MtFamily f;
+  f.p = parse_list(params);
+  std::vector<double> x = parse_list(x0);
+  if ((n != 1 && n != 2) || f.p.size() != 5 * n || x.size() != n) {
+    std::fprintf(stderr, "bfgs-mt: n is 1 or 2, with 5 n parameters and n coordinates\n");
+    return 2;
+  }
+  const std::vector<double> start = x;
+  MtFamilyGrad g;
+  auto solver = nlsolver::BFGS<MtFamily, double, MtFamilyGrad>(f, g, max_iter, grad_eps, alpha);
+  auto res = solver.minimize(x);
+  auto [fcalls, iters, fval, gcalls, h] = res.get_summary();
+  (void)h;
+  std::printf("{\"n\":%zu,\"params\":", n);
+  put_vec(f.p);
+  std::printf(",\"x0\":");
+  put_vec(start);
+  std::printf(",\"alpha\":");
+  put_hex(alpha);
+  std::printf(",\"max_iter\":%zu,\"grad_eps\":", max_iter);
+  put_hex(grad_eps);
+  std::printf(",\"fcalls\":%zu,\"iters\":%zu,\"gcalls\":%zu,\"g_calls_seen\":%zu,\"f\":", fcalls, iters,
+              gcalls, f.g_calls);
+  put_hex(fval);
+  std::printf(",\"x\":");
+  put_vec(x);
+  std::printf(",\"f_vals\":");
+  put_vec(f.f_vals);
+  std::printf("}\n");
+  return 0;
+}
+
 // BFGS with the reference's DEFAULT gradient (fin_diff -> finite_difference_gradient<.,.,1>,
 // nlsolver.h:1385-1413, 2849-2855) on a built-in N-D objective; every objective value (the
 // finite-difference probes included: they go through the counting wrapper, 3218-3224) is
@@ -879,6 +953,14 @@ static int more_main(const std::string &cmd, int argc, char **argv) {
                     std::strtod(argv[4], nullptr), std::strtod(argv[5], nullptr),
                     std::strtod(argv[6], nullptr), std::strtod(argv[7], nullptr),
                     std::atoi(argv[8]));
+  }
+  if (cmd == "bfgs-mt") {
+    if (argc < 8) {
+      std::fprintf(stderr, "bfgs-mt n params(5n, comma separated) x0(n) alpha max_iter grad_eps\n");
+      return 2;
+    }
+    return run_bfgs_mt(std::strtoull(argv[2], nullptr, 10), argv[3], argv[4], std::strtod(argv[5], nullptr),
+                       std::strtoull(argv[6], nullptr, 10), std::strtod(argv[7], nullptr));
   }
   if (cmd == "bfgs-fd") {
     if (argc < 10) {

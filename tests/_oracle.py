@@ -131,6 +131,38 @@ def bfgs_fd(lib, obj, x0, *, max_iter=100, grad_eps=5e-3, alpha=1.0, tree=0, log
     return st, x, (flog[:min(cnt.f_count, log_cap)] if log_cap else None), cnt.f_count
 
 
+# oracle.h ORC_MT_*: the branches of the More-Thuente search, bit k of orc_bfgs_mt's mask = MT_BRANCHES[k]
+MT_BRANCHES = (
+    "c1_open", "c1_bracketed", "c1_left", "c1_cubic", "c1_average",
+    "c2_open", "c2_bracketed", "c2_left", "c2_cubic", "c2_secant",
+    "c3_open", "c3_bracketed", "c3_left", "c3_r_negative", "c3_stpmax", "c3_stpmin", "c3_root_clamped",
+    "c3_b_cubic", "c3_b_secant", "c3_o_cubic", "c3_o_secant",
+    "c4_bracketed", "c4_right", "c4_open_stpmax", "c4_open_stpmin",
+    "safeguard_up", "safeguard_down", "cstep_reject", "not_descent", "fallback_stx", "stage_2",
+    "modified", "bisection", "exit_1", "exit_2", "exit_3", "exit_4", "exit_5", "exit_6")
+
+
+def bfgs_mt(lib, params, x0, *, max_iter=1, grad_eps=0.0, alpha=1.0, tree=0):
+    """Oracle BFGS on the line-search family (oracle_bfgs.c fam_f / fam_g; 5 parameters per coordinate,
+    n = 1 or 2). Returns (status, x, f_log, set of MT_BRANCHES names taken, last gradient, last H)."""
+    x = np.ascontiguousarray(x0, dtype=np.float64).copy()
+    n = x.size
+    p = np.ascontiguousarray(params, dtype=np.float64)
+    assert n in (1, 2) and p.shape == (5 * n,)
+    cnt = BfgsCounters()
+    flog = np.zeros(22 * (max_iter + 1) + 4)
+    cnt.f_log, cnt.f_cap = _ptr(flog), flog.size
+    H = np.eye(n)
+    cnt.H_out = _ptr(H)
+    g = np.zeros(n)
+    mask = u64(0)
+    st = lib.orc_bfgs_mt(_ptr(p), _ptr(x), n, max_iter, grad_eps, alpha, tree, C.byref(cnt),
+                         C.byref(mask), _ptr(g))
+    assert mask.value >> len(MT_BRANCHES) == 0
+    taken = {name for k, name in enumerate(MT_BRANCHES) if mask.value >> k & 1}
+    return st, x, flog[:cnt.f_count], taken, g, H
+
+
 def lm_fd(lib, obj, x0, *, lam=10.0, up=10.0, down=10.0, max_iter=100, f_delta=1e-12, order=0,
           log_cap=0):
     """Oracle LevenbergMarquardt with the default finite-difference functors on a built-in
@@ -274,6 +306,9 @@ def load():
                               sz]
     lib.orc_bfgs_fd.restype = Status
     lib.orc_bfgs_fd.argtypes = [C.c_int, pd, sz, sz, f64, f64, C.c_int, C.POINTER(BfgsCounters)]
+    lib.orc_bfgs_mt.restype = Status
+    lib.orc_bfgs_mt.argtypes = [pd, pd, sz, sz, f64, f64, C.c_int, C.POINTER(BfgsCounters),
+                                C.POINTER(u64), pd]
     lib.orc_update_inverse_hessian.argtypes = [pd, pd, pd, pd, f64, sz, C.c_int]
     for name in ("orc_exp", "orc_tanh"):
         fn = getattr(lib, name)

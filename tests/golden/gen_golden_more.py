@@ -2,6 +2,75 @@
 Executed by gen_golden.py with `run` and `write` injected."""
 
 
+# The line-search family of bfgs_mt.json (oracle/ref_driver_more.inc MtFamily): members (a, b, c, d, e, x0,
+# alpha) found by searching the family for the branches of cstep / cvsrch (nlsolver.h:1527-1793). At n = 1 the
+# first turn of BFGS::solve is one More-Thuente search on phi(t) = f(x0 - t g(x0)) from stp = alpha. Several
+# run through inf and NaN on purpose. The keys say what each was found for; which branches a record takes is
+# measured, not declared: tests/test_oracle_bfgs_mt_golden.py reads it off the oracle's branch mask.
+MT_WITNESSES = {
+    "case1_open_and_bracketed_case3_case4_bisection_exit1": (0.5, -3, 5, 1, 0, 5, 1),
+    "case1_cubic_pick_and_left": (0.5, 3, -1, -1, -1, 0.7, 1e6),
+    "case2_bracketed_cubic_stage2": (0.5, 1, 0.1, 0, -10, 5, 4),
+    "case2_open_secant_case3_open_cubic_case4_right": (0, 0, 0.1, 0.3, 1, 5, 1),
+    "case2_left": (1, 0, 5, 0, 0, 0.7, 0.5),
+    "case3_left": (0, 1, 5, 0, 100, -3, 0.5),
+    "case3_stpmin": (0.5, 0, 0.1, 0, -10, 5, 1),
+    "case3_open_secant": (0.5, 0, -1, 0.3, -10, -0.5, 0.1),
+    "case3_root_clamped": (2, 3, 1, 0.3, -1, 1.2, 1e-15),
+    "case4_open_stpmax_fallback_exit3": (0, -3, 0.1, 0, -1, 0.25, 1e-15),
+    "exit4": (0.5, 0, 0.1, 0.3, 0, -0.5, 1e-15),
+    "exit5_one_evaluation": (0, 3, 0, -1, 0, 5, 1e15),
+    "exit6": (0, 0, 100, 1, 1, -1.5, 1e15),
+    "modified_function": (0, 0, 1, 0, 0, -1.5, 1),
+    "safeguard_down": (2, 1, 1, 0, -1, -0.5, 1),
+    "safeguard_up": (1, -3, 1, 0, 100, 10, 1e6),
+    "not_descent": (0, 0, 0, 0, 0, 10, 1e-15),
+    # directed constructions for the three branches a search of the value lists does not reach in a first
+    # turn: a quartic so steep that the first trial overflows (f = g = inf, then NaN steps), and a concave
+    # parabola whose bracket collapses below xtol; the last one reaches the xtol exit in a later turn
+    "cstep_reject_overflowing_quartic": (1e200, 0, 0, 0, 0, 0.7, 1),
+    "case4_open_stpmin_overflowing_quartic": (1e200, 0, 0, 0, 0, 0.7, 1e15),
+    "exit2_first_turn": (0, 1, -1e100, 0, 0, 0.7, 1),
+    "exit2_later_turn": (0, 1, -1, 0, -1, 1.2, 0.1),
+    # members on which a search differs when a threshold of cvsrch is nudged (found by running a deliberately
+    # altered copy of the oracle beside the true one): 0.66 width1 -> 0.7 width1 in the forced bisection, and
+    # dg >= dgtest -> dg > dgtest in exit 4
+    "bisection_threshold": (2, -3, -1, -1, 10, 2.5, 1e6),
+    "exit4_derivative_test": (0, 1e200, 0, 0.3, 0, 0.01, 1e-15),
+}
+# the value lists the witnesses were drawn from; the further members come from the same lists
+MT_LISTS = dict(a=[0, 0, 1, 0.5, 2, 10], b=[0, 0, -1, 1, 3, -3], c=[0, 1, -1, 5, 0.1, 100], d=[0, 1, -1, 0.3],
+                e=[0, 0, 1, -1, 10, -10, 100], x0=[-3, -1.5, -0.5, 0.25, 0.7, 1.2, 2.5, 5, 10, 0.01],
+                alpha=[1.0, 0.5, 0.1, 1e-3, 4.0, 50.0, 1e-15, 1e15, 1e6])
+
+
+def bfgs_mt_records():
+    """{name/m<max_iter>: the reference's run}: every witness, 40 further members and 20 two-coordinate pairs
+    (f = family(x_0; p[0..4]) + family(x_1; p[5..9]): H and dir = -H g take part from turn 2 on), each at
+    max_iter 1 and 6 with grad_eps 0."""
+    import random
+    rng = random.Random(20240607)
+
+    def draw():
+        return tuple(rng.choice(MT_LISTS[k]) for k in ("a", "b", "c", "d", "e", "x0"))
+
+    members = {name: (1, w[:5], w[5:6], w[6]) for name, w in MT_WITNESSES.items()}
+    for k in range(40):
+        m = draw()
+        members[f"member_{k:02d}"] = (1, m[:5], m[5:6], rng.choice(MT_LISTS["alpha"]))
+    for k in range(20):
+        m0, m1 = draw(), draw()
+        members[f"pair_{k:02d}"] = (2, m0[:5] + m1[:5], (m0[5], m1[5]), rng.choice(MT_LISTS["alpha"]))
+    out = {}
+    for name, (n, params, x0, alpha) in members.items():
+        for max_iter in (1, 6):
+            # args: n params x0 alpha max_iter grad_eps
+            out[f"{name}/m{max_iter}"] = run("bfgs-mt", n, ",".join(float(v).hex() for v in params),
+                                             ",".join(float(v).hex() for v in x0), float(alpha).hex(),
+                                             max_iter, 0)
+    return out
+
+
 def main():
     # G4 — PSO (nlsolver.h:2496-2742). Vanilla is only pinned where it is defined
     # behaviour (particles <= D, SURVEY B7).
@@ -31,6 +100,8 @@ def main():
         "hess_update_3x3": run("hess-update"),
     }
     write("bfgs.json", g6)
+
+    write("bfgs_mt.json", bfgs_mt_records())
 
     # BFGS with the DEFAULT gradient (fin_diff = finite_difference_gradient<.,.,1>,
     # nlsolver.h:1385-1413, 2849-2855) on built-in objectives; all objective values counted.

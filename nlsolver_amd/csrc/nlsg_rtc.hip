@@ -233,9 +233,13 @@ static int rtc_compile_source(const std::string &src, const char *what,
       return fail(NLSG_ERR_HIP, "hiprtcAddNameExpression(%s) failed", n.c_str());
     }
   // the flags of csrc/Makefile: device arithmetic must stay bit-reproducible
+  // ... and no spilling of vector registers to accumulation registers: for a kernel bounded to 1024
+  // threads (128 registers per lane) the compiler has placed 9 spill AGPRs behind 124 VGPRs (a user term
+  // body in nm_solve_driver_kernel), 133 in all -- the dispatch of a 1024-thread workgroup is then refused
+  // ("out of VGPRs"). Spills go to scratch instead, and the count stays within the bound.
   const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                        "-fno-fast-math"};
-  const hiprtcResult cr = api.CompileProgram(prog, 5, opts);
+                        "-fno-fast-math", "-mllvm", "-amdgpu-spill-vgpr-to-agpr=0"};
+  const hiprtcResult cr = api.CompileProgram(prog, 7, opts);
   if (cr != HIPRTC_SUCCESS) {
     size_t ls = 0;
     api.GetProgramLogSize(prog, &ls);

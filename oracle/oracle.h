@@ -57,6 +57,9 @@ double orc_cos_2pi(double x); /* cos(2 pi x), the device's Rastrigin cosine (nls
 double orc_log_unit(double x); /* log for x in [2^-64, 1]: det_rnorm's table-driven logarithm */
 double orc_cos_unit(double y); /* cos for y in [0, 6.3]: det_rnorm's one-polynomial cosine */
 double orc_rnorm(uint64_t z1); /* one normal variate from one 64-bit draw (nlsg_math.h det_rnorm) */
+/* out[i] = orc_u01 / orc_rnorm of orc_ctr_key(parent, first + stride i), i < count */
+void orc_u01_keys(uint64_t parent, uint64_t first, uint64_t stride, size_t count, double *out);
+void orc_rnorm_keys(uint64_t parent, uint64_t first, uint64_t stride, size_t count, double *out);
 void orc_probe_math(int fn, const uint64_t *in, uint64_t *out, size_t n); /* cf. nlsg_probe_math */
 
 /* ------------------------------------------------------------ objectives --- */

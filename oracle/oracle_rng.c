@@ -44,3 +44,12 @@ uint64_t orc_ctr_key(uint64_t parent, uint64_t index) {
 }
 
 double orc_u01(uint64_t bits) { return (double)bits * 0x1p-64; }
+
+/* Rows of keyed draws for the Python references of tests/_direct_ref.py (one call per particle
+ * instead of two per coordinate): out[i] = u01 / rnorm of key(parent, first + stride i). */
+void orc_u01_keys(uint64_t parent, uint64_t first, uint64_t stride, size_t count, double *out) {
+  for (size_t i = 0; i < count; i++) out[i] = orc_u01(orc_ctr_key(parent, first + stride * i));
+}
+void orc_rnorm_keys(uint64_t parent, uint64_t first, uint64_t stride, size_t count, double *out) {
+  for (size_t i = 0; i < count; i++) out[i] = orc_rnorm(orc_ctr_key(parent, first + stride * i));
+}

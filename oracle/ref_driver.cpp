@@ -230,6 +230,7 @@ static int bench_de(size_t D, size_t pop, size_t gens) {
 
 #include "ref_driver_more.inc"
 #include "ref_driver_stat.inc"
+#include "ref_driver_hostile.inc"
 
 int main(int argc, char **argv) {
   if (argc < 2) {
@@ -266,6 +267,7 @@ int main(int argc, char **argv) {
     const size_t gens = argc > 4 ? std::strtoull(argv[4], nullptr, 10) : 10;
     return bench_de(D, pop, gens);
   }
+  if (cmd == "nm-hostile") return run_nm_hostile(argc, argv);
   {
     bool handled = false;
     const int rc = stat_main(cmd, argc, argv, handled);

@@ -316,6 +316,9 @@ def load():
         fn.argtypes = [f64]
     lib.orc_rnorm.restype = f64
     lib.orc_rnorm.argtypes = [u64]
+    for name in ("orc_u01_keys", "orc_rnorm_keys"):
+        getattr(lib, name).restype = None
+        getattr(lib, name).argtypes = [u64, u64, u64, sz, pd]
     lib.orc_probe_math.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), sz]
     lib.orc_cholesky.argtypes = [pd, sz]
     lib.orc_update_with_hessian.argtypes = [pd, pd, pd, sz]

@@ -243,6 +243,37 @@ int nlsg_de_bound_counts(nlsg_de *e, uint64_t *out3);
 int nlsg_de_bound_state(const nlsg_de *e, int32_t *enabled, uint32_t *retry_period);
 int nlsg_de_bound_gate(int32_t objective, int32_t strategy, int32_t minimize, double CR, uint64_t dim);
 
+/* Test access to the half-row reject screen that rides on the bound at 65 <= dim <= 128
+ * (NLSG_DE_SCREEN=0 in the environment at create switches it off, NLSG_DE_SCREEN_RETRY moves its
+ * retry period): the bound's lane tree over coordinates 0..63 alone, two agents per wave. It only
+ * ever rejects what the bound rejects. No result depends on it.
+ *   nlsg_de_screen_counts : out2 = agents since nlsg_de_init whose trial the screen rejected (they
+ *                           are counted as decided by nlsg_de_bound_counts too) / that tried it and
+ *                           were not decided. Requires cfg.trace. Synchronises.
+ *   nlsg_de_screen_state  : whether this engine screens, and the period (a power of two) at which
+ *                           an agent with two or more misses in a row tries again
+ *   nlsg_de_screen_gate   : 1 when an engine of these settings would screen (host only)
+ *   nlsg_de_screen_env    : the two environment switches as nlsg_de_create reads them (host only)
+ *   nlsg_de_screen_rule   : the back-off rule as a pure function (host only): returns 1 when an
+ *                           agent whose selector byte is `selector` tries the screen in `generation`
+ *                           (retry periods of the bound and of the screen given), and the miss count
+ *                           after `outcome` (0 decided, 1 missed, 2 not tried or declined)
+ * An engine that may screen also chooses, wherever the host reads its state (status, best, download,
+ * upload, the polls of minimize), between the pair wave and the one-agent launches by the share of
+ * agents the screen decided since the last look (below 0.9: off, tried again 1024 generations
+ * later); nlsg_de_screen_state reports the launch in force. NLSG_DE_SCREEN_ADAPT=0 at create keeps
+ * the pair wave on. One exception to "nlsg_de_bound_counts is what it was": a trial with a NaN
+ * among its terms past coordinate 63 whose screen value reaches the old score is counted as decided
+ * (and its hint cleared) where the engine without the screen counts it as not decided and rejected;
+ * every output is the same.
+ * Optional symbols, as above. */
+int nlsg_de_screen_counts(nlsg_de *e, uint64_t *out2);
+int nlsg_de_screen_state(const nlsg_de *e, int32_t *enabled, uint32_t *retry_period);
+int nlsg_de_screen_gate(int32_t objective, int32_t strategy, int32_t minimize, double CR, uint64_t dim);
+int nlsg_de_screen_env(int32_t *enabled, uint32_t *retry_period);
+int nlsg_de_screen_rule(uint32_t selector, uint64_t generation, uint64_t agent, uint32_t bound_retry,
+                        uint32_t screen_retry, int32_t outcome, uint32_t *count_after);
+
 /* Measurement aid for bench.py: launches ONLY the generation kernel `launches`
  * times back to back on the engine's stream (buffers ping-pong, solver state is
  * restored afterwards) bracketed by two hipEvents; returns total milliseconds. */

@@ -272,6 +272,12 @@ OPTIONAL_SYMBOLS = {
     "nlsg_de_bound_counts": (C.c_int, [_H, pu]),
     "nlsg_de_bound_state": (C.c_int, [_H, C.POINTER(i32), C.POINTER(C.c_uint32)]),
     "nlsg_de_bound_gate": (C.c_int, [i32, i32, i32, f64, u64]),
+    "nlsg_de_screen_counts": (C.c_int, [_H, pu]),
+    "nlsg_de_screen_state": (C.c_int, [_H, C.POINTER(i32), C.POINTER(C.c_uint32)]),
+    "nlsg_de_screen_gate": (C.c_int, [i32, i32, i32, f64, u64]),
+    "nlsg_de_screen_env": (C.c_int, [C.POINTER(i32), C.POINTER(C.c_uint32)]),
+    "nlsg_de_screen_rule": (C.c_int, [C.c_uint32, u64, u64, C.c_uint32, C.c_uint32, i32,
+                                      C.POINTER(C.c_uint32)]),
     "nlsg_custom_params_lds_bytes": (u64, [i32]),
     "nlsg_de_batch_lds_bytes": (u64, [u64, u64]),
     "nlsg_de_batch_create": (C.c_int, [C.POINTER(DEBatchConfig), C.POINTER(_H)]),
@@ -327,6 +333,7 @@ OPTIONAL_SYMBOLS = {
 SYMBOLS.update(OPTIONAL_SYMBOLS)
 _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
                     "nlsg_de_bound_": "library has no lower-bound rejection in the DE generation",
+                    "nlsg_de_screen_": "library has no half-row screen in the DE generation",
                     "nlsg_custom_params_": "library has no run-time objective parameters",
                     "nlsg_de_batch_set_params": "library has no run-time objective parameters",
                     "nlsg_pso_batch_set_params": "library has no run-time objective parameters",

@@ -34,6 +34,18 @@ struct nlsg_de : EngineBase {
   DeRtcKernels rtc;           // objective == NLSG_OBJ_CUSTOM: the kernels hiprtc built for it
   bool overlap = false;
   bool fused = false;   // head k and generation k+1 share one launch (strategy random, one GPU)
+  // The pair wave pays where the screen decides nearly every agent and costs where it does not
+  // (two undecided agents run one after the other in one wave). Every 64th pair wave counts its
+  // decisions on the device; wherever the host reads the state anyway (status, best, download, the
+  // polls of minimize) it compares the count with the generations launched since the last look and
+  // drops bit kDeBoundScreen of DeParams.bound -- the parent's one-agent launches -- while the share
+  // of decided agents is below kDeScreenKeep, then tries the pair wave again for one interval after
+  // kDeScreenProbe generations. Switching changes the path only, never an output: the one-agent
+  // path clears the miss counts it writes over. NLSG_DE_SCREEN_ADAPT=0: the pair wave stays on.
+  bool screen_capable = false, screen_adapt = false;
+  uint32_t stat_seen = 0;   // the device's count at the last look
+  uint64_t k_seen = 0;      // generations launched at the last look
+  uint64_t k_off = 0;       // generations launched when the pair wave was switched off
 };
 
 namespace {
@@ -126,11 +138,16 @@ void launch_generation_groups(nlsg_de *e, dim3 grid, int par, uint64_t generatio
   }
 }
 
+// waves of a generation: one per agent, one per 64 / group agents (D <= 64), or one per two agents
+// (the screen's pair wave, kDeBoundScreen)
+uint64_t generation_waves(const nlsg_de *e) {
+  const uint64_t per_wave = (e->p.bound & kDeBoundScreen) ? 2 : e->group ? 64 / e->group : 1;
+  return (e->p.shard_n + per_wave - 1) / per_wave;
+}
+
 void launch_generation(nlsg_de *e, int par, uint64_t generation, int ignore_done = 0) {
   e->p.gen_key = ctr_key(e->p.seed, generation);
-  // waves: one per agent, or one per 64 / group agents
-  const uint64_t per_wave = e->group ? 64 / e->group : 1;
-  const uint64_t waves = (e->p.shard_n + per_wave - 1) / per_wave;
+  const uint64_t waves = generation_waves(e);
   const dim3 grid(static_cast<unsigned>((waves + 3) / 4)), block(256);
   if (e->cfg.objective == NLSG_OBJ_CUSTOM) {
     void *args[] = {&e->p, &par, &generation, &ignore_done};
@@ -167,15 +184,19 @@ void launch_generation(nlsg_de *e, int par, uint64_t generation, int ignore_done
     return;
   }
   // (an engine that uses the bound launches the instantiation that has it: DeParams.bound)
-#define CALL_B(OBJ, C, V, B)                                                                   \
-  hipLaunchKernelGGL((de_generation_kernel<OBJ, C, V, B>), grid, block, 0, e->stream, e->p, par, \
+  // (and one that screens, the instantiation with the pair wave: kDeBoundScreen, one chunk only)
+#define CALL_B(OBJ, C, V, B, S)                                                                   \
+  hipLaunchKernelGGL((de_generation_kernel<OBJ, C, V, B, S>), grid, block, 0, e->stream, e->p, par, \
                      generation, ignore_done)
-#define CALL(OBJ, C)                                                   \
-  if (e->p.bound) {                                                    \
-    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value);  \
-    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value);          \
-  } else if (e->p.vec) CALL_B(OBJ, C, true, false);                    \
-  else CALL_B(OBJ, C, false, false)
+#define CALL(OBJ, C)                                                          \
+  if (e->p.bound & kDeBoundScreen) {                                          \
+    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value, (TermsNonNegative<OBJ>::value && C == 1));  \
+    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value, (TermsNonNegative<OBJ>::value && C == 1));          \
+  } else if (e->p.bound) {                                                    \
+    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value, false);  \
+    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value, false);          \
+  } else if (e->p.vec) CALL_B(OBJ, C, true, false, false);                    \
+  else CALL_B(OBJ, C, false, false, false)
   NLSG_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
 #undef CALL
 #undef CALL_B
@@ -203,8 +224,7 @@ void launch_fused_turn_groups(nlsg_de *e, dim3 grid, int par, uint64_t generatio
 // head k and generation k+1 in one launch (de_turn_kernel)
 void launch_fused_turn(nlsg_de *e, int par, uint64_t generation) {
   e->p.gen_key = ctr_key(e->p.seed, generation);
-  const uint64_t per_wave = e->group ? 64 / e->group : 1;
-  const uint64_t waves = (e->p.shard_n + per_wave - 1) / per_wave;
+  const uint64_t waves = generation_waves(e);
   const dim3 grid(static_cast<unsigned>((waves + 3) / 4 + e->p.ntiles)), block(256);
   if (e->cfg.objective == NLSG_OBJ_CUSTOM) {
     void *args[] = {&e->p, &par, &generation};
@@ -222,14 +242,17 @@ void launch_fused_turn(nlsg_de *e, int par, uint64_t generation) {
     }
     return;
   }
-#define CALL_B(OBJ, C, V, B) \
-  hipLaunchKernelGGL((de_turn_kernel<OBJ, C, V, B>), grid, block, 0, e->stream, e->p, par, generation)
-#define CALL(OBJ, C)                                                   \
-  if (e->p.bound) {                                                    \
-    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value);  \
-    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value);          \
-  } else if (e->p.vec) CALL_B(OBJ, C, true, false);                    \
-  else CALL_B(OBJ, C, false, false)
+#define CALL_B(OBJ, C, V, B, S) \
+  hipLaunchKernelGGL((de_turn_kernel<OBJ, C, V, B, S>), grid, block, 0, e->stream, e->p, par, generation)
+#define CALL(OBJ, C)                                                          \
+  if (e->p.bound & kDeBoundScreen) {                                          \
+    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value, (TermsNonNegative<OBJ>::value && C == 1));  \
+    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value, (TermsNonNegative<OBJ>::value && C == 1));          \
+  } else if (e->p.bound) {                                                    \
+    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value, false);  \
+    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value, false);          \
+  } else if (e->p.vec) CALL_B(OBJ, C, true, false, false);                    \
+  else CALL_B(OBJ, C, false, false, false)
   NLSG_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
 #undef CALL
 #undef CALL_B
@@ -272,6 +295,30 @@ int join_side(nlsg_de *e) {
   return NLSG_OK;
 }
 
+constexpr double kDeScreenKeep = 0.9;       // share of decided agents below which the pair wave is dropped
+constexpr uint64_t kDeScreenProbe = 1024;   // generations after which it is tried again
+constexpr uint64_t kDeScreenLook = 8;       // generations a look needs to judge
+
+// the pair wave on or off by what the sampled waves decided since the last look (nlsg_de.screen_adapt)
+void adapt_screen(nlsg_de *e, uint32_t stat) {
+  if (!e->screen_adapt) return;
+  const uint64_t gens = e->k - e->k_seen;
+  if (e->p.bound & kDeBoundScreen) {
+    if (gens < kDeScreenLook) return;  // (the counters keep running: judged at a later look)
+    const uint64_t pairs = (e->p.shard_n + 1) / 2;
+    const uint64_t sampled = std::min<uint64_t>(2 * ((pairs + 63) / 64), e->p.shard_n);  // agents of the counting waves
+    const double share = static_cast<double>(stat - e->stat_seen) / (static_cast<double>(sampled) * static_cast<double>(gens));
+    if (share < kDeScreenKeep) {
+      e->p.bound &= ~kDeBoundScreen;
+      e->k_off = e->k;
+    }
+  } else if (e->k - e->k_off >= kDeScreenProbe) {
+    e->p.bound |= kDeBoundScreen;
+  }
+  e->stat_seen = stat;
+  e->k_seen = e->k;
+}
+
 int read_state(nlsg_de *e, DeState *host) {
   int rc = join_side(e);
   if (rc) return rc;
@@ -279,6 +326,7 @@ int read_state(nlsg_de *e, DeState *host) {
   NLSG_HIP(hipMemcpyAsync(host, e->p.state, sizeof(DeState), hipMemcpyDeviceToHost, e->stream));
   NLSG_HIP(hipStreamSynchronize(e->stream));
   NLSG_HIP(launches_status());
+  adapt_screen(e, static_cast<uint32_t>(host->pad[0]));
   return NLSG_OK;
 }
 
@@ -394,11 +442,11 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   alloc(&p.home[1], n);
   alloc(&p.best_x, D * sizeof(double));
   if (cfg->trace) alloc(&p.trace, n * kTraceWords * sizeof(uint64_t));
-  if (cfg->trace) alloc(&p.counts, 3 * sizeof(uint64_t));  // the bound's path counters (cleared by init)
+  if (cfg->trace) alloc(&p.counts, kDeCounts * sizeof(uint64_t));  // the bound's and the screen's path counters (cleared by init)
   alloc(&p.state, sizeof(DeState));
   p.ntiles = static_cast<uint32_t>((n + kTile - 1) / kTile);
   alloc(&p.part, p.ntiles * sizeof(TilePartial));
-  own.zeroed(&p.ticket, 8);
+  own.zeroed(&p.ticket, (kDeScreenStat + 1) * sizeof(uint32_t));  // the head's ticket, and the screen's sampled count
   own.zeroed(&e->zero_dev, 16);
   p.zero = e->zero_dev;
   alloc(&e->x0_dev, D * sizeof(double));
@@ -460,6 +508,18 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
                 ? 1
                 : 0;
   p.retry_mask = retry - 1;
+  // the half-row screen on top of the bound (kDeBoundScreen): NLSG_DE_SCREEN=0 off,
+  // NLSG_DE_SCREEN_RETRY another retry period (the sweep of DESIGN.md section 3)
+  bool screen_on = true;
+  uint32_t screen_retry = kDeScreenRetry;
+  de_screen_env(std::getenv("NLSG_DE_SCREEN"), std::getenv("NLSG_DE_SCREEN_RETRY"), &screen_on, &screen_retry);
+  if (p.bound && screen_on && e->chunks == 1 &&
+      de_screen_gate(cfg->objective, cfg->strategy, cfg->minimize != 0, cfg->CR, D, min_cr, max_cr))
+    p.bound |= kDeBoundScreen;
+  p.screen_retry_mask = screen_retry - 1;
+  e->screen_capable = (p.bound & kDeBoundScreen) != 0;
+  const char *ad = std::getenv("NLSG_DE_SCREEN_ADAPT");
+  e->screen_adapt = e->screen_capable && !(ad && ad[0] == '0');
   if (custom) {
     const int rc2 = rtc_build_de(custom, e->long_rows ? 0 : e->chunks, p.vec != 0, e->group, &e->rtc);
     if (rc2) {
@@ -493,9 +553,13 @@ int nlsg_de_init(nlsg_de *e, const double *x0_host) {
   int rcj = join_side(e);  // a previous run's last head may still be queued on the side stream
   if (rcj) return rcj;
   hipLaunchKernelGGL(de_reset_state_kernel, dim3(1), dim3(1), 0, e->stream, e->p);
-  if (e->p.counts) NLSG_HIP(hipMemsetAsync(e->p.counts, 0, 3 * sizeof(uint64_t), e->stream));
+  if (e->p.counts) NLSG_HIP(hipMemsetAsync(e->p.counts, 0, kDeCounts * sizeof(uint64_t), e->stream));
   launch_init(e);
   e->k = 0;
+  if (e->screen_capable) {  // a new solve starts with the pair wave; the device's count keeps running
+    e->p.bound |= kDeBoundScreen;
+    e->k_seen = e->k_off = 0;
+  }
   if (e->overlap) NLSG_HIP(hipEventRecord(e->ev_gen[0], e->stream));
   NLSG_HIP(launches_status());
   e->initialised = true;
@@ -589,13 +653,53 @@ int nlsg_de_bound_counts(nlsg_de *e, uint64_t *out3) {
 
 int nlsg_de_bound_state(const nlsg_de *e, int32_t *enabled, uint32_t *retry_period) {
   if (!e) return fail(NLSG_ERR_INVALID_ARG, "null engine");
-  if (enabled) *enabled = e->p.bound;
+  if (enabled) *enabled = e->p.bound != 0;
   if (retry_period) *retry_period = e->p.retry_mask + 1;
   return NLSG_OK;
 }
 
 int nlsg_de_bound_gate(int32_t objective, int32_t strategy, int32_t minimize, double CR, uint64_t dim) {
   return de_bound_gate(objective, strategy, minimize != 0, CR, dim) ? 1 : 0;
+}
+
+int nlsg_de_screen_counts(nlsg_de *e, uint64_t *out2) {
+  if (!e || !out2) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_de_init has not been called");
+  if (!e->p.counts) return fail(NLSG_ERR_STATE, "engine was created without cfg.trace");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  int rc = join_side(e);
+  if (rc) return rc;
+  NLSG_HIP(hipMemcpyAsync(out2, e->p.counts + kDeScreenDecided, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                          e->stream));
+  NLSG_HIP(hipStreamSynchronize(e->stream));
+  NLSG_HIP(launches_status());
+  return NLSG_OK;
+}
+
+int nlsg_de_screen_state(const nlsg_de *e, int32_t *enabled, uint32_t *retry_period) {
+  if (!e) return fail(NLSG_ERR_INVALID_ARG, "null engine");
+  if (enabled) *enabled = (e->p.bound & kDeBoundScreen) != 0;
+  if (retry_period) *retry_period = e->p.screen_retry_mask + 1;
+  return NLSG_OK;
+}
+
+int nlsg_de_screen_gate(int32_t objective, int32_t strategy, int32_t minimize, double CR, uint64_t dim) {
+  return de_screen_gate(objective, strategy, minimize != 0, CR, dim) ? 1 : 0;
+}
+
+int nlsg_de_screen_env(int32_t *enabled, uint32_t *retry_period) {
+  bool on = true;
+  uint32_t period = kDeScreenRetry;
+  de_screen_env(std::getenv("NLSG_DE_SCREEN"), std::getenv("NLSG_DE_SCREEN_RETRY"), &on, &period);
+  if (enabled) *enabled = on ? 1 : 0;
+  if (retry_period) *retry_period = period;
+  return NLSG_OK;
+}
+
+int nlsg_de_screen_rule(uint32_t selector, uint64_t generation, uint64_t agent, uint32_t bound_retry,
+                        uint32_t screen_retry, int32_t outcome, uint32_t *count_after) {
+  if (count_after) *count_after = de_screen_count_after((selector >> 2) & 3u, outcome);
+  return de_screen_tries(selector, generation, static_cast<uint32_t>(agent), bound_retry - 1, screen_retry - 1) ? 1 : 0;
 }
 
 int nlsg_de_upload(nlsg_de *e, const double *pop_host, const double *scores_host) {

@@ -45,7 +45,8 @@ constexpr int kTraceWords = 5;        // r1, r2, r3, jrand, accept
 // (DeParams.bound below). Every reader of a selector therefore takes `& 1`: de_row, the `row`
 // lambdas of de_fetch_agent and of the packed generation, DeAgent.home, de_gather_kernel and the
 // head's best row (both through de_row). Init stores 0 and upload's memset stores the parity
-// (0 or 1), so both clear the hint.
+// (0 or 1), so both clear the hint. Bits 2-3 are the screen's miss count (kDeBoundScreen), kept by
+// the pair wave alone and carried through select() as DeAgent.miss; the same readers ignore them.
 struct DeParams {
   double *buf[2];      // population ping-pong, rows addressed through `home`
   double *scores[2];   // [shard_n] each, ping-pong with the population: a generation reads
@@ -83,14 +84,31 @@ struct DeParams {
   // (generation + a) & retry_mask == 0, when it tries the bound again. The path taken never
   // changes an output.
   int32_t bound;
-  uint64_t *counts;    // cfg.trace only, else nullptr: [3] agents per path (kDeBound*), for tests
+  uint64_t *counts;    // cfg.trace only, else nullptr: [kDeCounts] agents per path (kDeBound*, kDeScreen*), for tests
   uint32_t retry_mask; // R - 1, R a power of two
-  uint32_t pad2;
+  // Half-row reject screen (host-set, wave-uniform; de_screen_gate in nlsg_de_state.h; 65 <= D <= 128
+  // with `bound` set). The same lane tree with +0.0 in place of every term that touches a coordinate
+  // >= 64 is <= the bound above, hence <= the score, by the same argument: screen >= old_score
+  // rejects the trial on 512 B of each donor row and 64 crossover draws. Half a row is 32 lanes, so
+  // a wave of the generation takes two agents, one per half-wave (de_generation_pair); an agent the
+  // screen does not decide goes through de_fetch_agent / de_process_agent unchanged. Bits 2-3 of an
+  // agent's selector byte count its consecutive screen misses (saturating at 3; a decision clears
+  // them): from two misses on the agent skips the screen except in the generations where
+  // (generation + a) & screen_retry_mask == 0. The screen only ever rejects, and only in a
+  // generation in which the agent tries the bound; no output depends on it.
+  // The flag is bit 1 of `bound` (kDeBoundScreen; the kernels only test `bound` for non-zero): the
+  // argument block keeps its size, and the engines that do not screen their exact launches.
+  uint32_t screen_retry_mask;  // R - 1, R a power of two
 };
+constexpr int32_t kDeBoundScreen = 2;
+constexpr int kDeScreenStat = 32;  // word of the `ticket` block, a cache line away from the head's ticket
 
 // DeParams.counts: the bound decided / it did not and the trial was rejected / it did not (or every
-// coordinate came from the mutant: the bound is the score) and the trial was accepted
+// coordinate came from the mutant: the bound is the score) and the trial was accepted; then the
+// screen's own two: it decided (counted under kDeBoundDecided as well: what the screen rejects the
+// bound rejects) / it was tried and did not
 constexpr int kDeBoundDecided = 0, kDeBoundRejected = 1, kDeBoundAccepted = 2;
+constexpr int kDeScreenDecided = 3, kDeScreenMissed = 4, kDeCounts = 5;
 
 // agent `local`'s row in buffer h (a home selector value; the select keeps DeParams out of
 // scratch and any stray byte inside the two buffers)
@@ -146,7 +164,8 @@ struct DeAgent {
   uint64_t a, ka, r0, r1, r2, jrand;
   uint32_t home;          // home[par][a] & 1: the buffer holding the agent's row
   uint32_t hint;          // home[par][a] & 2: the bound did not decide this agent's last try
-  bool bound;             // wave-uniform: this generation tries the bound, `keep` is not loaded yet
+  uint32_t miss;          // bits 2-3 of the selector byte to leave behind (the pair wave sets it, else 0)
+  bool bound;            // wave-uniform: this generation tries the bound, `keep` is not loaded yet
   uint64_t cross[CHUNKS][2];  // lane masks (lane_bit): the trial takes the mutant here (crossover draw or jrand)
   double keep[CHUNKS][2], d1[CHUNKS][2], d2[CHUNKS][2], d3[CHUNKS][2];
   double old_score;
@@ -290,6 +309,7 @@ __device__ inline void de_fetch_agent(const DeParams &p, int par, uint64_t kg, u
   const uint32_t hraw = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(hsel), 0));
   c.home = hraw & 1u;
   c.hint = 0;
+  c.miss = 0;
   c.bound = false;
   if constexpr (BOUND) {
     c.hint = hraw & 2u;
@@ -336,7 +356,7 @@ __device__ inline void de_process_agent(const DeParams &p, int par, DeAgent<CHUN
     }
     if (lane == 0) {
       p.scores[par ^ 1][c.a] = accept ? score : c.old_score;
-      p.home[par ^ 1][c.a] = static_cast<uint8_t>((accept ? c.home ^ 1u : c.home) | hint);
+      p.home[par ^ 1][c.a] = static_cast<uint8_t>((accept ? c.home ^ 1u : c.home) | hint | c.miss);
     }
     if (p.trace != nullptr && lane == 0) {
       uint64_t *t = p.trace + c.a * kTraceWords;
@@ -528,11 +548,187 @@ __global__ __launch_bounds__(256) void de_generation_groups_kernel(DeParams p, i
   de_generation_groups_block<OBJ, G>(p, par, generation, ignore_done, blockIdx.x);
 }
 
+// ---- the half-row reject screen: two agents per wave, one per half-wave (kDeBoundScreen) ---------
+// Wave w of the generation takes agents 2w and 2w + 1 (a lone last agent: the upper half shadows it
+// and writes nothing). Half-lane j = lane & 31 holds coordinates 2j, 2j + 1 of its half's agent, and
+// everything that is wave-uniform in de_fetch_agent is half-uniform here and lives in vector
+// registers: the agent's key, draw D + j of its stream (j = 0 jrand, j = 1..31 donor candidates
+// 0..30 -- the values lanes 0..31 of the one-agent path hold), and the donor picks, made by the same
+// rule on each half's 32 bits of the ballots. An agent declines the screen when 31 candidates do
+// not give three donors or when a pick lies past candidate 6 (its selector is not among the bytes
+// lanes 1..7 loaded; tiny shards): it takes the one-agent path like an agent the screen missed.
+//
+// The screen value. Lane j accumulates as wave_objective_masked does -- 0.0, then term 2j, then
+// term 2j + 1, +0.0 in place of a term that reads a kept coordinate -- with term 63 always +0.0
+// (its neighbour x64 is not loaded), and the butterfly levels 16 .. 1 run inside the half. Proof
+// that this is wave_objective_masked's tree with every term >= 64 replaced by +0.0: there lanes
+// 32..63 hold +0.0 before the butterfly, level 32 of wave_sum runs first and leaves
+// acc_j + (+0.0) = acc_j in lanes j and 32 + j (acc_j is >= +0 or NaN), and levels 16 .. 1 never
+// cross the half. Terms are >= +0 or NaN (TermsNonNegative) and round-to-nearest addition is
+// monotone in each operand, so screen <= bound <= score bit for bit whenever the bound is not NaN,
+// and screen >= old_score (false for NaN) implies bound >= old_score: the bound's "decided" exit,
+// whose stores are the ones made here. (A NaN among the terms past 63 makes bound and score NaN:
+// the trial is rejected all the same, every output equal; only the bound's hint and its counters,
+// which no output depends on, would then say "not decided".)
+template <int OBJ, bool VEC>
+__device__ inline void de_generation_pair(const DeParams &p, int par, uint64_t generation, uint64_t block) {
+  static_assert(TermsNonNegative<OBJ>::value, "the screen needs terms >= 0");
+  using O = Objective<OBJ>;
+  const uint64_t a0 = 2 * (block * 4 + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6));
+  if (a0 >= p.shard_n) return;
+  const bool two = a0 + 1 < p.shard_n;  // wave-uniform
+  const int lane = lane_id();
+  const uint32_t j = static_cast<uint32_t>(lane) & 31u;
+  const bool upper = lane >= 32;
+  const bool live = !upper || two;
+  // (shard sizes fit 32 bits: the shard-local agent index is a 32-bit value per half)
+  const uint32_t a = static_cast<uint32_t>(a0) + ((upper && two) ? 1u : 0u);
+  const uint8_t *__restrict__ hp = p.home[par];
+  const uint32_t hraw = hp[a];
+  double old_score = p.scores[par][a];  // with the selector byte: not a round trip of its own later
+  const uint32_t d32 = static_cast<uint32_t>(p.D);
+  // the agent's key on the vector unit, one value per half
+  const uint64_t ka = ctr_key(p.gen_key, p.shard_lo + a);
+  const uint32_t lim = j == 0 ? d32 : static_cast<uint32_t>(p.shard_n);
+  const uint32_t idx = static_cast<uint32_t>(u01(mix64(ka + golden_times(d32 + j + 1u))) * static_cast<double>(lim));
+  const uint32_t drawn = idx >= lim ? lim - 1 : idx;  // the u == 1.0 corner clamped (B10)
+  // who tries: the generations in which the one-agent path would try the bound (DeAgent.bound),
+  // less the agents that missed the screen twice in a row outside their retry generations
+  // (the selector byte is first needed here: tied to the draw, its load's latency hides behind the
+  // key and the draw instead of stalling the wave in front of them; and the rule is written without
+  // short-circuits: straight-line mask arithmetic, no branches on a per-lane value)
+  uint32_t sel = hraw;
+  asm("" : "+v"(sel), "+v"(old_score) : "v"(drawn));
+  const uint32_t cnt = (sel >> 2) & 3u;
+  const bool tries = live & de_screen_tries(sel, generation, a, p.retry_mask, p.screen_retry_mask);
+  bool dec = false;         // the screen rejected this half's trial
+  uint32_t left = cnt << 2;  // bits 2-3 of the selector byte this generation leaves behind
+  if (__ballot(tries) != 0ull) {  // wave-uniform
+    // selectors of donor candidates 0..6, as in de_fetch_agent
+    const uint32_t hsel = hp[(j >= 1 && j < 8) ? drawn : a];
+    auto half_of = [&](uint32_t lo, uint32_t hi) { return upper ? hi : lo; };
+    auto lane32 = [&](uint32_t v, int src) {
+      return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), src));
+    };
+    const uint32_t jrand = half_of(lane32(drawn, 0), lane32(drawn, 32));  // :2364
+    // generate_indices (nlsolver.h:2331-2355) per half: the first three candidates in order that
+    // differ from the agent and from each other (de_fetch_agent's compares, 32 bits of each ballot)
+    constexpr uint32_t top = 1u << 31;
+    const uint64_t b0 = __ballot(drawn != a) & ~0x0000000100000001ull;  // half-lane 0 holds jrand
+    const uint32_t m0l = static_cast<uint32_t>(b0), m0h = static_cast<uint32_t>(b0 >> 32);
+    const int i0l = __builtin_ctz(m0l | top), i0h = __builtin_ctz(m0h | top);
+    const uint32_t r0 = half_of(lane32(drawn, i0l), lane32(drawn, 32 + i0h));
+    const uint64_t b1 = __ballot(drawn != r0);
+    const uint32_t m1l = m0l & static_cast<uint32_t>(b1) & ((~0u << i0l) << 1);
+    const uint32_t m1h = m0h & static_cast<uint32_t>(b1 >> 32) & ((~0u << i0h) << 1);
+    const int i1l = __builtin_ctz(m1l | top), i1h = __builtin_ctz(m1h | top);
+    const uint32_t r1 = half_of(lane32(drawn, i1l), lane32(drawn, 32 + i1h));
+    const uint64_t b2 = __ballot(drawn != r1);
+    const uint32_t m2l = m1l & static_cast<uint32_t>(b2) & ((~0u << i1l) << 1);
+    const uint32_t m2h = m1h & static_cast<uint32_t>(b2 >> 32) & ((~0u << i1h) << 1);
+    const int i2l = __builtin_ctz(m2l | top), i2h = __builtin_ctz(m2h | top);
+    const uint32_t r2 = half_of(lane32(drawn, i2l), lane32(drawn, 32 + i2h));
+    // three donors among the 31 candidates, the last one (i0 < i1 < i2) within candidates 0..6
+    const bool okl = m0l != 0 && m1l != 0 && m2l != 0 && i2l < 8;
+    const bool okh = m0h != 0 && m1h != 0 && m2h != 0 && i2h < 8;
+    const bool run = tries && (upper ? okh : okl);
+    // (a half that does not run reads in-bounds garbage: every index is some lane's `drawn`)
+    const uint32_t h0 = half_of(lane32(hsel, i0l), lane32(hsel, 32 + i0h));
+    const uint32_t h1 = half_of(lane32(hsel, i1l), lane32(hsel, 32 + i1h));
+    const uint32_t h2 = half_of(lane32(hsel, i2l), lane32(hsel, 32 + i2h));
+    // crossover masks of coordinates 2j, 2j + 1 (propose_new_agent, nlsolver.h:2357-2375)
+    const uint64_t ka_lane = ka + golden_times(2 * j + 1u);
+    const bool c0 = mix64(ka_lane) < p.cr_thresh || p.cr_all || 2 * j == jrand;
+    const bool c1 = mix64(ka_lane + kGolden) < p.cr_thresh || p.cr_all || 2 * j + 1 == jrand;
+    // the first 512 B of the three donor rows (coordinates 0..63 < D), never the own row
+    // (both buffer bases out of the kernel arguments once, the selector selects between the two
+    // values: see de_fetch_agent -- left alone the compiler loads the base through the selector, a
+    // dependent load in front of every row)
+    typedef double __attribute__((address_space(1))) global_double;
+    global_double *base0 = (global_double *)p.buf[0], *base1 = (global_double *)p.buf[1];
+    asm("" : "+s"(base0), "+s"(base1));
+    auto load2 = [&](uint32_t h, uint32_t r, double (&v)[2]) {
+      const double *src = (double *)((h & 1u) ? base1 : base0) + static_cast<uint64_t>(r) * d32 + 2 * j;
+      if (VEC) {
+        const double2 t = *reinterpret_cast<const double2 *>(src);
+        v[0] = t.x;
+        v[1] = t.y;
+      } else {
+        v[0] = src[0];
+        v[1] = src[1];
+      }
+    };
+    double d1[2], d2[2], d3[2];
+    load2(h0, r0, d1);
+    load2(h1, r1, d2);
+    load2(h2, r2, d3);
+    const double x0 = d1[0] + p.F * (d2[0] - d3[0]);  // the mutant
+    const double x1 = d1[1] + p.F * (d2[1] - d3[1]);
+    // lane j + 1's first coordinate and its flag; half-lane 31's neighbour is x64: never known
+    const double xn = lane_down1(x0);
+    const bool cn = lane_bit(__ballot(c0) >> 1) && j != 31;
+    const bool k0 = c0 && (O::kChain ? c1 : true);
+    const bool k1 = c1 && (O::kChain ? cn : j != 31);
+    double acc = 0.0;
+    acc = acc + (k0 ? O::term(x0, x1) : 0.0);
+    acc = acc + (k1 ? O::term(x1, xn) : 0.0);
+    butterfly_levels<16>([&](auto off) { acc = xor_add<decltype(off)::value>(acc); });
+    dec = run && acc >= old_score;  // (false for NaN) the score cannot be lower: rejected
+    left = de_screen_count_after(cnt, dec ? 0 : run ? 1 : 2) << 2;
+    if (j == 0 && dec) {  // what the bound's "decided" exit stores (select(false, ..., 0u))
+      p.scores[par ^ 1][a] = old_score;
+      p.home[par ^ 1][a] = static_cast<uint8_t>(hraw & 1u);
+      if (p.trace != nullptr) {
+        uint64_t *t = p.trace + static_cast<uint64_t>(a) * kTraceWords;
+        t[0] = p.shard_lo + r0;
+        t[1] = p.shard_lo + r1;
+        t[2] = p.shard_lo + r2;
+        t[3] = jrand;
+        t[4] = 0u;
+      }
+    }
+    if (p.counts != nullptr && j == 0 && run) {  // engines created with cfg.trace only
+      if (dec) atomicAdd(reinterpret_cast<unsigned long long *>(p.counts + kDeBoundDecided), 1ull);
+      atomicAdd(reinterpret_cast<unsigned long long *>(p.counts + (dec ? kDeScreenDecided : kDeScreenMissed)), 1ull);
+    }
+  }
+  // not decided here: the trial goes through the one-agent path, run by the whole wave
+  const uint64_t decided = __ballot(dec);
+  // every 64th wave adds its decisions to a running count the host reads with the state
+  // (kDeScreenStat): what the engine switches the pair wave off and on by, see nlsg_de.hip
+  // (one scalar test and branch for the 63 waves in 64 that do not count: folded into one
+  // predicate with the rest, the test costs every wave ten scalar instructions, 1 us per turn)
+  if (((a0 >> 1) & 63u) == 0) {
+    asm volatile("" ::: "memory");
+    if (decided != 0ull && lane == 0)
+      atomicAdd(p.ticket + kDeScreenStat, static_cast<uint32_t>(__builtin_popcountll(decided & 0x0000000100000001ull)));
+  }
+  // (left first: what the loop below needs in every pass is set up in front of it, and a wave whose
+  // agents are both decided -- nearly every wave where the screen pays -- must not pay for that)
+  if ((~decided & (two ? 0x0000000100000001ull : 1ull)) == 0ull) return;
+  const uint32_t left_l = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(left), 0));
+  const uint32_t left_h = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(left), 32));
+  const uint64_t best_id = p.state->best_id;
+  auto one_agent = [&](int h) {
+    DeAgent<1> A;
+    de_fetch_agent<true, 1, VEC>(p, par, p.gen_key, generation, best_id, a0 + h, A);
+    A.miss = h ? left_h : left_l;
+    de_process_agent<OBJ, 1, VEC, true>(p, par, A);
+  };
+  // (two inlined calls, not a loop over the halves: a loop has the compiler set up both passes'
+  // invariants in scalar registers in front of it -- 106 of them, 7 waves per SIMD instead of 8.
+  // Fetching both agents before processing either was measured too: it costs a wave per SIMD as
+  // well, +7 % at pop 2^20, and gains 2 % where the screen never decides. Not kept.)
+  if (!(decided & 1ull)) one_agent(0);
+  if (two && !((decided >> 32) & 1ull)) one_agent(1);
+}
+
 // One agent per wave. (Two agents per wave — ten gathers in flight — measured -7 % kernel time at
 // pop = 65536 but +9 % at pop = 2^20 and only -2 % per turn; not kept.)
 // BOUND: the instantiation an engine with DeParams.bound set launches (TermsNonNegative objectives
-// only); every other engine runs BOUND = false, the code without the bound.
-template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false>
+// only); every other engine runs BOUND = false, the code without the bound. SCREEN: the instantiation
+// an engine with kDeBoundScreen set launches (de_generation_pair); the others are the code without it.
+template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false, bool SCREEN = false>
 __device__ inline void de_generation_block(const DeParams &p, int par, uint64_t generation,
                                            int ignore_done, uint64_t block) {
   // `generation` (k+1) and the source buffer `par` (k & 1) come from the host: the k-th
@@ -541,6 +737,11 @@ __device__ inline void de_generation_block(const DeParams &p, int par, uint64_t 
   // final for every head older than that one.
   const DeState *__restrict__ st = p.state;
   if (!ignore_done && st->done) return;  // a stop test fired: the turn is a no-op
+  if constexpr (SCREEN) {  // kDeBoundScreen: the launch's grid has a block per 8 agents
+    static_assert(BOUND && CHUNKS == 1, "the screen rides on the bound, rows of 65..128 coordinates");
+    de_generation_pair<OBJ, VEC>(p, par, generation, block);
+    return;
+  }
   const uint64_t a0 = block * 4 + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
   if (a0 >= p.shard_n) return;
   const uint64_t kg = p.gen_key;  // = ctr_key(p.seed, generation), from the host
@@ -550,10 +751,10 @@ __device__ inline void de_generation_block(const DeParams &p, int par, uint64_t 
   de_process_agent<OBJ, CHUNKS, VEC, BOUND>(p, par, A);
 }
 
-template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false>
+template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false, bool SCREEN = false>
 __global__ __launch_bounds__(256) void de_generation_kernel(DeParams p, int par, uint64_t generation,
                                                           int ignore_done) {
-  de_generation_block<OBJ, CHUNKS, VEC, BOUND>(p, par, generation, ignore_done, blockIdx.x);
+  de_generation_block<OBJ, CHUNKS, VEC, BOUND, SCREEN>(p, par, generation, ignore_done, blockIdx.x);
 }
 
 // Gather of the population `par` into one contiguous [shard_n][D] block (host download)
@@ -715,13 +916,13 @@ __global__ __launch_bounds__(256) void de_scan_head_kernel(DeParams p, uint64_t 
 // k at the same time. Random donors do not depend on the head's result; if head k fires a
 // stop test, generation k+1 went to the other buffers and is never adopted (exactly the
 // speculative turn of the sharded path), so results equal the serial order head -> generation.
-template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false>
+template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false, bool SCREEN = false>
 __global__ __launch_bounds__(256) void de_turn_kernel(DeParams p, int par, uint64_t generation) {
   if (blockIdx.x < p.ntiles) {
     de_scan_head_block(p, generation - 1, blockIdx.x, nullptr);
     return;
   }
-  de_generation_block<OBJ, CHUNKS, VEC, BOUND>(p, par, generation, 0, blockIdx.x - p.ntiles);
+  de_generation_block<OBJ, CHUNKS, VEC, BOUND, SCREEN>(p, par, generation, 0, blockIdx.x - p.ntiles);
 }
 
 // the same turn with the packed generation (agents of at most 64 coordinates, several per wave)
@@ -931,8 +1132,10 @@ __global__ __launch_bounds__(256) void de_generation_long_kernel(DeParams p, int
 
 // Before the host reads the state: unless a stop test fired, the engine stands after the
 // k generations it has launched (the last head only saw k-1 of them).
+// (and the screen's running count of sampled decisions travels with the state: kDeScreenStat)
 __global__ void de_settle_kernel(DeParams p, uint64_t k) {
   if (!p.state->done) head_position(p.state, p, k);
+  p.state->pad[0] = static_cast<int32_t>(p.ticket[kDeScreenStat]);
 }
 
 }  // namespace nlsg

@@ -4,6 +4,10 @@
 // solve's counters and stop decisions cannot differ between them.
 #pragma once
 
+#ifndef __HIPCC_RTC__
+#include <cstdlib>
+#endif
+
 #include "nlsg_common.h"
 
 namespace nlsg {
@@ -88,6 +92,44 @@ inline bool de_bound_gate(int objective, int strategy, bool minimize, double cr,
          strategy == NLSG_DE_RANDOM && minimize && dim >= 65 && dim <= 1024 && cr >= min_cr &&
          cr < max_cr;
 }
+
+// Host side, at create: may the generation screen trials on half a row, two agents per wave
+// (kDeBoundScreen)? Wherever the bound may and the row fills one chunk past its half: 65 <= D <=
+// 128. Below 65 the packed kernels run; above 128 half a chunk is no longer half a wave's lanes.
+// kDeScreenRetry comes from the sweep in DESIGN.md section 3.
+constexpr uint32_t kDeScreenRetry = 16;  // an agent with >= 2 misses in a row tries every R-th generation
+inline bool de_screen_gate(int objective, int strategy, bool minimize, double cr, uint64_t dim,
+                           double min_cr = kDeBoundMinCR, double max_cr = kDeBoundMaxCR) {
+  return de_bound_gate(objective, strategy, minimize, cr, dim, min_cr, max_cr) && dim >= 65 && dim <= 128;
+}
+// The screen's two A/B switches as nlsg_de_create reads them: NLSG_DE_SCREEN=0 off,
+// NLSG_DE_SCREEN_RETRY another retry period (a power of two up to 2^30, else ignored).
+inline void de_screen_env(const char *screen, const char *retry, bool *on, uint32_t *period) {
+  *on = !(screen && screen[0] == '0');
+  *period = kDeScreenRetry;
+  if (retry) {
+    const long r = std::atol(retry);
+    if (r >= 1 && r <= (1l << 30) && (r & (r - 1)) == 0) *period = static_cast<uint32_t>(r);
+  }
+}
+
 #endif
+
+// The miss count in bits 2-3 of a selector byte (kDeBoundScreen), as a pure function: does an
+// agent with this byte try the screen in `generation`, and what the count becomes. The pair wave
+// (de_generation_pair) calls these two, and nlsg_de_screen_rule hands them to the host's tests.
+// Written without short-circuits: in the kernel the operands are per-lane values, and a branch on
+// one costs more than the mask arithmetic.
+//   outcome: 0 the screen decided, 1 it was tried and missed, 2 it was not tried or declined
+__host__ __device__ inline bool de_screen_tries(uint32_t sel, uint64_t generation, uint32_t a,
+                                                uint32_t bound_retry_mask, uint32_t screen_retry_mask) {
+  const uint32_t ga = static_cast<uint32_t>(generation) + a;  // the masks fit 32 bits
+  const bool bound_tries = ((sel & 2u) == 0) | ((ga & bound_retry_mask) == 0);
+  const uint32_t cnt = (sel >> 2) & 3u;
+  return bound_tries & ((cnt < 2) | ((ga & screen_retry_mask) == 0));
+}
+__host__ __device__ inline uint32_t de_screen_count_after(uint32_t cnt, int outcome) {
+  return outcome == 0 ? 0u : outcome == 1 ? (cnt < 3 ? cnt + 1 : 3u) : cnt;
+}
 
 }  // namespace nlsg

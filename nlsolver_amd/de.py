@@ -199,6 +199,20 @@ class DEEngine:
         check(require("nlsg_de_bound_state")(self._h, C.byref(on), C.byref(r)))
         return bool(on.value), r.value
 
+    def screen_counts(self):
+        """(decided, missed): agents since init() whose trial the half-row screen rejected (they
+        count as decided in bound_counts too) / that tried it and went on to the one-agent path.
+        Needs trace=True; both zero in an engine that does not screen (screen_state)."""
+        out = np.zeros(2, dtype=np.uint64)
+        check(require("nlsg_de_screen_counts")(self._h, out.ctypes.data_as(_capi.pu)))
+        return tuple(int(v) for v in out)
+
+    def screen_state(self):
+        """(enabled, retry period in generations) of the generation's half-row screen"""
+        on, r = C.c_int32(), C.c_uint32()
+        check(require("nlsg_de_screen_state")(self._h, C.byref(on), C.byref(r)))
+        return bool(on.value), r.value
+
     def minimize(self, x, poll_every=0):
         st = Status()
         check(lib().nlsg_de_minimize(self._h, x.ctypes.data_as(_capi.pd), poll_every, C.byref(st)))

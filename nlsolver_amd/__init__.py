@@ -4,6 +4,8 @@ Layout:
     csrc/                 HIP kernels for gfx950 + the extern "C" boundary
     libnlsolver_hip.so    built in-tree by `make -C nlsolver_amd/csrc`
     _capi.py              ctypes binding of include/nlsg_c_api.h
+    _engine.py            Engine: the base of every engine class (handle, config header, parameter rows),
+                          CustomObjective and the numpy <-> C-ABI helpers the modules below share
     de.py                 DE / DESolver: mirror of nlsolver::DE (nlsolver.h:2379-2477)
     rng.py                XorShift: pure-Python rng::xorshift<double> (nlsolver.h:1344-1378)
     pso.py                PSO / PSOSolver: mirror of nlsolver::PSO (nlsolver.h:2498-2742)

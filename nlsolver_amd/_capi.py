@@ -331,35 +331,27 @@ OPTIONAL_SYMBOLS = {
     "nlsg_sann_lds_bytes": (u64, [u64, i32]),
 }
 SYMBOLS.update(OPTIONAL_SYMBOLS)
+_PARAMS = "library has no run-time objective parameters"
+_CURVE = "library has no curve models for Levenberg-Marquardt"
+# what require() says about a missing entry point: the longest prefix of its name that stands here
 _MISSING_MESSAGE = {"nlsg_de_ref_": "library has no reference-order DE",
                     "nlsg_de_bound_": "library has no lower-bound rejection in the DE generation",
                     "nlsg_de_screen_": "library has no half-row screen in the DE generation",
-                    "nlsg_custom_params_": "library has no run-time objective parameters",
-                    "nlsg_de_batch_set_params": "library has no run-time objective parameters",
-                    "nlsg_pso_batch_set_params": "library has no run-time objective parameters",
-                    "nlsg_nm_create_params": "library has no run-time objective parameters for Nelder-Mead",
-                    "nlsg_nm_set_params": "library has no run-time objective parameters for Nelder-Mead",
-                    "nlsg_nm_lds_bytes": "library has no run-time objective parameters for Nelder-Mead",
-                    "nlsg_nmpso_create_params": "library has no run-time objective parameters for the hybrid",
-                    "nlsg_nmpso_set_params": "library has no run-time objective parameters for the hybrid",
-                    "nlsg_nmpso_lds_bytes": "library has no run-time objective parameters for the hybrid",
-                    "nlsg_lm_create_params": "library has no run-time objective parameters for Levenberg-Marquardt",
-                    "nlsg_lm_set_params": "library has no run-time objective parameters for Levenberg-Marquardt",
-                    "nlsg_lm_lds_bytes": "library has no run-time objective parameters for Levenberg-Marquardt",
-                    "nlsg_lm_create_link": "library has no user-supplied link functions for Levenberg-Marquardt",
-                    "nlsg_lm_create_curve": "library has no curve models for Levenberg-Marquardt",
-                    "nlsg_lm_set_curve_data": "library has no curve models for Levenberg-Marquardt",
-                    "nlsg_lm_covariance": "library has no parameter covariance for Levenberg-Marquardt",
-                    "nlsg_bfgs_create_gradient": "library has no analytic gradients of compiled objectives for BFGS",
-                    "nlsg_bfgs_create_params": "library has no run-time objective parameters for BFGS",
-                    "nlsg_bfgs_set_params": "library has no run-time objective parameters for BFGS",
-                    "nlsg_bfgs_lds_bytes": "library has no run-time objective parameters for BFGS",
-                    "nlsg_sann_create_params": "library has no run-time objective parameters for simulated annealing",
-                    "nlsg_sann_set_params": "library has no run-time objective parameters for simulated annealing",
-                    "nlsg_sann_chains_per_wave": "library has no run-time objective parameters for simulated annealing",
-                    "nlsg_sann_lds_bytes": "library has no run-time objective parameters for simulated annealing",
                     "nlsg_de_batch_": "library has no resident batch DE",
-                    "nlsg_pso_batch_": "library has no resident batch PSO"}
+                    "nlsg_pso_batch_": "library has no resident batch PSO",
+                    "nlsg_custom_params_": _PARAMS,
+                    "nlsg_de_batch_set_params": _PARAMS,
+                    "nlsg_pso_batch_set_params": _PARAMS,
+                    "nlsg_nm_": _PARAMS + " for Nelder-Mead",
+                    "nlsg_nmpso_": _PARAMS + " for the hybrid",
+                    "nlsg_lm_": _PARAMS + " for Levenberg-Marquardt",
+                    "nlsg_bfgs_": _PARAMS + " for BFGS",
+                    "nlsg_sann_": _PARAMS + " for simulated annealing",
+                    "nlsg_lm_create_link": "library has no user-supplied link functions for Levenberg-Marquardt",
+                    "nlsg_lm_create_curve": _CURVE,
+                    "nlsg_lm_set_curve_data": _CURVE,
+                    "nlsg_lm_covariance": "library has no parameter covariance for Levenberg-Marquardt",
+                    "nlsg_bfgs_create_gradient": "library has no analytic gradients of compiled objectives for BFGS"}
 
 _lib = None
 
@@ -384,7 +376,8 @@ def require(name):
     """The optional entry point `name`; NlsgError if this build of the library lacks it."""
     fn = getattr(lib(), name, None)
     if fn is None:
-        msg = next((m for p, m in _MISSING_MESSAGE.items() if name.startswith(p)), f"library has no {name}")
+        prefix = max((p for p in _MISSING_MESSAGE if name.startswith(p)), key=len, default=None)
+        msg = _MISSING_MESSAGE.get(prefix, f"library has no {name}")
         raise NlsgError(NLSG_ERR_UNSUPPORTED, msg)
     return fn
 

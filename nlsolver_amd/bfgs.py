@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import BFGSConfig, NlsgError, Status, check, lib, require
+from ._engine import LDS_BUDGET, CustomObjective, Engine, _rows_for_batch, check_driver, pair_params, pd_of
 
 
 class QuadDiagRank1:
@@ -33,7 +34,7 @@ class QuadDiagRank1:
         return 0.5 * np.sum(self.d * x * x) + 0.5 * self.c * np.sum(x) ** 2 - np.sum(self.b * x)
 
 
-class BFGSEngine:
+class BFGSEngine(Engine):
     """symmetric=True: the rank-2 update restated so that H stays bitwise symmetric and only its
     upper 128 x 128 blocks are kept and streamed (NLSG_BFGS_SYMMETRIC, include/nlsg_c_api.h):
     56 % of the memory and traffic at dim = 1024; results agree with the literal update to rounding.
@@ -63,6 +64,7 @@ class BFGSEngine:
     whether a shape is taken."""
 
     GRADIENTS = (None, "analytic", "finite_difference")
+    _destroy, _set_params = "nlsg_bfgs_destroy", "nlsg_bfgs_set_params"
 
     @staticmethod
     def lds_bytes(dim, reference_order=False, n_params=0, resident=False):
@@ -71,6 +73,8 @@ class BFGSEngine:
         resident workgroup's block — H, its vectors, one wave's buffers — and ONE row; 0 where the library
         or the shape has no resident mode."""
         flags = _capi.BFGS_REFERENCE_ORDER if reference_order else 0
+        # (not _with_params_lds: that answers 0 where the row's size is 0, n_params past the range; this
+        # one keeps `need` there, and the lock-step launch takes four rows)
         if resident:
             need = int(require("nlsg_bfgs_lds_bytes")(dim, flags | _capi.BFGS_RESIDENT))
             if need == 0:
@@ -91,7 +95,6 @@ class BFGSEngine:
     def fits_resident(dim, symmetric=False, n_params=0):
         """whether an engine with resident=True takes the shape: 1 <= dim <= 64, the literal update,
         0 <= n_params <= 4096 (either summation order: the workgroup's block stays below 75 KiB)"""
-        from .de import LDS_BUDGET
         if symmetric or not (1 <= dim <= 64 and 0 <= n_params <= _capi.CUSTOM_MAX_PARAMS):
             return False
         if not BFGSEngine.has_resident():
@@ -103,7 +106,6 @@ class BFGSEngine:
     def fits(dim, reference_order=False, n_params=0):
         """whether nlsg_bfgs_create_params takes the shape: 1 <= dim <= 1024, 0 <= n_params <= 4096
         and lds_bytes within the workgroup's 160 KiB"""
-        from .de import LDS_BUDGET
         if not (1 <= dim <= 1024 and 0 <= n_params <= _capi.CUSTOM_MAX_PARAMS):
             return False
         return BFGSEngine.lds_bytes(dim, reference_order, n_params) <= LDS_BUDGET
@@ -111,7 +113,6 @@ class BFGSEngine:
     def __init__(self, objective, batch, *, dim=None, max_iter=100, grad_eps=5e-3, alpha=1.0,
                  device=0, stream=None, symmetric=False, reference_order=False, gradient=None,
                  resident=False):
-        from .de import CustomObjective, rtc_library_path
         if gradient not in self.GRADIENTS:
             raise ValueError(f"gradient must be one of {self.GRADIENTS}, not {gradient!r}")
         custom = isinstance(objective, CustomObjective)
@@ -122,82 +123,42 @@ class BFGSEngine:
         if gradient == "finite_difference" and not custom and not isinstance(objective, str):
             raise ValueError("QuadDiagRank1 is minimised with its analytic gradient only")
         self.gradient_used = "analytic" if has_analytic and gradient != "finite_difference" else "finite_difference"
-        cfg = BFGSConfig()
+        cfg = self._header(BFGSConfig, device, stream)
         cfg.flags = (_capi.BFGS_SYMMETRIC if symmetric else 0) | \
             (_capi.BFGS_REFERENCE_ORDER if reference_order else 0) | \
             (_capi.BFGS_RESIDENT if resident else 0)
         self.symmetric = bool(symmetric)
         self.resident = bool(resident)
-        cfg.struct_size = C.sizeof(BFGSConfig)
-        cfg.device = device
-        cfg.stream = None if stream is None else (stream or 1)
         cfg.batch = batch
         cfg.max_iter, cfg.grad_eps, cfg.alpha = max_iter, grad_eps, alpha
-        self._h = C.c_void_p()
-        self.n_params = 0
+        self.n_params = objective.n_params if custom else 0
         if custom:  # user objective + its gradient body or the finite-difference gradient
             if dim is None:
                 raise TypeError("a custom objective needs dim=")
             cfg.objective, cfg.dim, cfg.quad_c = _capi.OBJ_CUSTOM, dim, 0.0
-            self.cfg = cfg
-            self.n_params = objective.n_params
-            analytic = self.gradient_used == "analytic"
-            create = require("nlsg_bfgs_create_gradient") if analytic else lib().nlsg_bfgs_create_custom
-            if self.n_params:  # (zero stays with the creator it always had)
-                if not analytic:
-                    create = require("nlsg_bfgs_create_params")
-                require("nlsg_bfgs_set_params")
-            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
-            obj = _capi.CustomObjectiveC(objective.term_body.encode(), objective.finish_body.encode(),
-                                         int(objective.chain), self.n_params)
-            if analytic:
-                grad = _capi.BFGSGradientC(C.sizeof(_capi.BFGSGradientC), 0, objective.grad_body.encode())
-                check(create(C.byref(cfg), C.byref(obj), C.byref(grad), C.byref(self._h)))
+            if self.gradient_used == "analytic":  # (with or without parameters)
+                create = self._creator(require("nlsg_bfgs_create_gradient"))
+                grad = [_capi.BFGSGradientC(C.sizeof(_capi.BFGSGradientC), 0, objective.grad_body.encode())]
             else:
-                check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
-            return
-        if isinstance(objective, str):  # built-in objective + finite-difference gradient
+                create, grad = self._creator(lib().nlsg_bfgs_create_custom, "nlsg_bfgs_create_params"), []
+            self._create_custom(create, cfg, objective, *grad)
+        elif isinstance(objective, str):  # built-in objective + finite-difference gradient
             if dim is None:
                 raise TypeError("a built-in objective needs dim=")
             cfg.objective, cfg.dim, cfg.quad_c = _capi.OBJECTIVES[objective], dim, 0.0
-            self.cfg = cfg
-            check(lib().nlsg_bfgs_create(C.byref(cfg), None, None, C.byref(self._h)))
-            return
-        cfg.objective = objective.nlsg_objective
-        cfg.dim, cfg.quad_c = objective.d.size, objective.c
-        self.cfg = cfg
-        check(lib().nlsg_bfgs_create(C.byref(cfg), objective.d.ctypes.data_as(_capi.pd),
-                                     objective.b.ctypes.data_as(_capi.pd), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().nlsg_bfgs_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+            self._create(lib().nlsg_bfgs_create, cfg, None, None)
+        else:
+            cfg.objective = objective.nlsg_objective
+            cfg.dim, cfg.quad_c = objective.d.size, objective.c
+            self._create(lib().nlsg_bfgs_create, cfg, pd_of(objective.d), pd_of(objective.b))
 
     def _x(self, x):
         x = np.ascontiguousarray(x, dtype=np.float64)
         assert x.shape == (self.cfg.batch, self.cfg.dim)
         return x
 
-    def set_params(self, params):
-        """params [batch, n_params]: problem b's objective reads row b as p(k). The rows hold from the
-        next launch on and can be replaced at any time without recompiling."""
-        if self.n_params == 0:
-            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
-        from .de import _params_rows
-        rows = _params_rows(params, self.cfg.batch, self.n_params)
-        check(require("nlsg_bfgs_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
-
     def init(self, x0):
-        check(lib().nlsg_bfgs_init(self._h, self._x(x0).ctypes.data_as(_capi.pd)))
+        check(lib().nlsg_bfgs_init(self._h, pd_of(self._x(x0))))
 
     def step(self, iters=1):
         check(lib().nlsg_bfgs_step(self._h, iters))
@@ -218,24 +179,22 @@ class BFGSEngine:
         B, n = self.cfg.batch, self.cfg.dim
         x = np.empty((B, n))
         st = (Status * B)()
-        check(lib().nlsg_bfgs_download(self._h, x.ctypes.data_as(_capi.pd), st))
+        check(lib().nlsg_bfgs_download(self._h, pd_of(x), st))
         return x, list(st)
 
     def download_state(self, hessian=True):
         B, n = self.cfg.batch, self.cfg.dim
         g = np.empty((B, n))
         H = np.empty((B, n, n)) if hessian else None
-        check(lib().nlsg_bfgs_download_state(self._h, g.ctypes.data_as(_capi.pd),
-                                             H.ctypes.data_as(_capi.pd) if hessian else None))
+        check(lib().nlsg_bfgs_download_state(self._h, pd_of(g), pd_of(H)))
         return g, H
 
     def minimize(self, x, params=None):
         """params: set_params(params) first."""
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         x = self._x(x)
         st = (Status * self.cfg.batch)()
-        check(lib().nlsg_bfgs_minimize(self._h, x.ctypes.data_as(_capi.pd), st))
+        check(lib().nlsg_bfgs_minimize(self._h, pd_of(x), st))
         return x, list(st)
 
     def hessian_bytes_per_iteration(self):
@@ -275,15 +234,9 @@ class BFGS:
 
     def __init__(self, f, g=None, max_iter=100, grad_eps=5e-3, alpha=1.0, *, device=0,
                  symmetric=False, reference_order=None, params=None, driver="turns"):
-        from .nm import _drop_in_rows
-        if driver not in ("turns", "resident"):
-            raise ValueError(f"driver must be 'turns' or 'resident', not {driver!r}")
+        check_driver(driver)
         self.driver, self.driver_used = driver, None
-        self.n_params = getattr(f, "n_params", 0)
-        if (params is not None) != bool(self.n_params):
-            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
-                             "objective needs it")
-        self.params = None if params is None else _drop_in_rows(params, self.n_params)
+        self.n_params, self.params = pair_params(f, params)
         if g is not None:
             raise TypeError("device objectives carry their analytic gradient or use the default "
                             "finite-difference one; pass g=None")
@@ -298,7 +251,6 @@ class BFGS:
             raise TypeError("x must be a float64 numpy array of shape (n,) or (batch, n); "
                             "it is updated in place")
         xb = x.reshape(1, -1) if x.ndim == 1 else x
-        from .de import CustomObjective
         extra = dict(dim=xb.shape[1]) if isinstance(self.f, (str, CustomObjective)) else {}
         args = dict(self.args)
         if args["reference_order"] is None:
@@ -306,7 +258,6 @@ class BFGS:
                 (isinstance(self.f, CustomObjective) and self.f.chain != 2)  # (terms: index order is the body's own loop)
             quad = isinstance(self.f, QuadDiagRank1)
             args["reference_order"] = (fd or quad) and not args["symmetric"]
-        from .nm import _rows_for_batch
         rows = _rows_for_batch(self.params, xb.shape[0])
         resident = self.driver == "resident" and \
             BFGSEngine.fits_resident(xb.shape[1], bool(args["symmetric"]), self.n_params)

@@ -15,7 +15,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import LMConfig, NlsgError, Status, check, lib, require
+from ._capi import LMConfig, NlsgError, Status, check, lib, require  # noqa: F401
+from ._engine import LDS_BUDGET, CustomObjective, Engine, _rows_for_batch, pair_params, pd_of, timed_ms
 
 
 class TanhRegression:
@@ -172,7 +173,7 @@ def _cov_scale(scale):
     raise ValueError(f'scale is "residual" or "absolute" (LM_COV_RESIDUAL / LM_COV_ABSOLUTE): got {scale!r}')
 
 
-class LMEngine:
+class LMEngine(Engine):
     """model: a TanhRegression, a LinkRegression or a CurveModel, or the name / id of a built-in objective ("rosenbrock", "sphere",
     "styblinski_tang") or a CustomObjective, with batch= and n= (default functors: fin_diff +
     fin_diff_h).
@@ -180,6 +181,7 @@ class LMEngine:
     A CustomObjective with n_params > 0 (nlsg_lm_create_params): problem b minimises the objective under
     row b of set_params(rows) ([batch, n_params], read as p(k)) — one fit per series; rows are replaced
     without recompiling. The row lives in the workgroup's LDS: fits() says whether a shape has room."""
+    _destroy, _set_params = "nlsg_lm_destroy", "nlsg_lm_set_params"
 
     @staticmethod
     def lds_bytes(n, reference_order=False, n_params=0):
@@ -187,107 +189,64 @@ class LMEngine:
         objective parameters included (host only; tree order past 64 parameters takes none of its own)"""
         solver = _capi.LM_CHOLESKY_REFERENCE_ORDER if reference_order else _capi.LM_CHOLESKY
         need = int(require("nlsg_lm_lds_bytes")(n, solver))
+        # (not _with_params_lds: need == 0 is a valid answer here, and the row is added to it)
         return need + (int(require("nlsg_custom_params_lds_bytes")(n_params)) if n_params else 0)
 
     @staticmethod
     def fits(n, reference_order=False, n_params=0):
         """whether nlsg_lm_create_params takes the shape: 1 <= n <= 1024, 0 <= n_params <= 4096 and
         lds_bytes within the workgroup's 160 KiB"""
-        from .de import LDS_BUDGET
         if not (1 <= n <= 1024 and 0 <= n_params <= _capi.CUSTOM_MAX_PARAMS):
             return False
         return LMEngine.lds_bytes(n, reference_order, n_params) <= LDS_BUDGET
 
     def __init__(self, model, *, lam=10.0, up=10.0, down=10.0, max_iter=100, f_delta=1e-12,
                  solver=_capi.LM_CHOLESKY, device=0, stream=None, batch=None, n=None):
-        from .de import CustomObjective, rtc_library_path
         custom = model if isinstance(model, CustomObjective) else None
         fd = custom is not None or isinstance(model, (str, int))
         if fd:
             if batch is None or n is None:
                 raise TypeError("an objective needs batch= and n=")
             B, m = batch, 0
-            objective = (_capi.OBJ_CUSTOM if custom else
-                         _capi.OBJECTIVES[model] if isinstance(model, str) else model)
+            objective = self._objective_id(model)[0]
         elif isinstance(model, CurveModel):
             (B, m), n = model.y.shape, model.n
             objective = model.nlsg_nlls_objective
         else:
             B, m, n = model.A.shape
             objective = model.nlsg_nlls_objective
-        cfg = LMConfig()
-        cfg.struct_size = C.sizeof(LMConfig)
-        cfg.device = device
-        cfg.stream = None if stream is None else (stream or 1)
+        cfg = self._header(LMConfig, device, stream)
         cfg.objective, cfg.solver = objective, solver
         cfg.batch, cfg.m, cfg.n = B, m, n
         cfg.lambda_, cfg.up, cfg.down, cfg.max_iter, cfg.f_delta = lam, up, down, max_iter, f_delta
-        self.cfg = cfg
         self.n_params = custom.n_params if custom else 0
-        self._h = C.c_void_p()
         if custom:
-            create = lib().nlsg_lm_create_custom
-            if self.n_params:  # (zero stays with the creator it always had)
-                create = require("nlsg_lm_create_params")
-                require("nlsg_lm_set_params")
-            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
-            obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), self.n_params)
-            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+            self._create_custom(self._creator(lib().nlsg_lm_create_custom, "nlsg_lm_create_params"), cfg, custom)
         elif isinstance(model, LinkRegression):
-            create = require("nlsg_lm_create_link")
-            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
-            link = _capi.LMLinkC(model.value_body.encode(), model.slope_body.encode())
-            check(create(C.byref(cfg), C.byref(link), C.byref(self._h)))
+            self._create_custom(require("nlsg_lm_create_link"), cfg,
+                                _capi.LMLinkC(model.value_body.encode(), model.slope_body.encode()))
         elif isinstance(model, CurveModel):
             create, set_data = require("nlsg_lm_create_curve"), require("nlsg_lm_set_curve_data")
-            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
-            curve = _capi.LMCurveC(model.body.encode(), model.t.shape[2])
-            check(create(C.byref(cfg), C.byref(curve), C.byref(self._h)))
-            check(set_data(self._h, model.t.ctypes.data_as(_capi.pd), model.y.ctypes.data_as(_capi.pd)))
+            self._create_custom(create, cfg, _capi.LMCurveC(model.body.encode(), model.t.shape[2]))
+            check(set_data(self._h, pd_of(model.t), pd_of(model.y)))
         else:
-            check(lib().nlsg_lm_create(C.byref(cfg), C.byref(self._h)))
+            self._create(lib().nlsg_lm_create, cfg)
         if not fd and not isinstance(model, CurveModel):
-            check(lib().nlsg_lm_set_data(self._h, model.A.ctypes.data_as(_capi.pd),
-                                         model.y.ctypes.data_as(_capi.pd)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().nlsg_lm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+            check(lib().nlsg_lm_set_data(self._h, pd_of(model.A), pd_of(model.y)))
 
     def set_solver(self, solver):
         """LM_CHOLESKY / LM_QR for the next solves; the model data stays on the device."""
         check(lib().nlsg_lm_set_solver(self._h, solver))
         self.cfg.solver = solver
 
-    def set_params(self, params):
-        """params [batch, n_params]: problem b's objective reads row b as p(k). The rows hold from the
-        next solve on and can be replaced at any time without recompiling."""
-        if self.n_params == 0:
-            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
-        from .de import _params_rows
-        rows = _params_rows(params, self.cfg.batch, self.n_params)
-        check(require("nlsg_lm_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
-
     def minimize(self, theta, params=None):
         """params: set_params(params) first."""
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         theta = np.ascontiguousarray(theta, dtype=np.float64)
         assert theta.shape == (self.cfg.batch, self.cfg.n)
         st = (Status * self.cfg.batch)()
         lam = np.empty(self.cfg.batch)
-        check(lib().nlsg_lm_minimize(self._h, theta.ctypes.data_as(_capi.pd), st,
-                                     lam.ctypes.data_as(_capi.pd)))
+        check(lib().nlsg_lm_minimize(self._h, pd_of(theta), st, pd_of(lam)))
         return theta, list(st), lam
 
     def covariance(self, theta, scale="residual"):
@@ -304,8 +263,8 @@ class LMEngine:
             raise ValueError(f"theta must be (batch, n) = ({B}, {n}): got {theta.shape}")
         fn = require("nlsg_lm_covariance")
         cov, s2, ok = np.empty((B, n, n)), np.empty(B), np.empty(B, dtype=np.int32)
-        check(fn(self._h, theta.ctypes.data_as(_capi.pd), scale, cov.ctypes.data_as(_capi.pd),
-                 s2.ctypes.data_as(_capi.pd), ok.ctypes.data_as(C.POINTER(C.c_int32))))
+        check(fn(self._h, pd_of(theta), scale, pd_of(cov), pd_of(s2),
+                 ok.ctypes.data_as(C.POINTER(C.c_int32))))
         return cov, s2, ok.astype(bool)
 
     def stderr(self, theta, scale="residual"):
@@ -314,29 +273,19 @@ class LMEngine:
         return np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
 
     def time_solve(self, theta0, repeats=1, params=None):
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
-        ms = C.c_float()
-        check(lib().nlsg_lm_time_solve(self._h, theta0.ctypes.data_as(_capi.pd), repeats, C.byref(ms)))
-        return ms.value
+        return timed_ms(lib().nlsg_lm_time_solve, self._h, pd_of(theta0), repeats)
 
     def time_eval_kernel(self, theta0, repeats=1):
         """Total ms of `repeats` launches of the evaluation kernel (f, g, H at theta0)."""
         theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
-        ms = C.c_float()
-        check(lib().nlsg_lm_time_eval_kernel(self._h, theta0.ctypes.data_as(_capi.pd), repeats,
-                                             C.byref(ms)))
-        return ms.value
-
+        return timed_ms(lib().nlsg_lm_time_eval_kernel, self._h, pd_of(theta0), repeats)
 
     def time_qr_kernel(self, theta0, repeats=1):
         """Total ms of `repeats` launches of the QR step kernel (after one evaluation at theta0)."""
         theta0 = np.ascontiguousarray(theta0, dtype=np.float64)
-        ms = C.c_float()
-        check(lib().nlsg_lm_time_qr_kernel(self._h, theta0.ctypes.data_as(_capi.pd), repeats,
-                                           C.byref(ms)))
-        return ms.value
+        return timed_ms(lib().nlsg_lm_time_qr_kernel, self._h, pd_of(theta0), repeats)
 
 
 class LevenbergMarquardt:
@@ -351,12 +300,7 @@ class LevenbergMarquardt:
 
     def __init__(self, f, lam=10.0, upward_mult=10.0, downward_mult=10.0, max_iter=100,
                  f_delta=1e-12, g=None, h=None, *, solver=None, device=0, params=None):
-        from .nm import _drop_in_rows
-        self.n_params = getattr(f, "n_params", 0)
-        if (params is not None) != bool(self.n_params):
-            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
-                             "objective needs it")
-        self.params = None if params is None else _drop_in_rows(params, self.n_params)
+        self.n_params, self.params = pair_params(f, params)
         if g is not None or h is not None:
             raise TypeError("device models carry their functors (Gauss-Newton for NLLS models, "
                             "the reference's finite-difference defaults for objectives)")
@@ -373,12 +317,9 @@ class LevenbergMarquardt:
         shape = {} if has_data else dict(batch=xb.shape[0], n=xb.shape[1])
         args = dict(self.args)
         if args["solver"] is None:
-            from .de import CustomObjective
-            has_it = (isinstance(self.f, str) and self.f in ("rosenbrock", "sphere", "styblinski_tang")) or \
+            ref = (isinstance(self.f, str) and self.f in ("rosenbrock", "sphere", "styblinski_tang")) or \
                 (isinstance(self.f, CustomObjective) and self.f.chain != 2)  # (given by its terms)
-            ref = has_it
             args["solver"] = _capi.LM_CHOLESKY_REFERENCE_ORDER if ref else _capi.LM_CHOLESKY
-        from .nm import _rows_for_batch
         rows = _rows_for_batch(self.params, xb.shape[0])
         return xb, LMEngine(self.f, **args, **shape), rows
 

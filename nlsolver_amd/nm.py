@@ -7,15 +7,17 @@ Reference interface (nlsolver.h:2099-2165):
 (upper before lower — the opposite of PSO). x may be (n,) or (batch, n): independent starts,
 one simplex per GPU workgroup.
 """
-import ctypes as C
+import ctypes as C  # noqa: F401 - names the module had before _engine.py stay importable from it
 
 import numpy as np
 
 from . import _capi
-from ._capi import NMConfig, NlsgError, Status, check, lib, require
+from ._capi import NMConfig, NlsgError, Status, check, lib, require  # noqa: F401
+from ._engine import (LDS_BUDGET, CustomObjective, Engine, _drop_in_rows, _rows_for_batch, _with_params_lds,  # noqa: F401
+                      pair_params, pd_of, pu_of, timed_ms)
 
 
-class NMEngine:
+class NMEngine(Engine):
     """reference_order=True (NLSG_NM_REFERENCE_ORDER): the objective's terms and std_err's sums in index
     order, as the reference adds them — its own runs bit for bit at every dimension (the lane-tree sums
     can break a tie between two vertices the other way: same algorithm, another branch).
@@ -23,77 +25,38 @@ class NMEngine:
     A CustomObjective with n_params > 0 (nlsg_nm_create_params): start b minimises the objective under
     row b of set_params(rows) ([batch, n_params], read as p(k)); rows are replaced without recompiling.
     The row lives in the workgroup's LDS in front of the simplex: fits() says whether a shape has room."""
+    _destroy, _set_params = "nlsg_nm_destroy", "nlsg_nm_set_params"
 
     @staticmethod
     def lds_bytes(dim, reference_order=False, n_params=0):
         """LDS bytes a start's workgroup needs at the least (in reference order: with one term buffer),
         the row of n_params objective parameters included; 0 outside the ranges (host only)"""
-        from .de import _with_params_lds
         need = int(require("nlsg_nm_lds_bytes")(dim, _capi.NM_REFERENCE_ORDER if reference_order else 0))
         return _with_params_lds(need, n_params)
 
     @staticmethod
     def fits(dim, reference_order=False, n_params=0):
-        from .de import LDS_BUDGET
         return 0 < NMEngine.lds_bytes(dim, reference_order, n_params) <= LDS_BUDGET
 
     def __init__(self, objective, batch, dim, *, minimize=True, bounded=False, step=-1.0, alpha=1.0,
                  gamma=2.0, rho=0.5, sigma=0.5, eps=1e-6, max_iter=500, no_change_best_tol=20,
                  restarts=0, device=0, stream=None, reference_order=False):
-        cfg = NMConfig()
+        cfg = self._header(NMConfig, device, stream)
         cfg.flags = _capi.NM_REFERENCE_ORDER if reference_order else 0
-        cfg.struct_size = C.sizeof(NMConfig)
-        cfg.device = device
-        cfg.stream = None if stream is None else (stream or 1)
-        from .de import CustomObjective, rtc_library_path
-        custom = objective if isinstance(objective, CustomObjective) else None
-        cfg.objective = (_capi.OBJ_CUSTOM if custom else
-                         _capi.OBJECTIVES[objective] if isinstance(objective, str) else objective)
+        cfg.objective, custom = self._objective_id(objective)
         cfg.minimize, cfg.bounded = int(bool(minimize)), int(bool(bounded))
         cfg.batch, cfg.dim = batch, dim
         cfg.step, cfg.alpha, cfg.gamma, cfg.rho, cfg.sigma, cfg.eps = step, alpha, gamma, rho, sigma, eps
         cfg.max_iter, cfg.no_change_best_tol, cfg.restarts = max_iter, no_change_best_tol, restarts
-        self.cfg = cfg
         self.n_params = custom.n_params if custom else 0
-        self._h = C.c_void_p()
         if custom:
-            create = lib().nlsg_nm_create_custom
-            if self.n_params:  # (zero stays with the creator it always had)
-                create = require("nlsg_nm_create_params")
-                require("nlsg_nm_set_params")
-            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
-            obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), self.n_params)
-            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+            self._create_custom(self._creator(lib().nlsg_nm_create_custom, "nlsg_nm_create_params"), cfg, custom)
         else:
-            check(lib().nlsg_nm_create(C.byref(cfg), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().nlsg_nm_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def set_params(self, params):
-        """params [batch, n_params]: start b's objective reads row b as p(k). The rows hold from the
-        next solve on and can be replaced at any time without recompiling."""
-        if self.n_params == 0:
-            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
-        from .de import _params_rows
-        rows = _params_rows(params, self.cfg.batch, self.n_params)
-        check(require("nlsg_nm_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
+            self._create(lib().nlsg_nm_create, cfg)
 
     def minimize(self, x, upper=None, lower=None, params=None):
         """params: set_params(params) first."""
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         B, n = self.cfg.batch, self.cfg.dim
         x = np.ascontiguousarray(x, dtype=np.float64)
         assert x.shape == (B, n)
@@ -103,10 +66,7 @@ class NMEngine:
             lo = np.ascontiguousarray(np.broadcast_to(lower, (n,)), dtype=np.float64)
         st = (Status * B)()
         eps = np.empty(B)
-        check(lib().nlsg_nm_minimize(self._h, x.ctypes.data_as(_capi.pd),
-                                     up.ctypes.data_as(_capi.pd) if up is not None else None,
-                                     lo.ctypes.data_as(_capi.pd) if lo is not None else None,
-                                     st, eps.ctypes.data_as(_capi.pd)))
+        check(lib().nlsg_nm_minimize(self._h, pd_of(x), pd_of(up), pd_of(lo), st, pd_of(eps)))
         return x, list(st), eps
 
     def phase_cycles(self, x0):
@@ -114,38 +74,13 @@ class NMEngine:
         (scan, centroid, reflection, expansion / contraction, shrink, -, iterations, shrinks)."""
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         out = np.zeros((self.cfg.batch, 8), dtype=np.uint64)
-        check(lib().nlsg_nm_phase_cycles(self._h, x0.ctypes.data_as(_capi.pd),
-                                         out.ctypes.data_as(_capi.pu)))
+        check(lib().nlsg_nm_phase_cycles(self._h, pd_of(x0), pu_of(out)))
         return out
 
     def time_solve(self, x0, repeats=1, params=None):
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        ms = C.c_float()
-        check(lib().nlsg_nm_time_solve(self._h, x0.ctypes.data_as(_capi.pd), repeats, C.byref(ms)))
-        return ms.value
-
-
-def _drop_in_rows(params, n_params):
-    """params= of a drop-in: (n_params,) -> [1, n_params]; (batch, n_params) stays"""
-    rows = np.ascontiguousarray(np.asarray(params, dtype=np.float64))
-    if rows.ndim == 1:
-        rows = rows.reshape(1, -1)
-    if rows.ndim != 2 or rows.shape[1] != n_params:
-        raise ValueError(f"params must be ({n_params},) or (batch, {n_params}), not {rows.shape}")
-    return rows
-
-
-def _rows_for_batch(rows, batch):
-    """the drop-in's rows for a solve of `batch` starts: one row goes to every start"""
-    if rows is None:
-        return None
-    if rows.shape[0] == 1:
-        return np.ascontiguousarray(np.broadcast_to(rows, (batch, rows.shape[1])))
-    if rows.shape[0] != batch:
-        raise ValueError(f"params has {rows.shape[0]} rows and x {batch} starts")
-    return rows
+        return timed_ms(lib().nlsg_nm_time_solve, self._h, pd_of(x0), repeats)
 
 
 class NelderMead:
@@ -160,12 +95,7 @@ class NelderMead:
     def __init__(self, f, step=-1.0, alpha=1.0, gamma=2.0, rho=0.5, sigma=0.5, eps=1e-6,
                  max_iter=500, no_change_best_tol=20, restarts=0, *, device=0, reference_order=None,
                  params=None):
-        from .de import CustomObjective
-        self.n_params = getattr(f, "n_params", 0)
-        if (params is not None) != bool(self.n_params):
-            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
-                             "objective needs it")
-        self.params = None if params is None else _drop_in_rows(params, self.n_params)
+        self.n_params, self.params = pair_params(f, params)
         if reference_order is None:
             reference_order = (isinstance(f, str) and f in ("rosenbrock", "sphere", "styblinski_tang")) or \
                 (isinstance(f, CustomObjective) and f.chain != 2)

@@ -8,89 +8,51 @@ Reference interface (nlsolver.h:3546-3620):
 (lower before upper, like PSO). x may be (n,) or (batch, n): independent instances, one GPU
 workgroup each. The generator only seeds the instances (draws are keyed on the device).
 """
-import ctypes as C
+import ctypes as C  # noqa: F401 - names the module had before _engine.py stay importable from it
 
 import numpy as np
 
-from . import _capi
-from ._capi import NMPSOConfig, NlsgError, Status, check, lib, require
-from .de import DEFAULT_SEED, seed_from_generator
+from ._capi import NMPSOConfig, NlsgError, Status, check, lib, require  # noqa: F401
+from ._engine import (DEFAULT_SEED, LDS_BUDGET, Engine, _rows_for_batch, _with_params_lds, pair_params, pd_of,
+                      seed_from_generator, timed_ms)
 
 
-class NMPSOEngine:
+class NMPSOEngine(Engine):
     """A CustomObjective with n_params > 0 (nlsg_nmpso_create_params): instance b minimises the
     objective under row b of set_params(rows) ([batch, n_params], read as p(k)); rows are replaced
     without recompiling. The row lives in the workgroup's LDS: fits() says whether a shape has room."""
+    _destroy, _set_params = "nlsg_nmpso_destroy", "nlsg_nmpso_set_params"
 
     @staticmethod
     def lds_bytes(dim, n_params=0):
         """LDS bytes of an instance's workgroup, the row of n_params objective parameters included;
         0 outside the ranges (host only)"""
-        from .de import _with_params_lds
         return _with_params_lds(int(require("nlsg_nmpso_lds_bytes")(dim)), n_params)
 
     @staticmethod
     def fits(dim, n_params=0):
-        from .de import LDS_BUDGET
         return 0 < NMPSOEngine.lds_bytes(dim, n_params) <= LDS_BUDGET
 
     def __init__(self, objective, batch, dim, *, minimize=True, bounded=False, alpha=1.0, gamma=2.0,
                  rho=0.5, sigma=0.5, inertia=0.8, cognitive=1.8, social=1.8, eps=1e-6, max_iter=1000,
                  no_change_best_iter=20, seed=DEFAULT_SEED, inst_lo=0, device=0, stream=None):
-        cfg = NMPSOConfig()
-        cfg.struct_size = C.sizeof(NMPSOConfig)
-        cfg.device = device
-        cfg.stream = None if stream is None else (stream or 1)
-        from .de import CustomObjective, rtc_library_path
-        custom = objective if isinstance(objective, CustomObjective) else None
-        cfg.objective = (_capi.OBJ_CUSTOM if custom else
-                         _capi.OBJECTIVES[objective] if isinstance(objective, str) else objective)
+        cfg = self._header(NMPSOConfig, device, stream)
+        cfg.objective, custom = self._objective_id(objective)
         cfg.minimize, cfg.bounded = int(bool(minimize)), int(bool(bounded))
         cfg.batch, cfg.dim, cfg.inst_lo = batch, dim, inst_lo
         cfg.alpha, cfg.gamma, cfg.rho, cfg.sigma = alpha, gamma, rho, sigma
         cfg.inertia, cfg.cognitive, cfg.social, cfg.eps = inertia, cognitive, social, eps
         cfg.max_iter, cfg.no_change_best_iter, cfg.seed = max_iter, no_change_best_iter, seed
-        self.cfg = cfg
         self.n_params = custom.n_params if custom else 0
-        self._h = C.c_void_p()
         if custom:
-            create = lib().nlsg_nmpso_create_custom
-            if self.n_params:  # (zero stays with the creator it always had)
-                create = require("nlsg_nmpso_create_params")
-                require("nlsg_nmpso_set_params")
-            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
-            obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), self.n_params)
-            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+            self._create_custom(self._creator(lib().nlsg_nmpso_create_custom, "nlsg_nmpso_create_params"), cfg,
+                                custom)
         else:
-            check(lib().nlsg_nmpso_create(C.byref(cfg), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().nlsg_nmpso_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def set_params(self, params):
-        """params [batch, n_params]: instance b's objective reads row b as p(k). The rows hold from
-        the next solve on and can be replaced at any time without recompiling."""
-        if self.n_params == 0:
-            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
-        from .de import _params_rows
-        rows = _params_rows(params, self.cfg.batch, self.n_params)
-        check(require("nlsg_nmpso_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
+            self._create(lib().nlsg_nmpso_create, cfg)
 
     def minimize(self, x, lower=None, upper=None, params=None):
         """x: (batch, dim) starts; returns (best particles, [Status]). params: set_params(params) first."""
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         n = self.cfg.dim
         x = np.ascontiguousarray(x, dtype=np.float64).copy()
         assert x.shape == (self.cfg.batch, n)
@@ -99,18 +61,13 @@ class NMPSOEngine:
             lo = np.ascontiguousarray(np.broadcast_to(lower, (n,)), dtype=np.float64)
             up = np.ascontiguousarray(np.broadcast_to(upper, (n,)), dtype=np.float64)
         st = (Status * self.cfg.batch)()
-        check(lib().nlsg_nmpso_minimize(self._h, x.ctypes.data_as(_capi.pd),
-                                        lo.ctypes.data_as(_capi.pd) if lo is not None else None,
-                                        up.ctypes.data_as(_capi.pd) if up is not None else None, st))
+        check(lib().nlsg_nmpso_minimize(self._h, pd_of(x), pd_of(lo), pd_of(up), st))
         return x, list(st)
 
     def time_solve(self, x0, repeats=1, params=None):
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        ms = C.c_float()
-        check(lib().nlsg_nmpso_time_solve(self._h, x0.ctypes.data_as(_capi.pd), repeats, C.byref(ms)))
-        return ms.value
+        return timed_ms(lib().nlsg_nmpso_time_solve, self._h, pd_of(x0), repeats)
 
 
 class NelderMeadPSO:
@@ -122,12 +79,7 @@ class NelderMeadPSO:
     def __init__(self, f, generator=None, alpha=1.0, gamma=2.0, rho=0.5, sigma=0.5, inertia=0.8,
                  cognitive_coef=1.8, social_coef=1.8, eps=1e-6, max_iter=1000,
                  no_change_best_iter=20, *, device=0, params=None):
-        from .nm import _drop_in_rows
-        self.n_params = getattr(f, "n_params", 0)
-        if (params is not None) != bool(self.n_params):
-            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
-                             "objective needs it")
-        self.params = None if params is None else _drop_in_rows(params, self.n_params)
+        self.n_params, self.params = pair_params(f, params)
         self.f, self.generator = f, generator
         self.args = dict(alpha=alpha, gamma=gamma, rho=rho, sigma=sigma, inertia=inertia,
                          cognitive=cognitive_coef, social=social_coef, eps=eps, max_iter=max_iter,
@@ -141,7 +93,6 @@ class NelderMeadPSO:
             st = Status()
             st.f_value = 999999
             return st if x.ndim == 1 else [st] * xb.shape[0]
-        from .nm import _rows_for_batch
         rows = _rows_for_batch(self.params, xb.shape[0])
         with NMPSOEngine(self.f, xb.shape[0], xb.shape[1], minimize=minimize,
                          bounded=lower is not None, seed=seed_from_generator(self.generator),

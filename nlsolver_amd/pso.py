@@ -14,52 +14,30 @@ import numpy as np
 from . import _capi
 from ._capi import (PSO_ACCELERATED, PSO_VANILLA, NlsgError, PSOBatchConfig, PSOConfig, Status, check, lib,
                     require)
-from .de import DEFAULT_SEED, LDS_BUDGET, _params_rows, _with_params_lds, seed_from_generator
+from ._engine import (DEFAULT_SEED, LDS_BUDGET, Engine, _params_rows, _with_params_lds, check_driver, pair_params,
+                      pd_of, pu_of, seed_from_generator, seeds_u64, timed_ms)
 
 
-class PSOEngine:
+class PSOEngine(Engine):
     """RAII wrapper over the nlsg_pso_* C-ABI."""
+    _destroy = "nlsg_pso_destroy"
 
     def __init__(self, objective, n_particles, dim, *, type=PSO_VANILLA, bounded=False,
                  minimize=True, inertia=0.8, cognitive=1.8, social=1.8, eps=10e-4, max_iter=5000,
                  best_val_no_change=50, seed=DEFAULT_SEED, device=0, stream=None, shard_lo=0,
                  shard_n=None):
-        cfg = PSOConfig()
-        cfg.struct_size = C.sizeof(PSOConfig)
-        cfg.device = device
-        cfg.stream = None if stream is None else (stream or 1)
-        from .de import CustomObjective, rtc_library_path
-        custom = objective if isinstance(objective, CustomObjective) else None
-        cfg.objective = (_capi.OBJ_CUSTOM if custom else
-                         _capi.OBJECTIVES[objective] if isinstance(objective, str) else objective)
+        cfg = self._header(PSOConfig, device, stream)
+        cfg.objective, custom = self._objective_id(objective)
         cfg.minimize, cfg.type, cfg.bounded = int(bool(minimize)), type, int(bool(bounded))
         cfg.n_particles, cfg.dim = n_particles, dim
         cfg.shard_lo = shard_lo
         cfg.shard_n = n_particles if shard_n is None else shard_n
         cfg.inertia, cfg.cognitive, cfg.social, cfg.eps = inertia, cognitive, social, eps
         cfg.max_iter, cfg.best_val_no_change, cfg.seed = max_iter, best_val_no_change, seed
-        self.cfg = cfg
-        self._h = C.c_void_p()
-        if custom:
-            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
-            obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), custom.n_params)
-            check(lib().nlsg_pso_create_custom(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+        if custom:  # (its n_params goes through: the C side refuses an objective with parameters)
+            self._create_custom(lib().nlsg_pso_create_custom, cfg, custom)
         else:
-            check(lib().nlsg_pso_create(C.byref(cfg), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().nlsg_pso_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+            self._create(lib().nlsg_pso_create, cfg)
 
     def _bounds(self, lower, upper):
         D = self.cfg.dim
@@ -69,7 +47,7 @@ class PSOEngine:
 
     def init(self, lower, upper):
         lo, hi = self._bounds(lower, upper)
-        check(lib().nlsg_pso_init(self._h, lo.ctypes.data_as(_capi.pd), hi.ctypes.data_as(_capi.pd)))
+        check(lib().nlsg_pso_init(self._h, pd_of(lo), pd_of(hi)))
 
     def step(self, turns=1):
         check(lib().nlsg_pso_step(self._h, turns))
@@ -82,7 +60,7 @@ class PSOEngine:
     def best(self):
         x = np.empty(self.cfg.dim)
         f, idx = C.c_double(), C.c_uint64()
-        check(lib().nlsg_pso_best(self._h, x.ctypes.data_as(_capi.pd), C.byref(f), C.byref(idx)))
+        check(lib().nlsg_pso_best(self._h, pd_of(x), C.byref(f), C.byref(idx)))
         return x, f.value, idx.value
 
     def download(self):
@@ -90,23 +68,17 @@ class PSOEngine:
         vanilla = self.cfg.type == PSO_VANILLA
         pos, vel = np.empty((n, D)), (np.empty((n, D)) if vanilla else None)
         pbest, cur = np.empty(n), np.empty(n)
-        check(lib().nlsg_pso_download(self._h, pos.ctypes.data_as(_capi.pd),
-                                      vel.ctypes.data_as(_capi.pd) if vanilla else None,
-                                      pbest.ctypes.data_as(_capi.pd), cur.ctypes.data_as(_capi.pd)))
+        check(lib().nlsg_pso_download(self._h, pd_of(pos), pd_of(vel), pd_of(pbest), pd_of(cur)))
         return pos, vel, pbest, cur
 
     def minimize(self, x, lower, upper, poll_every=0):
         lo, hi = self._bounds(lower, upper)
         st = Status()
-        check(lib().nlsg_pso_minimize(self._h, x.ctypes.data_as(_capi.pd),
-                                      lo.ctypes.data_as(_capi.pd), hi.ctypes.data_as(_capi.pd),
-                                      poll_every, C.byref(st)))
+        check(lib().nlsg_pso_minimize(self._h, pd_of(x), pd_of(lo), pd_of(hi), poll_every, C.byref(st)))
         return st
 
     def time_move_kernel(self, launches):
-        ms = C.c_float()
-        check(lib().nlsg_pso_time_move_kernel(self._h, launches, C.byref(ms)))
-        return ms.value
+        return timed_ms(lib().nlsg_pso_time_move_kernel, self._h, launches)
 
     def record_doubles(self):
         return lib().nlsg_pso_record_doubles(self._h)
@@ -132,14 +104,18 @@ class PSOEngine:
         return w.value, r.value
 
 
-class PSOBatchEngine:
+class PSOBatchEngine(Engine):
     """Resident batch PSO (nlsg_pso_batch_*): `batch` independent solves of the keyed engine of one
     shape, each with its own 64-bit seed and its own bounds, one workgroup per solve with the swarm
     in LDS and the whole turn loop inside one kernel. Solve b is bit-identical to
     PSOEngine(objective, n_particles, dim, seed=seeds[b], ...) driven by the same calls with
     lower[b], upper[b]; it ends independently of its neighbours. 1 <= n_particles <= 1024,
     1 <= dim <= 128 and lds_bytes(n_particles, dim, type) within LDS_BUDGET, else NlsgError
-    (code 2): there is no global-memory fallback."""
+    (code 2): there is no global-memory fallback.
+
+    set_params: values already stored are not re-evaluated, so call init / minimize afterwards to
+    solve under the new rows."""
+    _destroy, _set_params = "nlsg_pso_batch_destroy", "nlsg_pso_batch_set_params"
 
     @staticmethod
     def lds_bytes(n_particles, dim, type=PSO_VANILLA, n_params=0):
@@ -156,69 +132,30 @@ class PSOBatchEngine:
     def __init__(self, objective, batch, n_particles, dim, *, type=PSO_VANILLA, bounded=False,
                  minimize=True, inertia=0.8, cognitive=1.8, social=1.8, eps=10e-4, max_iter=5000,
                  best_val_no_change=50, turns_per_launch=0, device=0, stream=None):
-        cfg = PSOBatchConfig()
-        cfg.struct_size = C.sizeof(PSOBatchConfig)
-        cfg.device = device
-        cfg.stream = None if stream is None else (stream or 1)
-        from .de import CustomObjective, rtc_library_path
-        custom = objective if isinstance(objective, CustomObjective) else None
-        cfg.objective = (_capi.OBJ_CUSTOM if custom else
-                         _capi.OBJECTIVES[objective] if isinstance(objective, str) else objective)
+        cfg = self._header(PSOBatchConfig, device, stream)
+        cfg.objective, custom = self._objective_id(objective)
         cfg.minimize, cfg.type, cfg.bounded = int(bool(minimize)), type, int(bool(bounded))
         cfg.batch, cfg.n_particles, cfg.dim = batch, n_particles, dim
         cfg.inertia, cfg.cognitive, cfg.social, cfg.eps = inertia, cognitive, social, eps
         cfg.max_iter, cfg.best_val_no_change = max_iter, best_val_no_change
         cfg.turns_per_launch = turns_per_launch
-        self.cfg = cfg
         self.n_params = custom.n_params if custom else 0
-        self._h = C.c_void_p()
         if custom:
-            create = require("nlsg_pso_batch_create_custom")
-            if self.n_params:
-                require("nlsg_pso_batch_set_params")
-            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
-            obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), self.n_params)
-            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+            self._create_custom(self._creator(require("nlsg_pso_batch_create_custom")), cfg, custom)
         else:
-            check(require("nlsg_pso_batch_create")(C.byref(cfg), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().nlsg_pso_batch_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+            self._create(require("nlsg_pso_batch_create"), cfg)
 
     def _inputs(self, lower, upper, seeds):
         """lower / upper: anything that broadcasts to [batch, dim]; seeds [batch]"""
         B, D = self.cfg.batch, self.cfg.dim
         lo = np.ascontiguousarray(np.broadcast_to(np.asarray(lower, dtype=np.float64), (B, D)))
         hi = np.ascontiguousarray(np.broadcast_to(np.asarray(upper, dtype=np.float64), (B, D)))
-        seeds = np.array([int(s) & (2**64 - 1) for s in np.asarray(seeds, dtype=object).ravel()],
-                         dtype=np.uint64).reshape(B)
-        return lo, hi, seeds
-
-    def set_params(self, params):
-        """params [batch, n_params]: solve b's objective reads row b as p(k). The rows hold from the
-        next launch on and can be replaced at any time without recompiling; values already stored
-        are not re-evaluated, so call init / minimize afterwards to solve under the new rows."""
-        if self.n_params == 0:
-            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
-        rows = _params_rows(params, self.cfg.batch, self.n_params)
-        check(require("nlsg_pso_batch_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
+        return lo, hi, seeds_u64(seeds, B)
 
     def init(self, lower, upper, seeds):
         """PSOEngine.init of every solve under its own seed and bounds"""
         lo, hi, seeds = self._inputs(lower, upper, seeds)
-        check(lib().nlsg_pso_batch_init(self._h, lo.ctypes.data_as(_capi.pd), hi.ctypes.data_as(_capi.pd),
-                                        seeds.ctypes.data_as(_capi.pu)))
+        check(lib().nlsg_pso_batch_init(self._h, pd_of(lo), pd_of(hi), pu_of(seeds)))
 
     def step(self, turns=1):
         check(lib().nlsg_pso_batch_step(self._h, turns))
@@ -233,8 +170,7 @@ class PSOBatchEngine:
         """(x [batch, dim], f [batch], index [batch]): every solve's swarm best"""
         B, D = self.cfg.batch, self.cfg.dim
         x, f, idx = np.empty((B, D)), np.empty(B), np.empty(B, dtype=np.uint64)
-        check(lib().nlsg_pso_batch_best(self._h, x.ctypes.data_as(_capi.pd), f.ctypes.data_as(_capi.pd),
-                                        idx.ctypes.data_as(_capi.pu)))
+        check(lib().nlsg_pso_batch_best(self._h, pd_of(x), pd_of(f), pu_of(idx)))
         return x, f, idx
 
     def download(self, b):
@@ -243,33 +179,24 @@ class PSOBatchEngine:
         vanilla = self.cfg.type == PSO_VANILLA
         pos, vel = np.empty((n, D)), (np.empty((n, D)) if vanilla else None)
         pbest, cur = np.empty(n), np.empty(n)
-        check(lib().nlsg_pso_batch_download(self._h, b, pos.ctypes.data_as(_capi.pd),
-                                            vel.ctypes.data_as(_capi.pd) if vanilla else None,
-                                            pbest.ctypes.data_as(_capi.pd), cur.ctypes.data_as(_capi.pd)))
+        check(lib().nlsg_pso_batch_download(self._h, b, pd_of(pos), pd_of(vel), pd_of(pbest), pd_of(cur)))
         return pos, vel, pbest, cur
 
     def minimize(self, lower, upper, seeds, params=None):
         """init, then turns until every solve is done -> (x [batch, dim], [Status] * batch).
         params: set_params(params) first."""
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         lo, hi, seeds = self._inputs(lower, upper, seeds)
         x = np.empty((self.cfg.batch, self.cfg.dim))
         st = (Status * self.cfg.batch)()
-        check(lib().nlsg_pso_batch_minimize(self._h, x.ctypes.data_as(_capi.pd), lo.ctypes.data_as(_capi.pd),
-                                            hi.ctypes.data_as(_capi.pd), seeds.ctypes.data_as(_capi.pu), st))
+        check(lib().nlsg_pso_batch_minimize(self._h, pd_of(x), pd_of(lo), pd_of(hi), pu_of(seeds), st))
         return x, list(st)
 
     def time_solve(self, lower, upper, seeds, repeats=1, params=None):
         """milliseconds of `repeats` whole solves (hipEvents). params: set_params(params) first."""
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         lo, hi, seeds = self._inputs(lower, upper, seeds)
-        ms = C.c_float()
-        check(lib().nlsg_pso_batch_time_solve(self._h, lo.ctypes.data_as(_capi.pd),
-                                              hi.ctypes.data_as(_capi.pd), seeds.ctypes.data_as(_capi.pu),
-                                              repeats, C.byref(ms)))
-        return ms.value
+        return timed_ms(lib().nlsg_pso_batch_time_solve, self._h, pd_of(lo), pd_of(hi), pu_of(seeds), repeats)
 
 
 class PSO:
@@ -287,14 +214,9 @@ class PSO:
     def __init__(self, f, generator=None, inertia=0.8, cognitive_coef=1.8, social_coef=1.8,
                  n_particles=10, max_iter=5000, best_val_no_change=50, eps=10e-4, *,
                  type=PSO_VANILLA, device=0, driver="turns", params=None):
-        if driver not in ("turns", "resident"):
-            raise ValueError(f"driver must be 'turns' or 'resident', not {driver!r}")
+        check_driver(driver)
         self.driver, self.driver_used = driver, None
-        self.n_params = getattr(f, "n_params", 0)
-        if (params is not None) != bool(self.n_params):
-            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
-                             "objective needs it")
-        self.params = None if params is None else _params_rows(params, 1, self.n_params)
+        self.n_params, self.params = pair_params(f, params, lambda p, n: _params_rows(p, 1, n))
         self.f, self.generator, self.n_particles = f, generator, n_particles
         self.args = dict(inertia=inertia, cognitive=cognitive_coef, social=social_coef, eps=eps,
                          max_iter=max_iter, best_val_no_change=best_val_no_change, type=type,

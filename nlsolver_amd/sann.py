@@ -10,16 +10,17 @@ chains: draws are keyed by (seed, chain, step, slot) on the device (oracle: orc_
 A CustomObjective with n_params > 0 (nlsg_sann_create_params): chain b anneals the objective under
 row b of set_params(rows) ([batch, n_params], read as p(k)); rows are replaced without recompiling.
 """
-import ctypes as C
+import ctypes as C  # noqa: F401 - names the module had before _engine.py stay importable from it
 
 import numpy as np
 
-from . import _capi
-from ._capi import NlsgError, SANNConfig, Status, check, lib, require
-from .de import DEFAULT_SEED, seed_from_generator
+from ._capi import NlsgError, SANNConfig, Status, check, lib, require  # noqa: F401
+from ._engine import DEFAULT_SEED, Engine, _rows_for_batch, pair_params, pd_of, seed_from_generator, timed_ms
 
 
-class SANNEngine:
+class SANNEngine(Engine):
+    _destroy, _set_params = "nlsg_sann_destroy", "nlsg_sann_set_params"
+
     @staticmethod
     def chains_per_wave(dim, n_params=0):
         """chains that share a wave at this shape: 64 / G for dim <= 64 while the parameter rows of the
@@ -33,72 +34,31 @@ class SANNEngine:
 
     def __init__(self, objective, batch, dim, *, minimize=True, max_iter=5000, temperature_iter=10,
                  temperature_max=10.0, seed=DEFAULT_SEED, chain_lo=0, device=0, stream=None):
-        cfg = SANNConfig()
-        cfg.struct_size = C.sizeof(SANNConfig)
-        cfg.device = device
-        cfg.stream = None if stream is None else (stream or 1)
-        from .de import CustomObjective, rtc_library_path
-        custom = objective if isinstance(objective, CustomObjective) else None
-        cfg.objective = (_capi.OBJ_CUSTOM if custom else
-                         _capi.OBJECTIVES[objective] if isinstance(objective, str) else objective)
+        cfg = self._header(SANNConfig, device, stream)
+        cfg.objective, custom = self._objective_id(objective)
         cfg.minimize = int(bool(minimize))
         cfg.batch, cfg.dim, cfg.chain_lo = batch, dim, chain_lo
         cfg.max_iter, cfg.temperature_iter = max_iter, temperature_iter
         cfg.temperature_max, cfg.seed = temperature_max, seed
-        self.cfg = cfg
         self.n_params = custom.n_params if custom else 0
-        self._h = C.c_void_p()
         if custom:
-            create = lib().nlsg_sann_create_custom
-            if self.n_params:  # (zero stays with the creator it always had)
-                create = require("nlsg_sann_create_params")
-                require("nlsg_sann_set_params")
-            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
-            obj = _capi.CustomObjectiveC(custom.term_body.encode(), custom.finish_body.encode(),
-                                         int(custom.chain), self.n_params)
-            check(create(C.byref(cfg), C.byref(obj), C.byref(self._h)))
+            self._create_custom(self._creator(lib().nlsg_sann_create_custom, "nlsg_sann_create_params"), cfg, custom)
         else:
-            check(lib().nlsg_sann_create(C.byref(cfg), C.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().nlsg_sann_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def set_params(self, params):
-        """params [batch, n_params]: chain b's objective reads row b as p(k). The rows hold from the
-        next solve on and can be replaced at any time without recompiling."""
-        if self.n_params == 0:
-            raise NlsgError(_capi.NLSG_ERR_INVALID_ARG, "the engine's objective declares no parameters")
-        from .de import _params_rows
-        rows = _params_rows(params, self.cfg.batch, self.n_params)
-        check(require("nlsg_sann_set_params")(self._h, rows.ctypes.data_as(_capi.pd)))
+            self._create(lib().nlsg_sann_create, cfg)
 
     def minimize(self, x, params=None):
         """x: (batch, dim) starts; returns (best points, [Status]). params: set_params(params) first."""
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         x = np.ascontiguousarray(x, dtype=np.float64).copy()
         assert x.shape == (self.cfg.batch, self.cfg.dim)
         st = (Status * self.cfg.batch)()
-        check(lib().nlsg_sann_minimize(self._h, x.ctypes.data_as(_capi.pd), st))
+        check(lib().nlsg_sann_minimize(self._h, pd_of(x), st))
         return x, list(st)
 
     def time_solve(self, x0, repeats=1, params=None):
-        if params is not None:
-            self.set_params(params)
+        self._apply_params(params)
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
-        ms = C.c_float()
-        check(lib().nlsg_sann_time_solve(self._h, x0.ctypes.data_as(_capi.pd), repeats, C.byref(ms)))
-        return ms.value
+        return timed_ms(lib().nlsg_sann_time_solve, self._h, pd_of(x0), repeats)
 
 
 class SANN:
@@ -109,12 +69,7 @@ class SANN:
 
     def __init__(self, f, generator=None, max_iter=5000, temperature_iter=10, temperature_max=10.0,
                  *, device=0, params=None):
-        from .nm import _drop_in_rows
-        self.n_params = getattr(f, "n_params", 0)
-        if (params is not None) != bool(self.n_params):
-            raise ValueError("params= goes with a CustomObjective whose n_params > 0, and such an "
-                             "objective needs it")
-        self.params = None if params is None else _drop_in_rows(params, self.n_params)
+        self.n_params, self.params = pair_params(f, params)
         self.f, self.generator = f, generator
         self.args = dict(max_iter=max_iter, temperature_iter=temperature_iter,
                          temperature_max=temperature_max, device=device)
@@ -123,7 +78,6 @@ class SANN:
         if not isinstance(x, np.ndarray) or x.dtype != np.float64 or x.ndim not in (1, 2):
             raise TypeError("x must be a float64 numpy array of shape (n,) or (batch, n)")
         xb = x.reshape(1, -1) if x.ndim == 1 else x
-        from .nm import _rows_for_batch
         rows = _rows_for_batch(self.params, xb.shape[0])
         with SANNEngine(self.f, xb.shape[0], xb.shape[1], minimize=minimize,
                         seed=seed_from_generator(self.generator), **self.args) as eng:

@@ -8,12 +8,10 @@ solved side by side on the GPU (n >= p, p <= 64). There is no CPU fallback.
 qr_decomposition() and lm(..., reference_order=True) run the reference's own order of operations
 on the device (nlsg_tinyqr_qr): Q, R and beta equal the reference's bit for bit, any p.
 """
-import ctypes as C
-
 import numpy as np
 
-from . import _capi
 from ._capi import check, lib
+from ._engine import pd_of, timed_ms
 
 
 def _reference_order(X, y, tol, device, want_q, want_r, want_beta):
@@ -22,8 +20,8 @@ def _reference_order(X, y, tol, device, want_q, want_r, want_beta):
     Q = np.empty((batch, p, n)) if want_q else None
     R = np.empty((batch, p, p)) if want_r else None
     beta = np.empty((batch, p)) if want_beta else None
-    ptr = lambda a: a.ctypes.data_as(_capi.pd) if a is not None else None  # noqa: E731
-    check(lib().nlsg_tinyqr_qr(ptr(X), ptr(y), batch, n, p, float(tol), device, ptr(Q), ptr(R), ptr(beta)))
+    check(lib().nlsg_tinyqr_qr(pd_of(X), pd_of(y), batch, n, p, float(tol), device, pd_of(Q), pd_of(R),
+                               pd_of(beta)))
     return Q, R, beta
 
 
@@ -59,8 +57,6 @@ def lm(X, y, tol=1e-12, *, device=0, return_ms=False, reference_order=False):
         beta = _reference_order(X, y, tol, device, False, False, True)[2]
         return beta[0] if single else beta
     beta = np.empty((batch, p))
-    ms = C.c_float()
-    check(lib().nlsg_tinyqr_lm(X.ctypes.data_as(_capi.pd), y.ctypes.data_as(_capi.pd), batch, n, p,
-                               float(tol), device, beta.ctypes.data_as(_capi.pd), C.byref(ms)))
+    ms = timed_ms(lib().nlsg_tinyqr_lm, pd_of(X), pd_of(y), batch, n, p, float(tol), device, pd_of(beta))
     out = beta[0] if single else beta
-    return (out, ms.value) if return_ms else out
+    return (out, ms) if return_ms else out

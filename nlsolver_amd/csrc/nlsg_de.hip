@@ -34,18 +34,18 @@ struct nlsg_de : EngineBase {
   DeRtcKernels rtc;           // objective == NLSG_OBJ_CUSTOM: the kernels hiprtc built for it
   bool overlap = false;
   bool fused = false;   // head k and generation k+1 share one launch (strategy random, one GPU)
-  // The pair wave pays where the screen decides nearly every agent and costs where it does not
-  // (two undecided agents run one after the other in one wave). Every 64th pair wave counts its
-  // decisions on the device; wherever the host reads the state anyway (status, best, download, the
+  // The screening wave pays where the screen decides nearly every agent and costs where it does not
+  // (its undecided agents run one after the other in one wave). The waves that start at a multiple
+  // of 128 agents count the decisions of their first two agents on the device; wherever the host reads the state anyway (status, best, download, the
   // polls of minimize) it compares the count with the generations launched since the last look and
   // drops bit kDeBoundScreen of DeParams.bound -- the parent's one-agent launches -- while the share
-  // of decided agents is below kDeScreenKeep, then tries the pair wave again for one interval after
+  // of decided agents is below kDeScreenKeep, then tries the screening wave again for one interval after
   // kDeScreenProbe generations. Switching changes the path only, never an output: the one-agent
-  // path clears the miss counts it writes over. NLSG_DE_SCREEN_ADAPT=0: the pair wave stays on.
+  // path clears the miss counts it writes over. NLSG_DE_SCREEN_ADAPT=0: the screening wave stays on.
   bool screen_capable = false, screen_adapt = false;
   uint32_t stat_seen = 0;   // the device's count at the last look
   uint64_t k_seen = 0;      // generations launched at the last look
-  uint64_t k_off = 0;       // generations launched when the pair wave was switched off
+  uint64_t k_off = 0;       // generations launched when the screening wave was switched off
 };
 
 namespace {
@@ -138,10 +138,10 @@ void launch_generation_groups(nlsg_de *e, dim3 grid, int par, uint64_t generatio
   }
 }
 
-// waves of a generation: one per agent, one per 64 / group agents (D <= 64), or one per two agents
-// (the screen's pair wave, kDeBoundScreen)
+// waves of a generation: one per agent, one per 64 / group agents (D <= 64), or one per
+// kDeScreenAgents = 4 agents (the screening wave, kDeBoundScreen)
 uint64_t generation_waves(const nlsg_de *e) {
-  const uint64_t per_wave = (e->p.bound & kDeBoundScreen) ? 2 : e->group ? 64 / e->group : 1;
+  const uint64_t per_wave = (e->p.bound & kDeBoundScreen) ? kDeScreenAgents : e->group ? 64 / e->group : 1;
   return (e->p.shard_n + per_wave - 1) / per_wave;
 }
 
@@ -184,7 +184,7 @@ void launch_generation(nlsg_de *e, int par, uint64_t generation, int ignore_done
     return;
   }
   // (an engine that uses the bound launches the instantiation that has it: DeParams.bound)
-  // (and one that screens, the instantiation with the pair wave: kDeBoundScreen, one chunk only)
+  // (and one that screens, the instantiation with the screening wave: kDeBoundScreen, one chunk only)
 #define CALL_B(OBJ, C, V, B, S)                                                                   \
   hipLaunchKernelGGL((de_generation_kernel<OBJ, C, V, B, S>), grid, block, 0, e->stream, e->p, par, \
                      generation, ignore_done)
@@ -295,11 +295,11 @@ int join_side(nlsg_de *e) {
   return NLSG_OK;
 }
 
-constexpr double kDeScreenKeep = 0.9;       // share of decided agents below which the pair wave is dropped
+constexpr double kDeScreenKeep = 0.9;       // share of decided agents below which the screening wave is dropped
 constexpr uint64_t kDeScreenProbe = 1024;   // generations after which it is tried again
 constexpr uint64_t kDeScreenLook = 8;       // generations a look needs to judge
 
-// the pair wave on or off by what the sampled waves decided since the last look (nlsg_de.screen_adapt)
+// the screening wave on or off by what the sampled waves decided since the last look (nlsg_de.screen_adapt)
 void adapt_screen(nlsg_de *e, uint32_t stat) {
   if (!e->screen_adapt) return;
   const uint64_t gens = e->k - e->k_seen;
@@ -556,7 +556,7 @@ int nlsg_de_init(nlsg_de *e, const double *x0_host) {
   if (e->p.counts) NLSG_HIP(hipMemsetAsync(e->p.counts, 0, kDeCounts * sizeof(uint64_t), e->stream));
   launch_init(e);
   e->k = 0;
-  if (e->screen_capable) {  // a new solve starts with the pair wave; the device's count keeps running
+  if (e->screen_capable) {  // a new solve starts with the screening wave; the device's count keeps running
     e->p.bound |= kDeBoundScreen;
     e->k_seen = e->k_off = 0;
   }

@@ -46,7 +46,7 @@ constexpr int kTraceWords = 5;        // r1, r2, r3, jrand, accept
 // lambdas of de_fetch_agent and of the packed generation, DeAgent.home, de_gather_kernel and the
 // head's best row (both through de_row). Init stores 0 and upload's memset stores the parity
 // (0 or 1), so both clear the hint. Bits 2-3 are the screen's miss count (kDeBoundScreen), kept by
-// the pair wave alone and carried through select() as DeAgent.miss; the same readers ignore them.
+// the screening wave alone and carried through select() as DeAgent.miss; the same readers ignore them.
 struct DeParams {
   double *buf[2];      // population ping-pong, rows addressed through `home`
   double *scores[2];   // [shard_n] each, ping-pong with the population: a generation reads
@@ -90,7 +90,7 @@ struct DeParams {
   // with `bound` set). The same lane tree with +0.0 in place of every term that touches a coordinate
   // >= 64 is <= the bound above, hence <= the score, by the same argument: screen >= old_score
   // rejects the trial on 512 B of each donor row and 64 crossover draws. Half a row is 32 lanes, so
-  // a wave of the generation takes two agents, one per half-wave (de_generation_pair); an agent the
+  // a wave of the generation screens two agents at a time, one per half-wave (de_generation_screen); an agent the
   // screen does not decide goes through de_fetch_agent / de_process_agent unchanged. Bits 2-3 of an
   // agent's selector byte count its consecutive screen misses (saturating at 3; a decision clears
   // them): from two misses on the agent skips the screen except in the generations where
@@ -164,7 +164,7 @@ struct DeAgent {
   uint64_t a, ka, r0, r1, r2, jrand;
   uint32_t home;          // home[par][a] & 1: the buffer holding the agent's row
   uint32_t hint;          // home[par][a] & 2: the bound did not decide this agent's last try
-  uint32_t miss;          // bits 2-3 of the selector byte to leave behind (the pair wave sets it, else 0)
+  uint32_t miss;          // bits 2-3 of the selector byte to leave behind (the screening wave sets it, else 0)
   bool bound;            // wave-uniform: this generation tries the bound, `keep` is not loaded yet
   uint64_t cross[CHUNKS][2];  // lane masks (lane_bit): the trial takes the mutant here (crossover draw or jrand)
   double keep[CHUNKS][2], d1[CHUNKS][2], d2[CHUNKS][2], d3[CHUNKS][2];
@@ -548,15 +548,37 @@ __global__ __launch_bounds__(256) void de_generation_groups_kernel(DeParams p, i
   de_generation_groups_block<OBJ, G>(p, par, generation, ignore_done, blockIdx.x);
 }
 
-// ---- the half-row reject screen: two agents per wave, one per half-wave (kDeBoundScreen) ---------
-// Wave w of the generation takes agents 2w and 2w + 1 (a lone last agent: the upper half shadows it
-// and writes nothing). Half-lane j = lane & 31 holds coordinates 2j, 2j + 1 of its half's agent, and
-// everything that is wave-uniform in de_fetch_agent is half-uniform here and lives in vector
-// registers: the agent's key, draw D + j of its stream (j = 0 jrand, j = 1..31 donor candidates
-// 0..30 -- the values lanes 0..31 of the one-agent path hold), and the donor picks, made by the same
-// rule on each half's 32 bits of the ballots. An agent declines the screen when 31 candidates do
-// not give three donors or when a pick lies past candidate 6 (its selector is not among the bytes
-// lanes 1..7 loaded; tiny shards): it takes the one-agent path like an agent the screen missed.
+// ---- the half-row reject screen: four agents per wave, planned side by side (kDeBoundScreen) -----
+// Wave w of the generation takes agents 4w .. 4w + 3 (kDeScreenAgents) and runs in two phases.
+//
+// Phase 1, the plan, once per wave. Lane 8q + c works for agent 4w + q (the groups q >= 4, and
+// those past the shard's end, shadow agent 4w and never run). Every lane of a group computes the
+// agent's key; lane c takes draw D + c of its stream -- c = 0 jrand, c = 1..7 donor candidates
+// 0..6, the values lanes 0..7 of the one-agent path hold -- and loads a selector byte: the agent's
+// own (c = 0) or its candidate's (always in bounds), so every byte load of the wave is one round
+// trip. The picks are made inside the group by first occurrences: candidate k is kept when it
+// differs from the agent and from every candidate before it (six lane-shifted compares, masked to
+// the group), the picks are the first three kept ones in order (a lane's rank is the population
+// count of its group's kept bits below its own), and the agent runs the screen when there are
+// three. That is de_fetch_agent's rule -- the first three candidates in order that differ from the
+// agent and from each other -- wherever the third of them lies at candidate <= 6; every other agent
+// declines (fewer than three donors among the rule's candidates, or a pick whose selector byte no
+// lane loaded: both end in the one-agent path, and nothing the device writes tells them apart).
+// Checked exhaustively on the host (tests/test_de_picks_cpu.py). No value goes through scalar
+// registers. Each agent's plan -- the addresses of its three donor rows, key, old score, jrand,
+// selector byte, `run` -- goes into 64 B of LDS private to the wave: no block-level barrier, a
+// wave reads what it wrote.
+//
+// Phase 2, the rows, one pass per two agents: the lower half-wave works on agent 4w + 2i, the upper
+// one on 4w + 2i + 1, half-lane j = lane & 31 holding coordinates 2j, 2j + 1. A half reads its
+// agent's plan from LDS (one address per half: a broadcast), the first 512 B of the three donor
+// rows, and does the per-coordinate work: 64 crossover draws, mutant, terms, the half's tree, the
+// decision and the stores of the decided exit. The crossover masks of both passes are computed
+// ahead of the first use of a row.
+//
+// Afterwards the agents the screen did not decide -- missed, declined, backed off, no bound try
+// this generation -- go through de_fetch_agent / de_process_agent, run by the whole wave one after
+// the other, with the miss count phase 2 left for them.
 //
 // The screen value. Lane j accumulates as wave_objective_masked does -- 0.0, then term 2j, then
 // term 2j + 1, +0.0 in place of a term that reads a kept coordinate -- with term 63 always +0.0
@@ -570,87 +592,116 @@ __global__ __launch_bounds__(256) void de_generation_groups_kernel(DeParams p, i
 // whose stores are the ones made here. (A NaN among the terms past 63 makes bound and score NaN:
 // the trial is rejected all the same, every output equal; only the bound's hint and its counters,
 // which no output depends on, would then say "not decided".)
-template <int OBJ, bool VEC>
-__device__ inline void de_generation_pair(const DeParams &p, int par, uint64_t generation, uint64_t block) {
+//
+// Why four agents and not eight: with eight (four passes) the wave issues 80 vector instructions
+// per agent against 144 of the two-agent wave it replaces, but a population of 65 536 is then 8 192
+// waves, all resident at once and in step, and the turn was no faster.
+constexpr int kDeScreenPasses = 2;                      // passes of phase 2 (at most 4: a group per agent)
+constexpr int kDeScreenAgents = 2 * kDeScreenPasses;    // agents of a screening wave (nlsg_de.hip: the grid)
+constexpr int kDePlanWords = 16;  // 32-bit words of an agent's plan in LDS (de_generation_screen)
+
+template <int OBJ, bool VEC, int NP = kDeScreenPasses>
+__device__ inline void de_generation_screen(const DeParams &p, int par, uint64_t generation, uint64_t block) {
   static_assert(TermsNonNegative<OBJ>::value, "the screen needs terms >= 0");
   using O = Objective<OBJ>;
-  const uint64_t a0 = 2 * (block * 4 + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6));
+  typedef double __attribute__((address_space(1))) global_double;
+  typedef double __attribute__((ext_vector_type(2))) double_x2;
+  typedef double_x2 __attribute__((address_space(1))) global_double_x2;
+  // plan of agent a0 + q, written in phase 1 and read in phase 2 by this wave alone:
+  //   words 0-5 the addresses of the three donor rows, 6-7 the agent's key, 8-9 its old score,
+  //   10 jrand, 11 the selector byte (bits 0-7) and `run` (bit 8), 12-14 the donors' indices
+  __shared__ __attribute__((aligned(16))) uint32_t plans[4 * 8 * kDePlanWords];
+  const uint32_t tid = threadIdx.x;
+  constexpr uint32_t per_wave = 2 * NP;
+  const uint64_t a0 = per_wave * (block * 4 + __builtin_amdgcn_readfirstlane(static_cast<int>(tid >> 6)));
   if (a0 >= p.shard_n) return;
-  const bool two = a0 + 1 < p.shard_n;  // wave-uniform
-  const int lane = lane_id();
-  const uint32_t j = static_cast<uint32_t>(lane) & 31u;
-  const bool upper = lane >= 32;
-  const bool live = !upper || two;
-  // (shard sizes fit 32 bits: the shard-local agent index is a 32-bit value per half)
-  const uint32_t a = static_cast<uint32_t>(a0) + ((upper && two) ? 1u : 0u);
-  const uint8_t *__restrict__ hp = p.home[par];
-  const uint32_t hraw = hp[a];
-  double old_score = p.scores[par][a];  // with the selector byte: not a round trip of its own later
+  const uint64_t rest = p.shard_n - a0;
+  const uint32_t n_live = rest < per_wave ? static_cast<uint32_t>(rest) : per_wave;  // wave-uniform
+  const uint32_t lane = tid & 63u;
   const uint32_t d32 = static_cast<uint32_t>(p.D);
-  // the agent's key on the vector unit, one value per half
-  const uint64_t ka = ctr_key(p.gen_key, p.shard_lo + a);
-  const uint32_t lim = j == 0 ? d32 : static_cast<uint32_t>(p.shard_n);
-  const uint32_t idx = static_cast<uint32_t>(u01(mix64(ka + golden_times(d32 + j + 1u))) * static_cast<double>(lim));
-  const uint32_t drawn = idx >= lim ? lim - 1 : idx;  // the u == 1.0 corner clamped (B10)
-  // who tries: the generations in which the one-agent path would try the bound (DeAgent.bound),
-  // less the agents that missed the screen twice in a row outside their retry generations
-  // (the selector byte is first needed here: tied to the draw, its load's latency hides behind the
-  // key and the draw instead of stalling the wave in front of them; and the rule is written without
-  // short-circuits: straight-line mask arithmetic, no branches on a per-lane value)
-  uint32_t sel = hraw;
-  asm("" : "+v"(sel), "+v"(old_score) : "v"(drawn));
-  const uint32_t cnt = (sel >> 2) & 3u;
-  const bool tries = live & de_screen_tries(sel, generation, a, p.retry_mask, p.screen_retry_mask);
-  bool dec = false;         // the screen rejected this half's trial
-  uint32_t left = cnt << 2;  // bits 2-3 of the selector byte this generation leaves behind
-  if (__ballot(tries) != 0ull) {  // wave-uniform
-    // selectors of donor candidates 0..6, as in de_fetch_agent
-    const uint32_t hsel = hp[(j >= 1 && j < 8) ? drawn : a];
-    auto half_of = [&](uint32_t lo, uint32_t hi) { return upper ? hi : lo; };
-    auto lane32 = [&](uint32_t v, int src) {
-      return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), src));
-    };
-    const uint32_t jrand = half_of(lane32(drawn, 0), lane32(drawn, 32));  // :2364
-    // generate_indices (nlsolver.h:2331-2355) per half: the first three candidates in order that
-    // differ from the agent and from each other (de_fetch_agent's compares, 32 bits of each ballot)
-    constexpr uint32_t top = 1u << 31;
-    const uint64_t b0 = __ballot(drawn != a) & ~0x0000000100000001ull;  // half-lane 0 holds jrand
-    const uint32_t m0l = static_cast<uint32_t>(b0), m0h = static_cast<uint32_t>(b0 >> 32);
-    const int i0l = __builtin_ctz(m0l | top), i0h = __builtin_ctz(m0h | top);
-    const uint32_t r0 = half_of(lane32(drawn, i0l), lane32(drawn, 32 + i0h));
-    const uint64_t b1 = __ballot(drawn != r0);
-    const uint32_t m1l = m0l & static_cast<uint32_t>(b1) & ((~0u << i0l) << 1);
-    const uint32_t m1h = m0h & static_cast<uint32_t>(b1 >> 32) & ((~0u << i0h) << 1);
-    const int i1l = __builtin_ctz(m1l | top), i1h = __builtin_ctz(m1h | top);
-    const uint32_t r1 = half_of(lane32(drawn, i1l), lane32(drawn, 32 + i1h));
-    const uint64_t b2 = __ballot(drawn != r1);
-    const uint32_t m2l = m1l & static_cast<uint32_t>(b2) & ((~0u << i1l) << 1);
-    const uint32_t m2h = m1h & static_cast<uint32_t>(b2 >> 32) & ((~0u << i1h) << 1);
-    const int i2l = __builtin_ctz(m2l | top), i2h = __builtin_ctz(m2h | top);
-    const uint32_t r2 = half_of(lane32(drawn, i2l), lane32(drawn, 32 + i2h));
-    // three donors among the 31 candidates, the last one (i0 < i1 < i2) within candidates 0..6
-    const bool okl = m0l != 0 && m1l != 0 && m2l != 0 && i2l < 8;
-    const bool okh = m0h != 0 && m1h != 0 && m2h != 0 && i2h < 8;
-    const bool run = tries && (upper ? okh : okl);
-    // (a half that does not run reads in-bounds garbage: every index is some lane's `drawn`)
-    const uint32_t h0 = half_of(lane32(hsel, i0l), lane32(hsel, 32 + i0h));
-    const uint32_t h1 = half_of(lane32(hsel, i1l), lane32(hsel, 32 + i1h));
-    const uint32_t h2 = half_of(lane32(hsel, i2l), lane32(hsel, 32 + i2h));
-    // crossover masks of coordinates 2j, 2j + 1 (propose_new_agent, nlsolver.h:2357-2375)
-    const uint64_t ka_lane = ka + golden_times(2 * j + 1u);
-    const bool c0 = mix64(ka_lane) < p.cr_thresh || p.cr_all || 2 * j == jrand;
-    const bool c1 = mix64(ka_lane + kGolden) < p.cr_thresh || p.cr_all || 2 * j + 1 == jrand;
-    // the first 512 B of the three donor rows (coordinates 0..63 < D), never the own row
-    // (both buffer bases out of the kernel arguments once, the selector selects between the two
-    // values: see de_fetch_agent -- left alone the compiler loads the base through the selector, a
-    // dependent load in front of every row)
-    typedef double __attribute__((address_space(1))) global_double;
-    global_double *base0 = (global_double *)p.buf[0], *base1 = (global_double *)p.buf[1];
-    asm("" : "+s"(base0), "+s"(base1));
-    auto load2 = [&](uint32_t h, uint32_t r, double (&v)[2]) {
-      const double *src = (double *)((h & 1u) ? base1 : base0) + static_cast<uint64_t>(r) * d32 + 2 * j;
+  // both buffer bases out of the kernel arguments once (see de_fetch_agent)
+  global_double *base0 = (global_double *)p.buf[0], *base1 = (global_double *)p.buf[1];
+  asm("" : "+s"(base0), "+s"(base1));
+  {  // ---- phase 1, the plan: lane 8q + c works for agent a0 + q
+    const uint32_t c = lane & 7u, q = lane >> 3;
+    const bool live = q < n_live;
+    // (shard sizes fit 32 bits; a group past the shard's end shadows agent a0 and never runs)
+    const uint32_t a = static_cast<uint32_t>(a0) + (live ? q : 0u);
+    const uint8_t *__restrict__ hp = p.home[par];
+    const uint64_t ka = ctr_key(p.gen_key, p.shard_lo + a);
+    // draw D + c of the agent's stream: c = 0 jrand (:2364), c = 1..7 donor candidates 0..6
+    const uint32_t lim = c == 0 ? d32 : static_cast<uint32_t>(p.shard_n);
+    const uint32_t idx = static_cast<uint32_t>(u01(mix64(ka + golden_times(d32 + c + 1u))) * static_cast<double>(lim));
+    const uint32_t drawn = idx >= lim ? lim - 1 : idx;  // the u == 1.0 corner clamped (B10)
+    // every byte load of the wave in one round trip: c = 0 the agent's selector byte, c = 1..7 the
+    // candidates' (always in bounds), and the old score beside them
+    const uint32_t sel = hp[c == 0 ? a : drawn];
+    const double old_score = p.scores[par][a];
+    // generate_indices (nlsolver.h:2331-2355) on candidates 0..6: a candidate is kept when it differs
+    // from the agent and from every candidate before it; the picks are the first three kept ones.
+    // row_shr:s brings lane c - s's draw; the masks leave only compares of candidates of one group
+    // (c - s >= 1). A lane whose source lies outside its row keeps its own value and is masked too.
+    constexpr uint64_t each = 0x0101010101010101ull;
+    uint64_t dup = __ballot(dpp_mov32<0x111, 0xF>(drawn, drawn) == drawn) & (0xFCull * each);
+    dup |= __ballot(dpp_mov32<0x112, 0xF>(drawn, drawn) == drawn) & (0xF8ull * each);
+    dup |= __ballot(dpp_mov32<0x113, 0xF>(drawn, drawn) == drawn) & (0xF0ull * each);
+    dup |= __ballot(dpp_mov32<0x114, 0xF>(drawn, drawn) == drawn) & (0xE0ull * each);
+    dup |= __ballot(dpp_mov32<0x115, 0xF>(drawn, drawn) == drawn) & (0xC0ull * each);
+    dup |= __ballot(dpp_mov32<0x116, 0xF>(drawn, drawn) == drawn) & (0x80ull * each);
+    const uint64_t keep = __ballot(drawn != a) & ~dup & (0xFEull * each);
+    const uint32_t grp = static_cast<uint32_t>(keep >> (lane & 56u)) & 0xFFu;  // the group's byte
+    const uint32_t rank = static_cast<uint32_t>(__builtin_popcount(grp & ((1u << c) - 1u)));
+    const bool ok = __builtin_popcount(grp) >= 3;
+    const bool mine = ((grp >> c) & 1u) != 0 && rank < 3;
+    const bool run = live & ok & de_screen_tries(sel, generation, a, p.retry_mask, p.screen_retry_mask);
+    uint32_t *rec = plans + (tid >> 3) * kDePlanWords;
+    if (c == 0) {
+      // (an agent that does not run has fewer than three picks: every address it leaves behind is
+      // a row's all the same)
+      const uint64_t b = reinterpret_cast<uint64_t>(base0);
+      const uint64_t os = static_cast<uint64_t>(__double_as_longlong(old_score));
+      const uint32_t bl = static_cast<uint32_t>(b), bh = static_cast<uint32_t>(b >> 32);
+      *reinterpret_cast<uint4 *>(rec) = make_uint4(bl, bh, bl, bh);
+      *reinterpret_cast<uint4 *>(rec + 4) =
+          make_uint4(bl, bh, static_cast<uint32_t>(ka), static_cast<uint32_t>(ka >> 32));
+      *reinterpret_cast<uint4 *>(rec + 8) = make_uint4(static_cast<uint32_t>(os), static_cast<uint32_t>(os >> 32),
+                                                       drawn, (sel & 0xFFu) | (run ? 0x100u : 0u));
+    }
+    if (mine) {
+      global_double *row = ((sel & 1u) ? base1 : base0) + static_cast<uint64_t>(drawn) * d32;
+      *reinterpret_cast<uint64_t *>(rec + 2 * rank) = reinterpret_cast<uint64_t>(row);
+      rec[12 + rank] = drawn;
+    }
+  }
+  // the wave reads what its own lanes wrote: LDS operations of a wave complete in order, and the
+  // compiler must not move the reads up
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  // ---- phase 2, the rows: in pass i the lower half-wave works on agent a0 + 2i, the upper one on
+  // a0 + 2i + 1; half-lane j holds coordinates 2j, 2j + 1
+  const uint32_t j = lane & 31u;
+  const bool upper = lane >= 32;
+  const uint32_t *plan0 = plans + (tid >> 6) * (8 * kDePlanWords) + (upper ? kDePlanWords : 0);
+  struct Pass {
+    double old_score;
+    uint32_t jrand, flags;
+    double d1[2], d2[2], d3[2];
+  };
+  // the plan and the first 512 B of the three donor rows (coordinates 0..63 < D), never the own row
+  auto fetch = [&](int i, Pass &R) {
+    const uint32_t *rd = plan0 + i * (2 * kDePlanWords);
+    const uint4 w0 = *reinterpret_cast<const uint4 *>(rd);
+    const uint2 w1 = *reinterpret_cast<const uint2 *>(rd + 4);
+    const uint4 w2 = *reinterpret_cast<const uint4 *>(rd + 8);
+    auto u64 = [](uint32_t lo, uint32_t hi) { return (static_cast<uint64_t>(hi) << 32) | lo; };
+    R.old_score = __longlong_as_double(static_cast<long long>(u64(w2.x, w2.y)));
+    R.jrand = w2.z;
+    R.flags = w2.w;
+    auto load2 = [&](uint64_t row, double (&v)[2]) {
+      const global_double *src = reinterpret_cast<const global_double *>(row) + 2 * j;
       if (VEC) {
-        const double2 t = *reinterpret_cast<const double2 *>(src);
+        const double_x2 t = *reinterpret_cast<const global_double_x2 *>(src);
         v[0] = t.x;
         v[1] = t.y;
       } else {
@@ -658,32 +709,50 @@ __device__ inline void de_generation_pair(const DeParams &p, int par, uint64_t g
         v[1] = src[1];
       }
     };
-    double d1[2], d2[2], d3[2];
-    load2(h0, r0, d1);
-    load2(h1, r1, d2);
-    load2(h2, r2, d3);
-    const double x0 = d1[0] + p.F * (d2[0] - d3[0]);  // the mutant
-    const double x1 = d1[1] + p.F * (d2[1] - d3[1]);
-    // lane j + 1's first coordinate and its flag; half-lane 31's neighbour is x64: never known
-    const double xn = lane_down1(x0);
-    const bool cn = lane_bit(__ballot(c0) >> 1) && j != 31;
-    const bool k0 = c0 && (O::kChain ? c1 : true);
-    const bool k1 = c1 && (O::kChain ? cn : j != 31);
+    load2(u64(w0.x, w0.y), R.d1);
+    load2(u64(w0.z, w0.w), R.d2);
+    load2(u64(w1.x, w1.y), R.d3);
+  };
+  // Crossover masks of coordinates 2j, 2j + 1 (propose_new_agent, nlsolver.h:2357-2375) as lane masks,
+  // for every pass and ahead of the first use of a row: this is the work a wave has while its rows
+  // are on their way. known0 / known1: the terms 2j and 2j + 1 read mutant coordinates only (lane
+  // j + 1's first flag is the next bit; half-lane 31's neighbour is x64: never known).
+  const uint64_t golden_j = golden_times(2 * j + 1u);
+  const uint64_t cr_all = p.cr_all ? ~0ull : 0ull;
+  uint64_t known0[NP], known1[NP];
+  auto masks = [&](int i) {
+    const uint32_t *rd = plan0 + i * (2 * kDePlanWords);
+    const uint64_t ka_lane = *reinterpret_cast<const uint64_t *>(rd + 6) + golden_j;
+    const uint32_t jrand = rd[10];
+    const uint64_t c0 = __ballot(mix64(ka_lane) < p.cr_thresh) | cr_all | __ballot(2 * j == jrand);
+    const uint64_t c1 = __ballot(mix64(ka_lane + kGolden) < p.cr_thresh) | cr_all | __ballot(2 * j + 1 == jrand);
+    constexpr uint64_t not31 = ~((1ull << 31) | (1ull << 63));
+    known0[i] = O::kChain ? (c0 & c1) : c0;
+    known1[i] = c1 & (O::kChain ? (c0 >> 1) : ~0ull) & not31;
+  };
+  uint32_t decided = 0;  // bit q: the screen rejected the trial of agent a0 + q
+  uint32_t lefts = 0;    // byte i: bits 2-3 of the selector byte pass i's agent leaves behind
+  auto rows = [&](int i, const Pass &R, double x0, double x1) {
+    const uint32_t a = static_cast<uint32_t>(a0) + 2 * i + (upper ? 1u : 0u);
+    const bool run = (R.flags & 0x100u) != 0;
+    const uint32_t cnt = (R.flags >> 2) & 3u;
+    const double xn = lane_down1(x0);  // lane j + 1's first coordinate
     double acc = 0.0;
-    acc = acc + (k0 ? O::term(x0, x1) : 0.0);
-    acc = acc + (k1 ? O::term(x1, xn) : 0.0);
+    acc = acc + (lane_bit(known0[i]) ? O::term(x0, x1) : 0.0);
+    acc = acc + (lane_bit(known1[i]) ? O::term(x1, xn) : 0.0);
     butterfly_levels<16>([&](auto off) { acc = xor_add<decltype(off)::value>(acc); });
-    dec = run && acc >= old_score;  // (false for NaN) the score cannot be lower: rejected
-    left = de_screen_count_after(cnt, dec ? 0 : run ? 1 : 2) << 2;
+    const bool dec = run && acc >= R.old_score;  // (false for NaN) the score cannot be lower: rejected
+    lefts |= (de_screen_count_after(cnt, dec ? 0 : run ? 1 : 2) << 2) << (8 * i);
     if (j == 0 && dec) {  // what the bound's "decided" exit stores (select(false, ..., 0u))
-      p.scores[par ^ 1][a] = old_score;
-      p.home[par ^ 1][a] = static_cast<uint8_t>(hraw & 1u);
+      p.scores[par ^ 1][a] = R.old_score;
+      p.home[par ^ 1][a] = static_cast<uint8_t>(R.flags & 1u);
       if (p.trace != nullptr) {
+        const uint32_t *rd = plan0 + i * (2 * kDePlanWords);
         uint64_t *t = p.trace + static_cast<uint64_t>(a) * kTraceWords;
-        t[0] = p.shard_lo + r0;
-        t[1] = p.shard_lo + r1;
-        t[2] = p.shard_lo + r2;
-        t[3] = jrand;
+        t[0] = p.shard_lo + rd[12];
+        t[1] = p.shard_lo + rd[13];
+        t[2] = p.shard_lo + rd[14];
+        t[3] = R.jrand;
         t[4] = 0u;
       }
     }
@@ -691,43 +760,55 @@ __device__ inline void de_generation_pair(const DeParams &p, int par, uint64_t g
       if (dec) atomicAdd(reinterpret_cast<unsigned long long *>(p.counts + kDeBoundDecided), 1ull);
       atomicAdd(reinterpret_cast<unsigned long long *>(p.counts + (dec ? kDeScreenDecided : kDeScreenMissed)), 1ull);
     }
-  }
-  // not decided here: the trial goes through the one-agent path, run by the whole wave
-  const uint64_t decided = __ballot(dec);
-  // every 64th wave adds its decisions to a running count the host reads with the state
-  // (kDeScreenStat): what the engine switches the pair wave off and on by, see nlsg_de.hip
-  // (one scalar test and branch for the 63 waves in 64 that do not count: folded into one
-  // predicate with the rest, the test costs every wave ten scalar instructions, 1 us per turn)
-  if (((a0 >> 1) & 63u) == 0) {
-    asm volatile("" ::: "memory");
-    if (decided != 0ull && lane == 0)
-      atomicAdd(p.ticket + kDeScreenStat, static_cast<uint32_t>(__builtin_popcountll(decided & 0x0000000100000001ull)));
-  }
-  // (left first: what the loop below needs in every pass is set up in front of it, and a wave whose
-  // agents are both decided -- nearly every wave where the screen pays -- must not pay for that)
-  if ((~decided & (two ? 0x0000000100000001ull : 1ull)) == 0ull) return;
-  const uint32_t left_l = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(left), 0));
-  const uint32_t left_h = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(left), 32));
-  const uint64_t best_id = p.state->best_id;
-  auto one_agent = [&](int h) {
-    DeAgent<1> A;
-    de_fetch_agent<true, 1, VEC>(p, par, p.gen_key, generation, best_id, a0 + h, A);
-    A.miss = h ? left_h : left_l;
-    de_process_agent<OBJ, 1, VEC, true>(p, par, A);
+    const uint64_t d = __ballot(dec);
+    decided |= ((static_cast<uint32_t>(d) & 1u) | ((static_cast<uint32_t>(d >> 32) & 1u) << 1)) << (2 * i);
+    // pass 0 of the waves that start at a multiple of 128 (agents 128 m and 128 m + 1) adds its
+    // decisions to a running count the host reads with the state (kDeScreenStat): what the engine
+    // switches the screening wave off and on by, see nlsg_de.hip
+    if (i == 0 && (a0 & 127u) == 0) {
+      asm volatile("" ::: "memory");
+      if (d != 0ull && lane == 0)
+        atomicAdd(p.ticket + kDeScreenStat, static_cast<uint32_t>(__builtin_popcountll(d & 0x0000000100000001ull)));
+    }
   };
-  // (two inlined calls, not a loop over the halves: a loop has the compiler set up both passes'
-  // invariants in scalar registers in front of it -- 106 of them, 7 waves per SIMD instead of 8.
-  // Fetching both agents before processing either was measured too: it costs a wave per SIMD as
-  // well, +7 % at pop 2^20, and gains 2 % where the screen never decides. Not kept.)
-  if (!(decided & 1ull)) one_agent(0);
-  if (two && !((decided >> 32) & 1ull)) one_agent(1);
+  // the row loads of two passes are in flight at a time: those of pass i + 2 leave as soon as the
+  // mutant of pass i has freed their registers
+  Pass R[2];
+  fetch(0, R[0]);
+  if (NP > 1) fetch(1, R[1]);
+#pragma unroll
+  for (int i = 0; i < NP; i++) masks(i);
+#pragma unroll
+  for (int i = 0; i < NP; i++) {
+    Pass &C = R[i & 1];
+    const Pass S = C;
+    const double x0 = C.d1[0] + p.F * (C.d2[0] - C.d3[0]);  // the mutant
+    const double x1 = C.d1[1] + p.F * (C.d2[1] - C.d3[1]);
+    if (i + 2 < NP) fetch(i + 2, C);
+    rows(i, S, x0, x1);
+  }
+  // not decided here (missed, declined, backed off, no bound try): the trial goes through the
+  // one-agent path, run by the whole wave, one agent after the other
+  uint32_t undecided = ~decided & ((1u << n_live) - 1u);
+  if (undecided == 0) return;
+  const uint32_t lefts_l = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(lefts), 0));
+  const uint32_t lefts_h = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(lefts), 32));
+  const uint64_t best_id = p.state->best_id;
+  do {
+    const uint32_t q = static_cast<uint32_t>(__builtin_ctz(undecided));
+    undecided &= undecided - 1u;
+    DeAgent<1> A;
+    de_fetch_agent<true, 1, VEC>(p, par, p.gen_key, generation, best_id, a0 + q, A);
+    A.miss = (((q & 1u) ? lefts_h : lefts_l) >> (8 * (q >> 1))) & 0xCu;
+    de_process_agent<OBJ, 1, VEC, true>(p, par, A);
+  } while (undecided != 0);
 }
 
 // One agent per wave. (Two agents per wave — ten gathers in flight — measured -7 % kernel time at
 // pop = 65536 but +9 % at pop = 2^20 and only -2 % per turn; not kept.)
 // BOUND: the instantiation an engine with DeParams.bound set launches (TermsNonNegative objectives
 // only); every other engine runs BOUND = false, the code without the bound. SCREEN: the instantiation
-// an engine with kDeBoundScreen set launches (de_generation_pair); the others are the code without it.
+// an engine with kDeBoundScreen set launches (de_generation_screen); the others are the code without it.
 template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false, bool SCREEN = false>
 __device__ inline void de_generation_block(const DeParams &p, int par, uint64_t generation,
                                            int ignore_done, uint64_t block) {
@@ -737,9 +818,9 @@ __device__ inline void de_generation_block(const DeParams &p, int par, uint64_t 
   // final for every head older than that one.
   const DeState *__restrict__ st = p.state;
   if (!ignore_done && st->done) return;  // a stop test fired: the turn is a no-op
-  if constexpr (SCREEN) {  // kDeBoundScreen: the launch's grid has a block per 8 agents
+  if constexpr (SCREEN) {  // kDeBoundScreen: the launch's grid has a block per 4 * kDeScreenAgents agents
     static_assert(BOUND && CHUNKS == 1, "the screen rides on the bound, rows of 65..128 coordinates");
-    de_generation_pair<OBJ, VEC>(p, par, generation, block);
+    de_generation_screen<OBJ, VEC>(p, par, generation, block);
     return;
   }
   const uint64_t a0 = block * 4 + __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
@@ -752,7 +833,7 @@ __device__ inline void de_generation_block(const DeParams &p, int par, uint64_t 
 }
 
 template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false, bool SCREEN = false>
-__global__ __launch_bounds__(256) void de_generation_kernel(DeParams p, int par, uint64_t generation,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCREEN ? 8 : 1, 8))) void de_generation_kernel(DeParams p, int par, uint64_t generation,
                                                           int ignore_done) {
   de_generation_block<OBJ, CHUNKS, VEC, BOUND, SCREEN>(p, par, generation, ignore_done, blockIdx.x);
 }
@@ -917,7 +998,7 @@ __global__ __launch_bounds__(256) void de_scan_head_kernel(DeParams p, uint64_t 
 // stop test, generation k+1 went to the other buffers and is never adopted (exactly the
 // speculative turn of the sharded path), so results equal the serial order head -> generation.
 template <int OBJ, int CHUNKS, bool VEC, bool BOUND = false, bool SCREEN = false>
-__global__ __launch_bounds__(256) void de_turn_kernel(DeParams p, int par, uint64_t generation) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SCREEN ? 8 : 1, 8))) void de_turn_kernel(DeParams p, int par, uint64_t generation) {
   if (blockIdx.x < p.ntiles) {
     de_scan_head_block(p, generation - 1, blockIdx.x, nullptr);
     return;

@@ -116,8 +116,8 @@ inline void de_screen_env(const char *screen, const char *retry, bool *on, uint3
 #endif
 
 // The miss count in bits 2-3 of a selector byte (kDeBoundScreen), as a pure function: does an
-// agent with this byte try the screen in `generation`, and what the count becomes. The pair wave
-// (de_generation_pair) calls these two, and nlsg_de_screen_rule hands them to the host's tests.
+// agent with this byte try the screen in `generation`, and what the count becomes. The screening wave
+// (de_generation_screen) calls these two, and nlsg_de_screen_rule hands them to the host's tests.
 // Written without short-circuits: in the kernel the operands are per-lane values, and a branch on
 // one costs more than the mask arithmetic.
 //   outcome: 0 the screen decided, 1 it was tried and missed, 2 it was not tried or declined

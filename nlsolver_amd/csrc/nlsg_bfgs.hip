@@ -28,87 +28,45 @@ struct nlsg_bfgs : EngineBase {  // (n_params: nlsg_bfgs_create_params, a row pe
 
 namespace {
 
-#define BFGS_DISPATCH(KERNEL, grid, ...)                                                         \
-  do {                                                                                           \
-    const dim3 g_(grid), b_(256);                                                                \
-    switch (e->chunks * 2 + (e->vec ? 1 : 0)) {                                                  \
-      case 2: hipLaunchKernelGGL((KERNEL<1, false>), g_, b_, 0, e->stream, __VA_ARGS__); break;  \
-      case 3: hipLaunchKernelGGL((KERNEL<1, true>), g_, b_, 0, e->stream, __VA_ARGS__); break;   \
-      case 4: hipLaunchKernelGGL((KERNEL<2, false>), g_, b_, 0, e->stream, __VA_ARGS__); break;  \
-      case 5: hipLaunchKernelGGL((KERNEL<2, true>), g_, b_, 0, e->stream, __VA_ARGS__); break;   \
-      case 8: hipLaunchKernelGGL((KERNEL<4, false>), g_, b_, 0, e->stream, __VA_ARGS__); break;  \
-      case 9: hipLaunchKernelGGL((KERNEL<4, true>), g_, b_, 0, e->stream, __VA_ARGS__); break;   \
-      case 16: hipLaunchKernelGGL((KERNEL<8, false>), g_, b_, 0, e->stream, __VA_ARGS__); break; \
-      case 17: hipLaunchKernelGGL((KERNEL<8, true>), g_, b_, 0, e->stream, __VA_ARGS__); break;  \
-      default: break;                                                                            \
-    }                                                                                            \
-  } while (0)
+// the row width class and the row alignment of an engine's kernels: f(C, V)
+template <typename F>
+bool with_row_shape(const nlsg_bfgs *e, F &&f) {
+  return with_chunks(e->chunks, [&](auto C) {
+    return with_bool(e->vec, [&](auto V) { return dispatch_call(f, C, V); });
+  });
+}
 
-// search / init kernels also depend on what is minimised
-#define BFGS_MODEL_CASE(KERNEL, C, V, grid, ...)                                                    \
-  const unsigned fd_lds_ = e->p.seq ? static_cast<unsigned>(bfgs_fd_seq_lds_bytes(C)) : 0u;          \
-  switch (e->p.model) {                                                                             \
-    case kBfgsQuad:                                                                                 \
-      hipLaunchKernelGGL((KERNEL<C, V, kBfgsQuad>), dim3(grid), dim3(256), fd_lds_, e->stream, __VA_ARGS__); \
-      break;                                                                                        \
-    case NLSG_OBJ_ROSENBROCK:                                                                       \
-        hipLaunchKernelGGL((KERNEL<C, V, NLSG_OBJ_ROSENBROCK>), dim3(grid), dim3(256), fd_lds_,  e->stream, \
-                           __VA_ARGS__);                                                            \
-      break;                                                                                        \
-    case NLSG_OBJ_SPHERE:                                                                           \
-        hipLaunchKernelGGL((KERNEL<C, V, NLSG_OBJ_SPHERE>), dim3(grid), dim3(256), fd_lds_,  e->stream,    \
-                           __VA_ARGS__);                                                            \
-      break;                                                                                        \
-    case NLSG_OBJ_STYBLINSKI_TANG:                                                                  \
-        hipLaunchKernelGGL((KERNEL<C, V, NLSG_OBJ_STYBLINSKI_TANG>), dim3(grid), dim3(256), fd_lds_,       \
-                           e->stream, __VA_ARGS__);                                                 \
-      break;                                                                                        \
-    case NLSG_OBJ_RASTRIGIN:                                                                        \
-        hipLaunchKernelGGL((KERNEL<C, V, NLSG_OBJ_RASTRIGIN>), dim3(grid), dim3(256), fd_lds_,  e->stream, \
-                           __VA_ARGS__);                                                            \
-      break;                                                                                        \
-    default: break;                                                                                 \
-  }
-#define BFGS_DISPATCH_MODEL(KERNEL, grid, ...)                           \
-  do {                                                                   \
-    switch (e->chunks * 2 + (e->vec ? 1 : 0)) {                          \
-      case 2: { BFGS_MODEL_CASE(KERNEL, 1, false, grid, __VA_ARGS__) } break; \
-      case 3: { BFGS_MODEL_CASE(KERNEL, 1, true, grid, __VA_ARGS__) } break;  \
-      case 4: { BFGS_MODEL_CASE(KERNEL, 2, false, grid, __VA_ARGS__) } break; \
-      case 5: { BFGS_MODEL_CASE(KERNEL, 2, true, grid, __VA_ARGS__) } break;  \
-      case 8: { BFGS_MODEL_CASE(KERNEL, 4, false, grid, __VA_ARGS__) } break; \
-      case 9: { BFGS_MODEL_CASE(KERNEL, 4, true, grid, __VA_ARGS__) } break;  \
-      case 16: { BFGS_MODEL_CASE(KERNEL, 8, false, grid, __VA_ARGS__) } break; \
-      case 17: { BFGS_MODEL_CASE(KERNEL, 8, true, grid, __VA_ARGS__) } break;  \
-      default: break;                                                    \
-    }                                                                    \
-  } while (0)
+// what is minimised, for the kernels that evaluate it: the quadratic or a built-in objective
+template <typename F>
+bool with_model(int model, F &&f) {
+  return with_value<kBfgsQuad, NLSG_OBJ_ROSENBROCK, NLSG_OBJ_SPHERE, NLSG_OBJ_STYBLINSKI_TANG, NLSG_OBJ_RASTRIGIN>(
+      model, std::forward<F>(f));
+}
 
-// the resident kernel: CHUNKS = 1 only, a 64-lane workgroup per problem
-#define BFGS_RESIDENT_CASE(V, M)                                                                                \
-  hipLaunchKernelGGL((bfgs_resident_kernel<1, V, M>), dim3(static_cast<unsigned>(e->p.batch)), dim3(64), lds_, \
-                     e->stream, e->p, iters, e->res.h_at, e->res.vec_at)
-#define BFGS_RESIDENT_MODELS(V)                                                       \
-  switch (e->p.model) {                                                               \
-    case kBfgsQuad: BFGS_RESIDENT_CASE(V, kBfgsQuad); break;                          \
-    case NLSG_OBJ_ROSENBROCK: BFGS_RESIDENT_CASE(V, NLSG_OBJ_ROSENBROCK); break;      \
-    case NLSG_OBJ_SPHERE: BFGS_RESIDENT_CASE(V, NLSG_OBJ_SPHERE); break;              \
-    case NLSG_OBJ_STYBLINSKI_TANG: BFGS_RESIDENT_CASE(V, NLSG_OBJ_STYBLINSKI_TANG); break; \
-    case NLSG_OBJ_RASTRIGIN: BFGS_RESIDENT_CASE(V, NLSG_OBJ_RASTRIGIN); break;        \
-    default: break;                                                                   \
-  }
+// search / init kernels depend on the row shape and on what is minimised: launch(C, V, M, lds)
+template <typename Launch>
+bool with_model_kernel(const nlsg_bfgs *e, Launch &&launch) {
+  return with_row_shape(e, [&](auto C, auto V) {
+    const unsigned fd_lds = e->p.seq ? static_cast<unsigned>(bfgs_fd_seq_lds_bytes(C)) : 0u;
+    return with_model(e->p.model, [&](auto M) { launch(C, V, M, fd_lds); });
+  });
+}
 
 // one resident launch: every unfinished problem makes up to `iters` turns
+// (the resident kernel: CHUNKS = 1 only, a 64-lane workgroup per problem)
 void launch_resident(nlsg_bfgs *e, uint32_t iters) {
   const unsigned lds_ = e->res.total * static_cast<unsigned>(sizeof(double));
   if (e->p.model == NLSG_OBJ_CUSTOM) {
     void *args[] = {&e->p, &iters, &e->res.h_at, &e->res.vec_at};
     launch_module_kernel(e->rtc.resident, static_cast<unsigned>(e->p.batch), 64, lds_, e->stream, args);
-  } else if (e->vec) {
-    BFGS_RESIDENT_MODELS(true)
-  } else {
-    BFGS_RESIDENT_MODELS(false)
+    return;
   }
+  routed(with_bool(e->vec, [&](auto V) {
+    return with_model(e->p.model, [&](auto M) {
+      hipLaunchKernelGGL((bfgs_resident_kernel<1, V, M>), dim3(static_cast<unsigned>(e->p.batch)), dim3(64), lds_,
+                         e->stream, e->p, iters, e->res.h_at, e->res.vec_at);
+    });
+  }));
 }
 
 void launch_iteration(nlsg_bfgs *e, bool timed) {
@@ -118,7 +76,9 @@ void launch_iteration(nlsg_bfgs *e, bool timed) {
     void *args[] = {&e->p};
     launch_module_kernel(e->rtc.search, wave_grid, 256, e->fd_lds, e->stream, args);
   } else {
-    BFGS_DISPATCH_MODEL(bfgs_search_kernel, wave_grid, e->p);
+    routed(with_model_kernel(e, [&](auto C, auto V, auto M, unsigned fd_lds) {
+      hipLaunchKernelGGL((bfgs_search_kernel<C, V, M>), dim3(wave_grid), dim3(256), fd_lds, e->stream, e->p);
+    }));
   }
   if (timed) hipEventRecord(e->ev2, e->stream);
   if (e->symmetric) {
@@ -143,8 +103,10 @@ void launch_iteration(nlsg_bfgs *e, bool timed) {
       hipLaunchKernelGGL(bfgs_update_seq_kernel<false>, grid, dim3(256), lds3, e->stream, e->p, bpp);
     }
   } else {
-    BFGS_DISPATCH(bfgs_hy_kernel, row_grid, e->p, e->bpp);
-    BFGS_DISPATCH(bfgs_update_kernel, row_grid, e->p, e->bpp);
+    routed(with_row_shape(e, [&](auto C, auto V) {
+      hipLaunchKernelGGL((bfgs_hy_kernel<C, V>), dim3(row_grid), dim3(256), 0, e->stream, e->p, e->bpp);
+      hipLaunchKernelGGL((bfgs_update_kernel<C, V>), dim3(row_grid), dim3(256), 0, e->stream, e->p, e->bpp);
+    }));
   }
   if (timed) hipEventRecord(e->ev3, e->stream);
 }
@@ -406,7 +368,10 @@ int nlsg_bfgs_init(nlsg_bfgs *e, const double *x0_host) {
     launch_module_kernel(e->rtc.init, static_cast<unsigned>((e->p.batch + 3) / 4), 256, e->fd_lds, e->stream,
                          args);
   } else {
-    BFGS_DISPATCH_MODEL(bfgs_init_kernel, static_cast<unsigned>((e->p.batch + 3) / 4), e->p);
+    routed(with_model_kernel(e, [&](auto C, auto V, auto M, unsigned fd_lds) {
+      hipLaunchKernelGGL((bfgs_init_kernel<C, V, M>), dim3(static_cast<unsigned>((e->p.batch + 3) / 4)), dim3(256),
+                         fd_lds, e->stream, e->p);
+    }));
   }
   NLSG_HIP(launches_status());
   e->initialised = true;

@@ -50,42 +50,10 @@ struct nlsg_de : EngineBase {
 
 namespace {
 
-template <typename K>
-struct Dispatch;  // OBJ x CHUNKS dispatch of a kernel family
-
-#define NLSG_FOR_CHUNKS(OBJ, chunks, CALL) \
-  switch (chunks) {                        \
-    case 1: CALL(OBJ, 1); break;           \
-    case 2: CALL(OBJ, 2); break;           \
-    case 4: CALL(OBJ, 4); break;           \
-    case 8: CALL(OBJ, 8); break;           \
-    default: break;                        \
-  }
-#define NLSG_FOR_OBJ(obj, chunks, CALL)                                              \
-  switch (obj) {                                                                     \
-    case NLSG_OBJ_ROSENBROCK: NLSG_FOR_CHUNKS(NLSG_OBJ_ROSENBROCK, chunks, CALL); break; \
-    case NLSG_OBJ_SPHERE: NLSG_FOR_CHUNKS(NLSG_OBJ_SPHERE, chunks, CALL); break;     \
-    case NLSG_OBJ_STYBLINSKI_TANG:                                                   \
-      NLSG_FOR_CHUNKS(NLSG_OBJ_STYBLINSKI_TANG, chunks, CALL);                       \
-      break;                                                                         \
-    case NLSG_OBJ_RASTRIGIN: NLSG_FOR_CHUNKS(NLSG_OBJ_RASTRIGIN, chunks, CALL); break; \
-    default: break;                                                                  \
-  }
-
 // kernels of a run-time compiled objective take the same arguments through the module API
 void launch_module(nlsg_de *e, hipFunction_t fn, unsigned grid, void **args) {
   launch_module_kernel(fn, grid, 256, 0, e->stream, args);
 }
-
-// D > 1024: the segment-streaming kernels, per objective and row alignment only
-#define NLSG_FOR_OBJ_LONG(obj, CALL)                                  \
-  switch (obj) {                                                      \
-    case NLSG_OBJ_ROSENBROCK: CALL(NLSG_OBJ_ROSENBROCK); break;       \
-    case NLSG_OBJ_SPHERE: CALL(NLSG_OBJ_SPHERE); break;               \
-    case NLSG_OBJ_STYBLINSKI_TANG: CALL(NLSG_OBJ_STYBLINSKI_TANG); break; \
-    case NLSG_OBJ_RASTRIGIN: CALL(NLSG_OBJ_RASTRIGIN); break;         \
-    default: break;                                                   \
-  }
 
 void launch_init(nlsg_de *e) {
   const dim3 grid(static_cast<unsigned>((e->p.shard_n + 3) / 4)), block(256);
@@ -94,48 +62,37 @@ void launch_init(nlsg_de *e) {
     launch_module(e, e->rtc.init, grid.x, args);
     return;
   }
-  if (e->long_rows) {
-#define CALL(OBJ)                                                                              \
-  if (e->p.vec)                                                                                \
-    hipLaunchKernelGGL((de_init_long_kernel<OBJ, true>), grid, block, 0, e->stream, e->p, e->x0_dev); \
-  else                                                                                         \
-    hipLaunchKernelGGL((de_init_long_kernel<OBJ, false>), grid, block, 0, e->stream, e->p, e->x0_dev)
-    NLSG_FOR_OBJ_LONG(e->cfg.objective, CALL)
-#undef CALL
-    return;
-  }
-#define CALL(OBJ, C)                                                                          \
-  if (e->p.vec)                                                                               \
-    hipLaunchKernelGGL((de_init_kernel<OBJ, C, true>), grid, block, 0, e->stream, e->p,       \
-                       e->x0_dev);                                                            \
-  else                                                                                        \
-    hipLaunchKernelGGL((de_init_kernel<OBJ, C, false>), grid, block, 0, e->stream, e->p,      \
-                       e->x0_dev)
-  NLSG_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
-#undef CALL
+  routed(with_objective(e->cfg.objective, [&](auto O) {
+    return with_bool(e->p.vec, [&](auto V) {
+      if (e->long_rows) {  // D > 1024: the segment-streaming kernels, per objective and row alignment only
+        hipLaunchKernelGGL((de_init_long_kernel<O, V>), grid, block, 0, e->stream, e->p, e->x0_dev);
+        return true;
+      }
+      return with_chunks(e->chunks, [&](auto C) {
+        hipLaunchKernelGGL((de_init_kernel<O, C, V>), grid, block, 0, e->stream, e->p, e->x0_dev);
+      });
+    });
+  }));
 }
 
-template <int OBJ>
-void launch_generation_groups(nlsg_de *e, dim3 grid, int par, uint64_t generation, int ignore_done) {
-  const dim3 block(256);
-  switch (e->group) {
-    case 4:
-      hipLaunchKernelGGL((de_generation_groups_kernel<OBJ, 4>), grid, block, 0, e->stream, e->p, par,
-                         generation, ignore_done);
-      break;
-    case 8:
-      hipLaunchKernelGGL((de_generation_groups_kernel<OBJ, 8>), grid, block, 0, e->stream, e->p, par,
-                         generation, ignore_done);
-      break;
-    case 16:
-      hipLaunchKernelGGL((de_generation_groups_kernel<OBJ, 16>), grid, block, 0, e->stream, e->p, par,
-                         generation, ignore_done);
-      break;
-    default:
-      hipLaunchKernelGGL((de_generation_groups_kernel<OBJ, 32>), grid, block, 0, e->stream, e->p, par,
-                         generation, ignore_done);
-      break;
-  }
+// The instantiation <OBJ, C, V, B, S> of a one-agent-per-wave generation family (de_generation_kernel,
+// de_turn_kernel) that this engine launches; launch(O, C, V, B, S) enqueues it. An engine that uses
+// the bound launches the instantiation that has it (DeParams.bound, objectives with terms >= 0
+// only), and one that screens, the instantiation with the screening wave (kDeBoundScreen, one
+// chunk only).
+template <typename Launch>
+bool with_wave_kernel(const nlsg_de *e, Launch &&launch) {
+  return with_objective(e->cfg.objective, [&](auto O) {
+    return with_chunks(e->chunks, [&](auto C) {
+      return with_bool(e->p.vec, [&](auto V) {
+        using B = std::bool_constant<TermsNonNegative<O>::value>;
+        using S = std::bool_constant<B::value && C == 1>;
+        if (e->p.bound & kDeBoundScreen) launch(O, C, V, B{}, S{});
+        else if (e->p.bound) launch(O, C, V, B{}, std::false_type{});
+        else launch(O, C, V, std::false_type{}, std::false_type{});
+      });
+    });
+  });
 }
 
 // waves of a generation: one per agent, one per 64 / group agents (D <= 64), or one per
@@ -155,70 +112,27 @@ void launch_generation(nlsg_de *e, int par, uint64_t generation, int ignore_done
     return;
   }
   if (e->long_rows) {
-#define CALL(OBJ)                                                                               \
-  if (e->p.vec)                                                                                 \
-    hipLaunchKernelGGL((de_generation_long_kernel<OBJ, true>), grid, block, 0, e->stream, e->p, \
-                       par, generation, ignore_done);                                           \
-  else                                                                                          \
-    hipLaunchKernelGGL((de_generation_long_kernel<OBJ, false>), grid, block, 0, e->stream, e->p, \
-                       par, generation, ignore_done)
-    NLSG_FOR_OBJ_LONG(e->cfg.objective, CALL)
-#undef CALL
+    routed(with_objective(e->cfg.objective, [&](auto O) {
+      return with_bool(e->p.vec, [&](auto V) {
+        hipLaunchKernelGGL((de_generation_long_kernel<O, V>), grid, block, 0, e->stream, e->p, par, generation,
+                           ignore_done);
+      });
+    }));
     return;
   }
   if (e->group) {
-    switch (e->cfg.objective) {
-      case NLSG_OBJ_ROSENBROCK:
-        launch_generation_groups<NLSG_OBJ_ROSENBROCK>(e, grid, par, generation, ignore_done);
-        break;
-      case NLSG_OBJ_SPHERE:
-        launch_generation_groups<NLSG_OBJ_SPHERE>(e, grid, par, generation, ignore_done);
-        break;
-      case NLSG_OBJ_STYBLINSKI_TANG:
-        launch_generation_groups<NLSG_OBJ_STYBLINSKI_TANG>(e, grid, par, generation, ignore_done);
-        break;
-      default:
-        launch_generation_groups<NLSG_OBJ_RASTRIGIN>(e, grid, par, generation, ignore_done);
-        break;
-    }
+    routed(with_objective(e->cfg.objective, [&](auto O) {
+      return with_groups(e->group, [&](auto G) {
+        hipLaunchKernelGGL((de_generation_groups_kernel<O, G>), grid, block, 0, e->stream, e->p, par, generation,
+                           ignore_done);
+      });
+    }));
     return;
   }
-  // (an engine that uses the bound launches the instantiation that has it: DeParams.bound)
-  // (and one that screens, the instantiation with the screening wave: kDeBoundScreen, one chunk only)
-#define CALL_B(OBJ, C, V, B, S)                                                                   \
-  hipLaunchKernelGGL((de_generation_kernel<OBJ, C, V, B, S>), grid, block, 0, e->stream, e->p, par, \
-                     generation, ignore_done)
-#define CALL(OBJ, C)                                                          \
-  if (e->p.bound & kDeBoundScreen) {                                          \
-    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value, (TermsNonNegative<OBJ>::value && C == 1));  \
-    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value, (TermsNonNegative<OBJ>::value && C == 1));          \
-  } else if (e->p.bound) {                                                    \
-    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value, false);  \
-    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value, false);          \
-  } else if (e->p.vec) CALL_B(OBJ, C, true, false, false);                    \
-  else CALL_B(OBJ, C, false, false, false)
-  NLSG_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
-#undef CALL
-#undef CALL_B
-}
-
-template <int OBJ>
-void launch_fused_turn_groups(nlsg_de *e, dim3 grid, int par, uint64_t generation) {
-  const dim3 block(256);
-  switch (e->group) {
-    case 4:
-      hipLaunchKernelGGL((de_turn_groups_kernel<OBJ, 4>), grid, block, 0, e->stream, e->p, par, generation);
-      break;
-    case 8:
-      hipLaunchKernelGGL((de_turn_groups_kernel<OBJ, 8>), grid, block, 0, e->stream, e->p, par, generation);
-      break;
-    case 16:
-      hipLaunchKernelGGL((de_turn_groups_kernel<OBJ, 16>), grid, block, 0, e->stream, e->p, par, generation);
-      break;
-    default:
-      hipLaunchKernelGGL((de_turn_groups_kernel<OBJ, 32>), grid, block, 0, e->stream, e->p, par, generation);
-      break;
-  }
+  routed(with_wave_kernel(e, [&](auto O, auto C, auto V, auto B, auto S) {
+    hipLaunchKernelGGL((de_generation_kernel<O, C, V, B, S>), grid, block, 0, e->stream, e->p, par, generation,
+                       ignore_done);
+  }));
 }
 
 // head k and generation k+1 in one launch (de_turn_kernel)
@@ -232,30 +146,16 @@ void launch_fused_turn(nlsg_de *e, int par, uint64_t generation) {
     return;
   }
   if (e->group) {
-    switch (e->cfg.objective) {
-      case NLSG_OBJ_ROSENBROCK: launch_fused_turn_groups<NLSG_OBJ_ROSENBROCK>(e, grid, par, generation); break;
-      case NLSG_OBJ_SPHERE: launch_fused_turn_groups<NLSG_OBJ_SPHERE>(e, grid, par, generation); break;
-      case NLSG_OBJ_STYBLINSKI_TANG:
-        launch_fused_turn_groups<NLSG_OBJ_STYBLINSKI_TANG>(e, grid, par, generation);
-        break;
-      default: launch_fused_turn_groups<NLSG_OBJ_RASTRIGIN>(e, grid, par, generation); break;
-    }
+    routed(with_objective(e->cfg.objective, [&](auto O) {
+      return with_groups(e->group, [&](auto G) {
+        hipLaunchKernelGGL((de_turn_groups_kernel<O, G>), grid, block, 0, e->stream, e->p, par, generation);
+      });
+    }));
     return;
   }
-#define CALL_B(OBJ, C, V, B, S) \
-  hipLaunchKernelGGL((de_turn_kernel<OBJ, C, V, B, S>), grid, block, 0, e->stream, e->p, par, generation)
-#define CALL(OBJ, C)                                                          \
-  if (e->p.bound & kDeBoundScreen) {                                          \
-    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value, (TermsNonNegative<OBJ>::value && C == 1));  \
-    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value, (TermsNonNegative<OBJ>::value && C == 1));          \
-  } else if (e->p.bound) {                                                    \
-    if (e->p.vec) CALL_B(OBJ, C, true, TermsNonNegative<OBJ>::value, false);  \
-    else CALL_B(OBJ, C, false, TermsNonNegative<OBJ>::value, false);          \
-  } else if (e->p.vec) CALL_B(OBJ, C, true, false, false);                    \
-  else CALL_B(OBJ, C, false, false, false)
-  NLSG_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
-#undef CALL
-#undef CALL_B
+  routed(with_wave_kernel(e, [&](auto O, auto C, auto V, auto B, auto S) {
+    hipLaunchKernelGGL((de_turn_kernel<O, C, V, B, S>), grid, block, 0, e->stream, e->p, par, generation);
+  }));
 }
 
 // Head of turn k outside a fused turn, one launch. rec_dev == nullptr: one GPU, the head

@@ -31,35 +31,14 @@ namespace {
 // (nlsg_de_batch_config.turns_per_launch = 0)
 constexpr uint64_t kDeBatchTurnsPerLaunch = 1024;
 
-template <int OBJ>
-const void *turn_kernel(int group) {
-  switch (group) {
-    case 4: return reinterpret_cast<const void *>(de_batch_kernel<OBJ, 4>);
-    case 8: return reinterpret_cast<const void *>(de_batch_kernel<OBJ, 8>);
-    case 16: return reinterpret_cast<const void *>(de_batch_kernel<OBJ, 16>);
-    case 32: return reinterpret_cast<const void *>(de_batch_kernel<OBJ, 32>);
-    default: return reinterpret_cast<const void *>(de_batch_kernel<OBJ, 64>);
-  }
-}
-void pick_kernels(nlsg_de_batch *e) {
-  switch (e->cfg.objective) {
-    case NLSG_OBJ_ROSENBROCK:
-      e->init_fn = reinterpret_cast<const void *>(de_batch_init_kernel<NLSG_OBJ_ROSENBROCK>);
-      e->turn_fn = turn_kernel<NLSG_OBJ_ROSENBROCK>(e->group);
-      break;
-    case NLSG_OBJ_SPHERE:
-      e->init_fn = reinterpret_cast<const void *>(de_batch_init_kernel<NLSG_OBJ_SPHERE>);
-      e->turn_fn = turn_kernel<NLSG_OBJ_SPHERE>(e->group);
-      break;
-    case NLSG_OBJ_STYBLINSKI_TANG:
-      e->init_fn = reinterpret_cast<const void *>(de_batch_init_kernel<NLSG_OBJ_STYBLINSKI_TANG>);
-      e->turn_fn = turn_kernel<NLSG_OBJ_STYBLINSKI_TANG>(e->group);
-      break;
-    default:
-      e->init_fn = reinterpret_cast<const void *>(de_batch_init_kernel<NLSG_OBJ_RASTRIGIN>);
-      e->turn_fn = turn_kernel<NLSG_OBJ_RASTRIGIN>(e->group);
-      break;
-  }
+// the two kernels of a built-in objective; false (and nothing picked) for a value outside the lists
+bool pick_kernels(nlsg_de_batch *e) {
+  return with_objective(e->cfg.objective, [&](auto O) {
+    e->init_fn = reinterpret_cast<const void *>(de_batch_init_kernel<O>);
+    return with_batch_groups(e->group, [&](auto G) {
+      e->turn_fn = reinterpret_cast<const void *>(de_batch_kernel<O, G>);
+    });
+  });
 }
 
 uint32_t init_blocks_per(const nlsg_de_batch *e) { return static_cast<uint32_t>((e->p.pop + 3) / 4); }
@@ -223,9 +202,9 @@ int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective
   // every live engine of that class shares: it is set to the budget, never to one engine's size —
   // a later, smaller engine must not lower it under a kept larger one (as nlsg_nm.hip does).
   if (he == hipSuccess && !custom) {
-    pick_kernels(e);
-    he = hipFuncSetAttribute(e->turn_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             static_cast<int>(kDeBatchLdsBudget));
+    he = pick_kernels(e) ? hipFuncSetAttribute(e->turn_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               static_cast<int>(kDeBatchLdsBudget))
+                         : hipErrorInvalidValue;
   }
   if (he == hipSuccess && custom) {
     const int rc2 = rtc_build_de_batch(custom, e->group, &e->rtc);

@@ -57,17 +57,10 @@ void launch(nlsg_de_ref *e) {
     launch_module_kernel(e->rtc.solve, grid, block, static_cast<unsigned>(e->lds), e->stream, args);
     return;
   }
-  switch (e->cfg.objective) {
-    case NLSG_OBJ_ROSENBROCK:
-      hipLaunchKernelGGL(de_ref_kernel<NLSG_OBJ_ROSENBROCK>, grid, block, e->lds, e->stream, e->p);
-      break;
-    case NLSG_OBJ_SPHERE:
-      hipLaunchKernelGGL(de_ref_kernel<NLSG_OBJ_SPHERE>, grid, block, e->lds, e->stream, e->p);
-      break;
-    default:
-      hipLaunchKernelGGL(de_ref_kernel<NLSG_OBJ_STYBLINSKI_TANG>, grid, block, e->lds, e->stream, e->p);
-      break;
-  }
+  // (Rastrigin is rejected at creation)
+  routed(with_value<NLSG_OBJ_ROSENBROCK, NLSG_OBJ_SPHERE, NLSG_OBJ_STYBLINSKI_TANG>(e->cfg.objective, [&](auto O) {
+    hipLaunchKernelGGL(de_ref_kernel<O>, grid, block, e->lds, e->stream, e->p);
+  }));
 }
 
 // x0 and the states in, then launches of at most p.gens generations until every solve is done:

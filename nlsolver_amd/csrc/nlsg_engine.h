@@ -1,13 +1,15 @@
 // nlsolver_amd/csrc/nlsg_engine.h — the host skeleton every engine file (nlsg_*.hip) shares: who owns
 // the device blocks, streams and events of an engine or of one call, the fields and calls every
 // `struct nlsg_X` has in common, the event-timed repeat loop and the create clock. Host only: no
-// kernel header includes it and the run-time compiler never sees it.
+// kernel header includes it and the run-time compiler never sees it. (Which kernel instantiation a
+// launch site picks from run-time values: nlsg_dispatch.h, and `routed` below.)
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <new>
 #include <vector>
 
 #include "nlsg_common.h"
+#include "nlsg_dispatch.h"
 
 // (host plumbing of the translation units, not part of what libnlsolver_hip.so exports)
 #pragma GCC visibility push(hidden)
@@ -153,6 +155,12 @@ struct EngineBase {
   void drain() { own.drain(); }
   void close() { own.give_back(); }
 };
+
+// What a launch site does with the answer of its with_*(...) selection (nlsg_dispatch.h): a value no
+// list holds launched nothing, and the entry point's launches_status() reports hipErrorInvalidValue.
+inline void routed(bool matched) {
+  if (!matched && module_launch_error() == hipSuccess) module_launch_error() = hipErrorInvalidValue;
+}
 
 // `new` and open() for an engine struct; nothing to clean up when it fails
 template <typename E>

@@ -81,33 +81,14 @@ void launch_fd_iter(nlsg_lm *e, int first) {
     return;
   }
   if (e->cfg.solver == NLSG_LM_CHOLESKY_REFERENCE_ORDER) {  // (Rastrigin is rejected at creation)
-    switch (e->cfg.objective) {
-      case NLSG_OBJ_ROSENBROCK:
-        hipLaunchKernelGGL((lm_fd_iter_kernel<NLSG_OBJ_ROSENBROCK, true>), grid, dim3(64), lds, e->stream, e->p, first);
-        break;
-      case NLSG_OBJ_SPHERE:
-        hipLaunchKernelGGL((lm_fd_iter_kernel<NLSG_OBJ_SPHERE, true>), grid, dim3(64), lds, e->stream, e->p, first);
-        break;
-      default:
-        hipLaunchKernelGGL((lm_fd_iter_kernel<NLSG_OBJ_STYBLINSKI_TANG, true>), grid, dim3(64), lds, e->stream, e->p, first);
-        break;
-    }
+    routed(with_value<NLSG_OBJ_ROSENBROCK, NLSG_OBJ_SPHERE, NLSG_OBJ_STYBLINSKI_TANG>(e->cfg.objective, [&](auto O) {
+      hipLaunchKernelGGL((lm_fd_iter_kernel<O, true>), grid, dim3(64), lds, e->stream, e->p, first);
+    }));
     return;
   }
-  switch (e->cfg.objective) {
-    case NLSG_OBJ_ROSENBROCK:
-      hipLaunchKernelGGL(lm_fd_iter_kernel<NLSG_OBJ_ROSENBROCK>, grid, dim3(64), lds, e->stream, e->p, first);
-      break;
-    case NLSG_OBJ_SPHERE:
-      hipLaunchKernelGGL(lm_fd_iter_kernel<NLSG_OBJ_SPHERE>, grid, dim3(64), lds, e->stream, e->p, first);
-      break;
-    case NLSG_OBJ_RASTRIGIN:
-      hipLaunchKernelGGL(lm_fd_iter_kernel<NLSG_OBJ_RASTRIGIN>, grid, dim3(64), lds, e->stream, e->p, first);
-      break;
-    default:
-      hipLaunchKernelGGL(lm_fd_iter_kernel<NLSG_OBJ_STYBLINSKI_TANG>, grid, dim3(64), lds, e->stream, e->p, first);
-      break;
-  }
+  routed(with_objective(e->cfg.objective, [&](auto O) {
+    hipLaunchKernelGGL(lm_fd_iter_kernel<O>, grid, dim3(64), lds, e->stream, e->p, first);
+  }));
 }
 
 // Gauss-Newton model up to 64 parameters: step k (with_step) + evaluation k + 1, one wave per problem
@@ -121,37 +102,15 @@ void launch_gn_iter(nlsg_lm *e, int first, int with_step) {
   hipLaunchKernelGGL(lm_iter_kernel<>, dim3(grid), dim3(64), 0, e->stream, e->p, first, with_step);
 }
 
-// n > 64: evaluation (f, g, H at the current point) as one launch, a workgroup per problem
-template <int OBJ>
-void launch_wide_fd_ref(nlsg_lm *e, dim3 grid, int first) {  // NLSG_LM_CHOLESKY_REFERENCE_ORDER past 64 parameters
-  hipLaunchKernelGGL((lm_wide_fd_lanes_kernel<OBJ>), grid, dim3(256),
-                     static_cast<unsigned>(lm_wide_fd_lanes_lds_bytes(e->p.n)), e->stream, e->p, first);
-}
-template <int OBJ>
-void launch_wide_fd(nlsg_lm *e, dim3 grid, int first) {
-  if (e->cfg.solver == NLSG_LM_CHOLESKY_REFERENCE_ORDER) {
-    if constexpr (OBJ != NLSG_OBJ_RASTRIGIN) launch_wide_fd_ref<OBJ>(e, grid, first);  // (rejected at creation)
-    return;
-  }
-  switch (lm_wide_chunks(e->p.n)) {
-    case 1: hipLaunchKernelGGL((lm_wide_fd_eval_kernel<OBJ, 1>), grid, dim3(lm_wide_fd_threads(1)), 0, e->stream, e->p, first); break;
-    case 2: hipLaunchKernelGGL((lm_wide_fd_eval_kernel<OBJ, 2>), grid, dim3(lm_wide_fd_threads(2)), 0, e->stream, e->p, first); break;
-    case 4: hipLaunchKernelGGL((lm_wide_fd_eval_kernel<OBJ, 4>), grid, dim3(lm_wide_fd_threads(4)), 0, e->stream, e->p, first); break;
-    default: hipLaunchKernelGGL((lm_wide_fd_eval_kernel<OBJ, 8>), grid, dim3(lm_wide_fd_threads(8)), 0, e->stream, e->p, first); break;
-  }
-}
-template <bool EVEN>
-void launch_wide_chol_step_t(nlsg_lm *e, dim3 grid) {
-  switch (lm_wchol_threads(e->p.n)) {
-    case 256: hipLaunchKernelGGL((lm_wide_chol_step_kernel<256, EVEN>), grid, dim3(256), lm_wchol_lds_bytes(256), e->stream, e->p); break;
-    case 512: hipLaunchKernelGGL((lm_wide_chol_step_kernel<512, EVEN>), grid, dim3(512), lm_wchol_lds_bytes(512), e->stream, e->p); break;
-    default: hipLaunchKernelGGL((lm_wide_chol_step_kernel<1024, EVEN>), grid, dim3(1024), lm_wchol_lds_bytes(1024), e->stream, e->p); break;
-  }
-}
+// the blocked Cholesky step, by the threads of its workgroup and the parity of n
 void launch_wide_chol_step(nlsg_lm *e, dim3 grid) {
-  if (e->p.n & 1) launch_wide_chol_step_t<false>(e, grid);
-  else launch_wide_chol_step_t<true>(e, grid);
+  routed(with_value<256, 512, 1024>(lm_wchol_threads(e->p.n), [&](auto T) {
+    return with_bool(!(e->p.n & 1), [&](auto EVEN) {
+      hipLaunchKernelGGL((lm_wide_chol_step_kernel<T, EVEN>), grid, dim3(T), lm_wchol_lds_bytes(T), e->stream, e->p);
+    });
+  }));
 }
+// n > 64: evaluation (f, g, H at the current point) as one launch, a workgroup per problem
 void launch_wide_eval(nlsg_lm *e, int first) {
   // finite-difference model: enough workgroups per problem to fill the device when the batch is small
   const unsigned split = e->p.fd ? static_cast<unsigned>(std::min<uint64_t>(
@@ -187,12 +146,18 @@ void launch_wide_eval(nlsg_lm *e, int first) {
                            args, grid.y);
     return;
   }
-  switch (e->cfg.objective) {
-    case NLSG_OBJ_ROSENBROCK: launch_wide_fd<NLSG_OBJ_ROSENBROCK>(e, grid, first); break;
-    case NLSG_OBJ_SPHERE: launch_wide_fd<NLSG_OBJ_SPHERE>(e, grid, first); break;
-    case NLSG_OBJ_RASTRIGIN: launch_wide_fd<NLSG_OBJ_RASTRIGIN>(e, grid, first); break;
-    default: launch_wide_fd<NLSG_OBJ_STYBLINSKI_TANG>(e, grid, first); break;
+  if (e->cfg.solver == NLSG_LM_CHOLESKY_REFERENCE_ORDER) {  // past 64 parameters (Rastrigin is rejected at creation)
+    routed(with_value<NLSG_OBJ_ROSENBROCK, NLSG_OBJ_SPHERE, NLSG_OBJ_STYBLINSKI_TANG>(e->cfg.objective, [&](auto O) {
+      hipLaunchKernelGGL((lm_wide_fd_lanes_kernel<O>), grid, dim3(256),
+                         static_cast<unsigned>(lm_wide_fd_lanes_lds_bytes(e->p.n)), e->stream, e->p, first);
+    }));
+    return;
   }
+  routed(with_objective(e->cfg.objective, [&](auto O) {
+    return with_chunks(lm_wide_chunks(e->p.n), [&](auto C) {
+      hipLaunchKernelGGL((lm_wide_fd_eval_kernel<O, C>), grid, dim3(lm_wide_fd_threads(C)), 0, e->stream, e->p, first);
+    });
+  }));
 }
 
 int launch_solve(nlsg_lm *e) {

@@ -22,20 +22,15 @@ namespace {
 // The opt-in for more than 64 KiB of dynamic LDS belongs to the kernel instantiation <OBJ, CHUNKS>,
 // which every engine of that chunk class shares: it is set to the class maximum (the largest n the
 // instantiation serves), never to one engine's size — a later, smaller engine must not lower it.
-template <int OBJ, int CHUNKS>
-hipError_t prepare1() {
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(nm_solve_kernel<OBJ, CHUNKS>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                             160 * 1024);  // (reference order adds term buffers behind the image)
-}
 template <int OBJ>
 hipError_t prepare(int chunks) {
-  switch (chunks) {
-    case 1: return prepare1<OBJ, 1>();
-    case 2: return prepare1<OBJ, 2>();
-    case 4: return prepare1<OBJ, 4>();
-    default: return prepare1<OBJ, 8>();
-  }
+  hipError_t he = hipErrorInvalidValue;  // (what a chunk count outside the list leaves)
+  with_chunks(chunks, [&](auto C) {
+    he = hipFuncSetAttribute(reinterpret_cast<const void *>(nm_solve_kernel<OBJ, C>),
+                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                             160 * 1024);  // (reference order adds term buffers behind the image)
+  });
+  return he;
 }
 template <int OBJ>
 hipError_t prepare_driver() {
@@ -48,26 +43,6 @@ hipError_t prepare_driver() {
                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   return he;
 }
-template <int OBJ>
-void launch_obj(nlsg_nm *e, dim3 grid, dim3 block) {
-  if (e->driver) {
-    if constexpr (OBJ != NLSG_OBJ_RASTRIGIN) {
-      if (e->p.seq) {
-        hipLaunchKernelGGL((nm_solve_driver_kernel<OBJ, true>), grid, block, e->lds, e->stream, e->p);
-        return;
-      }
-    }
-    hipLaunchKernelGGL(nm_solve_driver_kernel<OBJ>, grid, block, e->lds, e->stream, e->p);
-    return;
-  }
-  switch (nm_chunks(e->p.n)) {
-    case 1: hipLaunchKernelGGL((nm_solve_kernel<OBJ, 1>), grid, block, e->lds, e->stream, e->p); break;
-    case 2: hipLaunchKernelGGL((nm_solve_kernel<OBJ, 2>), grid, block, e->lds, e->stream, e->p); break;
-    case 4: hipLaunchKernelGGL((nm_solve_kernel<OBJ, 4>), grid, block, e->lds, e->stream, e->p); break;
-    default: hipLaunchKernelGGL((nm_solve_kernel<OBJ, 8>), grid, block, e->lds, e->stream, e->p); break;
-  }
-}
-
 void launch(nlsg_nm *e) {
   const dim3 grid(static_cast<unsigned>(e->p.batch)), block(nm_block_threads(e->p.n));
   if (e->cfg.objective == NLSG_OBJ_CUSTOM) {
@@ -75,12 +50,21 @@ void launch(nlsg_nm *e) {
     launch_module_kernel(e->rtc.solve, grid.x, block.x, static_cast<unsigned>(e->lds), e->stream, args);
     return;
   }
-  switch (e->cfg.objective) {
-    case NLSG_OBJ_ROSENBROCK: launch_obj<NLSG_OBJ_ROSENBROCK>(e, grid, block); break;
-    case NLSG_OBJ_SPHERE: launch_obj<NLSG_OBJ_SPHERE>(e, grid, block); break;
-    case NLSG_OBJ_STYBLINSKI_TANG: launch_obj<NLSG_OBJ_STYBLINSKI_TANG>(e, grid, block); break;
-    default: launch_obj<NLSG_OBJ_RASTRIGIN>(e, grid, block); break;
-  }
+  routed(with_objective(e->cfg.objective, [&](auto O) {
+    if (e->driver) {
+      if constexpr (O != NLSG_OBJ_RASTRIGIN) {
+        if (e->p.seq) {
+          hipLaunchKernelGGL((nm_solve_driver_kernel<O, true>), grid, block, e->lds, e->stream, e->p);
+          return true;
+        }
+      }
+      hipLaunchKernelGGL(nm_solve_driver_kernel<O>, grid, block, e->lds, e->stream, e->p);
+      return true;
+    }
+    return with_chunks(nm_chunks(e->p.n), [&](auto C) {
+      hipLaunchKernelGGL((nm_solve_kernel<O, C>), grid, block, e->lds, e->stream, e->p);
+    });
+  }));
 }
 
 // a parametrised engine solves nothing before its first rows

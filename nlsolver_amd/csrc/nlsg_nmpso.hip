@@ -18,25 +18,12 @@ namespace {
 
 int wide_chunks(uint64_t n) { return n <= kHybMaxN ? 0 : n <= 256 ? 2 : n <= 512 ? 4 : 8; }
 
-template <int OBJ>
-void launch_wide(nlsg_nmpso *e, dim3 grid) {
-  const dim3 block(hyb_wide_threads(wide_chunks(e->p.n)));
-  const unsigned lds = static_cast<unsigned>(hyb_view_bytes(e->p.n));
-  switch (wide_chunks(e->p.n)) {
-    case 2: hipLaunchKernelGGL((nmpso_solve_wide_kernel<OBJ, 2>), grid, block, lds, e->stream, e->p); break;
-    case 4: hipLaunchKernelGGL((nmpso_solve_wide_kernel<OBJ, 4>), grid, block, lds, e->stream, e->p); break;
-    default: hipLaunchKernelGGL((nmpso_solve_wide_kernel<OBJ, 8>), grid, block, lds, e->stream, e->p); break;
-  }
-}
-template <int OBJ>
-hipError_t allow_wide_lds(uint64_t n) {  // past 64 KiB the dynamic allocation has to be announced
-  // the attribute belongs to the instantiation, shared by every engine of the chunk class: the class
-  // maximum, so that an engine created later with a smaller n cannot lower an earlier one's limit
-  const int bytes = static_cast<int>(hyb_view_bytes(128ull * wide_chunks(n)));
-  const void *fn = wide_chunks(n) == 2   ? reinterpret_cast<const void *>(nmpso_solve_wide_kernel<OBJ, 2>)
-                   : wide_chunks(n) == 4 ? reinterpret_cast<const void *>(nmpso_solve_wide_kernel<OBJ, 4>)
-                                         : reinterpret_cast<const void *>(nmpso_solve_wide_kernel<OBJ, 8>);
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+// the wide kernel <OBJ, C> of a built-in objective at n > kHybMaxN: f(O, C)
+template <typename F>
+bool with_wide_kernel(int objective, uint64_t n, F &&f) {
+  return with_objective(objective, [&](auto O) {
+    return with_value<2, 4, 8>(wide_chunks(n), [&](auto C) { return dispatch_call(f, O, C); });
+  });
 }
 
 void launch(nlsg_nmpso *e) {
@@ -50,28 +37,15 @@ void launch(nlsg_nmpso *e) {
     return;
   }
   if (wide) {
-    switch (e->cfg.objective) {
-      case NLSG_OBJ_ROSENBROCK: launch_wide<NLSG_OBJ_ROSENBROCK>(e, grid); break;
-      case NLSG_OBJ_SPHERE: launch_wide<NLSG_OBJ_SPHERE>(e, grid); break;
-      case NLSG_OBJ_STYBLINSKI_TANG: launch_wide<NLSG_OBJ_STYBLINSKI_TANG>(e, grid); break;
-      default: launch_wide<NLSG_OBJ_RASTRIGIN>(e, grid); break;
-    }
+    const unsigned lds = static_cast<unsigned>(hyb_view_bytes(e->p.n));
+    routed(with_wide_kernel(e->cfg.objective, e->p.n, [&](auto O, auto C) {
+      hipLaunchKernelGGL((nmpso_solve_wide_kernel<O, C>), grid, block, lds, e->stream, e->p);
+    }));
     return;
   }
-  switch (e->cfg.objective) {
-    case NLSG_OBJ_ROSENBROCK:
-      hipLaunchKernelGGL(nmpso_solve_kernel<NLSG_OBJ_ROSENBROCK>, grid, block, 0, e->stream, e->p);
-      break;
-    case NLSG_OBJ_SPHERE:
-      hipLaunchKernelGGL(nmpso_solve_kernel<NLSG_OBJ_SPHERE>, grid, block, 0, e->stream, e->p);
-      break;
-    case NLSG_OBJ_STYBLINSKI_TANG:
-      hipLaunchKernelGGL(nmpso_solve_kernel<NLSG_OBJ_STYBLINSKI_TANG>, grid, block, 0, e->stream, e->p);
-      break;
-    default:
-      hipLaunchKernelGGL(nmpso_solve_kernel<NLSG_OBJ_RASTRIGIN>, grid, block, 0, e->stream, e->p);
-      break;
-  }
+  routed(with_objective(e->cfg.objective, [&](auto O) {
+    hipLaunchKernelGGL(nmpso_solve_kernel<O>, grid, block, 0, e->stream, e->p);
+  }));
 }
 
 // a parametrised engine solves nothing before its first rows
@@ -170,13 +144,15 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
   own.zeroed(&e->zero_dev, 16);
   e->alloc_params(B, e->n_params);
   e->timing_events();
-  if (he == hipSuccess && n > kHybMaxN && !custom) {
-    switch (cfg->objective) {
-      case NLSG_OBJ_ROSENBROCK: he = allow_wide_lds<NLSG_OBJ_ROSENBROCK>(n); break;
-      case NLSG_OBJ_SPHERE: he = allow_wide_lds<NLSG_OBJ_SPHERE>(n); break;
-      case NLSG_OBJ_STYBLINSKI_TANG: he = allow_wide_lds<NLSG_OBJ_STYBLINSKI_TANG>(n); break;
-      default: he = allow_wide_lds<NLSG_OBJ_RASTRIGIN>(n); break;
-    }
+  if (he == hipSuccess && n > kHybMaxN && !custom) {  // past 64 KiB the dynamic allocation has to be announced
+    // the attribute belongs to the instantiation, shared by every engine of the chunk class: the class
+    // maximum, so that an engine created later with a smaller n cannot lower an earlier one's limit
+    he = hipErrorInvalidValue;  // (what a value outside the lists leaves)
+    with_wide_kernel(cfg->objective, n, [&](auto O, auto C) {
+      he = hipFuncSetAttribute(reinterpret_cast<const void *>(nmpso_solve_wide_kernel<O, C>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               static_cast<int>(hyb_view_bytes(128ull * C)));
+    });
   }
   if (const int rc = e->setup_status()) {
     nlsg_nmpso_destroy(e);

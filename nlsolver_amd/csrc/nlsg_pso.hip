@@ -28,34 +28,11 @@ struct nlsg_pso : EngineBase {
 
 namespace {
 
-#define PSO_FOR_CHUNKS(OBJ, chunks, CALL) \
-  switch (chunks) {                       \
-    case 1: CALL(OBJ, 1); break;          \
-    case 2: CALL(OBJ, 2); break;          \
-    case 4: CALL(OBJ, 4); break;          \
-    case 8: CALL(OBJ, 8); break;          \
-    default: break;                       \
-  }
-#define PSO_FOR_OBJ(obj, chunks, CALL)                                                  \
-  switch (obj) {                                                                        \
-    case NLSG_OBJ_ROSENBROCK: PSO_FOR_CHUNKS(NLSG_OBJ_ROSENBROCK, chunks, CALL); break; \
-    case NLSG_OBJ_SPHERE: PSO_FOR_CHUNKS(NLSG_OBJ_SPHERE, chunks, CALL); break;         \
-    case NLSG_OBJ_STYBLINSKI_TANG:                                                      \
-      PSO_FOR_CHUNKS(NLSG_OBJ_STYBLINSKI_TANG, chunks, CALL);                           \
-      break;                                                                            \
-    case NLSG_OBJ_RASTRIGIN: PSO_FOR_CHUNKS(NLSG_OBJ_RASTRIGIN, chunks, CALL); break;   \
-    default: break;                                                                     \
-  }
-
-// D > 1024: the segment-streaming kernels, per objective, row alignment and PSO type only
-#define PSO_FOR_OBJ_LONG(obj, CALL)                                   \
-  switch (obj) {                                                      \
-    case NLSG_OBJ_ROSENBROCK: CALL(NLSG_OBJ_ROSENBROCK); break;       \
-    case NLSG_OBJ_SPHERE: CALL(NLSG_OBJ_SPHERE); break;               \
-    case NLSG_OBJ_STYBLINSKI_TANG: CALL(NLSG_OBJ_STYBLINSKI_TANG); break; \
-    case NLSG_OBJ_RASTRIGIN: CALL(NLSG_OBJ_RASTRIGIN); break;         \
-    default: break;                                                   \
-  }
+// the two PSO types (nlsg_pso_create rejects every other value)
+template <typename F>
+bool with_type(int type, F &&f) {
+  return with_value<NLSG_PSO_VANILLA, NLSG_PSO_ACCELERATED>(type, std::forward<F>(f));
+}
 
 void launch_init(nlsg_pso *e) {
   const dim3 grid(static_cast<unsigned>((e->p.shard_n + 3) / 4)), block(256);
@@ -65,53 +42,17 @@ void launch_init(nlsg_pso *e) {
     launch_module_kernel(e->rtc.init, grid.x, 256, 0, e->stream, args);
     return;
   }
-  if (e->long_rows) {
-#define CALL(OBJ)                                                                            \
-  if (vec)                                                                                   \
-    hipLaunchKernelGGL((pso_init_long_kernel<OBJ, true>), grid, block, 0, e->stream, e->p);  \
-  else                                                                                       \
-    hipLaunchKernelGGL((pso_init_long_kernel<OBJ, false>), grid, block, 0, e->stream, e->p)
-    PSO_FOR_OBJ_LONG(e->cfg.objective, CALL)
-#undef CALL
-    return;
-  }
-#define CALL(OBJ, C)                                                                        \
-  if (vec)                                                                                  \
-    hipLaunchKernelGGL((pso_init_kernel<OBJ, C, true>), grid, block, 0, e->stream, e->p);   \
-  else                                                                                      \
-    hipLaunchKernelGGL((pso_init_kernel<OBJ, C, false>), grid, block, 0, e->stream, e->p)
-  PSO_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
-#undef CALL
-}
-
-template <int OBJ, int TYPE>
-void launch_move_groups(nlsg_pso *e, dim3 grid, int timing, uint64_t iter_ovr) {
-  const dim3 block(256);
-  switch (e->group) {
-    case 4:
-      hipLaunchKernelGGL((pso_move_groups_kernel<OBJ, 4, TYPE>), grid, block, 0, e->stream, e->p,
-                         timing, iter_ovr);
-      break;
-    case 8:
-      hipLaunchKernelGGL((pso_move_groups_kernel<OBJ, 8, TYPE>), grid, block, 0, e->stream, e->p,
-                         timing, iter_ovr);
-      break;
-    case 16:
-      hipLaunchKernelGGL((pso_move_groups_kernel<OBJ, 16, TYPE>), grid, block, 0, e->stream, e->p,
-                         timing, iter_ovr);
-      break;
-    default:
-      hipLaunchKernelGGL((pso_move_groups_kernel<OBJ, 32, TYPE>), grid, block, 0, e->stream, e->p,
-                         timing, iter_ovr);
-      break;
-  }
-}
-template <int OBJ>
-void launch_move_groups_type(nlsg_pso *e, dim3 grid, int timing, uint64_t iter_ovr) {
-  if (e->cfg.type == NLSG_PSO_ACCELERATED)
-    launch_move_groups<OBJ, NLSG_PSO_ACCELERATED>(e, grid, timing, iter_ovr);
-  else
-    launch_move_groups<OBJ, NLSG_PSO_VANILLA>(e, grid, timing, iter_ovr);
+  routed(with_objective(e->cfg.objective, [&](auto O) {
+    return with_bool(vec, [&](auto V) {
+      if (e->long_rows) {  // D > 1024: the segment-streaming kernels, per objective, row alignment and PSO type only
+        hipLaunchKernelGGL((pso_init_long_kernel<O, V>), grid, block, 0, e->stream, e->p);
+        return true;
+      }
+      return with_chunks(e->chunks, [&](auto C) {
+        hipLaunchKernelGGL((pso_init_kernel<O, C, V>), grid, block, 0, e->stream, e->p);
+      });
+    });
+  }));
 }
 
 void launch_move(nlsg_pso *e, int timing, uint64_t iter_ovr) {
@@ -131,50 +72,23 @@ void launch_move(nlsg_pso *e, int timing, uint64_t iter_ovr) {
     launch_module_kernel(e->rtc.move, grid.x, 256, 0, e->stream, args);
     return;
   }
-  if (e->long_rows) {
-#define CALL(OBJ)                                                                                \
-  if (vec && accel)                                                                              \
-    hipLaunchKernelGGL((pso_move_long_kernel<OBJ, true, NLSG_PSO_ACCELERATED>), grid, block, 0,  \
-                       e->stream, e->p, timing, iter_ovr);                                       \
-  else if (vec)                                                                                  \
-    hipLaunchKernelGGL((pso_move_long_kernel<OBJ, true, NLSG_PSO_VANILLA>), grid, block, 0,      \
-                       e->stream, e->p, timing, iter_ovr);                                       \
-  else if (accel)                                                                                \
-    hipLaunchKernelGGL((pso_move_long_kernel<OBJ, false, NLSG_PSO_ACCELERATED>), grid, block, 0, \
-                       e->stream, e->p, timing, iter_ovr);                                       \
-  else                                                                                           \
-    hipLaunchKernelGGL((pso_move_long_kernel<OBJ, false, NLSG_PSO_VANILLA>), grid, block, 0,     \
-                       e->stream, e->p, timing, iter_ovr)
-    PSO_FOR_OBJ_LONG(e->cfg.objective, CALL)
-#undef CALL
-    return;
-  }
-  if (e->group) {
-    switch (e->cfg.objective) {
-      case NLSG_OBJ_ROSENBROCK: launch_move_groups_type<NLSG_OBJ_ROSENBROCK>(e, grid, timing, iter_ovr); break;
-      case NLSG_OBJ_SPHERE: launch_move_groups_type<NLSG_OBJ_SPHERE>(e, grid, timing, iter_ovr); break;
-      case NLSG_OBJ_STYBLINSKI_TANG:
-        launch_move_groups_type<NLSG_OBJ_STYBLINSKI_TANG>(e, grid, timing, iter_ovr);
-        break;
-      default: launch_move_groups_type<NLSG_OBJ_RASTRIGIN>(e, grid, timing, iter_ovr); break;
-    }
-    return;
-  }
-#define CALL(OBJ, C)                                                                          \
-  if (vec && accel)                                                                           \
-    hipLaunchKernelGGL((pso_move_kernel<OBJ, C, true, NLSG_PSO_ACCELERATED>), grid, block, 0, \
-                       e->stream, e->p, timing, iter_ovr);                                    \
-  else if (vec)                                                                               \
-    hipLaunchKernelGGL((pso_move_kernel<OBJ, C, true, NLSG_PSO_VANILLA>), grid, block, 0,     \
-                       e->stream, e->p, timing, iter_ovr);                                    \
-  else if (accel)                                                                             \
-    hipLaunchKernelGGL((pso_move_kernel<OBJ, C, false, NLSG_PSO_ACCELERATED>), grid, block,   \
-                       0, e->stream, e->p, timing, iter_ovr);                                 \
-  else                                                                                        \
-    hipLaunchKernelGGL((pso_move_kernel<OBJ, C, false, NLSG_PSO_VANILLA>), grid, block, 0,    \
-                       e->stream, e->p, timing, iter_ovr)
-  PSO_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
-#undef CALL
+  routed(with_objective(e->cfg.objective, [&](auto O) {
+    return with_type(e->cfg.type, [&](auto T) {
+      if (e->group)  // (D <= 64, so never with long rows)
+        return with_groups(e->group, [&](auto G) {
+          hipLaunchKernelGGL((pso_move_groups_kernel<O, G, T>), grid, block, 0, e->stream, e->p, timing, iter_ovr);
+        });
+      return with_bool(vec, [&](auto V) {
+        if (e->long_rows) {
+          hipLaunchKernelGGL((pso_move_long_kernel<O, V, T>), grid, block, 0, e->stream, e->p, timing, iter_ovr);
+          return true;
+        }
+        return with_chunks(e->chunks, [&](auto C) {
+          hipLaunchKernelGGL((pso_move_kernel<O, C, V, T>), grid, block, 0, e->stream, e->p, timing, iter_ovr);
+        });
+      });
+    });
+  }));
 }
 
 // Workgroups per CU of the striding Accelerated move: eight (two more than the six a CU holds at

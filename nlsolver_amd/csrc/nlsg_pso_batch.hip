@@ -41,29 +41,16 @@ namespace {
 // (nlsg_pso_batch_config.turns_per_launch = 0)
 constexpr uint64_t kPsoBatchTurnsPerLaunch = 1024;
 
-template <int OBJ, int TYPE>
-const void *turn_kernel_of(int group) {
-  switch (group) {
-    case 4: return reinterpret_cast<const void *>(pso_batch_kernel<OBJ, 4, TYPE>);
-    case 8: return reinterpret_cast<const void *>(pso_batch_kernel<OBJ, 8, TYPE>);
-    case 16: return reinterpret_cast<const void *>(pso_batch_kernel<OBJ, 16, TYPE>);
-    case 32: return reinterpret_cast<const void *>(pso_batch_kernel<OBJ, 32, TYPE>);
-    default: return reinterpret_cast<const void *>(pso_batch_kernel<OBJ, 64, TYPE>);
-  }
-}
-template <int OBJ>
-void pick_kernels_obj(nlsg_pso_batch *e) {
-  e->init_fn = reinterpret_cast<const void *>(pso_batch_init_kernel<OBJ>);
-  e->turn_fn = e->cfg.type == NLSG_PSO_ACCELERATED ? turn_kernel_of<OBJ, NLSG_PSO_ACCELERATED>(e->group)
-                                                   : turn_kernel_of<OBJ, NLSG_PSO_VANILLA>(e->group);
-}
-void pick_kernels(nlsg_pso_batch *e) {
-  switch (e->cfg.objective) {
-    case NLSG_OBJ_ROSENBROCK: pick_kernels_obj<NLSG_OBJ_ROSENBROCK>(e); break;
-    case NLSG_OBJ_SPHERE: pick_kernels_obj<NLSG_OBJ_SPHERE>(e); break;
-    case NLSG_OBJ_STYBLINSKI_TANG: pick_kernels_obj<NLSG_OBJ_STYBLINSKI_TANG>(e); break;
-    default: pick_kernels_obj<NLSG_OBJ_RASTRIGIN>(e); break;
-  }
+// the two kernels of a built-in objective; false (and nothing picked) for a value outside the lists
+bool pick_kernels(nlsg_pso_batch *e) {
+  return with_objective(e->cfg.objective, [&](auto O) {
+    e->init_fn = reinterpret_cast<const void *>(pso_batch_init_kernel<O>);
+    return with_value<NLSG_PSO_VANILLA, NLSG_PSO_ACCELERATED>(e->cfg.type, [&](auto T) {
+      return with_batch_groups(e->group, [&](auto G) {
+        e->turn_fn = reinterpret_cast<const void *>(pso_batch_kernel<O, G, T>);
+      });
+    });
+  });
 }
 
 void launch_init(nlsg_pso_batch *e) {
@@ -261,9 +248,9 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
   // which every live engine of that class shares: it is set to the budget, never to one engine's
   // size — a later, smaller engine must not lower it under a kept larger one.
   if (he == hipSuccess && !custom) {
-    pick_kernels(e);
-    he = hipFuncSetAttribute(e->turn_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             static_cast<int>(kPsoBatchLdsBudget));
+    he = pick_kernels(e) ? hipFuncSetAttribute(e->turn_fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               static_cast<int>(kPsoBatchLdsBudget))
+                         : hipErrorInvalidValue;
   }
   if (he == hipSuccess && custom) {
     const int rc2 = rtc_build_pso_batch(custom, e->group, cfg->type, &e->rtc);

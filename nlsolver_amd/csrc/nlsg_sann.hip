@@ -39,48 +39,6 @@ int params_ready(const nlsg_sann *e) {
   return e->params_ready("the objective has %d parameters: call nlsg_sann_set_params first");
 }
 
-#define SANN_FOR_CHUNKS(OBJ, chunks, CALL) \
-  switch (chunks) {                        \
-    case 1: CALL(OBJ, 1); break;           \
-    case 2: CALL(OBJ, 2); break;           \
-    case 4: CALL(OBJ, 4); break;           \
-    case 8: CALL(OBJ, 8); break;           \
-    default: break;                        \
-  }
-#define SANN_FOR_OBJ(obj, chunks, CALL)                                                  \
-  switch (obj) {                                                                         \
-    case NLSG_OBJ_ROSENBROCK: SANN_FOR_CHUNKS(NLSG_OBJ_ROSENBROCK, chunks, CALL); break; \
-    case NLSG_OBJ_SPHERE: SANN_FOR_CHUNKS(NLSG_OBJ_SPHERE, chunks, CALL); break;         \
-    case NLSG_OBJ_STYBLINSKI_TANG:                                                       \
-      SANN_FOR_CHUNKS(NLSG_OBJ_STYBLINSKI_TANG, chunks, CALL);                           \
-      break;                                                                             \
-    case NLSG_OBJ_RASTRIGIN: SANN_FOR_CHUNKS(NLSG_OBJ_RASTRIGIN, chunks, CALL); break;   \
-    default: break;                                                                      \
-  }
-
-template <int OBJ>
-void launch_groups(nlsg_sann *e, dim3 grid, uint64_t iter_begin, uint64_t iter_end) {
-  const dim3 block(256);
-  switch (e->group) {
-    case 4:
-      hipLaunchKernelGGL((sann_anneal_groups_kernel<OBJ, 4>), grid, block, 0, e->stream, e->p,
-                         iter_begin, iter_end);
-      break;
-    case 8:
-      hipLaunchKernelGGL((sann_anneal_groups_kernel<OBJ, 8>), grid, block, 0, e->stream, e->p,
-                         iter_begin, iter_end);
-      break;
-    case 16:
-      hipLaunchKernelGGL((sann_anneal_groups_kernel<OBJ, 16>), grid, block, 0, e->stream, e->p,
-                         iter_begin, iter_end);
-      break;
-    default:
-      hipLaunchKernelGGL((sann_anneal_groups_kernel<OBJ, 32>), grid, block, 0, e->stream, e->p,
-                         iter_begin, iter_end);
-      break;
-  }
-}
-
 void launch_anneal(nlsg_sann *e, uint64_t iter_begin, uint64_t iter_end) {
   // waves: one per chain, or one per 64 / group chains
   const uint64_t per_wave = e->group ? 64 / e->group : 1;
@@ -92,43 +50,21 @@ void launch_anneal(nlsg_sann *e, uint64_t iter_begin, uint64_t iter_end) {
     launch_module_kernel(e->rtc.anneal, grid.x, 256, e->lds, e->stream, args);
     return;
   }
-  if (e->p.D > 1024) {  // chains streamed in segments
-#define CALL(OBJ)                                                                                  \
-  if (vec)                                                                                         \
-    hipLaunchKernelGGL((sann_anneal_long_kernel<OBJ, true>), grid, block, 0, e->stream, e->p,      \
-                       iter_begin, iter_end);                                                      \
-  else                                                                                             \
-    hipLaunchKernelGGL((sann_anneal_long_kernel<OBJ, false>), grid, block, 0, e->stream, e->p,     \
-                       iter_begin, iter_end)
-    switch (e->cfg.objective) {
-      case NLSG_OBJ_ROSENBROCK: CALL(NLSG_OBJ_ROSENBROCK); break;
-      case NLSG_OBJ_SPHERE: CALL(NLSG_OBJ_SPHERE); break;
-      case NLSG_OBJ_STYBLINSKI_TANG: CALL(NLSG_OBJ_STYBLINSKI_TANG); break;
-      default: CALL(NLSG_OBJ_RASTRIGIN); break;
-    }
-#undef CALL
-    return;
-  }
-  if (e->group) {
-    switch (e->cfg.objective) {
-      case NLSG_OBJ_ROSENBROCK: launch_groups<NLSG_OBJ_ROSENBROCK>(e, grid, iter_begin, iter_end); break;
-      case NLSG_OBJ_SPHERE: launch_groups<NLSG_OBJ_SPHERE>(e, grid, iter_begin, iter_end); break;
-      case NLSG_OBJ_STYBLINSKI_TANG:
-        launch_groups<NLSG_OBJ_STYBLINSKI_TANG>(e, grid, iter_begin, iter_end);
-        break;
-      default: launch_groups<NLSG_OBJ_RASTRIGIN>(e, grid, iter_begin, iter_end); break;
-    }
-    return;
-  }
-#define CALL(OBJ, C)                                                                            \
-  if (vec)                                                                                      \
-    hipLaunchKernelGGL((sann_anneal_kernel<OBJ, C, true>), grid, block, 0, e->stream, e->p,     \
-                       iter_begin, iter_end);                                                   \
-  else                                                                                          \
-    hipLaunchKernelGGL((sann_anneal_kernel<OBJ, C, false>), grid, block, 0, e->stream, e->p,    \
-                       iter_begin, iter_end)
-  SANN_FOR_OBJ(e->cfg.objective, e->chunks, CALL)
-#undef CALL
+  routed(with_objective(e->cfg.objective, [&](auto O) {
+    if (e->group)  // (dim <= 64)
+      return with_groups(e->group, [&](auto G) {
+        hipLaunchKernelGGL((sann_anneal_groups_kernel<O, G>), grid, block, 0, e->stream, e->p, iter_begin, iter_end);
+      });
+    return with_bool(vec, [&](auto V) {
+      if (e->p.D > 1024) {  // chains streamed in segments
+        hipLaunchKernelGGL((sann_anneal_long_kernel<O, V>), grid, block, 0, e->stream, e->p, iter_begin, iter_end);
+        return true;
+      }
+      return with_chunks(e->chunks, [&](auto C) {
+        hipLaunchKernelGGL((sann_anneal_kernel<O, C, V>), grid, block, 0, e->stream, e->p, iter_begin, iter_end);
+      });
+    });
+  }));
 }
 
 // The whole schedule; long schedules are cut into launches of a bounded number of trial points so

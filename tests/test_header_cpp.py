@@ -689,3 +689,10 @@ def test_tinyqr_device_batch_through_header(built, oracle):
         oracle.orc_tinyqr_lm_order(O._ptr(np.ascontiguousarray(X[b].reshape(-1))),
                                    O._ptr(np.ascontiguousarray(y[b])), n, p, O._ptr(ref), 1)
         assert np.array_equal(beta[b], ref), b
+
+
+def test_kernel_dispatch_matchers_reach_each_listed_value_once_and_nothing_else(built):
+    """tests/cpp/dispatch_table.cpp: the library's host-side kernel selection (nlsg_dispatch.h) on every
+    named list, values outside them included, and a three-level nest over its 32 cells."""
+    r = subprocess.run([os.path.join(built, "dispatch_table")], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", (r.returncode, r.stdout, r.stderr)

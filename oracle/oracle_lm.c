@@ -327,12 +327,15 @@ static double gn_all(const orc_nlls *q, const double *x, double *g, double *H, d
       for (size_t i = 0; i < m; i++) acc += J[i * n + j] * r[i];
       g[j] = 2 * acc;
     }
-    for (size_t j = 0; j < n; j++)
-      for (size_t k = 0; k < n; k++) {
-        double acc = 0.0;
-        for (size_t i = 0; i < m; i++) acc += J[i * n + j] * J[i * n + k];
-        H[j * n + k] = 2 * acc;
+    /* every H[j][k] adds its rows' products in row order; the rows are the outer loop so that J is read
+     * along its rows (same sums, same roundings as an accumulator per element) */
+    for (size_t e = 0; e < n * n; e++) H[e] = 0.0;
+    for (size_t i = 0; i < m; i++)
+      for (size_t j = 0; j < n; j++) {
+        const double a = J[i * n + j];
+        for (size_t k = 0; k < n; k++) H[j * n + k] = H[j * n + k] + a * J[i * n + k];
       }
+    for (size_t e = 0; e < n * n; e++) H[e] = 2 * H[e];
   } else {
     double part[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (size_t i = 0; i < m; i++) { /* 8 accumulators: idx = 2*((i%64)/16) + i%2 */
@@ -346,12 +349,14 @@ static double gn_all(const orc_nlls *q, const double *x, double *g, double *H, d
       for (size_t i = 0; i < m; i++) a[i % 4] = fma(J[i * n + j], r[i], a[i % 4]);
       g[j] = 2 * (((a[0] + a[1]) + a[2]) + a[3]);
     }
-    for (size_t j = 0; j < n; j++) /* fp64 MFMA: one fma chain over the rows, in order */
-      for (size_t k = 0; k < n; k++) {
-        double acc = 0.0;
-        for (size_t i = 0; i < m; i++) acc = fma(J[i * n + j], J[i * n + k], acc);
-        H[j * n + k] = 2 * acc;
+    /* fp64 MFMA: one fma chain per element over the rows, in order (rows outermost: see above) */
+    for (size_t e = 0; e < n * n; e++) H[e] = 0.0;
+    for (size_t i = 0; i < m; i++)
+      for (size_t j = 0; j < n; j++) {
+        const double a = J[i * n + j];
+        for (size_t k = 0; k < n; k++) H[j * n + k] = fma(a, J[i * n + k], H[j * n + k]);
       }
+    for (size_t e = 0; e < n * n; e++) H[e] = 2 * H[e];
   }
   return f;
 }

@@ -2,11 +2,11 @@
 LinkRegression), as far as the host decides them before any device is touched: the entry point, the
 order and codes of the creator's checks, the model class's argument handling.
 
-Also here: lm_link_solve, a numpy restatement of oracle/oracle_lm.c's order-0 loop (sequential sums,
-libm's functions: the arithmetic of the reference run) with the link as a parameter. With tanh it must
-give what the oracle's own serial loop gives, within the bounds tests/test_lm_gpu.py holds the device
-to against that loop (parameters 1e-12 absolute, f 1e-12 relative): that makes it the yardstick of
-tests/test_lm_link_gpu.py for links the oracle does not have."""
+Also used here: lm_link_solve (tests/_lm_planted.py), a numpy restatement of oracle/oracle_lm.c's order-0
+loop (sequential sums, libm's functions: the arithmetic of the reference run) with the link as a
+parameter. With tanh it must give what the oracle's own serial loop gives, within the bounds
+tests/test_lm_gpu.py holds the device to against that loop (parameters 1e-12 absolute, f 1e-12 relative):
+that makes it the yardstick of tests/test_lm_link_gpu.py for links the oracle does not have."""
 import ctypes as C
 
 import numpy as np
@@ -15,79 +15,13 @@ import pytest
 import nlsolver_amd
 from nlsolver_amd import _capi
 from tests import _oracle as O
+from tests._lm_planted import _gn_all, _update_with_hessian, lm_link_solve  # noqa: F401
 
 SEED = 12374563468
 LOGISTIC = (b"return 1.0 / (1.0 + det_exp(-z));", b"return v * (1.0 - v);")
 
 
-# ---- the yardstick --------------------------------------------------------------------------------------
-def _update_with_hessian(H, g):
-    """math::get_update_with_hessian (oracle_lm.c orc_update_with_hessian_order, order 0): the diagonal
-    shortcut, else Cholesky and the two substitutions, every sum taken in index order"""
-    n = g.size
-    off = H.copy()
-    np.fill_diagonal(off, 0.0)
-    if not np.any(off > 2.220446049250313e-16 * 1e12):
-        return g / np.diag(H)
-    L = H.copy()
-    for i in range(n):
-        for j in range(i):
-            s = 0.0
-            for k in range(j):
-                s += L[i, k] * L[j, k]
-            L[i, j] = 1.0 / L[j, j] * (L[i, j] - s)
-        s = 0.0
-        for k in range(i):
-            s += L[i, k] * L[i, k]
-        L[i, i] = np.sqrt(L[i, i] - s)
-    u = np.zeros(n)
-    for i in range(n):
-        s = 0.0
-        for j in range(i):
-            s += L[i, j] * u[j]
-        u[i] = (g[i] - s) / L[i, i]
-    for i in range(n - 1, -1, -1):
-        s = 0.0
-        for j in range(i + 1, n):
-            s += L[j, i] * u[j]
-        u[i] = (u[i] - s) / L[i, i]
-    return u
-
-
-def _gn_all(A, y, x, value, slope):
-    """f = sum r^2, g = 2 J^T r, H = 2 J^T J (gn_all, order 0): sums over the rows in row order"""
-    m, n = A.shape
-    z = np.zeros(m)
-    for j in range(n):
-        z += A[:, j] * x[j]
-    v = value(z)
-    r = y - v
-    J = -(slope(z, v)[:, None] * A)
-    f, g, H = 0.0, np.zeros(n), np.zeros((n, n))
-    for i in range(m):
-        f += r[i] * r[i]
-        g += J[i] * r[i]
-        H += np.outer(J[i], J[i])
-    return f, 2 * g, 2 * H
-
-
-def lm_link_solve(A, y, x0, value, slope, *, lam=10.0, up=10.0, down=10.0, max_iter=100, f_delta=1e-12):
-    """orc_lm_solve with solver 0, order 0, on r = y - value(A x); value(z) and slope(z, v) take and
-    return numpy vectors. Returns (f, iterations, x, final lambda)."""
-    x = np.array(x0, dtype=np.float64)
-    n = x.size
-    cur, g, H = _gn_all(A, y, x, value, slope)
-    prev, it = 0.0, 0
-    while not (it >= max_iter or abs(prev - cur) < f_delta or np.isnan(prev)):
-        H[np.arange(n), np.arange(n)] += lam
-        x = x - _update_with_hessian(H, g)
-        prev = cur
-        cur, g, H = _gn_all(A, y, x, value, slope)
-        it += 1
-        lam = lam / down if cur < prev else lam * up
-    return cur, it, x, lam
-
-
+# ---- the yardstick (tests/_lm_planted.py holds it now) ------------------------------------------------------
 def np_tanh():
     return np.tanh, lambda z, v: 1 - v * v
 

@@ -378,7 +378,7 @@ struct BfgsModel<kBfgsQuad, CHUNKS> {
 };
 
 // kBfgsCustomGrad: a user objective that comes with its gradient as a second body (nlsg_bfgs_create_gradient;
-// rtc_compile emits Objective<NLSG_OBJ_CUSTOM>::grad). f is the finite-difference model's — the same
+// rtc_custom_source emits Objective<NLSG_OBJ_CUSTOM>::grad). f is the finite-difference model's — the same
 // wave_objective / wave_objective_seq_buf — and the gradient costs about one evaluation instead of 4 n. As with
 // a Grad functor of the caller's in the reference (g_lam, nlsolver.h:3218-3230) a gradient counts in
 // gradient_evals_used only: the sum of terms handed to the body as `s` is no call of the solver's.

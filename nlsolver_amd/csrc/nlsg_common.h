@@ -420,7 +420,7 @@ struct Objective<NLSG_OBJ_RASTRIGIN> {
 // run-time parameters of a user objective (nlsg_custom_objective.n_params > 0; the engines whose
 // kernel owns a workgroup per solve: resident batch DE / PSO, Nelder-Mead, the NM/PSO hybrid and
 // Levenberg-Marquardt made by their *_create_params — and BFGS, whose kernels own a WAVE per solve,
-// below). rtc_compile defines NLSG_N_PARAMS ahead of the kernel header, so the
+// below). rtc_custom_source defines NLSG_N_PARAMS ahead of the kernel header, so the
 // block below exists in that translation unit alone: static LDS in front of the kernels' dynamic block, one
 // solve's row, staged once per launch by the workgroup and read by Objective<NLSG_OBJ_CUSTOM>::p(k)
 // with ds_read. Rounded to an even count: 16-byte size, so the dynamic block behind it keeps the

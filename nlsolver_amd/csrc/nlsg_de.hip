@@ -326,7 +326,7 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   const uint64_t D = cfg->dim, n = cfg->shard_n;
   e->chunks = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
   e->long_rows = D > 1024;  // the reference has no limit (nlsolver.h:2302-2477)
-  e->group = D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 0;
+  e->group = lane_group_of(D, false);
   if (const char *g = std::getenv("NLSG_DE_GROUPS"))  // A/B switch: 0 = one agent per wave at any D
     if (g[0] == '0') e->group = 0;
   DeParams &p = e->p;

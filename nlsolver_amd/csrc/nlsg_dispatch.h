@@ -63,5 +63,10 @@ template <typename F>
 bool with_batch_groups(int group, F &&f) {
   return with_value<4, 8, 16, 32, 64>(group, std::forward<F>(f));
 }
+// lanes per row of D coordinates, two to a lane. Past 64 coordinates a row takes the whole wave: 64 where
+// that is one more group size (the resident batch engines), 0 where other kernels take over
+inline int lane_group_of(uint64_t D, bool whole_wave) {
+  return D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : whole_wave ? 64 : 0;
+}
 
 }  // namespace nlsg

@@ -198,7 +198,7 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
   const uint64_t D = cfg->dim, n = cfg->shard_n;
   e->chunks = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
   e->long_rows = D > 1024;  // the reference has no limit (nlsolver.h:2498-2742)
-  e->group = D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 0;
+  e->group = lane_group_of(D, false);
   if (const char *g = std::getenv("NLSG_PSO_GROUPS"))  // A/B switch: 0 = one particle per wave at any D
     if (g[0] == '0') e->group = 0;
   PsoParams &p = e->p;
@@ -223,23 +223,7 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
   own.zeroed(&p.ticket, 8);
   alloc(&e->loc, sizeof(ShardLocal));
   alloc(&e->rec, (kRecHeader + D) * sizeof(double));
-  // inertia schedule pow(inertia, iter) (:2613) computed with the host libm, as the
-  // reference does, so the device uses bit-identical values
-  // (max_iter + 1 entries — guarded against wrapping — or up to the first fixed point of the
-  // sequence: 0 after underflow, 1, inf; at most 2^22 entries)
-  const uint64_t want = cfg->max_iter == ~0ull ? ~0ull : cfg->max_iter + 1;
-  const uint64_t cap = std::min<uint64_t>(want, 1u << 22);
-  std::vector<double> tab;
-  tab.reserve(std::min<uint64_t>(cap, 4096));
-  p.tab_fixed = 0;
-  for (uint64_t k = 0; k < cap; k++) {
-    tab.push_back(std::pow(cfg->inertia, static_cast<double>(k)));
-    if (k >= 2 && std::memcmp(&tab[k], &tab[k - 1], 8) == 0 && std::memcmp(&tab[k], &tab[k - 2], 8) == 0 &&
-        (tab[k] == 0.0 || tab[k] == 1.0 || std::isinf(tab[k]))) {
-      p.tab_fixed = 1;
-      break;
-    }
-  }
+  const std::vector<double> tab = pso_inertia_table(cfg->inertia, cfg->max_iter, &p.tab_fixed);
   p.tab_len = tab.size();
   alloc(&e->tab_dev, p.tab_len * sizeof(double));
   if (he == hipSuccess)

@@ -6,7 +6,7 @@
 // Solve b is bit-identical to the turn engine (nlsg_pso_kernels.h) with seed seeds[b] and bounds
 // lower[b] / upper[b]: the draw layout, det_rnorm, the update expressions, the objective trees, the
 // argmin and std_err below restate that engine's kernels line by line; pso_apply_pending,
-// pso_finish_turn and pso_inertia_at ARE its functions.
+// pso_finish_turn and pso_inertia_at ARE its functions (nlsg_pso_state.h).
 //   pso_batch_init_kernel   pso_reset_state_kernel + pso_init_kernel per solve (rows to HBM)
 //   pso_batch_kernel        at most `turns` turns of every solve that is not done
 //
@@ -28,7 +28,7 @@
 // both kernels stage it before the first evaluation.
 #pragma once
 
-#include "nlsg_pso_kernels.h"
+#include "nlsg_pso_state.h"
 
 namespace nlsg {
 

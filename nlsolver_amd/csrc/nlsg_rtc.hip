@@ -70,24 +70,26 @@ int rtc_load(const char *path_in) {
 
 }  // namespace
 
-static int rtc_compile_source(const std::string &src, const char *what,
-                              const std::vector<std::string> &name_exprs, hipModule_t *mod_out,
-                              std::vector<hipFunction_t> *fns_out, bool keep_code = false);
+// What rtc_build compiles: the text, and what the user's part of it is called in the error of a failed
+// compilation. rc != 0: the text could not be made of what the user gave, and the error is recorded.
+struct RtcSource {
+  int rc;
+  std::string text;
+  const char *what;
+};
 
-// Compiles `kernel_header` around the user's Objective<NLSG_OBJ_CUSTOM> and returns the module
-// with one function per name expression (kernel template-ids).
+// `kernel_header` around the user's Objective<NLSG_OBJ_CUSTOM>.
 // wave_rows_offset >= 0 (rtc_build_bfgs, with n_params > 0 only): the kernels own a wave per solve, so the
 // rows live per wave in the dynamic LDS block, that many doubles from its start (NLSG_PARAMS_PER_WAVE).
 // grad_body (rtc_build_bfgs for nlsg_bfgs_create_gradient only): one more member, Objective::grad, made of it;
 // without one the source is byte for byte what it is without this argument.
 // params_group > 0 (rtc_build_sann's packed kernel, with n_params > 0 only): a row per group of that many lanes
-// (NLSG_PARAMS_PER_GROUP) instead of one per wave. keep_code: as rtc_compile_source's.
-static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_header,
-                       const std::vector<std::string> &name_exprs, hipModule_t *mod_out,
-                       std::vector<hipFunction_t> *fns_out, long wave_rows_offset = -1,
-                       const char *grad_body = nullptr, int params_group = 0, bool keep_code = false) {
+// (NLSG_PARAMS_PER_GROUP) instead of one per wave.
+static RtcSource rtc_custom_source(const nlsg_custom_objective *obj, const char *kernel_header,
+                                   long wave_rows_offset = -1, const char *grad_body = nullptr,
+                                   int params_group = 0) {
   if (!obj || !obj->term_body || !obj->term_body[0])
-    return fail(NLSG_ERR_INVALID_ARG, "a custom objective needs a term body");
+    return {fail(NLSG_ERR_INVALID_ARG, "a custom objective needs a term body"), "", "custom objective"};
   // n_params > 0 (resident batch engines and nlsg_nm / nmpso / lm / bfgs_create_params; every
   // *_create_custom besides has rejected it): the macro
   // puts the solve's row into static LDS (nlsg_common.h) and the bodies read it as p(k); for BFGS a
@@ -155,7 +157,7 @@ static int rtc_compile(const nlsg_custom_objective *obj, const char *kernel_head
     }
     src += "};\n}  // namespace nlsg\n";
   }
-  return rtc_compile_source(src, "custom objective", name_exprs, mod_out, fns_out, keep_code);
+  return {NLSG_OK, src, "custom objective"};
 }
 
 // A compiled code object and the lowered names of its kernels, kept by source text: a second engine
@@ -288,119 +290,84 @@ static int rtc_compile_source(const std::string &src, const char *what,
   return lrc;
 }
 
+// a kernel's template-id (a name expression) and where its function goes
+struct RtcBind {
+  std::string name;
+  hipFunction_t *fn;
+};
+
+// What every rtc_build_* ends in: the source to a module, the binds' functions out of it. `binds` point into
+// *out, which is written on success only: then it holds the module, the bound kernels and nothing else.
+template <typename K>
+static int rtc_build(const RtcSource &source, bool keep_code, K *out, const std::vector<RtcBind> &binds) {
+  if (source.rc) return source.rc;
+  std::vector<std::string> names;
+  for (const RtcBind &b : binds) names.push_back(b.name);
+  hipModule_t mod = nullptr;
+  std::vector<hipFunction_t> fns;
+  if (const int rc = rtc_compile_source(source.text, source.what, names, &mod, &fns, keep_code)) return rc;
+  *out = K();
+  out->mod = mod;
+  for (size_t i = 0; i < binds.size(); i++) *binds[i].fn = fns[i];
+  return NLSG_OK;
+}
+
+// the objective id every kernel of a user objective is instantiated on
+static std::string custom_id() { return std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)); }
 static std::string targs(int chunks, bool vec) {
-  return std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) + ", " + std::to_string(chunks) + ", " +
-         (vec ? "true" : "false");
+  return custom_id() + ", " + std::to_string(chunks) + ", " + (vec ? "true" : "false");
 }
 
 int rtc_build_de(const nlsg_custom_objective *obj, int chunks, bool vec, int group,
                  DeRtcKernels *out) {
+  const RtcSource source = rtc_custom_source(obj, "nlsg_de_kernels.h");
   if (chunks == 0) {  // D > 1024: the segment-streaming kernels (no fused turn)
-    const std::string t = std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) + ", " + (vec ? "true" : "false");
-    std::vector<hipFunction_t> f;
-    DeRtcKernels k;
-    const int rc = rtc_compile(obj, "nlsg_de_kernels.h",
-                               {"nlsg::de_init_long_kernel<" + t + ">", "nlsg::de_generation_long_kernel<" + t + ">"},
-                               &k.mod, &f);
-    if (rc) return rc;
-    k.init = f[0];
-    k.generation = f[1];
-    k.turn = nullptr;
-    *out = k;
-    return NLSG_OK;
+    const std::string t = custom_id() + ", " + (vec ? "true" : "false");
+    return rtc_build(source, false, out,
+                     {{"nlsg::de_init_long_kernel<" + t + ">", &out->init},
+                      {"nlsg::de_generation_long_kernel<" + t + ">", &out->generation}});
   }
-  const std::string t = targs(chunks, vec);
-  const std::string gen =
-      group ? "nlsg::de_generation_groups_kernel<" + std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) +
-                  ", " + std::to_string(group) + ">"
-            : "nlsg::de_generation_kernel<" + t + ">";
-  std::vector<hipFunction_t> f;
-  DeRtcKernels k;
-  const std::string turn =
-      group ? "nlsg::de_turn_groups_kernel<" + std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) + ", " +
-                  std::to_string(group) + ">"
-            : "nlsg::de_turn_kernel<" + t + ">";
-  const int rc = rtc_compile(obj, "nlsg_de_kernels.h", {"nlsg::de_init_kernel<" + t + ">", gen, turn},
-                             &k.mod, &f);
-  if (rc) return rc;
-  k.init = f[0];
-  k.generation = f[1];
-  k.turn = f[2];
-  *out = k;
-  return NLSG_OK;
+  const std::string t = targs(chunks, vec), g = custom_id() + ", " + std::to_string(group);
+  return rtc_build(source, false, out,
+                   {{"nlsg::de_init_kernel<" + t + ">", &out->init},
+                    {group ? "nlsg::de_generation_groups_kernel<" + g + ">" : "nlsg::de_generation_kernel<" + t + ">",
+                     &out->generation},
+                    {group ? "nlsg::de_turn_groups_kernel<" + g + ">" : "nlsg::de_turn_kernel<" + t + ">",
+                     &out->turn}});
 }
 
 // the resident batch engine's two kernels, next to the turn kernels they restate
-int rtc_build_de_batch(const nlsg_custom_objective *obj, int group, DeBatchRtcKernels *out) {
-  const std::string id = std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM));
-  std::vector<hipFunction_t> f;
-  DeBatchRtcKernels k;
-  const int rc = rtc_compile(obj, "nlsg_de_batch_kernels.h",
-                             {"nlsg::de_batch_init_kernel<" + id + ">",
-                              "nlsg::de_batch_kernel<" + id + ", " + std::to_string(group) + ">"},
-                             &k.mod, &f);
-  if (rc) return rc;
-  k.init = f[0];
-  k.turns = f[1];
-  *out = k;
-  return NLSG_OK;
-}
-void rtc_release(DeBatchRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = DeBatchRtcKernels();
+int rtc_build_de_batch(const nlsg_custom_objective *obj, int group, ResidentRtcKernels *out) {
+  return rtc_build(rtc_custom_source(obj, "nlsg_de_batch_kernels.h"), false, out,
+                   {{"nlsg::de_batch_init_kernel<" + custom_id() + ">", &out->init},
+                    {"nlsg::de_batch_kernel<" + custom_id() + ", " + std::to_string(group) + ">", &out->turns}});
 }
 
 // the resident batch PSO engine's two kernels, next to the turn kernels they restate
-int rtc_build_pso_batch(const nlsg_custom_objective *obj, int group, int type, PsoBatchRtcKernels *out) {
-  const std::string id = std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM));
-  std::vector<hipFunction_t> f;
-  PsoBatchRtcKernels k;
-  const int rc = rtc_compile(obj, "nlsg_pso_batch_kernels.h",
-                             {"nlsg::pso_batch_init_kernel<" + id + ">",
-                              "nlsg::pso_batch_kernel<" + id + ", " + std::to_string(group) + ", " +
-                                  std::to_string(type) + ">"},
-                             &k.mod, &f);
-  if (rc) return rc;
-  k.init = f[0];
-  k.turns = f[1];
-  *out = k;
-  return NLSG_OK;
-}
-void rtc_release(PsoBatchRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = PsoBatchRtcKernels();
+int rtc_build_pso_batch(const nlsg_custom_objective *obj, int group, int type, ResidentRtcKernels *out) {
+  return rtc_build(rtc_custom_source(obj, "nlsg_pso_batch_kernels.h"), false, out,
+                   {{"nlsg::pso_batch_init_kernel<" + custom_id() + ">", &out->init},
+                    {"nlsg::pso_batch_kernel<" + custom_id() + ", " + std::to_string(group) + ", " +
+                         std::to_string(type) + ">",
+                     &out->turns}});
 }
 
 int rtc_build_pso(const nlsg_custom_objective *obj, int chunks, bool vec, int type, int group,
                   PsoRtcKernels *out) {
+  const RtcSource source = rtc_custom_source(obj, "nlsg_pso_kernels.h");
+  const std::string ty = ", " + std::to_string(type) + ">";
   if (chunks == 0) {  // D > 1024: the segment-streaming kernels
-    const std::string t = std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) + ", " + (vec ? "true" : "false");
-    std::vector<hipFunction_t> f;
-    PsoRtcKernels k;
-    const int rc = rtc_compile(obj, "nlsg_pso_kernels.h",
-                               {"nlsg::pso_init_long_kernel<" + t + ">",
-                                "nlsg::pso_move_long_kernel<" + t + ", " + std::to_string(type) + ">"},
-                               &k.mod, &f);
-    if (rc) return rc;
-    k.init = f[0];
-    k.move = f[1];
-    *out = k;
-    return NLSG_OK;
+    const std::string t = custom_id() + ", " + (vec ? "true" : "false");
+    return rtc_build(source, false, out,
+                     {{"nlsg::pso_init_long_kernel<" + t + ">", &out->init},
+                      {"nlsg::pso_move_long_kernel<" + t + ty, &out->move}});
   }
   const std::string t = targs(chunks, vec);
-  const std::string move =
-      group ? "nlsg::pso_move_groups_kernel<" + std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) +
-                  ", " + std::to_string(group) + ", " + std::to_string(type) + ">"
-            : "nlsg::pso_move_kernel<" + t + ", " + std::to_string(type) + ">";
-  std::vector<hipFunction_t> f;
-  PsoRtcKernels k;
-  const int rc = rtc_compile(obj, "nlsg_pso_kernels.h", {"nlsg::pso_init_kernel<" + t + ">", move},
-                             &k.mod, &f);
-  if (rc) return rc;
-  k.init = f[0];
-  k.move = f[1];
-  *out = k;
-  return NLSG_OK;
+  return rtc_build(source, false, out,
+                   {{"nlsg::pso_init_kernel<" + t + ">", &out->init},
+                    {group ? "nlsg::pso_move_groups_kernel<" + custom_id() + ", " + std::to_string(group) + ty
+                           : "nlsg::pso_move_kernel<" + t + ty,
+                     &out->move}});
 }
 
 int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long wave_rows_offset,
@@ -408,121 +375,59 @@ int rtc_build_bfgs(const nlsg_custom_objective *obj, int chunks, bool vec, long 
   // <CHUNKS, VEC, MODEL>: MODEL = the objective id selects the finite-difference BfgsModel, kBfgsCustomGrad
   // (-2, nlsg_bfgs_kernels.h) the one that evaluates the objective's own gradient body
   const std::string t = std::to_string(chunks) + ", " + (vec ? "true" : "false") + ", " +
-                        (grad_body ? std::string("nlsg::kBfgsCustomGrad")
-                                   : std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)));
-  std::vector<hipFunction_t> f;
-  BfgsRtcKernels k;
+                        (grad_body ? std::string("nlsg::kBfgsCustomGrad") : custom_id());
   // (the resident kernel is instantiated for an engine that asks for it only: a lock-step engine compiles
   // what it always did)
-  std::vector<std::string> names = {"nlsg::bfgs_init_kernel<" + t + ">", "nlsg::bfgs_search_kernel<" + t + ">"};
-  if (resident) names.push_back("nlsg::bfgs_resident_kernel<" + t + ">");
+  std::vector<RtcBind> binds = {{"nlsg::bfgs_init_kernel<" + t + ">", &out->init},
+                                {"nlsg::bfgs_search_kernel<" + t + ">", &out->search}};
+  if (resident) binds.push_back({"nlsg::bfgs_resident_kernel<" + t + ">", &out->resident});
   // (a row per wave in the dynamic block.) The code object is kept by its source, as the annealer's: engines
   // that differ in alpha, max_iter or grad_eps only — a sweep of step lengths, the drop-in's engine per call —
   // load it instead of compiling.
-  const int rc = rtc_compile(obj, "nlsg_bfgs_kernels.h", names, &k.mod, &f, wave_rows_offset, grad_body, 0, true);
-  if (rc) return rc;
-  if (resident) k.resident = f[2];
-  k.init = f[0];
-  k.search = f[1];
-  *out = k;
-  return NLSG_OK;
-}
-void rtc_release(BfgsRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = BfgsRtcKernels();
+  return rtc_build(rtc_custom_source(obj, "nlsg_bfgs_kernels.h", wave_rows_offset, grad_body), true, out, binds);
 }
 
 int rtc_build_nm(const nlsg_custom_objective *obj, int chunks, bool reference_order, NmRtcKernels *out) {
-  std::vector<hipFunction_t> f;
-  NmRtcKernels k;
-  const std::string id = std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM));
   // chunks == 0: the driver-wave kernel (n <= 128)
-  const int rc = rtc_compile(obj, "nlsg_nm_kernels.h",
-                             {chunks == 0 ? "nlsg::nm_solve_driver_kernel<" + id + (reference_order ? ", true>" : ">")
-                                          : "nlsg::nm_solve_kernel<" + id + ", " + std::to_string(chunks) + ">"},
-                             &k.mod, &f);
-  if (rc) return rc;
-  k.solve = f[0];
-  *out = k;
-  return NLSG_OK;
-}
-void rtc_release(NmRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = NmRtcKernels();
+  return rtc_build(rtc_custom_source(obj, "nlsg_nm_kernels.h"), false, out,
+                   {{chunks == 0 ? "nlsg::nm_solve_driver_kernel<" + custom_id() + (reference_order ? ", true>" : ">")
+                                 : "nlsg::nm_solve_kernel<" + custom_id() + ", " + std::to_string(chunks) + ">",
+                     &out->solve}});
 }
 
 int rtc_build_de_ref(const nlsg_custom_objective *obj, DeRefRtcKernels *out) {
-  std::vector<hipFunction_t> f;
-  DeRefRtcKernels k;
-  const int rc = rtc_compile(obj, "nlsg_de_ref_kernels.h",
-                             {"nlsg::de_ref_kernel<" + std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) + ">"},
-                             &k.mod, &f);
-  if (rc) return rc;
-  k.solve = f[0];
-  *out = k;
-  return NLSG_OK;
-}
-void rtc_release(DeRefRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = DeRefRtcKernels();
+  return rtc_build(rtc_custom_source(obj, "nlsg_de_ref_kernels.h"), false, out,
+                   {{"nlsg::de_ref_kernel<" + custom_id() + ">", &out->solve}});
 }
 
 int rtc_build_nmpso(const nlsg_custom_objective *obj, int wide_chunks, HybRtcKernels *out) {
-  std::vector<hipFunction_t> f;
-  HybRtcKernels k;
-  const std::string id = std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM));
-  const std::string name = wide_chunks ? "nlsg::nmpso_solve_wide_kernel<" + id + ", " +
-                                             std::to_string(wide_chunks) + ">"
-                                       : "nlsg::nmpso_solve_kernel<" + id + ">";
-  const int rc = rtc_compile(obj, "nlsg_nmpso_kernels.h", {name}, &k.mod, &f);
-  if (rc) return rc;
-  k.solve = f[0];
-  *out = k;
-  return NLSG_OK;
-}
-void rtc_release(HybRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = HybRtcKernels();
+  return rtc_build(rtc_custom_source(obj, "nlsg_nmpso_kernels.h"), false, out,
+                   {{wide_chunks ? "nlsg::nmpso_solve_wide_kernel<" + custom_id() + ", " +
+                                       std::to_string(wide_chunks) + ">"
+                                 : "nlsg::nmpso_solve_kernel<" + custom_id() + ">",
+                     &out->solve}});
 }
 
 int rtc_build_sann(const nlsg_custom_objective *obj, int chunks, bool vec, int group,
                    SannRtcKernels *out) {
-  std::vector<hipFunction_t> f;
-  SannRtcKernels k;
   const std::string name =
-      chunks == 0 ? "nlsg::sann_anneal_long_kernel<" + std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) +
-                        ", " + (vec ? "true" : "false") + ">"
-      : group ? "nlsg::sann_anneal_groups_kernel<" + std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM)) +
-                  ", " + std::to_string(group) + ">"
-            : "nlsg::sann_anneal_kernel<" + targs(chunks, vec) + ">";
+      chunks == 0 ? "nlsg::sann_anneal_long_kernel<" + custom_id() + ", " + (vec ? "true" : "false") + ">"
+      : group     ? "nlsg::sann_anneal_groups_kernel<" + custom_id() + ", " + std::to_string(group) + ">"
+                  : "nlsg::sann_anneal_kernel<" + targs(chunks, vec) + ">";
   // n_params > 0 (nlsg_sann_create_params): the rows start the dynamic block (offset 0), one per wave, or with
   // `group` one per lane group. The code object is kept by its source: the engines of a sweep, of the drop-in's
   // calls and of a sharded batch differ in their configuration only and load it instead of compiling.
-  const int rc = rtc_compile(obj, "nlsg_sann_kernels.h", {name}, &k.mod, &f, obj && obj->n_params > 0 ? 0 : -1,
-                             nullptr, group, true);
-  if (rc) return rc;
-  k.anneal = f[0];
-  *out = k;
-  return NLSG_OK;
-}
-void rtc_release(SannRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = SannRtcKernels();
+  return rtc_build(rtc_custom_source(obj, "nlsg_sann_kernels.h", obj && obj->n_params > 0 ? 0 : -1, nullptr, group),
+                   true, out, {{name, &out->anneal}});
 }
 
 int rtc_build_lm(const nlsg_custom_objective *obj, int wide_chunks, bool reference_order, LmRtcKernels *out) {
-  std::vector<hipFunction_t> f;
-  LmRtcKernels k;
-  const std::string id = std::to_string(static_cast<int>(NLSG_OBJ_CUSTOM));
+  const std::string id = custom_id();
   const std::string name =
       wide_chunks ? (reference_order ? "nlsg::lm_wide_fd_lanes_kernel<" + id + ">"
                                      : "nlsg::lm_wide_fd_eval_kernel<" + id + ", " + std::to_string(wide_chunks) + ">")
                   : "nlsg::lm_fd_iter_kernel<" + id + (reference_order ? ", true>" : ">");
-  const int rc = rtc_compile(obj, "nlsg_lm_kernels.h", {name}, &k.mod, &f);
-  if (rc) return rc;
-  k.iter = f[0];
-  *out = k;
-  return NLSG_OK;
+  return rtc_build(rtc_custom_source(obj, "nlsg_lm_kernels.h"), false, out, {{name, &out->iter}});
 }
 // The Gauss-Newton evaluation kernel of the shape, instantiated on a link made of the two bodies
 // (nlsg_lm_kernels.h LmTanhLink is the pattern). The same selection by n as the built-in engine's, the
@@ -545,14 +450,8 @@ int rtc_build_lm_link(const nlsg_lm_link *link, uint64_t n, LmRtcKernels *out) {
   src += "\n  }\n};\n}  // namespace nlsg\n";
   const char *kernel = n <= 64 ? "lm_iter_kernel" : n <= 128 ? "lm_wide128x8_tanh_eval_kernel"
                      : n <= 256 ? "lm_wide256x8_tanh_eval_kernel" : "lm_wide_mfma_tanh_eval_kernel";
-  std::vector<hipFunction_t> f;
-  LmRtcKernels k;
-  const int rc = rtc_compile_source(src, "link", {std::string("nlsg::") + kernel + "<nlsg::LmUserLink>"},
-                                    &k.mod, &f, true);
-  if (rc) return rc;
-  k.iter = f[0];
-  *out = k;
-  return NLSG_OK;
+  return rtc_build({NLSG_OK, src, "link"}, true, out,
+                   {{std::string("nlsg::") + kernel + "<nlsg::LmUserLink>", &out->iter}});
 }
 // lm_curve_iter_kernel on a model made of the body (nlsg_lm_kernels.h): K data per observation, the
 // padded column count chosen from n. The body sees th(j), t(k), y, n, r and J(j).
@@ -571,28 +470,8 @@ int rtc_build_lm_curve(const nlsg_lm_curve *curve, uint64_t n, LmRtcKernels *out
   src += curve->body;
   src += "\n  }\n};\n}  // namespace nlsg\n";
   const int npad = n <= 16 ? 16 : n <= 32 ? 32 : 64;
-  std::vector<hipFunction_t> f;
-  LmRtcKernels k;
-  const int rc = rtc_compile_source(
-      src, "curve model", {"nlsg::lm_curve_iter_kernel<nlsg::LmUserCurve, " + std::to_string(npad) + ">"},
-      &k.mod, &f, true);
-  if (rc) return rc;
-  k.iter = f[0];
-  *out = k;
-  return NLSG_OK;
-}
-void rtc_release(LmRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = LmRtcKernels();
-}
-
-void rtc_release(DeRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = DeRtcKernels();
-}
-void rtc_release(PsoRtcKernels *k) {
-  if (k && k->mod) hipModuleUnload(k->mod);
-  if (k) *k = PsoRtcKernels();
+  return rtc_build({NLSG_OK, src, "curve model"}, true, out,
+                   {{"nlsg::lm_curve_iter_kernel<nlsg::LmUserCurve, " + std::to_string(npad) + ">", &out->iter}});
 }
 
 }  // namespace nlsg

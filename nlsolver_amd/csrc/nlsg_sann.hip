@@ -21,7 +21,6 @@ namespace {
 
 constexpr uint64_t kSannLdsBudget = 160ull * 1024;                      // a workgroup's LDS
 constexpr uint64_t kSannTableBytes = 8ull * kRnormTabDoubles;           // rn_tab, static, in every kernel
-int sann_group_of(uint64_t D) { return D <= 8 ? 4 : D <= 16 ? 8 : D <= 32 ? 16 : D <= 64 ? 32 : 0; }
 // dynamic LDS of the packed kernel with `group` lanes per chain: a row per group, 4 * (64 / group) to the block
 uint64_t sann_group_rows_bytes(int group, int64_t n_params) {
   return 4ull * (64 / group) * 8 * custom_params_group_stride(n_params);
@@ -30,7 +29,7 @@ uint64_t sann_group_rows_bytes(int group, int64_t n_params) {
 // parametrised objective do not fit next to rn_tab — then one chain per wave (0), whose four rows always do.
 // A chain's history does not depend on the packing, so the rule moves no bit.
 int sann_group_for(uint64_t D, int64_t n_params) {
-  const int group = sann_group_of(D);
+  const int group = lane_group_of(D, false);
   if (group && n_params > 0 && kSannTableBytes + sann_group_rows_bytes(group, n_params) > kSannLdsBudget) return 0;
   return group;
 }

@@ -44,7 +44,11 @@ def lm(X, y, tol=1e-12, *, device=0, return_ms=False, reference_order=False):
     """Least-squares coefficients beta (p,) or (batch, p): tinyqr::lm(X, y, tol) per system.
     X[..., j, i] is element (i, j) of the system's n x p matrix (column-major, as tinyqr takes it).
     reference_order=True: the parity mode — Q formed, the reference's summation orders, beta equal to
-    the reference's bit for bit (slower: one wave per system, serial rotations)."""
+    the reference's bit for bit (slower: one wave per system, serial rotations).
+    As in the reference, two zeros stacked in a pivot column are 0 / 0 in the Givens pair: a zero column,
+    a one-hot design or zero rows at the bottom return NaN in every coefficient of THAT system (its
+    neighbours in the batch are untouched), and entries of R below tol are read as 0 and divided by
+    (a column scaled to 2^-160 needs tol = 0). DESIGN.md §6c, "Off the benign path"."""
     X = np.ascontiguousarray(X, dtype=np.float64)
     y = np.ascontiguousarray(y, dtype=np.float64)
     single = X.ndim == 2

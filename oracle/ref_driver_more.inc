@@ -774,6 +774,45 @@ static int run_tinyqr_rect(size_t n, size_t p, uint64_t seed) {
   return 0;
 }
 
+// tinyqr on a system GIVEN on stdin (tests/_tinyqr_cases.py: graded, zero-laden, non-finite, scaled):
+// X (column-major n x p) and y as hexfloat / nan / inf tokens. Output as tinyqr-rect, plus beta at
+// `tol`; the hashes read every NaN as the one quiet NaN (its sign and payload are not pinned).
+static int run_tinyqr_hex(size_t n, size_t p, double tol) {
+  std::vector<double> X(n * p), y(n);
+  auto read = [](double &v) {
+    char tok[64];
+    if (std::scanf("%63s", tok) != 1) std::exit(3);
+    v = std::strtod(tok, nullptr);
+  };
+  for (double &v : X) read(v);
+  for (double &v : y) read(v);
+  auto beta = tinyqr::lm(X, y);
+  auto beta_t = tinyqr::lm(X, y, tol);
+  auto qr = tinyqr::qr_decomposition(X, n, p);
+  auto beta2 = tinyqr::back_solve(qr.Q, qr.R, y, n, p);  // with qr_decomposition's default tol
+  Fnv hq, hr;
+  const double qnan = std::strtod("nan", nullptr);
+  for (double v : qr.Q) hq.add(v != v ? qnan : v);
+  for (double v : qr.R) hr.add(v != v ? qnan : v);
+  std::printf("{\"n\":%zu,\"p\":%zu,\"tol\":", n, p);
+  put_hex(tol);
+  std::printf(",\"beta\":");
+  put_vec(beta);
+  std::printf(",\"beta_tol\":");
+  put_vec(beta_t);
+  std::printf(",\"beta_tol1e-8\":");
+  put_vec(beta2);
+  std::printf(",\"Q_fnv\":\"%" PRIu64 "\",\"R_fnv\":\"%" PRIu64 "\"", hq.h, hr.h);
+  if (n <= 40 && p <= 12) {
+    std::printf(",\"Q\":");
+    put_vec(qr.Q);
+    std::printf(",\"R\":");
+    put_vec(qr.R);
+  }
+  std::printf("}\n");
+  return 0;
+}
+
 // timing of the reference's tinyqr::lm on `count` pseudo-random n x p systems, one thread
 static int bench_tinyqr(size_t n, size_t p, size_t count) {
   double total = 0, acc = 0;
@@ -934,6 +973,11 @@ static int more_main(const std::string &cmd, int argc, char **argv) {
     if (argc < 5) return 2;
     return run_tinyqr_rect(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10),
                            std::strtoull(argv[4], nullptr, 10));
+  }
+  if (cmd == "tinyqr-hex") {  // tinyqr-hex n p tol < X y
+    if (argc < 5) return 2;
+    return run_tinyqr_hex(std::strtoull(argv[2], nullptr, 10), std::strtoull(argv[3], nullptr, 10),
+                          std::strtod(argv[4], nullptr));
   }
   if (cmd == "bench-tinyqr")
     return bench_tinyqr(argc > 2 ? std::strtoull(argv[2], nullptr, 10) : 576,

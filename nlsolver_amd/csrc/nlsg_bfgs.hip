@@ -111,12 +111,17 @@ void launch_iteration(nlsg_bfgs *e, bool timed) {
   if (timed) hipEventRecord(e->ev3, e->stream);
 }
 
-// a parametrised engine launches no evaluation before its first rows
-int params_ready(const nlsg_bfgs *e) {
-  return e->params_ready("the objective has %d parameters: call nlsg_bfgs_set_params first");
+// the unfinished problems a kernel counts into count_dev (kernel(p, count_dev), a thread per problem)
+template <typename Kernel>
+int count_problems(nlsg_bfgs *e, Kernel kernel, uint64_t *count) {
+  if (!e || !count) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_bfgs_init has not been called");
+  NLSG_HIP(hipSetDevice(e->cfg.device));
+  return device_count(e->stream, e->count_dev, count, [&] {
+    hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>((e->p.batch + 255) / 256)), dim3(256), 0, e->stream, e->p,
+                       e->count_dev);
+  });
 }
-
-constexpr int bfgs_chunks(uint64_t n) { return n <= 128 ? 1 : n <= 256 ? 2 : n <= 512 ? 4 : 8; }
 
 }  // namespace
 
@@ -128,25 +133,19 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
 
 int nlsg_bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const double *lin_host,
                      nlsg_bfgs **out) {
-  if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_bfgs_create_custom");
+  if (const int rc = builtin_door(cfg, "nlsg_bfgs")) return rc;
   return timed_create([&] { return bfgs_create(cfg, diag_host, lin_host, nullptr, out); });
 }
 
 int nlsg_bfgs_create_custom(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
                             nlsg_bfgs **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  if (const int prc = reject_custom_params(obj)) return prc;
+  if (const int rc = custom_door(cfg, obj, out)) return rc;
   return timed_create([&] { return bfgs_create(cfg, nullptr, nullptr, obj, out); });
 }
 
 int nlsg_bfgs_create_params(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
                             nlsg_bfgs **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int rc = runtime_door(cfg, obj, out)) return rc;
   return timed_create([&] { return bfgs_create(cfg, nullptr, nullptr, obj, out, true); });
 }
 
@@ -154,9 +153,8 @@ int nlsg_bfgs_create_params(const nlsg_bfgs_config *cfg, const nlsg_custom_objec
 // Parameters are optional here (n_params == 0 is an objective without any).
 int nlsg_bfgs_create_gradient(const nlsg_bfgs_config *cfg, const nlsg_custom_objective *obj,
                               const nlsg_bfgs_gradient *grad, nlsg_bfgs **out) {
-  if (!cfg || !obj || !grad) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (!grad) return fail(NLSG_ERR_INVALID_ARG, "null argument");
+  if (const int rc = runtime_door(cfg, obj, out)) return rc;
   if (grad->struct_size != sizeof(nlsg_bfgs_gradient))
     return fail(NLSG_ERR_INVALID_ARG, "nlsg_bfgs_gradient size mismatch (%u vs %zu)", grad->struct_size,
                 sizeof(nlsg_bfgs_gradient));
@@ -181,13 +179,10 @@ uint64_t nlsg_bfgs_lds_bytes(uint64_t dim, uint32_t flags) {
     return bfgs_resident_layout(dim, (flags & NLSG_BFGS_REFERENCE_ORDER) ? 1 : 0, 0).total * sizeof(double);
   }
   if (!(flags & NLSG_BFGS_REFERENCE_ORDER) || (flags & NLSG_BFGS_SYMMETRIC)) return 0;
-  return bfgs_fd_seq_lds_bytes(bfgs_chunks(dim));
+  return bfgs_fd_seq_lds_bytes(row_chunks(dim));
 }
 
-int nlsg_bfgs_set_params(nlsg_bfgs *e, const double *params_host) {
-  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (nlsg_bfgs_create_params)");
-}
+int nlsg_bfgs_set_params(nlsg_bfgs *e, const double *params_host) { return set_params_entry(e, params_host); }
 
 static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, const double *lin_host,
                        const nlsg_custom_objective *custom, nlsg_bfgs **out, bool with_params,
@@ -240,10 +235,11 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
                                             "nlsg_bfgs_create_custom", resident ? 1 : 4))
       return prc;
   nlsg_bfgs *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_bfgs", &e)) return rc;
+  CreateGuard<nlsg_bfgs> guard(e, nlsg_bfgs_destroy);
   e->cfg = *cfg;
   const uint64_t n = cfg->dim, B = cfg->batch;
-  e->chunks = bfgs_chunks(n);
+  e->chunks = row_chunks(n);
   e->n_params = with_params ? custom->n_params : 0;
   // the launch's dynamic block: the reference-order buffers, then the rows — ONE layout, from which both the
   // launch size and the offset the kernels are compiled with (NLSG_PARAMS_PER_WAVE) are taken
@@ -256,10 +252,8 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   e->bpp = static_cast<uint32_t>((n + 4 * kBfgsRowsPerWave - 1) / (4 * kBfgsRowsPerWave));
   e->symmetric = (cfg->flags & NLSG_BFGS_SYMMETRIC) != 0;
   const uint32_t nb = static_cast<uint32_t>((n + kBfgsSymB - 1) / kBfgsSymB), nstored = nb * (nb + 1) / 2;
-  if (B * e->bpp > 0x7fffffffull || B * nstored > 0x7fffffffull) {
-    delete e;  // (its stream goes back with it)
+  if (B * e->bpp > 0x7fffffffull || B * nstored > 0x7fffffffull)
     return fail(NLSG_ERR_UNSUPPORTED, "batch * dim too large for one launch grid");
-  }
   BfgsParams &p = e->p;
   std::memset(&p, 0, sizeof p);
   p.ldh = seq && (n * sizeof(double)) % 4096 == 0 ? n + 16 : n;  // (BfgsParams::ldh)
@@ -292,10 +286,7 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   e->timing_events();
   own.event(&e->ev2);
   own.event(&e->ev3);
-  if (const int rc = e->setup_status("device allocation failed: %s")) {
-    nlsg_bfgs_destroy(e);
-    return rc;
-  }
+  if (const int rc = e->setup_status("device allocation failed: %s")) return rc;
   p.qd = e->qd_dev;
   p.qb = e->qb_dev;
   p.zero = e->zero_dev;
@@ -311,54 +302,28 @@ static int bfgs_create(const nlsg_bfgs_config *cfg, const double *diag_host, con
   p.nb = nb;
   p.nstored = nstored;
   if (custom) {
-    const int rc2 = rtc_build_bfgs(custom, e->chunks, e->vec, static_cast<long>(rows_at / sizeof(double)), &e->rtc,
-                                   grad_body, resident);
-    if (rc2) {
-      nlsg_bfgs_destroy(e);
-      return rc2;
-    }
-    // the module API's counterpart of hipFuncSetAttribute on a kernel symbol: four rows of parameters go
-    // past the 64 KiB a launch may take without it
-    if (e->fd_lds > 64 * 1024) {
-      hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.search),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->fd_lds));
-      if (ae == hipSuccess)
-        ae = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.init),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->fd_lds));
-      if (ae != hipSuccess) {
-        nlsg_bfgs_destroy(e);
-        return fail(NLSG_ERR_HIP, "raising the kernels' dynamic LDS limit failed: %s", hipGetErrorString(ae));
-      }
-    }
+    if (const int rc = rtc_build_bfgs(custom, e->chunks, e->vec, static_cast<long>(rows_at / sizeof(double)), &e->rtc,
+                                      grad_body, resident))
+      return rc;
+    // four rows of parameters go past the 64 KiB a launch may take without the opt-in
+    const char *raising = "raising the kernels' dynamic LDS limit failed: %s";
+    if (const int rc = module_kernel_lds(e->rtc.search, e->fd_lds, raising, true)) return rc;
+    if (const int rc = module_kernel_lds(e->rtc.init, e->fd_lds, raising, true)) return rc;
     // (only a module kernel has a parameter row: the built-in resident kernels stay below 64 KiB)
-    if (resident && e->res.total * sizeof(double) > 64 * 1024) {
-      const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.resident),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                static_cast<int>(e->res.total * sizeof(double)));
-      if (ae != hipSuccess) {
-        nlsg_bfgs_destroy(e);
-        return fail(NLSG_ERR_HIP, "raising the resident kernel's dynamic LDS limit failed: %s", hipGetErrorString(ae));
-      }
-    }
+    if (resident)
+      if (const int rc = module_kernel_lds(e->rtc.resident, e->res.total * sizeof(double),
+                                           "raising the resident kernel's dynamic LDS limit failed: %s", true))
+        return rc;
   }
-  *out = e;
+  *out = guard.release();
   return NLSG_OK;
 }
 
-int nlsg_bfgs_destroy(nlsg_bfgs *e) {
-  if (!e) return NLSG_OK;
-  PhaseClock clk;
-  e->drain();
-  rtc_release(&e->rtc);
-  e->close();
-  delete e;
-  call_timing().destroy_ms = clk.lap();
-  return NLSG_OK;
-}
+int nlsg_bfgs_destroy(nlsg_bfgs *e) { return timed_destroy(e); }
 
 int nlsg_bfgs_init(nlsg_bfgs *e, const double *x0_host) {
   if (!e || !x0_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   NLSG_HIP(hipMemcpyAsync(e->p.x, x0_host, e->p.batch * e->p.n * sizeof(double),
                           hipMemcpyHostToDevice, e->stream));
@@ -380,7 +345,7 @@ int nlsg_bfgs_init(nlsg_bfgs *e, const double *x0_host) {
 
 int nlsg_bfgs_step(nlsg_bfgs *e, uint64_t iters) {
   if (!e) return fail(NLSG_ERR_INVALID_ARG, "null engine");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_bfgs_init has not been called");
   NLSG_HIP(hipSetDevice(e->cfg.device));
   if (e->resident) {  // the host cuts at a constant number of turns per launch
@@ -397,33 +362,11 @@ int nlsg_bfgs_step(nlsg_bfgs *e, uint64_t iters) {
 }
 
 int nlsg_bfgs_unfinished(nlsg_bfgs *e, uint64_t *count) {
-  if (!e || !count) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_bfgs_init has not been called");
-  NLSG_HIP(hipSetDevice(e->cfg.device));
-  NLSG_HIP(hipMemsetAsync(e->count_dev, 0, 8, e->stream));
-  hipLaunchKernelGGL(bfgs_count_unfinished_kernel,
-                     dim3(static_cast<unsigned>((e->p.batch + 255) / 256)), dim3(256), 0, e->stream,
-                     e->p, e->count_dev);
-  unsigned long long c = 0;
-  NLSG_HIP(hipMemcpyAsync(&c, e->count_dev, 8, hipMemcpyDeviceToHost, e->stream));
-  NLSG_HIP(hipStreamSynchronize(e->stream));
-  *count = c;
-  return NLSG_OK;
+  return count_problems(e, bfgs_count_unfinished_kernel, count);
 }
 
 int nlsg_bfgs_identity_count(nlsg_bfgs *e, uint64_t *count) {
-  if (!e || !count) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_bfgs_init has not been called");
-  NLSG_HIP(hipSetDevice(e->cfg.device));
-  NLSG_HIP(hipMemsetAsync(e->count_dev, 0, 8, e->stream));
-  hipLaunchKernelGGL(bfgs_count_identity_kernel,
-                     dim3(static_cast<unsigned>((e->p.batch + 255) / 256)), dim3(256), 0, e->stream,
-                     e->p, e->count_dev);
-  unsigned long long c = 0;
-  NLSG_HIP(hipMemcpyAsync(&c, e->count_dev, 8, hipMemcpyDeviceToHost, e->stream));
-  NLSG_HIP(hipStreamSynchronize(e->stream));
-  *count = c;
-  return NLSG_OK;
+  return count_problems(e, bfgs_count_identity_kernel, count);
 }
 
 int nlsg_bfgs_download(nlsg_bfgs *e, double *x_host, nlsg_status *status_host) {
@@ -433,24 +376,13 @@ int nlsg_bfgs_download(nlsg_bfgs *e, double *x_host, nlsg_status *status_host) {
   NLSG_HIP(hipStreamSynchronize(e->stream));
   const uint64_t B = e->p.batch, n = e->p.n;
   if (x_host) NLSG_HIP(hipMemcpy(x_host, e->p.x, B * n * sizeof(double), hipMemcpyDeviceToHost));
-  if (status_host) {
-    std::vector<BfgsProblem> pr(B);
-    NLSG_HIP(hipMemcpy(pr.data(), e->p.prob, B * sizeof(BfgsProblem), hipMemcpyDeviceToHost));
-    for (uint64_t i = 0; i < B; i++) {
-      nlsg_status &st = status_host[i];
-      st.f_value = pr[i].fval;
-      st.iteration = pr[i].iter;
-      st.function_calls_used = pr[i].fcalls;
-      st.gradient_evals_used = pr[i].gcalls;
-      st.hessian_evals_used = 0;
-      st.best_index = i;
-      st.val_no_change = 0;
-      st.std_err = pr[i].cur_norm;  // gradient norm at the last iterate
-      st.done = pr[i].done;
-      st.reserved = 0;
-    }
-  }
-  return NLSG_OK;
+  return download_rows(e->p.prob, B, status_host, [](const BfgsProblem &pr, uint64_t b) {
+    nlsg_status st = status_row(pr.fval, pr.iter, pr.fcalls, b);
+    st.gradient_evals_used = pr.gcalls;
+    st.std_err = pr.cur_norm;  // gradient norm at the last iterate
+    st.done = pr.done;
+    return st;
+  });
 }
 
 int nlsg_bfgs_download_state(nlsg_bfgs *e, double *g_host, double *h_host) {
@@ -483,7 +415,7 @@ int nlsg_bfgs_download_state(nlsg_bfgs *e, double *g_host, double *h_host) {
 
 int nlsg_bfgs_minimize(nlsg_bfgs *e, double *x_inout_host, nlsg_status *status_host) {
   if (!e || !x_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   PhaseClock clk;
   int rc = nlsg_bfgs_init(e, x_inout_host);
   if (rc) return rc;
@@ -508,7 +440,7 @@ int nlsg_bfgs_minimize(nlsg_bfgs *e, double *x_inout_host, nlsg_status *status_h
 
 int nlsg_bfgs_time_steps(nlsg_bfgs *e, uint64_t iters, float *ms_total, float *ms_hessian) {
   if (!e || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   if (!e->initialised) return fail(NLSG_ERR_STATE, "nlsg_bfgs_init has not been called");
   if (e->resident)
     return fail(NLSG_ERR_UNSUPPORTED, "a resident engine has no separate H kernels to bracket: time nlsg_bfgs_step");

@@ -533,6 +533,25 @@ inline uint64_t custom_params_group_stride(int64_t n_params) {
   if (n_params <= 0 || n_params > NLSG_CUSTOM_MAX_PARAMS) return 0;
   return 4 * ((static_cast<uint64_t>(n_params) + 1) / 4) + 2;
 }
+// 128-coordinate chunks of a row of n <= 1024 coordinates that a lane holds in registers: the CHUNKS a host
+// picks its kernel instantiation by (nm_chunks and lm_wide_chunks are the kernels' own statement of the rule)
+constexpr int row_chunks(uint64_t n) { return n <= 128 ? 1 : n <= 256 ? 2 : n <= 512 ? 4 : 8; }
+// An nlsg_status row with the fields no engine leaves out; the rest are what an engine that does not
+// track them has always reported, and the caller overwrites the ones it does track
+inline nlsg_status status_row(double f_value, uint64_t iteration, uint64_t function_calls, uint64_t best_index) {
+  nlsg_status st;
+  st.f_value = f_value;
+  st.iteration = iteration;
+  st.function_calls_used = function_calls;
+  st.gradient_evals_used = 0;
+  st.hessian_evals_used = 0;
+  st.best_index = best_index;
+  st.val_no_change = 0;
+  st.std_err = 0.0;
+  st.done = 1;
+  st.reserved = 0;
+  return st;
+}
 // every engine but the two resident batch ones: among create_custom's argument checks
 inline int reject_custom_params(const nlsg_custom_objective *obj) {
   if (obj && obj->n_params != 0)

@@ -230,19 +230,6 @@ int read_state(nlsg_de *e, DeState *host) {
   return NLSG_OK;
 }
 
-void fill_status(const DeState &s, nlsg_status *out) {
-  out->f_value = s.best_f;
-  out->iteration = s.iter;
-  out->function_calls_used = s.fcalls;
-  out->gradient_evals_used = 0;
-  out->hessian_evals_used = 0;
-  out->best_index = s.best_id;
-  out->val_no_change = s.val_no_change;
-  out->std_err = s.std_err;
-  out->done = s.done;
-  out->reserved = 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -283,16 +270,12 @@ int nlsg_device_count(void) {
 static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *custom, nlsg_de **out);
 
 int nlsg_de_create(const nlsg_de_config *cfg, nlsg_de **out) {
-  if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_de_create_custom");
+  if (const int rc = builtin_door(cfg, "nlsg_de")) return rc;
   return timed_create([&] { return de_create(cfg, nullptr, out); });
 }
 
 int nlsg_de_create_custom(const nlsg_de_config *cfg, const nlsg_custom_objective *obj, nlsg_de **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  if (const int prc = reject_custom_params(obj)) return prc;
+  if (const int rc = custom_door(cfg, obj, out)) return rc;
   return timed_create([&] { return de_create(cfg, obj, out); });
 }
 
@@ -321,10 +304,11 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   if (cfg->shard_n > 0xffffffffull)  // donor indices are drawn as 32-bit values inside a shard
     return fail(NLSG_ERR_UNSUPPORTED, "shard_n >= 2^32 agents per engine");
   nlsg_de *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_de", &e)) return rc;
+  CreateGuard<nlsg_de> guard(e, nlsg_de_destroy);
   e->cfg = *cfg;
   const uint64_t D = cfg->dim, n = cfg->shard_n;
-  e->chunks = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
+  e->chunks = row_chunks(D);
   e->long_rows = D > 1024;  // the reference has no limit (nlsolver.h:2302-2477)
   e->group = lane_group_of(D, false);
   if (const char *g = std::getenv("NLSG_DE_GROUPS"))  // A/B switch: 0 = one agent per wave at any D
@@ -367,10 +351,7 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
       own.event(&e->ev_head[i], hipEventDisableTiming);
     }
   }
-  if (const int rc = e->setup_status("device allocation failed: %s")) {
-    nlsg_de_destroy(e);
-    return rc;
-  }
+  if (const int rc = e->setup_status("device allocation failed: %s")) return rc;
   p.pop = cfg->pop;
   p.D = D;
   p.shard_lo = cfg->shard_lo;
@@ -420,27 +401,14 @@ static int de_create(const nlsg_de_config *cfg, const nlsg_custom_objective *cus
   e->screen_capable = (p.bound & kDeBoundScreen) != 0;
   const char *ad = std::getenv("NLSG_DE_SCREEN_ADAPT");
   e->screen_adapt = e->screen_capable && !(ad && ad[0] == '0');
-  if (custom) {
-    const int rc2 = rtc_build_de(custom, e->long_rows ? 0 : e->chunks, p.vec != 0, e->group, &e->rtc);
-    if (rc2) {
-      nlsg_de_destroy(e);
-      return rc2;
-    }
-  }
-  *out = e;
+  if (custom)
+    if (const int rc = rtc_build_de(custom, e->long_rows ? 0 : e->chunks, p.vec != 0, e->group, &e->rtc)) return rc;
+  *out = guard.release();
   return NLSG_OK;
 }
 
-int nlsg_de_destroy(nlsg_de *e) {
-  if (!e) return NLSG_OK;
-  PhaseClock clk;
-  e->drain();  // the engine's stream and the side stream
-  comm_detach(e->comm);
-  rtc_release(&e->rtc);
-  e->close();
-  delete e;
-  call_timing().destroy_ms = clk.lap();
-  return NLSG_OK;
+int nlsg_de_destroy(nlsg_de *e) {  // (drained: the engine's stream and the side stream)
+  return timed_destroy(e, [&] { comm_detach(e->comm); });
 }
 
 int nlsg_de_init(nlsg_de *e, const double *x0_host) {

@@ -27,10 +27,6 @@ bool pick_kernels(nlsg_de_batch *e) {
   });
 }
 
-int params_ready(const nlsg_de_batch *e) {
-  return e->params_ready("the objective has %d parameters: nlsg_de_batch_set_params has not been called");
-}
-
 // x0 and the seeds on their way in. Asynchronous: the caller synchronises before it returns
 int upload_inputs(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host) {
   const uint64_t B = e->batch, D = e->dim;
@@ -45,19 +41,6 @@ int start(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host) {
   if (const int rc = reset_state(e)) return rc;
   NLSG_HIP(hipStreamSynchronize(e->stream));  // the host buffers are borrowed for this call only
   return begin(e, &e->p);
-}
-
-void fill_status(const DeState &s, nlsg_status *out) {
-  out->f_value = s.best_f;
-  out->iteration = s.iter;
-  out->function_calls_used = s.fcalls;
-  out->gradient_evals_used = 0;
-  out->hessian_evals_used = 0;
-  out->best_index = s.best_id;
-  out->val_no_change = s.val_no_change;
-  out->std_err = s.std_err;
-  out->done = s.done;
-  out->reserved = 0;
 }
 
 int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective *custom,
@@ -82,8 +65,9 @@ int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective
   if (cfg->strategy != NLSG_DE_BEST && cfg->strategy != NLSG_DE_RANDOM)
     return fail(NLSG_ERR_INVALID_ARG, "unknown strategy %d", cfg->strategy);
   nlsg_de_batch *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
-  resident_shape(e, cfg, "DE", "nlsg_de_batch", cfg->pop, lds);
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_de_batch", &e)) return rc;
+  CreateGuard<nlsg_de_batch> guard(e, nlsg_de_batch_destroy);
+  resident_shape(e, cfg, "DE", cfg->pop, lds);
   const uint64_t B = cfg->batch, n = cfg->pop, D = cfg->dim;
   DeBatchParams &p = e->p;
   std::memset(&p, 0, sizeof p);
@@ -113,13 +97,11 @@ int de_batch_create(const nlsg_de_batch_config *cfg, const nlsg_custom_objective
   p.max_iter = cfg->max_iter;
   p.best_val_no_change = cfg->best_val_no_change;
   p.strategy = cfg->strategy;
-  const int rc = resident_kernels(e, custom != nullptr, kDeBatchLdsBudget, pick_kernels,
-                                  [&](ResidentRtcKernels *k) { return rtc_build_de_batch(custom, e->group, k); });
-  if (rc) {
-    nlsg_de_batch_destroy(e);
+  if (const int rc = resident_kernels(e, custom != nullptr, kDeBatchLdsBudget, pick_kernels, [&](ResidentRtcKernels *k) {
+        return rtc_build_de_batch(custom, e->group, k);
+      }))
     return rc;
-  }
-  *out = e;
+  *out = guard.release();
   return NLSG_OK;
 }
 
@@ -130,24 +112,23 @@ extern "C" {
 uint64_t nlsg_de_batch_lds_bytes(uint64_t pop, uint64_t dim) { return de_batch_lds_bytes(pop, dim); }
 
 int nlsg_de_batch_create(const nlsg_de_batch_config *cfg, nlsg_de_batch **out) {
-  return resident_create(cfg, out, "nlsg_de_batch", [&] { return de_batch_create(cfg, nullptr, out); });
+  if (const int rc = builtin_door(cfg, "nlsg_de_batch")) return rc;
+  return timed_create([&] { return de_batch_create(cfg, nullptr, out); });
 }
 
 int nlsg_de_batch_create_custom(const nlsg_de_batch_config *cfg, const nlsg_custom_objective *obj,
                                 nlsg_de_batch **out) {
-  return resident_create_custom(cfg, obj, out, [&] { return de_batch_create(cfg, obj, out); });
+  if (const int rc = runtime_door(cfg, obj, out)) return rc;  // (takes the objective's parameters itself)
+  return timed_create([&] { return de_batch_create(cfg, obj, out); });
 }
 
-int nlsg_de_batch_destroy(nlsg_de_batch *e) { return resident_destroy(e); }
+int nlsg_de_batch_destroy(nlsg_de_batch *e) { return timed_destroy(e); }
 
-int nlsg_de_batch_set_params(nlsg_de_batch *e, const double *params_host) {
-  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  return e->set_params(e->batch, params_host, "the engine's objective declares no parameters (n_params == 0)");
-}
+int nlsg_de_batch_set_params(nlsg_de_batch *e, const double *params_host) { return set_params_entry(e, params_host); }
 
 int nlsg_de_batch_init(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host) {
   if (!e || !x0_host || !seeds_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (int rc = params_ready(e)) return rc;
+  if (const int rc = e->params_ready()) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   return start(e, x0_host, seeds_host);
 }
@@ -155,11 +136,11 @@ int nlsg_de_batch_init(nlsg_de_batch *e, const double *x0_host, const uint64_t *
 int nlsg_de_batch_step(nlsg_de_batch *e, uint64_t turns) { return resident_step(e, turns); }
 
 int nlsg_de_batch_status(nlsg_de_batch *e, nlsg_status *out) {
-  return resident_status(e, e ? e->p.state : nullptr, out, fill_status);
+  return resident_status(e, e ? e->p.state : nullptr, out);
 }
 
 int nlsg_de_batch_best(nlsg_de_batch *e, double *x_host, double *f, uint64_t *index) {
-  return resident_best(e, e ? e->p.state : nullptr, x_host, f, index, fill_status);
+  return resident_best(e, e ? e->p.state : nullptr, x_host, f, index);
 }
 
 int nlsg_de_batch_download(nlsg_de_batch *e, uint64_t b, double *pop_host, double *scores_host) {
@@ -189,16 +170,16 @@ int nlsg_de_batch_upload(nlsg_de_batch *e, const double *pops_host, const double
 int nlsg_de_batch_minimize(nlsg_de_batch *e, double *x_inout_host, const uint64_t *seeds_host,
                            nlsg_status *status_host) {
   if (!e || !x_inout_host || !seeds_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (int rc = params_ready(e)) return rc;
+  if (const int rc = e->params_ready()) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   return resident_minimize(e, [&] { return start(e, x_inout_host, seeds_host); }, x_inout_host, e->p.state,
-                           status_host, fill_status);
+                           status_host);
 }
 
 int nlsg_de_batch_time_solve(nlsg_de_batch *e, const double *x0_host, const uint64_t *seeds_host,
                              uint32_t repeats, float *ms_total) {
   if (!e || !x0_host || !seeds_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (int rc = params_ready(e)) return rc;
+  if (const int rc = e->params_ready()) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   if (const int rc = upload_inputs(e, x0_host, seeds_host)) return rc;
   NLSG_HIP(hipStreamSynchronize(e->stream));

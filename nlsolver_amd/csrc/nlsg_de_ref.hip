@@ -106,16 +106,13 @@ extern "C" {
 static int de_ref_create(const nlsg_de_ref_config *cfg, const nlsg_custom_objective *custom, nlsg_de_ref **out);
 
 int nlsg_de_ref_create(const nlsg_de_ref_config *cfg, nlsg_de_ref **out) {
-  if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_de_ref_create_custom");
+  if (const int rc = builtin_door(cfg, "nlsg_de_ref")) return rc;
   return de_ref_create(cfg, nullptr, out);
 }
 
 int nlsg_de_ref_create_custom(const nlsg_de_ref_config *cfg, const nlsg_custom_objective *obj,
                               nlsg_de_ref **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM) return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  if (const int prc = reject_custom_params(obj)) return prc;
+  if (const int rc = custom_door(cfg, obj, out)) return rc;
   return de_ref_create(cfg, obj, out);
 }
 
@@ -141,7 +138,8 @@ static int de_ref_create(const nlsg_de_ref_config *cfg, const nlsg_custom_object
   if (cfg->batch > 0x7fffffffull || cfg->pop > 0x7fffffffull)
     return fail(NLSG_ERR_UNSUPPORTED, "batch and pop must be < 2^31");
   nlsg_de_ref *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_de_ref", &e)) return rc;
+  CreateGuard<nlsg_de_ref> guard(e, nlsg_de_ref_destroy);
   e->cfg = *cfg;
   DeRefParams &p = e->p;
   std::memset(&p, 0, sizeof p);
@@ -170,18 +168,10 @@ static int de_ref_create(const nlsg_de_ref_config *cfg, const nlsg_custom_object
   if (he == hipSuccess && !custom) he = prepare<NLSG_OBJ_SPHERE>(e->lds);
   if (he == hipSuccess && !custom) he = prepare<NLSG_OBJ_STYBLINSKI_TANG>(e->lds);
   if (he == hipSuccess && custom) {
-    const int rc2 = rtc_build_de_ref(custom, &e->rtc);
-    if (rc2) {
-      nlsg_de_ref_destroy(e);
-      return rc2;
-    }
-    he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.solve),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->lds));
+    if (const int rc = rtc_build_de_ref(custom, &e->rtc)) return rc;
+    if (const int rc = module_kernel_lds(e->rtc.solve, e->lds, "device setup failed: %s")) return rc;
   }
-  if (const int rc = e->setup_status()) {
-    nlsg_de_ref_destroy(e);
-    return rc;
-  }
+  if (const int rc = e->setup_status()) return rc;
   p.jump = e->jump_dev;
   p.batch = B;
   p.pop = pop;
@@ -196,18 +186,11 @@ static int de_ref_create(const nlsg_de_ref_config *cfg, const nlsg_custom_object
   p.eps = cfg->eps;
   p.fmul = cfg->minimize ? 1.0 : -1.0;  // f_multiplier, nlsolver.h:2418
   p.strategy = cfg->strategy;
-  *out = e;
+  *out = guard.release();
   return NLSG_OK;
 }
 
-int nlsg_de_ref_destroy(nlsg_de_ref *e) {
-  if (!e) return NLSG_OK;
-  e->drain();
-  rtc_release(&e->rtc);
-  e->close();
-  delete e;
-  return NLSG_OK;
-}
+int nlsg_de_ref_destroy(nlsg_de_ref *e) { return destroy_engine(e); }
 
 int nlsg_de_ref_minimize(nlsg_de_ref *e, double *x_inout_host, uint64_t *rng_state_inout_host,
                          nlsg_status *status_host) {
@@ -228,13 +211,7 @@ int nlsg_de_ref_minimize(nlsg_de_ref *e, double *x_inout_host, uint64_t *rng_sta
     rng_state_inout_host[2 * b + 1] = c.s1;
     if (c.err != kDeRefErrNone && first_err == ~0ull) first_err = b;
     if (status_host) {
-      nlsg_status &st = status_host[b];
-      st.f_value = c.f_value;
-      st.iteration = c.iter;
-      st.function_calls_used = c.fcalls;
-      st.gradient_evals_used = 0;
-      st.hessian_evals_used = 0;
-      st.best_index = c.best_id;
+      nlsg_status &st = status_host[b] = status_row(c.f_value, c.iter, c.fcalls, c.best_id);
       st.val_no_change = c.val_no_change;
       st.std_err = c.std_err;
       st.done = c.err == kDeRefErrNone ? 1 : 0;

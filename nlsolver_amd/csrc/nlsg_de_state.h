@@ -113,6 +113,14 @@ inline void de_screen_env(const char *screen, const char *retry, bool *on, uint3
   }
 }
 
+// Host side: what nlsg_de_status and nlsg_de_batch_status report of a solve's state
+inline void fill_status(const DeState &s, nlsg_status *out) {
+  *out = status_row(s.best_f, s.iter, s.fcalls, s.best_id);
+  out->val_no_change = s.val_no_change;
+  out->std_err = s.std_err;
+  out->done = s.done;
+}
+
 #endif
 
 // The miss count in bits 2-3 of a selector byte (kDeBoundScreen), as a pure function: does an

@@ -44,6 +44,19 @@ int upload_theta(nlsg_lm *e, const double *theta_host) {
                      hipMemcpyHostToDevice));
   return NLSG_OK;
 }
+// its inverse: the padding taken off again
+int download_theta(nlsg_lm *e, double *theta_host) {
+  const uint64_t B = e->p.batch, n = e->p.n;
+  if (e->wide) {
+    NLSG_HIP(hipMemcpy(theta_host, e->p.theta, B * n * 8, hipMemcpyDeviceToHost));
+    return NLSG_OK;
+  }
+  std::vector<double> padded(B * kLmN);
+  NLSG_HIP(hipMemcpy(padded.data(), e->p.theta, padded.size() * 8, hipMemcpyDeviceToHost));
+  for (uint64_t b = 0; b < B; b++)
+    for (uint64_t j = 0; j < n; j++) theta_host[b * n + j] = padded[b * kLmN + j];
+  return NLSG_OK;
+}
 
 // All problems in lock step; the host polls the number of unfinished problems every few
 // iterations. Cholesky solver: one launch per iteration (step k, then evaluation k + 1, one wave
@@ -61,11 +74,6 @@ bool lm_fd_objective(int objective) {
 size_t lm_fd_launch_lds_bytes(uint64_t n, bool ref_order) {
   if (n <= kLmN) return (64 * static_cast<size_t>(lm_fd_chunks(n)) + 128 + 66) * sizeof(double);
   return ref_order ? lm_wide_fd_lanes_lds_bytes(n) : 0;
-}
-
-// a parametrised engine solves nothing before its first rows
-int params_ready(const nlsg_lm *e) {
-  return e->params_ready("the objective has %d parameters: call nlsg_lm_set_params first");
 }
 
 // the call that hands the engine its data
@@ -197,13 +205,12 @@ int launch_solve(nlsg_lm *e) {
     }
     launched += chunk;
     if (launched >= e->p.max_iter + 1) break;
-    NLSG_HIP(hipMemsetAsync(e->count_dev, 0, 8, e->stream));
-    hipLaunchKernelGGL(lm_count_unfinished_kernel,
-                       dim3(static_cast<unsigned>((e->p.batch + 255) / 256)), dim3(256), 0,
-                       e->stream, e->p, e->count_dev);
-    unsigned long long open = 0;
-    NLSG_HIP(hipMemcpyAsync(&open, e->count_dev, 8, hipMemcpyDeviceToHost, e->stream));
-    NLSG_HIP(hipStreamSynchronize(e->stream));
+    uint64_t open = 0;
+    if (const int rc = device_count(e->stream, e->count_dev, &open, [&] {
+          hipLaunchKernelGGL(lm_count_unfinished_kernel, dim3(static_cast<unsigned>((e->p.batch + 255) / 256)),
+                             dim3(256), 0, e->stream, e->p, e->count_dev);
+        }))
+      return rc;
     if (open == 0) break;
   }
   return NLSG_OK;
@@ -217,41 +224,29 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
 extern "C" {
 
 int nlsg_lm_create(const nlsg_lm_config *cfg, nlsg_lm **out) {
-  if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_lm_create_custom");
-  if (cfg && cfg->objective == NLSG_OBJ_LINK_REGRESSION)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_LINK_REGRESSION engines are made by nlsg_lm_create_link");
-  if (cfg && cfg->objective == NLSG_OBJ_CURVE_MODEL)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CURVE_MODEL engines are made by nlsg_lm_create_curve");
+  if (const int rc = builtin_door(cfg, "nlsg_lm")) return rc;
+  if (const int rc = builtin_door(cfg, "nlsg_lm", NLSG_OBJ_LINK_REGRESSION, "NLSG_OBJ_LINK_REGRESSION", "link")) return rc;
+  if (const int rc = builtin_door(cfg, "nlsg_lm", NLSG_OBJ_CURVE_MODEL, "NLSG_OBJ_CURVE_MODEL", "curve")) return rc;
   return timed_create([&] { return lm_create(cfg, nullptr, out); });
 }
 
 int nlsg_lm_create_custom(const nlsg_lm_config *cfg, const nlsg_custom_objective *obj, nlsg_lm **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  if (const int prc = reject_custom_params(obj)) return prc;
+  if (const int rc = custom_door(cfg, obj, out)) return rc;
   return timed_create([&] { return lm_create(cfg, obj, out); });
 }
 
 int nlsg_lm_create_params(const nlsg_lm_config *cfg, const nlsg_custom_objective *obj, nlsg_lm **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int rc = runtime_door(cfg, obj, out)) return rc;
   return timed_create([&] { return lm_create(cfg, obj, out, true); });
 }
 
 int nlsg_lm_create_link(const nlsg_lm_config *cfg, const nlsg_lm_link *link, nlsg_lm **out) {
-  if (!cfg || !link) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_LINK_REGRESSION)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_LINK_REGRESSION");
+  if (const int rc = runtime_door(cfg, link, out, NLSG_OBJ_LINK_REGRESSION, "NLSG_OBJ_LINK_REGRESSION")) return rc;
   return timed_create([&] { return lm_create(cfg, nullptr, out, false, link); });
 }
 
 int nlsg_lm_create_curve(const nlsg_lm_config *cfg, const nlsg_lm_curve *curve, nlsg_lm **out) {
-  if (!cfg || !curve || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CURVE_MODEL)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CURVE_MODEL");
+  if (const int rc = runtime_door(cfg, curve, out, NLSG_OBJ_CURVE_MODEL, "NLSG_OBJ_CURVE_MODEL")) return rc;
   return timed_create([&] { return lm_create(cfg, nullptr, out, false, nullptr, curve); });
 }
 
@@ -269,7 +264,7 @@ int nlsg_lm_set_params(nlsg_lm *e, const double *params_host) {
   if (e->curve_k)
     return fail(NLSG_ERR_INVALID_ARG, "a curve model has no p(k): per-problem constants ride in columns of t "
                                       "(nlsg_lm_set_curve_data)");
-  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (nlsg_lm_create_params)");
+  return e->set_params(params_host);
 }
 
 }  // extern "C"
@@ -321,7 +316,8 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   if (curve && (!curve->body || !curve->body[0]))
     return fail(NLSG_ERR_INVALID_ARG, "a curve model needs a body (nlsg_lm_curve)");
   nlsg_lm *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_lm", &e)) return rc;
+  CreateGuard<nlsg_lm> guard(e, nlsg_lm_destroy);
   e->cfg = *cfg;
   e->wide = wide;
   e->n_params = with_params ? custom->n_params : 0;
@@ -379,38 +375,16 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
                                   : reinterpret_cast<const void *>(lm_wide_chol_step_kernel<512, false>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, lm_wchol_lds_bytes(512));
   }
-  if (const int rc = e->setup_status()) {
-    nlsg_lm_destroy(e);
-    return rc;
-  }
-  if (custom) {
-    const uint64_t n = cfg->n;
-    const int rc2 = rtc_build_lm(custom, !wide ? 0 : lm_wide_chunks(n), ref_order, &e->rtc);
-    if (rc2) {
-      nlsg_lm_destroy(e);
-      return rc2;
-    }
-  }
+  if (const int rc = e->setup_status()) return rc;
+  if (custom)
+    if (const int rc = rtc_build_lm(custom, !wide ? 0 : lm_wide_chunks(cfg->n), ref_order, &e->rtc)) return rc;
   if (link) {
-    int rc2 = rtc_build_lm_link(link, cfg->n, &e->rtc);
-    if (!rc2 && cfg->n > 128 && cfg->n <= 256) {  // 70 KB of dynamic LDS: the module API's opt-in
-      const hipError_t ae = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.iter),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                static_cast<int>(sizeof(LmWide256Shared)));
-      if (ae != hipSuccess) rc2 = fail(NLSG_ERR_HIP, "device setup failed: %s", hipGetErrorString(ae));
-    }
-    if (rc2) {
-      nlsg_lm_destroy(e);
-      return rc2;
-    }
+    if (const int rc = rtc_build_lm_link(link, cfg->n, &e->rtc)) return rc;
+    if (cfg->n > 128 && cfg->n <= 256)  // 70 KB of dynamic LDS: the module API's opt-in
+      if (const int rc = module_kernel_lds(e->rtc.iter, sizeof(LmWide256Shared), "device setup failed: %s")) return rc;
   }
-  if (curve) {
-    const int rc2 = rtc_build_lm_curve(curve, cfg->n, &e->rtc);
-    if (rc2) {
-      nlsg_lm_destroy(e);
-      return rc2;
-    }
-  }
+  if (curve)
+    if (const int rc = rtc_build_lm_curve(curve, cfg->n, &e->rtc)) return rc;
   p.A = e->A_dev;
   p.y = e->y_dev;
   p.Aw = e->A_dev;
@@ -430,22 +404,13 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   p.verdict = (wide && !fd && !e->wide_valu) ? 1 : 0;
   p.eps_h = std::pow(DBL_EPSILON, 1.0 / 4.0);  // fin_diff_h's step (:1454)
   e->has_data = fd;  // the model is the objective itself
-  *out = e;
+  *out = guard.release();
   return NLSG_OK;
 }
 
 extern "C" {
 
-int nlsg_lm_destroy(nlsg_lm *e) {
-  if (!e) return NLSG_OK;
-  PhaseClock clk;
-  e->drain();
-  rtc_release(&e->rtc);
-  e->close();
-  delete e;
-  call_timing().destroy_ms = clk.lap();
-  return NLSG_OK;
-}
+int nlsg_lm_destroy(nlsg_lm *e) { return timed_destroy(e); }
 
 int nlsg_lm_set_data(nlsg_lm *e, const double *a_host, const double *y_host) {
   if (!e || !a_host || !y_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
@@ -576,7 +541,7 @@ int nlsg_lm_minimize(nlsg_lm *e, double *theta_inout_host, nlsg_status *status_h
                      double *lambda_out_host) {
   if (!e || !theta_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   PhaseClock clk;
   int rc = upload_theta(e, theta_inout_host);
@@ -587,35 +552,25 @@ int nlsg_lm_minimize(nlsg_lm *e, double *theta_inout_host, nlsg_status *status_h
   NLSG_HIP(launches_status());
   NLSG_HIP(hipStreamSynchronize(e->stream));
   call_timing().iterate_ms = clk.lap();
-  const uint64_t B = e->p.batch, n = e->p.n;
-  if (e->wide) {
-    NLSG_HIP(hipMemcpy(theta_inout_host, e->p.theta, B * n * 8, hipMemcpyDeviceToHost));
-  } else {
-    std::vector<double> padded(B * kLmN);
-    NLSG_HIP(hipMemcpy(padded.data(), e->p.theta, padded.size() * 8, hipMemcpyDeviceToHost));
-    for (uint64_t b = 0; b < B; b++)
-      for (uint64_t j = 0; j < n; j++) theta_inout_host[b * n + j] = padded[b * kLmN + j];
-  }
-  std::vector<LmProblem> pr(B);
-  NLSG_HIP(hipMemcpy(pr.data(), e->p.prob, B * sizeof(LmProblem), hipMemcpyDeviceToHost));
-  for (uint64_t b = 0; b < B; b++) {
-    if (status_host) {
-      nlsg_status &st = status_host[b];
-      st.f_value = pr[b].f;
-      st.iteration = pr[b].iter;
-      // f, grad and hess are evaluated together; behind the default functors every probe of
-      // fin_diff (4 n) and fin_diff_h (16 n^2) is a call of the objective
-      st.function_calls_used = pr[b].fcalls * (e->p.fd ? 1 + 4 * n + 16 * n * n : 1);
-      st.gradient_evals_used = pr[b].fcalls;
-      st.hessian_evals_used = pr[b].fcalls;
-      st.best_index = b;
-      st.val_no_change = 0;
-      st.std_err = pr[b].lambda;
-      st.done = pr[b].done;
-      st.reserved = 0;
-    }
-    if (lambda_out_host) lambda_out_host[b] = pr[b].lambda;
-  }
+  rc = download_theta(e, theta_inout_host);
+  if (rc) return rc;
+  // f, grad and hess are evaluated together; behind the default functors every probe of
+  // fin_diff (4 n) and fin_diff_h (16 n^2) is a call of the objective
+  const uint64_t n = e->p.n, calls_per_eval = e->p.fd ? 1 + 4 * n + 16 * n * n : 1;
+  rc = download_rows(
+      e->p.prob, e->p.batch, status_host,
+      [&](const LmProblem &pr, uint64_t b) {
+        nlsg_status st = status_row(pr.f, pr.iter, pr.fcalls * calls_per_eval, b);
+        st.gradient_evals_used = pr.fcalls;
+        st.hessian_evals_used = pr.fcalls;
+        st.std_err = pr.lambda;
+        st.done = pr.done;
+        return st;
+      },
+      [&](const LmProblem &pr, uint64_t b) {
+        if (lambda_out_host) lambda_out_host[b] = pr.lambda;
+      });
+  if (rc) return rc;
   call_timing().readback_ms = clk.lap();
   return NLSG_OK;
 }
@@ -676,7 +631,7 @@ int nlsg_lm_covariance(nlsg_lm *e, const double *theta_host, int32_t scale, doub
 
 int nlsg_lm_time_solve(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total) {
   if (!e || !theta0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));
   NLSG_HIP(hipSetDevice(e->cfg.device));
   return time_repeats(
@@ -688,7 +643,7 @@ int nlsg_lm_time_solve(nlsg_lm *e, const double *theta0_host, uint32_t repeats, 
 // for every problem) on the engine's stream, HIP events around each launch.
 int nlsg_lm_time_eval_kernel(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total) {
   if (!e || !theta0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;  // (before anything that could launch an evaluation)
+  if (const int prc = e->params_ready()) return prc;  // (before anything that could launch an evaluation)
   if (e->p.fd) return fail(NLSG_ERR_UNSUPPORTED, "Gauss-Newton model only");
   if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));
   NLSG_HIP(hipSetDevice(e->cfg.device));
@@ -707,7 +662,7 @@ int nlsg_lm_time_eval_kernel(nlsg_lm *e, const double *theta0_host, uint32_t rep
 // back-substitution, update) after one evaluation at theta0 has produced H and g.
 int nlsg_lm_time_qr_kernel(nlsg_lm *e, const double *theta0_host, uint32_t repeats, float *ms_total) {
   if (!e || !theta0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;  // (before anything that could launch an evaluation)
+  if (const int prc = e->params_ready()) return prc;  // (before anything that could launch an evaluation)
   if (e->p.fd) return fail(NLSG_ERR_UNSUPPORTED, "Gauss-Newton model only");
   if (e->wide) return fail(NLSG_ERR_UNSUPPORTED, "the tinyqr step kernel: n <= 64 only");
   if (!e->has_data) return fail(NLSG_ERR_STATE, "%s has not been called", data_call(e));

@@ -1,6 +1,5 @@
 // nlsolver_amd/csrc/nlsg_nm.hip — host side of the batched Nelder-Mead engine + C-ABI.
 #include <cstdlib>
-#include <vector>
 
 #include "nlsg_engine.h"
 #include "nlsg_nm_kernels.h"
@@ -67,11 +66,6 @@ void launch(nlsg_nm *e) {
   }));
 }
 
-// a parametrised engine solves nothing before its first rows
-int params_ready(const nlsg_nm *e) {
-  return e->params_ready("the objective has %d parameters: call nlsg_nm_set_params first");
-}
-
 int upload_bounds(nlsg_nm *e, const double *upper_host, const double *lower_host) {
   if (!e->cfg.bounded) return NLSG_OK;
   if (!upper_host || !lower_host)
@@ -88,23 +82,17 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
                      bool with_params = false);
 
 int nlsg_nm_create(const nlsg_nm_config *cfg, nlsg_nm **out) {
-  if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_nm_create_custom");
+  if (const int rc = builtin_door(cfg, "nlsg_nm")) return rc;
   return nm_create(cfg, nullptr, out);
 }
 
 int nlsg_nm_create_custom(const nlsg_nm_config *cfg, const nlsg_custom_objective *obj, nlsg_nm **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  if (const int prc = reject_custom_params(obj)) return prc;
+  if (const int rc = custom_door(cfg, obj, out)) return rc;
   return nm_create(cfg, obj, out);
 }
 
 int nlsg_nm_create_params(const nlsg_nm_config *cfg, const nlsg_custom_objective *obj, nlsg_nm **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int rc = runtime_door(cfg, obj, out)) return rc;
   return nm_create(cfg, obj, out, true);
 }
 
@@ -115,11 +103,7 @@ uint64_t nlsg_nm_lds_bytes(uint64_t dim, uint32_t flags) {
   return nm_launch_lds_bytes(dim, 1, (flags & NLSG_NM_REFERENCE_ORDER) != 0);
 }
 
-int nlsg_nm_set_params(nlsg_nm *e, const double *params_host) {
-  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  return e->set_params(e->p.batch, params_host,
-                       "the engine's objective declares no parameters (nlsg_nm_create_params)");
-}
+int nlsg_nm_set_params(nlsg_nm *e, const double *params_host) { return set_params_entry(e, params_host); }
 
 static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *custom, nlsg_nm **out,
                      bool with_params) {
@@ -146,7 +130,8 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
                                             "nlsg_nm_create_custom"))
       return prc;
   nlsg_nm *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_nm", &e)) return rc;
+  CreateGuard<nlsg_nm> guard(e, nlsg_nm_destroy);
   e->cfg = *cfg;
   NmParams &p = e->p;
   std::memset(&p, 0, sizeof p);
@@ -178,19 +163,11 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
   if (he == hipSuccess) he = prepare<NLSG_OBJ_STYBLINSKI_TANG>(chunks);
   if (he == hipSuccess) he = prepare<NLSG_OBJ_RASTRIGIN>(chunks);
   if (he == hipSuccess && custom) {
-    const int rc2 = rtc_build_nm(custom, e->driver ? 0 : chunks, seq, &e->rtc);
-    if (rc2) {
-      nlsg_nm_destroy(e);
-      return rc2;
-    }
+    if (const int rc = rtc_build_nm(custom, e->driver ? 0 : chunks, seq, &e->rtc)) return rc;
     // the module API's counterpart of prepare<>(): allow the simplex-sized dynamic LDS
-    he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.solve),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->lds));
+    if (const int rc = module_kernel_lds(e->rtc.solve, e->lds, "device setup failed: %s")) return rc;
   }
-  if (const int rc = e->setup_status()) {
-    nlsg_nm_destroy(e);
-    return rc;
-  }
+  if (const int rc = e->setup_status()) return rc;
   p.upper = e->upper_dev;
   p.lower = e->lower_dev;
   p.params = e->params_dev;
@@ -213,56 +190,36 @@ static int nm_create(const nlsg_nm_config *cfg, const nlsg_custom_objective *cus
     const int w = sw ? std::atoi(sw) : 16;
     p.seq = w < 1 ? 1 : (w > 16 ? 16 : w);
   }
-  *out = e;
+  *out = guard.release();
   return NLSG_OK;
 }
 
-int nlsg_nm_destroy(nlsg_nm *e) {
-  if (!e) return NLSG_OK;
-  e->drain();
-  rtc_release(&e->rtc);
-  e->close();
-  delete e;
-  return NLSG_OK;
-}
+int nlsg_nm_destroy(nlsg_nm *e) { return destroy_engine(e); }
 
 int nlsg_nm_minimize(nlsg_nm *e, double *x_inout_host, const double *upper_host,
                      const double *lower_host, nlsg_status *status_host, double *eps_out_host) {
   if (!e || !x_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  int rc = upload_bounds(e, upper_host, lower_host);
-  if (rc) return rc;
-  const uint64_t B = e->p.batch, n = e->p.n;
-  NLSG_HIP(hipMemcpy(e->p.x, x_inout_host, B * n * 8, hipMemcpyHostToDevice));
-  launch(e);
-  NLSG_HIP(launches_status());
-  NLSG_HIP(hipStreamSynchronize(e->stream));
-  NLSG_HIP(hipMemcpy(x_inout_host, e->p.x, B * n * 8, hipMemcpyDeviceToHost));
-  std::vector<NmProblem> pr(B);
-  NLSG_HIP(hipMemcpy(pr.data(), e->p.prob, B * sizeof(NmProblem), hipMemcpyDeviceToHost));
-  for (uint64_t b = 0; b < B; b++) {
-    if (status_host) {
-      nlsg_status &st = status_host[b];
-      st.f_value = pr[b].f;
-      st.iteration = pr[b].iter;
-      st.function_calls_used = pr[b].fcalls;
-      st.gradient_evals_used = 0;
-      st.hessian_evals_used = 0;
-      st.best_index = b;
-      st.val_no_change = 0;
-      st.std_err = pr[b].eps;
-      st.done = 1;
-      st.reserved = 0;
-    }
-    if (eps_out_host) eps_out_host[b] = pr[b].eps;
-  }
-  return NLSG_OK;
+  if (const int rc = upload_bounds(e, upper_host, lower_host)) return rc;
+  const uint64_t B = e->p.batch;
+  return one_launch_minimize(e, e->p.x, B * e->p.n, x_inout_host, [&] { launch(e); }, [&] {
+    return download_rows(
+        e->p.prob, B, status_host,
+        [](const NmProblem &pr, uint64_t b) {
+          nlsg_status st = status_row(pr.f, pr.iter, pr.fcalls, b);
+          st.std_err = pr.eps;
+          return st;
+        },
+        [&](const NmProblem &pr, uint64_t b) {
+          if (eps_out_host) eps_out_host[b] = pr.eps;
+        });
+  });
 }
 
 int nlsg_nm_phase_cycles(nlsg_nm *e, const double *x0_host, uint64_t *cycles_host) {
   if (!e || !x0_host || !cycles_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   const uint64_t B = e->p.batch;
   // a measurement aid: its buffer exists from its first use on, and it profiles the unbounded
@@ -282,18 +239,9 @@ int nlsg_nm_phase_cycles(nlsg_nm *e, const double *x0_host, uint64_t *cycles_hos
 
 int nlsg_nm_time_solve(nlsg_nm *e, const double *x0_host, uint32_t repeats, float *ms_total) {
   if (!e || !x0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  return time_repeats(
-      e->stream, e->ev0, e->ev1, repeats, ms_total,
-      [&]() -> int {
-        launch(e);
-        return NLSG_OK;
-      },
-      [&]() -> int {  // the start point again, outside the interval
-        NLSG_HIP(hipMemcpy(e->p.x, x0_host, e->p.batch * e->p.n * 8, hipMemcpyHostToDevice));
-        return NLSG_OK;
-      });
+  return one_launch_time_solve(e, e->p.x, e->p.batch * e->p.n, x0_host, repeats, ms_total, [&] { launch(e); });
 }
 
 }  // extern "C"

@@ -1,6 +1,4 @@
 // nlsolver_amd/csrc/nlsg_nmpso.hip — host side of the batched Nelder-Mead / PSO hybrid + C-ABI.
-#include <vector>
-
 #include "nlsg_engine.h"
 #include "nlsg_nmpso_kernels.h"
 #include "nlsg_rtc.h"
@@ -48,11 +46,6 @@ void launch(nlsg_nmpso *e) {
   }));
 }
 
-// a parametrised engine solves nothing before its first rows
-int params_ready(const nlsg_nmpso *e) {
-  return e->params_ready("the objective has %d parameters: call nlsg_nmpso_set_params first");
-}
-
 int upload_bounds(nlsg_nmpso *e, const double *lower_host, const double *upper_host) {
   if (!e->p.bounded) return NLSG_OK;
   if (!lower_host || !upper_host)
@@ -70,25 +63,19 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
 extern "C" {
 
 int nlsg_nmpso_create(const nlsg_nmpso_config *cfg, nlsg_nmpso **out) {
-  if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_nmpso_create_custom");
+  if (const int rc = builtin_door(cfg, "nlsg_nmpso")) return rc;
   return hyb_create(cfg, nullptr, out);
 }
 
 int nlsg_nmpso_create_custom(const nlsg_nmpso_config *cfg, const nlsg_custom_objective *obj,
                              nlsg_nmpso **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  if (const int prc = reject_custom_params(obj)) return prc;
+  if (const int rc = custom_door(cfg, obj, out)) return rc;
   return hyb_create(cfg, obj, out);
 }
 
 int nlsg_nmpso_create_params(const nlsg_nmpso_config *cfg, const nlsg_custom_objective *obj,
                              nlsg_nmpso **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int rc = runtime_door(cfg, obj, out)) return rc;
   return hyb_create(cfg, obj, out, true);
 }
 
@@ -98,10 +85,7 @@ uint64_t nlsg_nmpso_lds_bytes(uint64_t dim) {
   return dim <= kHybMaxN ? sizeof(HybShared) : hyb_view_bytes(dim);
 }
 
-int nlsg_nmpso_set_params(nlsg_nmpso *e, const double *params_host) {
-  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (nlsg_nmpso_create_params)");
-}
+int nlsg_nmpso_set_params(nlsg_nmpso *e, const double *params_host) { return set_params_entry(e, params_host); }
 
 }  // extern "C"
 
@@ -127,7 +111,8 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
                                             "nlsg_nmpso_create_custom"))
       return prc;
   nlsg_nmpso *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_nmpso", &e)) return rc;
+  CreateGuard<nlsg_nmpso> guard(e, nlsg_nmpso_destroy);
   e->cfg = *cfg;
   e->n_params = with_params ? custom->n_params : 0;
   HybParams &p = e->p;
@@ -154,17 +139,9 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
                                static_cast<int>(hyb_view_bytes(128ull * C)));
     });
   }
-  if (const int rc = e->setup_status()) {
-    nlsg_nmpso_destroy(e);
-    return rc;
-  }
-  if (custom) {
-    const int rc2 = rtc_build_nmpso(custom, wide_chunks(n), &e->rtc);
-    if (rc2) {
-      nlsg_nmpso_destroy(e);
-      return rc2;
-    }
-  }
+  if (const int rc = e->setup_status()) return rc;
+  if (custom)
+    if (const int rc = rtc_build_nmpso(custom, wide_chunks(n), &e->rtc)) return rc;
   p.upper = e->upper_dev;
   p.lower = e->lower_dev;
   p.zero = e->zero_dev;
@@ -185,69 +162,33 @@ static int hyb_create(const nlsg_nmpso_config *cfg, const nlsg_custom_objective 
   p.eps = cfg->eps;
   p.fmul = cfg->minimize ? 1.0 : -1.0;
   p.bounded = cfg->bounded ? 1 : 0;
-  *out = e;
+  *out = guard.release();
   return NLSG_OK;
 }
 
 extern "C" {
 
-int nlsg_nmpso_destroy(nlsg_nmpso *e) {
-  if (!e) return NLSG_OK;
-  e->drain();
-  rtc_release(&e->rtc);
-  e->close();
-  delete e;
-  return NLSG_OK;
-}
+int nlsg_nmpso_destroy(nlsg_nmpso *e) { return destroy_engine(e); }
 
 int nlsg_nmpso_minimize(nlsg_nmpso *e, double *x_inout_host, const double *lower_host,
                         const double *upper_host, nlsg_status *status_host) {
   if (!e || !x_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  int rc = upload_bounds(e, lower_host, upper_host);
-  if (rc) return rc;
-  const uint64_t B = e->p.batch, n = e->p.n;
-  NLSG_HIP(hipMemcpy(e->p.x, x_inout_host, B * n * 8, hipMemcpyHostToDevice));
-  launch(e);
-  NLSG_HIP(launches_status());
-  NLSG_HIP(hipStreamSynchronize(e->stream));
-  NLSG_HIP(hipMemcpy(x_inout_host, e->p.x, B * n * 8, hipMemcpyDeviceToHost));
-  if (status_host) {
-    std::vector<HybProblem> pr(B);
-    NLSG_HIP(hipMemcpy(pr.data(), e->p.prob, B * sizeof(HybProblem), hipMemcpyDeviceToHost));
-    for (uint64_t b = 0; b < B; b++) {
-      nlsg_status &st = status_host[b];
-      st.f_value = pr[b].f;
-      st.iteration = pr[b].iter;
-      st.function_calls_used = pr[b].fcalls;
-      st.gradient_evals_used = 0;
-      st.hessian_evals_used = 0;
-      st.best_index = b;
-      st.val_no_change = 0;
-      st.std_err = 0.0;
-      st.done = 1;
-      st.reserved = 0;
-    }
-  }
-  return NLSG_OK;
+  if (const int rc = upload_bounds(e, lower_host, upper_host)) return rc;
+  const uint64_t B = e->p.batch;
+  return one_launch_minimize(e, e->p.x, B * e->p.n, x_inout_host, [&] { launch(e); }, [&] {
+    return download_rows(e->p.prob, B, status_host,
+                         [](const HybProblem &pr, uint64_t b) { return status_row(pr.f, pr.iter, pr.fcalls, b); });
+  });
 }
 
 int nlsg_nmpso_time_solve(nlsg_nmpso *e, const double *x0_host, uint32_t repeats, float *ms_total) {
   if (!e || !x0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   if (e->p.bounded) return fail(NLSG_ERR_UNSUPPORTED, "timing aid of the unbounded overloads");
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  return time_repeats(
-      e->stream, e->ev0, e->ev1, repeats, ms_total,
-      [&]() -> int {
-        launch(e);
-        return NLSG_OK;
-      },
-      [&]() -> int {  // the start point again, outside the interval
-        NLSG_HIP(hipMemcpy(e->p.x, x0_host, e->p.batch * e->p.n * 8, hipMemcpyHostToDevice));
-        return NLSG_OK;
-      });
+  return one_launch_time_solve(e, e->p.x, e->p.batch * e->p.n, x0_host, repeats, ms_total, [&] { launch(e); });
 }
 
 }  // extern "C"

@@ -136,19 +136,6 @@ int read_state(nlsg_pso *e, PsoState *host) {
   return NLSG_OK;
 }
 
-void fill_status(const PsoState &s, nlsg_status *out) {
-  out->f_value = s.gbest_val;
-  out->iteration = s.iter;
-  out->function_calls_used = s.fevals;
-  out->gradient_evals_used = 0;
-  out->hessian_evals_used = 0;
-  out->best_index = s.gbest_idx;
-  out->val_no_change = s.val_no_change;
-  out->std_err = s.std_err;
-  out->done = s.done;
-  out->reserved = 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -156,17 +143,13 @@ extern "C" {
 static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *custom, nlsg_pso **out);
 
 int nlsg_pso_create(const nlsg_pso_config *cfg, nlsg_pso **out) {
-  if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_pso_create_custom");
+  if (const int rc = builtin_door(cfg, "nlsg_pso")) return rc;
   return timed_create([&] { return pso_create(cfg, nullptr, out); });
 }
 
 int nlsg_pso_create_custom(const nlsg_pso_config *cfg, const nlsg_custom_objective *obj,
                            nlsg_pso **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  if (const int prc = reject_custom_params(obj)) return prc;
+  if (const int rc = custom_door(cfg, obj, out)) return rc;
   return timed_create([&] { return pso_create(cfg, obj, out); });
 }
 
@@ -193,10 +176,11 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
   if (cfg->shard_n > (1ull << 32))
     return fail(NLSG_ERR_UNSUPPORTED, "shard_n > 2^32 particles per engine");
   nlsg_pso *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_pso", &e)) return rc;
+  CreateGuard<nlsg_pso> guard(e, nlsg_pso_destroy);
   e->cfg = *cfg;
   const uint64_t D = cfg->dim, n = cfg->shard_n;
-  e->chunks = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
+  e->chunks = row_chunks(D);
   e->long_rows = D > 1024;  // the reference has no limit (nlsolver.h:2498-2742)
   e->group = lane_group_of(D, false);
   if (const char *g = std::getenv("NLSG_PSO_GROUPS"))  // A/B switch: 0 = one particle per wave at any D
@@ -229,10 +213,7 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
   if (he == hipSuccess)
     he = hipMemcpy(e->tab_dev, tab.data(), p.tab_len * sizeof(double), hipMemcpyHostToDevice);
   e->timing_events();
-  if (const int rc = e->setup_status("device allocation failed: %s")) {
-    nlsg_pso_destroy(e);
-    return rc;
-  }
+  if (const int rc = e->setup_status("device allocation failed: %s")) return rc;
   p.lower = e->lower_dev;
   p.upper = e->upper_dev;
   p.zero = e->zero_dev;
@@ -251,32 +232,20 @@ static int pso_create(const nlsg_pso_config *cfg, const nlsg_custom_objective *c
   p.seed = cfg->seed;
   p.type = cfg->type;
   p.bounded = cfg->bounded ? 1 : 0;
-  if (custom) {
-    const int rc2 = rtc_build_pso(custom, e->long_rows ? 0 : e->chunks, p.D % 2 == 0, cfg->type, e->group, &e->rtc);
-    if (rc2) {
-      nlsg_pso_destroy(e);
-      return rc2;
-    }
-  }
+  if (custom)
+    if (const int rc = rtc_build_pso(custom, e->long_rows ? 0 : e->chunks, p.D % 2 == 0, cfg->type, e->group, &e->rtc))
+      return rc;
   if (cfg->type == NLSG_PSO_ACCELERATED && !e->group && !e->long_rows) {
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0)
       e->move_grid_cap = move_blocks_per_cu() * static_cast<unsigned>(cus);
   }
-  *out = e;
+  *out = guard.release();
   return NLSG_OK;
 }
 
 int nlsg_pso_destroy(nlsg_pso *e) {
-  if (!e) return NLSG_OK;
-  PhaseClock clk;
-  e->drain();
-  comm_detach(e->comm);
-  rtc_release(&e->rtc);
-  e->close();
-  delete e;
-  call_timing().destroy_ms = clk.lap();
-  return NLSG_OK;
+  return timed_destroy(e, [&] { comm_detach(e->comm); });
 }
 
 int nlsg_pso_init(nlsg_pso *e, const double *lower_host, const double *upper_host) {

@@ -29,10 +29,6 @@ bool pick_kernels(nlsg_pso_batch *e) {
   });
 }
 
-int params_ready(const nlsg_pso_batch *e) {
-  return e->params_ready("the objective has %d parameters: nlsg_pso_batch_set_params has not been called");
-}
-
 int upload_inputs(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
                   const uint64_t *seeds_host) {
   const uint64_t B = e->batch, D = e->dim;
@@ -48,19 +44,6 @@ int start(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
   if (const int rc = upload_inputs(e, lower_host, upper_host, seeds_host)) return rc;
   if (const int rc = reset_state(e)) return rc;
   return begin(e, &e->p);
-}
-
-void fill_status(const PsoState &s, nlsg_status *out) {
-  out->f_value = s.gbest_val;
-  out->iteration = s.iter;
-  out->function_calls_used = s.fevals;
-  out->gradient_evals_used = 0;
-  out->hessian_evals_used = 0;
-  out->best_index = s.gbest_idx;
-  out->val_no_change = s.val_no_change;
-  out->std_err = s.std_err;
-  out->done = s.done;
-  out->reserved = 0;
 }
 
 int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objective *custom,
@@ -84,8 +67,9 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
                                      kPsoBatchLdsBudget))
     return rc;
   nlsg_pso_batch *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
-  resident_shape(e, cfg, "PSO", "nlsg_pso_batch", cfg->n_particles, lds);
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_pso_batch", &e)) return rc;
+  CreateGuard<nlsg_pso_batch> guard(e, nlsg_pso_batch_destroy);
+  resident_shape(e, cfg, "PSO", cfg->n_particles, lds);
   const uint64_t B = cfg->batch, n = cfg->n_particles, D = cfg->dim;
   const bool vanilla = cfg->type == NLSG_PSO_VANILLA;
   PsoBatchParams &p = e->p;
@@ -133,14 +117,11 @@ int pso_batch_create(const nlsg_pso_batch_config *cfg, const nlsg_custom_objecti
   q.best_val_no_change = cfg->best_val_no_change;
   q.type = cfg->type;
   q.bounded = cfg->bounded ? 1 : 0;
-  const int rc = resident_kernels(e, custom != nullptr, kPsoBatchLdsBudget, pick_kernels, [&](ResidentRtcKernels *k) {
-    return rtc_build_pso_batch(custom, e->group, cfg->type, k);
-  });
-  if (rc) {
-    nlsg_pso_batch_destroy(e);
+  if (const int rc = resident_kernels(e, custom != nullptr, kPsoBatchLdsBudget, pick_kernels, [&](ResidentRtcKernels *k) {
+        return rtc_build_pso_batch(custom, e->group, cfg->type, k);
+      }))
     return rc;
-  }
-  *out = e;
+  *out = guard.release();
   return NLSG_OK;
 }
 
@@ -153,25 +134,24 @@ uint64_t nlsg_pso_batch_lds_bytes(uint64_t n_particles, uint64_t dim, int32_t ty
 }
 
 int nlsg_pso_batch_create(const nlsg_pso_batch_config *cfg, nlsg_pso_batch **out) {
-  return resident_create(cfg, out, "nlsg_pso_batch", [&] { return pso_batch_create(cfg, nullptr, out); });
+  if (const int rc = builtin_door(cfg, "nlsg_pso_batch")) return rc;
+  return timed_create([&] { return pso_batch_create(cfg, nullptr, out); });
 }
 
 int nlsg_pso_batch_create_custom(const nlsg_pso_batch_config *cfg, const nlsg_custom_objective *obj,
                                  nlsg_pso_batch **out) {
-  return resident_create_custom(cfg, obj, out, [&] { return pso_batch_create(cfg, obj, out); });
+  if (const int rc = runtime_door(cfg, obj, out)) return rc;  // (takes the objective's parameters itself)
+  return timed_create([&] { return pso_batch_create(cfg, obj, out); });
 }
 
-int nlsg_pso_batch_destroy(nlsg_pso_batch *e) { return resident_destroy(e); }
+int nlsg_pso_batch_destroy(nlsg_pso_batch *e) { return timed_destroy(e); }
 
-int nlsg_pso_batch_set_params(nlsg_pso_batch *e, const double *params_host) {
-  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  return e->set_params(e->batch, params_host, "the engine's objective declares no parameters (n_params == 0)");
-}
+int nlsg_pso_batch_set_params(nlsg_pso_batch *e, const double *params_host) { return set_params_entry(e, params_host); }
 
 int nlsg_pso_batch_init(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
                         const uint64_t *seeds_host) {
   if (!e || !lower_host || !upper_host || !seeds_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (int rc = params_ready(e)) return rc;
+  if (const int rc = e->params_ready()) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   return start(e, lower_host, upper_host, seeds_host);
 }
@@ -179,11 +159,11 @@ int nlsg_pso_batch_init(nlsg_pso_batch *e, const double *lower_host, const doubl
 int nlsg_pso_batch_step(nlsg_pso_batch *e, uint64_t turns) { return resident_step(e, turns); }
 
 int nlsg_pso_batch_status(nlsg_pso_batch *e, nlsg_status *out) {
-  return resident_status(e, e ? e->p.q.state : nullptr, out, fill_status);
+  return resident_status(e, e ? e->p.q.state : nullptr, out);
 }
 
 int nlsg_pso_batch_best(nlsg_pso_batch *e, double *x_host, double *f, uint64_t *index) {
-  return resident_best(e, e ? e->p.q.state : nullptr, x_host, f, index, fill_status);
+  return resident_best(e, e ? e->p.q.state : nullptr, x_host, f, index);
 }
 
 int nlsg_pso_batch_download(nlsg_pso_batch *e, uint64_t b, double *pos_host, double *vel_host,
@@ -211,17 +191,17 @@ int nlsg_pso_batch_minimize(nlsg_pso_batch *e, double *x_out_host, const double 
                             nlsg_status *status_host) {
   if (!e || !x_out_host || !lower_host || !upper_host || !seeds_host)
     return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (int rc = params_ready(e)) return rc;
+  if (const int rc = e->params_ready()) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   return resident_minimize(e, [&] { return start(e, lower_host, upper_host, seeds_host); }, x_out_host,
-                           e->p.q.state, status_host, fill_status);
+                           e->p.q.state, status_host);
 }
 
 int nlsg_pso_batch_time_solve(nlsg_pso_batch *e, const double *lower_host, const double *upper_host,
                               const uint64_t *seeds_host, uint32_t repeats, float *ms_total) {
   if (!e || !lower_host || !upper_host || !seeds_host || !ms_total)
     return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (int rc = params_ready(e)) return rc;
+  if (const int rc = e->params_ready()) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
   if (const int rc = upload_inputs(e, lower_host, upper_host, seeds_host)) return rc;
   return resident_time_solve(e, repeats, ms_total);

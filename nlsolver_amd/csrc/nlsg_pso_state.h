@@ -105,6 +105,14 @@ inline std::vector<double> pso_inertia_table(double inertia, uint64_t max_iter, 
   }
   return tab;
 }
+
+// Host side: what nlsg_pso_status and nlsg_pso_batch_status report of a solve's state
+inline void fill_status(const PsoState &s, nlsg_status *out) {
+  *out = status_row(s.gbest_val, s.iter, s.fevals, s.gbest_idx);
+  out->val_no_change = s.val_no_change;
+  out->std_err = s.std_err;
+  out->done = s.done;
+}
 #endif
 
 }  // namespace nlsg

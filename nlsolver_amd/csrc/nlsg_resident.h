@@ -2,7 +2,8 @@
 // nlsg_pso_batch.hip): `batch` keyed solves of one shape, one workgroup each, an init kernel and a kernel
 // that runs the turns, built in or of the engine's own run-time module. An engine file keeps its config
 // checks, its blocks and parameter struct (`p`, which both kernels take by value), pick_kernels, its input
-// upload, fill_status, download and upload; what it has in common with the other is here, on EngineBase.
+// upload, download and upload; what it has in common with the other is here, on EngineBase. A solve's
+// state becomes a status through fill_status(const State &, nlsg_status *) of nlsg_de_state.h / nlsg_pso_state.h.
 // Host only, as nlsg_engine.h.
 #pragma once
 #ifndef __HIPCC_RTC__
@@ -11,7 +12,6 @@
 #include <vector>
 
 #include "nlsg_engine.h"
-#include "nlsg_rtc.h"
 
 #pragma GCC visibility push(hidden)
 namespace nlsg {
@@ -21,8 +21,11 @@ namespace nlsg {
 constexpr uint64_t kResidentTurnsPerLaunch = 1024;
 
 struct ResidentEngine : EngineBase {  // (n_params: a row per solve, nlsg_X_batch_set_params)
+  ResidentEngine() {  // (this pair's own words for the two parameter errors)
+    params_first = "the objective has %d parameters: %s_set_params has not been called";
+    no_params = "the engine's objective declares no parameters (n_params == 0)";
+  }
   const char *name = "";         // "DE", "PSO": who speaks in an error
-  const char *api = "";          // "nlsg_de_batch", "nlsg_pso_batch": the prefix of its entry points
   size_t lds = 0;                // dynamic LDS of a turn workgroup
   int group = 0;                 // lanes per row: 4 / 8 / 16 / 32, or 64 = one wave per row
   const void *init_fn = nullptr, *turn_fn = nullptr;  // built-in objectives
@@ -120,9 +123,9 @@ int read_states(ResidentEngine *e, const State *states_dev, std::vector<State> &
   return NLSG_OK;
 }
 
-// a status per solve, through the engine's fill_status(const State &, nlsg_status *)
-template <typename State, typename Fill>
-int read_statuses(ResidentEngine *e, const State *states_dev, nlsg_status *out, Fill fill_status) {
+// a status per solve
+template <typename State>
+int read_statuses(ResidentEngine *e, const State *states_dev, nlsg_status *out) {
   std::vector<State> s;
   if (const int rc = read_states(e, states_dev, s)) return rc;
   for (uint64_t b = 0; b < e->batch; b++) fill_status(s[b], out + b);
@@ -130,17 +133,17 @@ int read_statuses(ResidentEngine *e, const State *states_dev, nlsg_status *out, 
 }
 
 // nlsg_X_batch_status
-template <typename E, typename State, typename Fill>
-int resident_status(E *e, const State *states_dev, nlsg_status *out, Fill fill_status) {
+template <typename E, typename State>
+int resident_status(E *e, const State *states_dev, nlsg_status *out) {
   if (!e || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
   if (const int rc = e->ready()) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  return read_statuses(e, states_dev, out, fill_status);
+  return read_statuses(e, states_dev, out);
 }
 
 // nlsg_X_batch_best: every output may be null
-template <typename E, typename State, typename Fill>
-int resident_best(E *e, const State *states_dev, double *x_host, double *f, uint64_t *index, Fill fill_status) {
+template <typename E, typename State>
+int resident_best(E *e, const State *states_dev, double *x_host, double *f, uint64_t *index) {
   if (!e) return fail(NLSG_ERR_INVALID_ARG, "null engine");
   if (const int rc = e->ready()) return rc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
@@ -157,9 +160,8 @@ int resident_best(E *e, const State *states_dev, double *x_host, double *f, uint
 }
 
 // nlsg_X_batch_minimize behind its argument checks: start() takes the inputs up and ends in begin()
-template <typename E, typename Start, typename State, typename Fill>
-int resident_minimize(E *e, Start start, double *x_host, const State *states_dev, nlsg_status *status_host,
-                      Fill fill_status) {
+template <typename E, typename Start, typename State>
+int resident_minimize(E *e, Start start, double *x_host, const State *states_dev, nlsg_status *status_host) {
   PhaseClock clk;
   int rc = start();
   if (rc) return rc;
@@ -170,7 +172,7 @@ int resident_minimize(E *e, Start start, double *x_host, const State *states_dev
   // x = the best row (nlsolver.h:2444, :2601)
   NLSG_HIP(hipMemcpyAsync(x_host, e->best_x, e->batch * e->dim * 8, hipMemcpyDeviceToHost, e->stream));
   if (status_host) {
-    rc = read_statuses(e, states_dev, status_host, fill_status);
+    rc = read_statuses(e, states_dev, status_host);
     if (rc) return rc;
   } else {
     NLSG_HIP(hipStreamSynchronize(e->stream));
@@ -222,11 +224,10 @@ int resident_checks(const Cfg *cfg, const nlsg_custom_objective *custom, const c
   return NLSG_OK;
 }
 
-// what a fresh engine knows before its blocks: its names, the config, the shape's launch geometry
+// what a fresh engine knows before its blocks: its name, the config, the shape's launch geometry
 template <typename E, typename Cfg>
-void resident_shape(E *e, const Cfg *cfg, const char *name, const char *api, uint64_t rows, uint64_t lds) {
+void resident_shape(E *e, const Cfg *cfg, const char *name, uint64_t rows, uint64_t lds) {
   e->name = name;
-  e->api = api;
   e->cfg = *cfg;
   e->lds = lds;
   e->batch = cfg->batch;
@@ -242,7 +243,7 @@ void resident_shape(E *e, const Cfg *cfg, const char *name, const char *api, uin
 // smaller engine must not lower it under a kept larger one (as nlsg_nm.hip does). A run-time module is the
 // engine's own; its static LDS (the parameter row) comes off the budget.
 // pick_kernels(e): init_fn and turn_fn of a built-in objective, false for a value outside the lists.
-// build_module(&e->rtc): the engine's rtc_build_*. Not NLSG_OK: the caller destroys the engine.
+// build_module(&e->rtc): the engine's rtc_build_*.
 template <typename E, typename Pick, typename Build>
 int resident_kernels(E *e, bool custom, uint64_t budget, Pick pick_kernels, Build build_module) {
   hipError_t &he = e->own.err;
@@ -253,39 +254,11 @@ int resident_kernels(E *e, bool custom, uint64_t budget, Pick pick_kernels, Buil
   }
   if (he == hipSuccess && custom) {
     if (const int rc = build_module(&e->rtc)) return rc;
-    he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.turns),
-                             hipFuncAttributeMaxDynamicSharedMemorySize,
-                             static_cast<int>(budget - custom_params_lds_bytes(e->n_params)));
+    if (const int rc = module_kernel_lds(e->rtc.turns, budget - custom_params_lds_bytes(e->n_params),
+                                         "device setup failed: %s"))
+      return rc;
   }
   return e->setup_status();
-}
-
-// nlsg_X_batch_create / _create_custom around the engine's own create
-template <typename Cfg, typename Create>
-int resident_create(const Cfg *cfg, const void *out, const char *api, Create create) {
-  if (cfg && out && cfg->struct_size == sizeof(Cfg) && cfg->objective == NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by %s_create_custom", api);
-  return timed_create(create);
-}
-template <typename Cfg, typename Create>
-int resident_create_custom(const Cfg *cfg, const nlsg_custom_objective *obj, const void *out, Create create) {
-  if (!cfg || !obj || !out) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->struct_size == sizeof(Cfg) && cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  return timed_create(create);
-}
-
-// nlsg_X_batch_destroy
-template <typename E>
-int resident_destroy(E *e) {
-  if (!e) return NLSG_OK;
-  PhaseClock clk;
-  e->drain();
-  rtc_release(&e->rtc);
-  e->close();
-  delete e;
-  call_timing().destroy_ms = clk.lap();
-  return NLSG_OK;
 }
 
 }  // namespace nlsg

@@ -1,6 +1,4 @@
 // nlsolver_amd/csrc/nlsg_sann.hip — host side of the batched simulated-annealing engine + C-ABI.
-#include <vector>
-
 #include "nlsg_engine.h"
 #include "nlsg_rtc.h"
 #include "nlsg_sann_kernels.h"
@@ -33,11 +31,6 @@ int sann_group_for(uint64_t D, int64_t n_params) {
   if (group && n_params > 0 && kSannTableBytes + sann_group_rows_bytes(group, n_params) > kSannLdsBudget) return 0;
   return group;
 }
-// a parametrised engine launches nothing before its first rows
-int params_ready(const nlsg_sann *e) {
-  return e->params_ready("the objective has %d parameters: call nlsg_sann_set_params first");
-}
-
 void launch_anneal(nlsg_sann *e, uint64_t iter_begin, uint64_t iter_end) {
   // waves: one per chain, or one per 64 / group chains
   const uint64_t per_wave = e->group ? 64 / e->group : 1;
@@ -89,25 +82,19 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
 extern "C" {
 
 int nlsg_sann_create(const nlsg_sann_config *cfg, nlsg_sann **out) {
-  if (cfg && cfg->objective == NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "NLSG_OBJ_CUSTOM engines are made by nlsg_sann_create_custom");
+  if (const int rc = builtin_door(cfg, "nlsg_sann")) return rc;
   return sann_create(cfg, nullptr, out);
 }
 
 int nlsg_sann_create_custom(const nlsg_sann_config *cfg, const nlsg_custom_objective *obj,
                             nlsg_sann **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
-  if (const int prc = reject_custom_params(obj)) return prc;
+  if (const int rc = custom_door(cfg, obj, out)) return rc;
   return sann_create(cfg, obj, out);
 }
 
 int nlsg_sann_create_params(const nlsg_sann_config *cfg, const nlsg_custom_objective *obj,
                             nlsg_sann **out) {
-  if (!cfg || !obj) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (cfg->objective != NLSG_OBJ_CUSTOM)
-    return fail(NLSG_ERR_INVALID_ARG, "cfg.objective must be NLSG_OBJ_CUSTOM");
+  if (const int rc = runtime_door(cfg, obj, out)) return rc;
   return sann_create(cfg, obj, out, true);
 }
 
@@ -126,10 +113,7 @@ uint64_t nlsg_sann_lds_bytes(uint64_t dim, int32_t n_params) {
   return group ? sann_group_rows_bytes(group, n_params) : 4 * custom_params_lds_bytes(n_params);
 }
 
-int nlsg_sann_set_params(nlsg_sann *e, const double *params_host) {
-  if (!e || !params_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  return e->set_params(e->p.batch, params_host, "the engine's objective declares no parameters (nlsg_sann_create_params)");
-}
+int nlsg_sann_set_params(nlsg_sann *e, const double *params_host) { return set_params_entry(e, params_host); }
 
 }  // extern "C"
 
@@ -153,10 +137,11 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
     if (const int prc = check_custom_params(custom, kSannTableBytes, "nlsg_sann", "nlsg_sann_create_custom", 4))
       return prc;
   nlsg_sann *e = nullptr;
-  if (const int rc = open_engine(cfg->device, cfg->stream, &e)) return rc;
+  if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_sann", &e)) return rc;
+  CreateGuard<nlsg_sann> guard(e, nlsg_sann_destroy);
   e->cfg = *cfg;
   const uint64_t B = cfg->batch, D = cfg->dim;
-  e->chunks = D <= 128 ? 1 : D <= 256 ? 2 : D <= 512 ? 4 : 8;
+  e->chunks = row_chunks(D);
   e->n_params = with_params ? custom->n_params : 0;
   e->group = sann_group_for(D, e->n_params);
   e->lds = static_cast<unsigned>(nlsg_sann_lds_bytes(D, e->n_params));
@@ -170,26 +155,12 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
   e->alloc_params(B, e->n_params);
   own.zeroed(&e->zero_dev, 16);
   e->timing_events();
-  if (const int rc = e->setup_status()) {
-    nlsg_sann_destroy(e);
-    return rc;
-  }
+  if (const int rc = e->setup_status()) return rc;
   if (custom) {
-    const int rc2 = rtc_build_sann(custom, D > 1024 ? 0 : e->chunks, D % 2 == 0, e->group, &e->rtc);
-    if (rc2) {
-      nlsg_sann_destroy(e);
-      return rc2;
-    }
-    // (the module API's counterpart of hipFuncSetAttribute on a kernel symbol: the rows can pass the 64 KiB
-    // a launch may take without it)
-    if (e->lds > 64 * 1024) {
-      const hipError_t he = hipFuncSetAttribute(reinterpret_cast<const void *>(e->rtc.anneal),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(e->lds));
-      if (he != hipSuccess) {
-        nlsg_sann_destroy(e);
-        return fail(NLSG_ERR_HIP, "raising the kernel's dynamic LDS limit failed: %s", hipGetErrorString(he));
-      }
-    }
+    if (const int rc = rtc_build_sann(custom, D > 1024 ? 0 : e->chunks, D % 2 == 0, e->group, &e->rtc)) return rc;
+    // (the rows can pass the 64 KiB a launch may take without the opt-in)
+    if (const int rc = module_kernel_lds(e->rtc.anneal, e->lds, "raising the kernel's dynamic LDS limit failed: %s", true))
+      return rc;
   }
   p.params = e->params_dev;
   p.zero = e->zero_dev;
@@ -200,65 +171,31 @@ static int sann_create(const nlsg_sann_config *cfg, const nlsg_custom_objective 
   p.inner = cfg->temperature_iter ? cfg->temperature_iter - 1 : 0;  // for (j = 1; j < t_iter; j++)
   p.temp_max = cfg->temperature_max;
   p.fmul = cfg->minimize ? 1.0 : -1.0;
-  *out = e;
+  *out = guard.release();
   return NLSG_OK;
 }
 
 extern "C" {
 
-int nlsg_sann_destroy(nlsg_sann *e) {
-  if (!e) return NLSG_OK;
-  e->drain();
-  rtc_release(&e->rtc);
-  e->close();
-  delete e;
-  return NLSG_OK;
-}
+int nlsg_sann_destroy(nlsg_sann *e) { return destroy_engine(e); }
 
 int nlsg_sann_minimize(nlsg_sann *e, double *x_inout_host, nlsg_status *status_host) {
   if (!e || !x_inout_host) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  const uint64_t B = e->p.batch, D = e->p.D;
-  NLSG_HIP(hipMemcpy(e->p.x, x_inout_host, B * D * 8, hipMemcpyHostToDevice));
-  launch_solve(e);
-  NLSG_HIP(launches_status());
-  NLSG_HIP(hipStreamSynchronize(e->stream));
-  NLSG_HIP(hipMemcpy(x_inout_host, e->p.x, B * D * 8, hipMemcpyDeviceToHost));
-  if (status_host) {
-    std::vector<SannProblem> pr(B);
-    NLSG_HIP(hipMemcpy(pr.data(), e->p.prob, B * sizeof(SannProblem), hipMemcpyDeviceToHost));
-    for (uint64_t b = 0; b < B; b++) {
-      nlsg_status &st = status_host[b];
-      st.f_value = pr[b].best;
-      st.iteration = pr[b].iter;
-      st.function_calls_used = pr[b].fcalls;
-      st.gradient_evals_used = 0;
-      st.hessian_evals_used = 0;
-      st.best_index = b;
-      st.val_no_change = 0;
-      st.std_err = 0.0;
-      st.done = 1;
-      st.reserved = 0;
-    }
-  }
-  return NLSG_OK;
+  const uint64_t B = e->p.batch;
+  return one_launch_minimize(e, e->p.x, B * e->p.D, x_inout_host, [&] { launch_solve(e); }, [&] {
+    return download_rows(e->p.prob, B, status_host, [](const SannProblem &pr, uint64_t b) {
+      return status_row(pr.best, pr.iter, pr.fcalls, b);
+    });
+  });
 }
 
 int nlsg_sann_time_solve(nlsg_sann *e, const double *x0_host, uint32_t repeats, float *ms_total) {
   if (!e || !x0_host || !ms_total) return fail(NLSG_ERR_INVALID_ARG, "null argument");
-  if (const int prc = params_ready(e)) return prc;
+  if (const int prc = e->params_ready()) return prc;
   NLSG_HIP(hipSetDevice(e->cfg.device));
-  return time_repeats(
-      e->stream, e->ev0, e->ev1, repeats, ms_total,
-      [&]() -> int {
-        launch_solve(e);
-        return NLSG_OK;
-      },
-      [&]() -> int {  // the start point again, outside the interval
-        NLSG_HIP(hipMemcpy(e->p.x, x0_host, e->p.batch * e->p.D * 8, hipMemcpyHostToDevice));
-        return NLSG_OK;
-      });
+  return one_launch_time_solve(e, e->p.x, e->p.batch * e->p.D, x0_host, repeats, ms_total, [&] { launch_solve(e); });
 }
 
 }  // extern "C"

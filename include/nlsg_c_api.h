@@ -564,6 +564,25 @@ typedef enum {
  * probe per lane on the base point's shared terms: 1.18e7 against 6.7e6 iteration-problems/s at
  * Rosenbrock-16D x 8192, 5 x past 64 parameters. */
 typedef enum { NLSG_LM_CHOLESKY = 0, NLSG_LM_QR = 1, NLSG_LM_CHOLESKY_REFERENCE_ORDER = 2 } nlsg_lm_solver;
+/* NLSG_LM_RESIDENT: the whole while(true) loop of 3513-3542 in ONE kernel, for batches of small fits. A
+ * flag bit OR-ed into nlsg_lm_config::solver and into the argument of nlsg_lm_set_solver; the low byte is the
+ * nlsg_lm_solver. One 64-lane workgroup per problem evaluates at x0 and then runs stop tests, damping,
+ * Cholesky solve, update and evaluation in a loop: H and g go from the matrix cores' accumulators into the
+ * step's LDS image, theta stays in LDS, f / prev / lambda / iter / fcalls in registers; a curve model of
+ * m <= 64 keeps its data in registers for the whole solve. A problem whose stop test fires frees its slot;
+ * the host launches ceil((max_iter + 1) / 256) times at most and counts unfinished problems between
+ * launches only. Same functions, same order of every sum: theta, every status field and lambda are the
+ * lock-step engine's bit for bit, wherever a launch is cut. Gauss-Newton models (NLSG_OBJ_TANH_REGRESSION,
+ * nlsg_lm_create_link, nlsg_lm_create_curve), NLSG_LM_CHOLESKY, n <= 64: with NLSG_LM_QR, with
+ * NLSG_LM_CHOLESKY_REFERENCE_ORDER, with a finite-difference objective or with n > 64 the flag is
+ * NLSG_ERR_UNSUPPORTED, any other bit above the low byte NLSG_ERR_INVALID_ARG — behind every check of the
+ * unflagged value, before the device is touched. The kernels are compiled at run time (hiprtc): a
+ * TanhRegression engine compiles its own the first time the driver is chosen (kept by source afterwards),
+ * and a process that cannot load hiprtc answers NLSG_ERR_UNSUPPORTED. nlsg_lm_time_eval_kernel and
+ * nlsg_lm_covariance run the lock-step evaluation launch whatever the driver. Ask whether a library has
+ * the mode with nlsg_lm_lds_bytes(2, NLSG_LM_CHOLESKY | NLSG_LM_RESIDENT) != 0 — one older than the flag
+ * answers 0. */
+#define NLSG_LM_RESIDENT 256
 
 typedef struct {
   uint32_t struct_size;
@@ -575,7 +594,7 @@ typedef struct {
                            * fin_diff_h at accuracy 1 (nlsolver.h:3494-3511, 1385-1413,
                            * 1446-1515), every probe evaluated on the device; Cholesky only;
                            * m is ignored and there is no nlsg_lm_set_data            */
-  int32_t solver;         /* nlsg_lm_solver                                          */
+  int32_t solver;         /* nlsg_lm_solver, | NLSG_LM_RESIDENT                      */
   uint64_t batch;         /* independent problems                                    */
   uint64_t m;             /* residuals per problem                                   */
   uint64_t n;             /* parameters per problem (<= 1024; NLSG_LM_QR: <= 64)     */
@@ -657,7 +676,9 @@ int nlsg_lm_set_curve_data(nlsg_lm *e, const double *t_host, const double *y_hos
 /* Dynamic LDS bytes of the launch that evaluates an objective of n parameters through the default
  * finite-difference functors (what a custom objective runs), solver = NLSG_LM_CHOLESKY or
  * NLSG_LM_CHOLESKY_REFERENCE_ORDER. 0 outside 1 <= n <= 1024 and for any other solver — and in tree
- * order past 64 parameters, whose evaluation kernel takes none. Host only, no device. */
+ * order past 64 parameters, whose evaluation kernel takes none. Host only, no device.
+ * With solver = NLSG_LM_CHOLESKY | NLSG_LM_RESIDENT: the LDS bytes of the resident workgroup of a regression
+ * model, for 1 <= n <= 64, and 0 outside (the probe for the mode; see NLSG_LM_RESIDENT). */
 uint64_t nlsg_lm_lds_bytes(uint64_t n, int32_t solver);
 int nlsg_lm_destroy(nlsg_lm *e);
 /* design matrices A [batch][m][n] row-major and targets y [batch][m] (copied to HBM, in chunks
@@ -668,7 +689,8 @@ int nlsg_lm_set_data(nlsg_lm *e, const double *a_host, const double *y_host);
 int nlsg_host_alloc(void **out, uint64_t bytes);
 int nlsg_host_free(void *ptr);
 /* Switch the damped-system solver of an existing engine (the model data stays resident): the
- * next nlsg_lm_minimize uses it. */
+ * next nlsg_lm_minimize uses it. NLSG_LM_CHOLESKY | NLSG_LM_RESIDENT switches to the resident driver, the
+ * value without the flag back to lock step. */
 int nlsg_lm_set_solver(nlsg_lm *e, int32_t solver);
 /* Whole solve() of every problem in one launch: theta [batch][n] in/out, one status per
  * problem (f, iterations, f/grad/hess evaluation counts), final damping per problem

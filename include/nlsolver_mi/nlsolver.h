@@ -409,7 +409,9 @@ struct is_device_objective<C, std::void_t<decltype(C::nlsg_objective)>> : std::t
   /* parameter covariance of a Gauss-Newton fit */                                                        \
   X(lm_covariance, false)                                                                                 \
   /* with it, whether the library has the resident BFGS mode (has_bfgs_resident) */                       \
-  X(bfgs_lds_bytes, false)
+  X(bfgs_lds_bytes, false)                                                                                \
+  /* with it, whether the library has the resident LM mode (has_lm_resident) */                           \
+  X(lm_lds_bytes, false)
 
 // Lazily bound entry points of libnlsolver_hip.so. Search order: $NLSG_LIBRARY,
 // then the default loader path.
@@ -432,6 +434,8 @@ class api {
   }
   // a library older than NLSG_BFGS_RESIDENT answers 0 to the flag it does not know
   bool has_bfgs_resident() const { return bfgs_lds_bytes && bfgs_lds_bytes(2, NLSG_BFGS_RESIDENT) != 0; }
+  // the same for NLSG_LM_RESIDENT
+  bool has_lm_resident() const { return lm_lds_bytes && lm_lds_bytes(2, NLSG_LM_CHOLESKY | NLSG_LM_RESIDENT) != 0; }
   // the resident engine's LDS need with the parameter row; throws when the library cannot take
   // parameters or the shape does not fit (`shape_need` = nlsg_*_batch_lds_bytes, 0 = out of range)
   void require_params_fit(bool has_engine, bool has_set, uint64_t shape_need, int32_t n_params,
@@ -685,6 +689,21 @@ constexpr uint64_t pso_resident_lds_budget = 160 * 1024;
 enum class bfgs_driver { turns, resident };
 inline bfgs_driver &bfgs_driver_mode() {
   static bfgs_driver mode = env_mode("NLSG_BFGS_DRIVER", "turns", "resident") ? bfgs_driver::resident : bfgs_driver::turns;
+  return mode;
+}
+// How LevenbergMarquardt<...>::minimize / minimize_batch run a device fit of a Gauss-Newton model (tanh, link,
+// curve) with at most 64 parameters:
+//   turns     the lock-step engine: one launch per iteration, H and g through memory between them (default)
+//   resident  the whole loop in one kernel, a workgroup per problem with H, g and theta in LDS
+//             (NLSG_LM_RESIDENT): the same theta, status and lambda bit for bit. Taken when n <= 64, the
+//             solver is Cholesky and the library has the mode (nlsg_lm_lds_bytes(n, NLSG_LM_CHOLESKY |
+//             NLSG_LM_RESIDENT) != 0) and can load hiprtc; the lock-step engine solves everything else
+//             (DESIGN.md §6g).
+// Set before the solves it should govern: `nlsolver::device::lm_driver_mode() = lm_driver::resident`,
+// or the environment variable NLSG_LM_DRIVER = turns | resident (read at first use).
+enum class lm_driver { turns, resident };
+inline lm_driver &lm_driver_mode() {
+  static lm_driver mode = env_mode("NLSG_LM_DRIVER", "turns", "resident") ? lm_driver::resident : lm_driver::turns;
   return mode;
 }
 }  // namespace device
@@ -2252,6 +2271,14 @@ class LevenbergMarquardt {
     cfg.down = downward_mult;
     cfg.max_iter = max_iter;
     cfg.f_delta = f_delta;
+    // device::lm_driver::resident: the same fit in the resident kernel, where it is taken (a process that
+    // cannot load hiprtc stays with the turns: the library would answer NLSG_ERR_UNSUPPORTED)
+    if constexpr (device::has_nlls_objective<Callable>::value) {
+      if (device::lm_driver_mode() == device::lm_driver::resident && n <= 64 && cfg.solver == NLSG_LM_CHOLESKY &&
+          api.has_lm_resident() && api.lm_lds_bytes(n, NLSG_LM_CHOLESKY | NLSG_LM_RESIDENT) != 0 &&
+          api.rtc_load(std::getenv("NLSG_HIPRTC")) == NLSG_OK)
+        cfg.solver = NLSG_LM_CHOLESKY | NLSG_LM_RESIDENT;
+    }
     device::engine<nlsg_lm> eng(api.lm_destroy);
     if constexpr (!device::has_nlls_objective<Callable>::value) {  // the objective itself, a Custom included
       device::create(eng, cfg, f, api.lm_create, api.lm_create_custom, api.lm_create_params, api.lm_set_params, B);

@@ -111,6 +111,8 @@ OBJ_TANH_REGRESSION = 32
 OBJ_LINK_REGRESSION = 33  # NLSG_OBJ_LINK_REGRESSION: nlsg_lm_create_link
 OBJ_CURVE_MODEL = 34  # NLSG_OBJ_CURVE_MODEL: nlsg_lm_create_curve
 LM_CHOLESKY, LM_QR, LM_CHOLESKY_REFERENCE_ORDER = 0, 1, 2
+LM_RESIDENT = 256  # NLSG_LM_RESIDENT: a flag OR-ed into the solver (the low byte is the nlsg_lm_solver)
+LM_RESIDENT_CUT = 256  # turns per launch of the resident driver (kLmResidentCut)
 LM_COV_RESIDUAL, LM_COV_ABSOLUTE = 0, 1  # nlsg_lm_cov_scale: cov = s2 (J^T J)^-1, or (J^T J)^-1
 
 

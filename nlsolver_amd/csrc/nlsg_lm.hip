@@ -26,6 +26,7 @@ struct nlsg_lm : EngineBase {  // (n_params: nlsg_lm_create_params, a row per pr
   LmRtcKernels rtc;  // objective == NLSG_OBJ_CUSTOM: the kernel hiprtc built for it;
                      // NLSG_OBJ_LINK_REGRESSION: the Gauss-Newton evaluation kernel on the user's link
   bool link = false;  // nlsg_lm_create_link
+  bool resident = false;  // NLSG_LM_RESIDENT: the whole loop in rtc.resident (cfg.solver holds the low byte only)
   uint32_t curve_k = 0;  // nlsg_lm_create_curve: data per observation (0: no curve engine); rtc.iter is
                          // lm_curve_iter_kernel, A_dev the repacked (t, y) of nlsg_lm_set_curve_data
 };
@@ -168,7 +169,74 @@ void launch_wide_eval(nlsg_lm *e, int first) {
   }));
 }
 
+// A solver argument of the C-ABI: the nlsg_lm_solver in the low byte, NLSG_LM_RESIDENT above it. A value
+// below 256 (negative ones included) is a plain solver, known or not, and answers as it always did.
+struct LmSolverArg {
+  int32_t solver;
+  bool resident, unknown_bits;
+};
+LmSolverArg lm_solver_arg(int32_t v) {
+  if (v < 256) return {v, false, false};
+  return {v & 0xff, (v & NLSG_LM_RESIDENT) != 0, (v & ~(0xff | NLSG_LM_RESIDENT)) != 0};
+}
+// the rules of the flag, behind every check of the plain value; nothing here touches the device
+int lm_resident_door(const LmSolverArg &a, int32_t given, bool fd, bool ref_order, uint64_t n) {
+  if (a.unknown_bits)
+    return fail(NLSG_ERR_INVALID_ARG, "unknown bits in solver 0x%x: above the low byte only NLSG_LM_RESIDENT (256) "
+                                      "is defined", static_cast<unsigned>(given));
+  if (!a.resident) return NLSG_OK;
+  if (a.solver == NLSG_LM_QR)
+    return fail(NLSG_ERR_UNSUPPORTED, "NLSG_LM_RESIDENT runs the Cholesky step: the tinyqr step is a 512-thread "
+                                      "workgroup of its own (NLSG_LM_QR)");
+  if (ref_order)
+    return fail(NLSG_ERR_UNSUPPORTED, "NLSG_LM_RESIDENT restates the tree-order turn: not with "
+                                      "NLSG_LM_CHOLESKY_REFERENCE_ORDER");
+  if (fd)
+    return fail(NLSG_ERR_UNSUPPORTED, "NLSG_LM_RESIDENT covers the Gauss-Newton models (tanh, link, curve): a "
+                                      "finite-difference objective runs in lock step");
+  if (n > kLmN)
+    return fail(NLSG_ERR_UNSUPPORTED, "NLSG_LM_RESIDENT runs one wave per problem: n = %llu > %d",
+                (unsigned long long)n, kLmN);
+  return NLSG_OK;
+}
+// the resident kernel of the engine's model: a link or curve module has it already, a tanh engine builds its
+// own here (hiprtc; the code object is kept by its source)
+int lm_resident_kernel_ready(nlsg_lm *e) {
+  if (e->rtc.resident) return NLSG_OK;
+  if (const int rc = rtc_build_lm_tanh_resident(&e->rtc)) {
+    if (rc == NLSG_ERR_UNSUPPORTED)
+      return fail(NLSG_ERR_UNSUPPORTED, "NLSG_LM_RESIDENT needs the run-time compiler, and hiprtc cannot be "
+                                        "loaded in this process (nlsg_rtc_load): the lock-step driver runs without it");
+    return rc;
+  }
+  return NLSG_OK;
+}
+
+// NLSG_LM_RESIDENT: every unfinished problem makes up to kLmResidentCut turns per launch; the host counts the
+// unfinished ones between launches only
+int launch_resident_solve(nlsg_lm *e) {
+  const uint64_t total = e->p.max_iter + 1;  // max_iter iterations plus the turn whose stop test fires
+  const unsigned grid = static_cast<unsigned>(e->p.batch);
+  uint64_t made = 0;
+  for (int first = 1;; first = 0) {
+    uint32_t turns = static_cast<uint32_t>(std::min<uint64_t>(total - made, kLmResidentCut));
+    void *args[] = {&e->p, &first, &turns};
+    launch_module_kernel(e->rtc.resident, grid, 64, 0, e->stream, args);
+    made += turns;
+    if (made >= total) break;
+    uint64_t open = 0;
+    if (const int rc = device_count(e->stream, e->count_dev, &open, [&] {
+          hipLaunchKernelGGL(lm_count_unfinished_kernel, dim3(static_cast<unsigned>((e->p.batch + 255) / 256)),
+                             dim3(256), 0, e->stream, e->p, e->count_dev);
+        }))
+      return rc;
+    if (open == 0) break;
+  }
+  return NLSG_OK;
+}
+
 int launch_solve(nlsg_lm *e) {
+  if (e->resident) return launch_resident_solve(e);
   const dim3 grid(static_cast<unsigned>(e->p.batch));
   const bool qr = e->cfg.solver == NLSG_LM_QR, fd = e->p.fd != 0;
   if (e->wide)
@@ -254,6 +322,9 @@ int nlsg_lm_create_curve(const nlsg_lm_config *cfg, const nlsg_lm_curve *curve, 
 // custom objective runs): 0 for a shape that model rejects (n outside 1 .. 1024, the QR solver, an
 // unknown solver) — and for tree order past 64 parameters, whose evaluation kernel takes none.
 uint64_t nlsg_lm_lds_bytes(uint64_t n, int32_t solver) {
+  if (solver >= 256)  // the resident workgroup of a regression model: the lock-step kernel's block
+    return solver == (NLSG_LM_CHOLESKY | NLSG_LM_RESIDENT) && n >= 1 && n <= kLmN
+               ? (kLmTri + 128) * sizeof(double) : 0;
   if (n < 1 || n > kLmWideMaxN) return 0;
   if (solver != NLSG_LM_CHOLESKY && solver != NLSG_LM_CHOLESKY_REFERENCE_ORDER) return 0;
   return lm_fd_launch_lds_bytes(n, solver == NLSG_LM_CHOLESKY_REFERENCE_ORDER);
@@ -277,13 +348,15 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
     return fail(NLSG_ERR_INVALID_ARG, "nlsg_lm_config size mismatch (%u vs %zu)", cfg->struct_size,
                 sizeof(nlsg_lm_config));
   const bool fd = lm_fd_objective(cfg->objective);
+  const LmSolverArg arg = lm_solver_arg(cfg->solver);
+  const int32_t solver = arg.solver;
   if (cfg->objective != NLSG_OBJ_TANH_REGRESSION && !(link && cfg->objective == NLSG_OBJ_LINK_REGRESSION) &&
       !(curve && cfg->objective == NLSG_OBJ_CURVE_MODEL) && !fd)
     return fail(NLSG_ERR_INVALID_ARG, "unknown objective %d", cfg->objective);
-  const bool ref_order = cfg->solver == NLSG_LM_CHOLESKY_REFERENCE_ORDER;
-  if (cfg->solver != NLSG_LM_CHOLESKY && cfg->solver != NLSG_LM_QR && !ref_order)
-    return fail(NLSG_ERR_INVALID_ARG, "unknown solver %d", cfg->solver);
-  if (fd && cfg->solver == NLSG_LM_QR)
+  const bool ref_order = solver == NLSG_LM_CHOLESKY_REFERENCE_ORDER;
+  if (solver != NLSG_LM_CHOLESKY && solver != NLSG_LM_QR && !ref_order)
+    return fail(NLSG_ERR_INVALID_ARG, "unknown solver %d", solver);
+  if (fd && solver == NLSG_LM_QR)
     return fail(NLSG_ERR_UNSUPPORTED,
                 "the finite-difference model runs the reference's own solve (Cholesky) only");
   if (ref_order && (!fd || cfg->objective == NLSG_OBJ_RASTRIGIN ||
@@ -301,12 +374,12 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   if (cfg->n > kLmWideMaxN)
     return fail(NLSG_ERR_UNSUPPORTED, "n = %llu > %d (a thread of the step follows at most four rows)",
                 (unsigned long long)cfg->n, kLmWideMaxN);
-  if (wide && cfg->solver == NLSG_LM_QR)
+  if (wide && solver == NLSG_LM_QR)
     return fail(NLSG_ERR_UNSUPPORTED, "the tinyqr solve is built for n <= 64; n = %llu runs the "
                 "class's own Cholesky solve", (unsigned long long)cfg->n);
   if (cfg->batch > 0x7fffffffull) return fail(NLSG_ERR_UNSUPPORTED, "batch too large");
   if (with_params)  // (the row is static LDS of the run-time compiled module, next to the launch's dynamic block)
-    if (const int prc = check_custom_params(custom, nlsg_lm_lds_bytes(cfg->n, cfg->solver), "nlsg_lm",
+    if (const int prc = check_custom_params(custom, nlsg_lm_lds_bytes(cfg->n, solver), "nlsg_lm",
                                             "nlsg_lm_create_custom"))
       return prc;
   if (link && (!link->value_body || !link->value_body[0] || !link->slope_body || !link->slope_body[0]))
@@ -315,10 +388,13 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
     return fail(NLSG_ERR_INVALID_ARG, "a curve model takes 1 .. 16 data per observation: k = %u", curve->k);
   if (curve && (!curve->body || !curve->body[0]))
     return fail(NLSG_ERR_INVALID_ARG, "a curve model needs a body (nlsg_lm_curve)");
+  if (const int rc = lm_resident_door(arg, cfg->solver, fd, ref_order, cfg->n)) return rc;
   nlsg_lm *e = nullptr;
   if (const int rc = open_engine(cfg->device, cfg->stream, "nlsg_lm", &e)) return rc;
   CreateGuard<nlsg_lm> guard(e, nlsg_lm_destroy);
   e->cfg = *cfg;
+  e->cfg.solver = solver;
+  e->resident = arg.resident;
   e->wide = wide;
   e->n_params = with_params ? custom->n_params : 0;
   e->link = link != nullptr;
@@ -385,6 +461,8 @@ static int lm_create(const nlsg_lm_config *cfg, const nlsg_custom_objective *cus
   }
   if (curve)
     if (const int rc = rtc_build_lm_curve(curve, cfg->n, &e->rtc)) return rc;
+  if (e->resident)
+    if (const int rc = lm_resident_kernel_ready(e)) return rc;
   p.A = e->A_dev;
   p.y = e->y_dev;
   p.Aw = e->A_dev;
@@ -521,6 +599,9 @@ int nlsg_host_free(void *ptr) {
 
 int nlsg_lm_set_solver(nlsg_lm *e, int32_t solver) {
   if (!e) return fail(NLSG_ERR_INVALID_ARG, "null engine");
+  const int32_t given = solver;
+  const LmSolverArg arg = lm_solver_arg(given);
+  solver = arg.solver;
   if (solver != NLSG_LM_CHOLESKY && solver != NLSG_LM_QR)
     return fail(NLSG_ERR_INVALID_ARG, "unknown solver %d (the reference-order mode is chosen at creation)",
                 solver);
@@ -533,7 +614,13 @@ int nlsg_lm_set_solver(nlsg_lm *e, int32_t solver) {
   if (e->p.fd && solver != NLSG_LM_CHOLESKY)
     return fail(NLSG_ERR_UNSUPPORTED,
                 "the finite-difference model runs the reference's own solve (Cholesky) only");
+  if (const int rc = lm_resident_door(arg, given, e->p.fd != 0, false, e->p.n)) return rc;
+  if (arg.resident) {
+    NLSG_HIP(hipSetDevice(e->cfg.device));
+    if (const int rc = lm_resident_kernel_ready(e)) return rc;
+  }
   e->cfg.solver = solver;
+  e->resident = arg.resident;
   return NLSG_OK;
 }
 

@@ -105,8 +105,7 @@ __device__ inline double lm_mad(double a, double b, double c) {
 // back-substitution's sums from j = i+1 up to n-1, which makes it a serial sweep).
 template <typename Rows, bool REF = false>
 __device__ inline void lm_solve_cholesky_wave(Rows H, const double *g, double *upd, int n,
-                                              bool off_upper = false) {
-  const int t = lane_id();
+                                              bool off_upper = false, const int t = lane_id()) {
   const bool row = t < n;
   // is_diagonal (:295-307): any off-diagonal above eps * 1e12 (positive values only). The
   // Gauss-Newton matrix is bitwise symmetric (fma chains of commuting products), so the lower
@@ -536,22 +535,40 @@ struct LmWaveShared {  // view of the wave's LDS during the evaluation
   double *r;           // [16]
 };
 
+// The wave-uniform state of one problem's solve, as the loop of :3513-3542 carries it. The lock-step
+// kernels keep it in LmProblem between launches; the resident kernels in registers, LmProblem written
+// when the problem stops or the launch is cut. One set of rules for both.
+struct LmRun {
+  double f, lambda, prev;
+  uint64_t iter, fcalls;
+};
+__device__ inline LmRun lm_run_first(const LmParams &p, double f) {  // g, H, f at x0 (:3513-3516)
+  return LmRun{f, p.lambda0, 0.0, 0, 1};
+}
+__device__ inline LmRun lm_run_next(const LmParams &p, const LmRun &s, double f) {  // :3535-3542
+  return LmRun{f, f < s.f ? s.lambda / p.down : s.lambda * p.up, s.f, s.iter + 1, s.fcalls + 1};
+}
+__device__ inline bool lm_run_stops(const LmParams &p, const LmRun &s) {  // :3520-3527
+  return s.iter >= p.max_iter || fabs(s.prev - s.f) < p.f_delta || isnan(s.prev);
+}
+__device__ inline LmRun lm_run_load(const LmProblem *pr) {
+  return LmRun{pr->f, pr->lambda, pr->prev, pr->iter, pr->fcalls};
+}
+__device__ inline void lm_run_store(LmProblem *pr, const LmRun &s) {  // (one lane)
+  pr->f = s.f;
+  pr->lambda = s.lambda;
+  pr->prev = s.prev;
+  pr->iter = s.iter;
+  pr->fcalls = s.fcalls;
+}
+
 // the iteration's bookkeeping after an evaluation (one lane)
 __device__ inline void lm_publish_state(const LmParams &p, LmProblem *pr, int first, double f) {
-  if (first) {  // g, H, f at x0 (:3513-3516)
-    pr->prev = 0.0;
-    pr->f = f;
-    pr->lambda = p.lambda0;
-    pr->iter = 0;
-    pr->fcalls = 1;
+  if (first) {
+    lm_run_store(pr, lm_run_first(p, f));
     pr->done = 0;
-  } else {  // :3535-3542
-    const double prev = pr->f;
-    pr->prev = prev;
-    pr->f = f;
-    pr->fcalls += 1;
-    pr->iter += 1;
-    pr->lambda = f < prev ? pr->lambda / p.down : pr->lambda * p.up;
+  } else {
+    lm_run_store(pr, lm_run_next(p, lm_run_load(pr), f));
   }
 }
 
@@ -570,36 +587,53 @@ struct LmTanhLink {
   __device__ static inline double slope(double, double v) { return 1 - v * v; }
 };
 
-// theta_lds: the parameters as the step left them in LDS (nullptr: read them from global)
-template <typename Link>
-__device__ inline void lm_eval_wave(const LmParams &p, int first, uint64_t pid, LmWaveShared sh,
-                                    const double *theta_lds) {
-  LmProblem *pr = p.prob + pid;
-  const int lane = threadIdx.x;
-  const int half = lane >> 5, lp = lane & 31, kk = lane >> 4, cc = lane & 15;
-  const double *theta = theta_lds ? theta_lds : p.theta + pid * kLmN;
-  const double th0 = theta[2 * lp], th1 = theta[2 * lp + 1];
-  // device layout of A: [row group s][problem][16 rows][64], zero padded past m; y alike
-  const double *Ap = p.A + pid * (16 * kLmN) + 2 * lp;
-  const double *yp = p.y + pid * 16 + 2 * (lp >> 2) + half;  // the row whose z this lane ends up with
+// Where an evaluation's results go. The lock-step kernels hand H and g to the next launch through
+// global memory; the resident kernels put them into the step's LDS image (LmSinkLds below).
+struct LmSinkGlobal {
+  double *H, *g;  // the problem's rows of Hg and gg
+  __device__ inline void h(int row, int col, double v) const { H[lm_tri_row(row) + col] = v; }
+  __device__ inline void grad(int j, double v) const { g[j] = v; }
+};
+
+// The sums of one evaluation at theta (64 doubles, LDS or global): the ten lower 16 x 16 tiles of J^T J
+// in acc, the partials of J^T r in gacc, f returned. NT: the design matrix is streamed with nontemporal
+// loads (read once per launch), else with plain ones (a resident solve reads it again every iteration);
+// the bits do not depend on it. LEAN (the resident kernels, whose loop around the evaluation leaves fewer
+// registers): what a row group derives from the lane index is made again for every group instead of being
+// kept across them — a few integer instructions per group for a dozen registers.
+template <typename Link, bool NT = true, bool LEAN = false>
+__device__ inline double lm_eval_sums(const LmParams &p, uint64_t pid, LmWaveShared sh, const double *theta,
+                                      v4d (&acc)[10], double (&gacc)[4], const int lane_in = threadIdx.x) {
+  auto lane_now = [&] {
+    int l = lane_in;
+    if constexpr (LEAN) asm volatile("" : "+v"(l));
+    return l;
+  };
+  const double th0 = theta[2 * (lane_in & 31)], th1 = theta[2 * (lane_in & 31) + 1];
   const uint64_t stride = p.batch * (16 * kLmN), ystride = p.batch * 16;
-  v4d acc[10];
 #pragma unroll
   for (int i = 0; i < 10; i++) acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
-  double gacc[4] = {0.0, 0.0, 0.0, 0.0}, facc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int b = 0; b < 4; b++) gacc[b] = 0.0;
+  double facc[4] = {0.0, 0.0, 0.0, 0.0};
   const uint64_t nstep = p.nstep;
   double2 a[8];
   double ysel;
   auto fetch = [&](uint64_t s) {
+    const int lane = lane_now(), half = lane >> 5, lp = lane & 31;
+    // device layout of A: [row group s][problem][16 rows][64], zero padded past m; y alike
+    const double *Ap = p.A + pid * (16 * kLmN) + 2 * lp;
+    const double *yp = p.y + pid * 16 + 2 * (lp >> 2) + half;  // the row whose z this lane ends up with
 #pragma unroll
     for (int k = 0; k < 8; k++) {  // the design matrix is read once per evaluation: streamed (nt)
-      const v2d_nt v = __builtin_nontemporal_load(
-          reinterpret_cast<const v2d_nt *>(Ap + s * stride + (2 * k + half) * kLmN));
+      const v2d_nt *src = reinterpret_cast<const v2d_nt *>(Ap + s * stride + (2 * k + half) * kLmN);
+      const v2d_nt v = NT ? __builtin_nontemporal_load(src) : *src;
       a[k] = make_double2(v.x, v.y);
     }
     ysel = yp[s * ystride];
   };
   auto step = [&](uint64_t s, double &fw) {
+    const int lane = lane_now(), half = lane >> 5, lp = lane & 31, kk = lane >> 4, cc = lane & 15;
     // z = A theta for 16 rows (8 per half): a reduce-scatter over the half's 32 lanes instead of
     // eight full butterflies — at the levels 16, 8, 4 a lane keeps half of its rows (by bit 4, 3,
     // 2 of its index) and hands the other half to its partner, then the last row standing takes
@@ -673,7 +707,20 @@ __device__ inline void lm_eval_wave(const LmParams &p, int first, uint64_t pid, 
     if (s0 + 2 < nstep) step(s0 + 2, facc[2]);
     if (s0 + 3 < nstep) step(s0 + 3, facc[3]);
   }
-  // ---- publish the lower triangle of H = 2 J^T J, g = 2 J^T r, f
+  double f = 0.0;
+#pragma unroll
+  for (int w = 0; w < 4; w++) {
+    f = f + __shfl(facc[w], 0, 64);
+    f = f + __shfl(facc[w], 32, 64);
+  }
+  return f;
+}
+
+// the lower triangle of H = 2 J^T J and g = 2 J^T r out of an evaluation's sums
+template <typename Sink>
+__device__ inline void lm_eval_emit(const v4d (&acc)[10], const double (&gacc)[4], const Sink &out,
+                                    const int lane = threadIdx.x) {
+  const int kk = lane >> 4, cc = lane & 15;
 #pragma unroll
   for (int rb = 0; rb < 4; rb++)
 #pragma unroll
@@ -681,22 +728,25 @@ __device__ inline void lm_eval_wave(const LmParams &p, int first, uint64_t pid, 
 #pragma unroll
       for (int rg = 0; rg < 4; rg++) {
         const int row = 16 * rb + kk + 4 * rg, col = 16 * cb + cc;
-        if (col <= row)
-          p.Hg[pid * kLmTri + lm_tri_row(row) + col] = 2 * acc[rb * (rb + 1) / 2 + cb][rg];
+        if (col <= row) out.h(row, col, 2 * acc[rb * (rb + 1) / 2 + cb][rg]);
       }
 #pragma unroll
   for (int b = 0; b < 4; b++) {
     const double g0 = __shfl(gacc[b], cc, 64), g1 = __shfl(gacc[b], cc + 16, 64);
     const double g2 = __shfl(gacc[b], cc + 32, 64), g3 = __shfl(gacc[b], cc + 48, 64);
-    if (kk == 0) p.gg[pid * kLmN + 16 * b + cc] = 2 * (((g0 + g1) + g2) + g3);
+    if (kk == 0) out.grad(16 * b + cc, 2 * (((g0 + g1) + g2) + g3));
   }
-  double f = 0.0;
-#pragma unroll
-  for (int w = 0; w < 4; w++) {
-    f = f + __shfl(facc[w], 0, 64);
-    f = f + __shfl(facc[w], 32, 64);
-  }
-  if (lane == 0) lm_publish_state(p, pr, first, f);
+}
+
+// theta_lds: the parameters as the step left them in LDS (nullptr: read them from global)
+template <typename Link>
+__device__ inline void lm_eval_wave(const LmParams &p, int first, uint64_t pid, LmWaveShared sh,
+                                    const double *theta_lds) {
+  v4d acc[10];
+  double gacc[4];
+  const double f = lm_eval_sums<Link>(p, pid, sh, theta_lds ? theta_lds : p.theta + pid * kLmN, acc, gacc);
+  lm_eval_emit(acc, gacc, LmSinkGlobal{p.Hg + pid * kLmTri, p.gg + pid * kLmN});
+  if (threadIdx.x == 0) lm_publish_state(p, p.prob + pid, first, f);
 }
 
 struct LmStepShared {  // view of the wave's LDS during the step
@@ -704,18 +754,36 @@ struct LmStepShared {  // view of the wave's LDS during the step
   double *g, *upd;     // [64] each; upd ends up holding the new parameters
 };
 
-// false: a stop test fired (the problem is done). FD = the finite-difference model: the LDS image
-// of the triangle ends with row n - 1 (`chunks` x 64 doubles), and is_diagonal also needs the
-// evaluation's verdict on the upper triangle.
+// The step on a triangle and g that are in LDS already (:3529-3533): damping, then the Cholesky solve, which
+// leaves the update in sh.upd[0 .. n). FD = the finite-difference model: the LDS image of the triangle
+// ends with row n - 1, and is_diagonal also needs the evaluation's verdict on the upper triangle.
 template <bool FD, bool REF = false>
-__device__ inline bool lm_step_wave(const LmParams &p, uint64_t pid, LmStepShared sh, int chunks = 33) {
-  LmProblem *pr = p.prob + pid;
-  const int t = threadIdx.x, n = static_cast<int>(p.n);
-  const double prev = pr->prev, cur = pr->f;
-  if (pr->iter >= p.max_iter || fabs(prev - cur) < p.f_delta || isnan(prev)) {  // :3520-3527
-    if (t == 0) pr->done = 1;
-    return false;
-  }
+__device__ inline void lm_step_solve(LmStepShared sh, int n, double lambda, bool off_upper,
+                                     const int t = threadIdx.x) {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  if (t < n) sh.tri[lm_tri_row(t) + t] += lambda;  // :3529-3531
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  if constexpr (FD)
+    lm_solve_cholesky_wave<LmRowsTriShort, REF>(LmRowsTriShort{sh.tri, n - 1}, sh.g, sh.upd, n, off_upper, t);
+  else
+    lm_solve_cholesky_wave(LmRowsTri{sh.tri}, sh.g, sh.upd, n, false, t);
+}
+// theta - update (:3534): the lane's new parameter, left in sh.upd for the evaluation that follows
+__device__ inline double lm_step_update(LmStepShared sh, int n, double th, const int t = threadIdx.x) {
+  const double tn = t < n ? th - sh.upd[t] : th;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  sh.upd[t] = tn;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  return tn;
+}
+// the triangle and g an evaluation left in global memory, into LDS (`chunks` x 64 doubles of the triangle)
+template <bool FD>
+__device__ inline void lm_step_load(const LmParams &p, uint64_t pid, LmStepShared sh, int chunks = 33) {
+  const int t = threadIdx.x;
   const double *src = p.Hg + pid * kLmTri;
   if constexpr (FD) {
     for (int q = 0; q < chunks; q++) sh.tri[64 * q + t] = src[64 * q + t];
@@ -729,24 +797,21 @@ __device__ inline bool lm_step_wave(const LmParams &p, uint64_t pid, LmStepShare
     for (int q = 0; q < 33; q++) sh.tri[64 * q + t] = h[q];
     sh.g[t] = gv;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  if (t < n) sh.tri[lm_tri_row(t) + t] += pr->lambda;  // :3529-3531
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  if constexpr (FD)
-    lm_solve_cholesky_wave<LmRowsTriShort, REF>(LmRowsTriShort{sh.tri, n - 1}, sh.g, sh.upd, n,
-                                                pr->upper != 0);
-  else
-    lm_solve_cholesky_wave(LmRowsTri{sh.tri}, sh.g, sh.upd, n);
-  const double th = p.theta[pid * kLmN + t];
-  const double tn = t < n ? th - sh.upd[t] : th;  // :3534
-  p.theta[pid * kLmN + t] = tn;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  sh.upd[t] = tn;  // handed to the evaluation of the same launch
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
+}
+
+// The lock-step turn's step. false: a stop test fired (the problem is done).
+template <bool FD, bool REF = false>
+__device__ inline bool lm_step_wave(const LmParams &p, uint64_t pid, LmStepShared sh, int chunks = 33) {
+  LmProblem *pr = p.prob + pid;
+  const int t = threadIdx.x, n = static_cast<int>(p.n);
+  const LmRun run = lm_run_load(pr);
+  if (lm_run_stops(p, run)) {
+    if (t == 0) pr->done = 1;
+    return false;
+  }
+  lm_step_load<FD>(p, pid, sh, chunks);
+  lm_step_solve<FD, REF>(sh, n, run.lambda, FD ? pr->upper != 0 : false);
+  p.theta[pid * kLmN + t] = lm_step_update(sh, n, p.theta[pid * kLmN + t]);
   return true;
 }
 
@@ -769,6 +834,86 @@ __global__ __launch_bounds__(64, 2) void lm_iter_kernel(LmParams p, int first, i
     }
   }
   lm_eval_wave<Link>(p, first, pid, LmWaveShared{smem, smem + 16 * kLmJStride}, theta_lds);
+}
+
+// ---- The resident driver (NLSG_LM_RESIDENT): the loop of :3513-3542 for one problem in ONE launch, the
+// lock-step turn above in a loop. Between the evaluation and the step nothing passes through global
+// memory: the evaluation's sums go from the accumulators into the step's LDS image (the Jacobian tile
+// that overlays it is dead behind the evaluation's last fence), the parameters stay in `upd`, and f, prev,
+// lambda, iter, fcalls are wave-uniform registers (LmRun). LmProblem and the row of theta are written once,
+// when the problem stops or the launch is cut; a problem that stops frees its slot. The host cuts a
+// launch at kLmResidentCut turns: the evaluation of a launch's last turn also leaves H and g in Hg / gg
+// (a second pass over the accumulators into LmSinkGlobal), where the next launch's first step finds them
+// as a lock-step step would — a resumed problem evaluates nothing twice, and its bits do not depend on
+// where the cut fell. Every function that rounds is the lock-step pair's own.
+// f is taken through lane_broadcast: the sums leave it equal in every lane but in a vector register; read
+// from lane 0 it is a scalar, so LmRun, the stop tests and the loop's branches stay on the scalar unit.
+constexpr uint32_t kLmResidentCut = 256;  // turns per launch (as the resident BFGS kernel's)
+struct LmSinkLds {
+  double *tri, *g;  // the step's image
+  __device__ inline void h(int row, int col, double v) const { tri[lm_tri_row(row) + col] = v; }
+  __device__ inline void grad(int j, double v) const { g[j] = v; }
+};
+// The lane's index through an opaque move, made again at the head of every phase of the resident loop: what
+// a phase derives from it (addresses, tile and triangle offsets) then does not live in registers across the
+// other phases, and the kernels stay inside the 256 registers of two waves per SIMD without scratch.
+__device__ inline int lm_fresh_lane() {
+  int lane = threadIdx.x;
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+// what a resident workgroup leaves when it returns: theta, the state, and whether a stop test fired
+__device__ inline void lm_resident_leave(const LmParams &p, uint64_t pid, const double *upd, const LmRun &run,
+                                         bool done) {
+  const int lane = lm_fresh_lane();
+  p.theta[pid * kLmN + lane] = upd[lane];
+  if (lane == 0) {
+    lm_run_store(p.prob + pid, run);
+    p.prob[pid].done = done ? 1 : 0;
+  }
+}
+
+// first: the launch starts at x0 (evaluation, then turns); else it resumes at the step of a cut problem.
+// turns: how many (stop tests, step, evaluation) the launch may run per problem.
+// NT: the data are re-read with nontemporal loads (the A/B form NLSG_LM_RESIDENT_NT=1 binds), else plain.
+template <typename Link, bool NT = false>
+__global__ __launch_bounds__(64, 2) void lm_resident_kernel(LmParams p, int first, uint32_t turns) {
+  __shared__ __align__(16) double smem[kLmTri + 128];
+  const uint64_t pid = blockIdx.x;
+  const int t = lm_fresh_lane(), n = static_cast<int>(p.n);
+  if (!first && p.prob[pid].done) return;
+  const LmStepShared sh{smem, smem + kLmTri, smem + kLmTri + 64};
+  const LmWaveShared ev{smem, smem + 16 * kLmJStride};
+  const LmSinkGlobal glob{p.Hg + pid * kLmTri, p.gg + pid * kLmN};
+  v4d acc[10];
+  double gacc[4];
+  sh.upd[t] = p.theta[pid * kLmN + t];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  LmRun run{};
+  bool fresh = first != 0, evaluate = fresh, done = false;
+  if (!first) {
+    run = lm_run_load(p.prob + pid);
+    lm_step_load<false>(p, pid, sh);
+  }
+  for (uint32_t k = 0;; k++) {  // turn k: (stop tests, step, evaluation); the evaluation at x0 comes before turn 0
+    if (evaluate) {
+      const int lane = lm_fresh_lane();
+      const double f = lane_broadcast(lm_eval_sums<Link, NT, true>(p, pid, ev, sh.upd, acc, gacc, lane), 0);
+      lm_eval_emit(acc, gacc, LmSinkLds{sh.tri, sh.g}, lane);
+      if (k == turns) lm_eval_emit(acc, gacc, glob, lane);  // the launch ends here: the next one resumes from these
+      run = fresh ? lm_run_first(p, f) : lm_run_next(p, run, f);
+      fresh = false;
+    }
+    if (k == turns) break;  // the launch is cut here
+    if ((done = lm_run_stops(p, run))) break;
+    const int lane = lm_fresh_lane();
+    const double th = sh.upd[lane];
+    lm_step_solve<false>(sh, n, run.lambda, false, lane);
+    lm_step_update(sh, n, th, lm_fresh_lane());
+    evaluate = true;
+  }
+  lm_resident_leave(p, pid, sh.upd, run, done);
 }
 
 // ---- The curve model r_i(theta) = residual(theta; t_i, y_i): the residual and its Jacobian row come
@@ -823,30 +968,31 @@ struct LmCurveTh {  // th(j): parameter j, a broadcast read of the wave's LDS co
   __device__ inline double operator()(int j) const { return theta[j & 63]; }  // (never outside the copy)
 };
 
-// theta: the parameters in LDS (64 doubles); tile: [64][NPAD + 1]
-template <typename Model, int NPAD>
-__device__ inline void lm_curve_eval_wave(const LmParams &p, int first, uint64_t pid, double *tile,
-                                          const double *theta) {
+// The sums of one evaluation. theta: the parameters in LDS (64 doubles); tile: [64][NPAD + 1].
+// d: the lane's K + 1 data of the super-step in flight; `loaded`: they are those of super-step 0 already
+// (a resident solve of one super-step keeps them across its evaluations). NT as in lm_eval_sums.
+template <typename Model, int NPAD, bool NT = true>
+__device__ inline double lm_curve_eval_sums(const LmParams &p, uint64_t pid, double *tile, const double *theta,
+                                            v4d (&acc)[NPAD / 16 * (NPAD / 16 + 1) / 2],
+                                            double (&gacc)[NPAD / 16], double (&d)[Model::kK + 1],
+                                            bool loaded) {
   static_assert(NPAD == 16 || NPAD == 32 || NPAD == 64, "padded column count");
   constexpr int K = Model::kK, S = NPAD + 1, NB = NPAD / 16, NACC = NB * (NB + 1) / 2;
-  LmProblem *pr = p.prob + pid;
   const int lane = threadIdx.x, kk = lane >> 4, cc = lane & 15, n = static_cast<int>(p.n);
   const double *dp = p.A + pid * ((K + 1) * 64) + lane;
   const uint64_t stride = p.batch * ((K + 1) * 64), nstep = p.nstep;
-  v4d acc[NACC];
 #pragma unroll
   for (int i = 0; i < NACC; i++) acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
-  double gacc[NB], facc = 0.0;
+  double facc = 0.0;
 #pragma unroll
   for (int b = 0; b < NB; b++) gacc[b] = 0.0;
-  double d[K + 1];
   auto fetch = [&](uint64_t s) {
 #pragma unroll
     for (int k = 0; k <= K; k++)  // read once per evaluation: streamed (nt)
-      d[k] = __builtin_nontemporal_load(dp + s * stride + k * 64);
+      d[k] = NT ? __builtin_nontemporal_load(dp + s * stride + k * 64) : dp[s * stride + k * 64];
   };
   double *myrow = tile + lane * S;
-  fetch(0);
+  if (!loaded) fetch(0);
   for (uint64_t s = 0; s < nstep; s++) {
     const bool in = 64 * s + static_cast<uint64_t>(lane) < p.m;
 #pragma unroll
@@ -882,8 +1028,16 @@ __device__ inline void lm_curve_eval_wave(const LmParams &p, int first, uint64_t
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
-  // ---- publish the lower triangle of H = 2 J^T J (rows below n only: the rest of Hg stays zero),
-  // g = 2 J^T r (zeros from n on), f
+  return wave_sum(facc);
+}
+
+// the lower triangle of H = 2 J^T J (rows below n only: the rest of Hg stays zero) and g = 2 J^T r (zeros
+// from n on) out of an evaluation's sums
+template <int NPAD, typename Sink>
+__device__ inline void lm_curve_eval_emit(const v4d (&acc)[NPAD / 16 * (NPAD / 16 + 1) / 2],
+                                          const double (&gacc)[NPAD / 16], int n, const Sink &out) {
+  constexpr int NB = NPAD / 16;
+  const int lane = threadIdx.x, kk = lane >> 4, cc = lane & 15;
 #pragma unroll
   for (int rb = 0; rb < NB; rb++)
 #pragma unroll
@@ -891,8 +1045,7 @@ __device__ inline void lm_curve_eval_wave(const LmParams &p, int first, uint64_t
 #pragma unroll
       for (int rg = 0; rg < 4; rg++) {
         const int row = 16 * rb + kk + 4 * rg, col = 16 * cb + cc;
-        if (col <= row && row < n)
-          p.Hg[pid * kLmTri + lm_tri_row(row) + col] = 2 * acc[rb * (rb + 1) / 2 + cb][rg];
+        if (col <= row && row < n) out.h(row, col, 2 * acc[rb * (rb + 1) / 2 + cb][rg]);
       }
 #pragma unroll
   for (int b = 0; b < 4; b++) {
@@ -903,10 +1056,19 @@ __device__ inline void lm_curve_eval_wave(const LmParams &p, int first, uint64_t
       const double g2 = __shfl(gb, cc + 32, 64), g3 = __shfl(gb, cc + 48, 64);
       gv = 2 * (((g0 + g1) + g2) + g3);
     }
-    if (kk == 0) p.gg[pid * kLmN + 16 * b + cc] = gv;
+    if (kk == 0) out.grad(16 * b + cc, gv);
   }
-  const double f = wave_sum(facc);
-  if (lane == 0) lm_publish_state(p, pr, first, f);
+}
+
+template <typename Model, int NPAD>
+__device__ inline void lm_curve_eval_wave(const LmParams &p, int first, uint64_t pid, double *tile,
+                                          const double *theta) {
+  constexpr int NB = NPAD / 16;
+  v4d acc[NB * (NB + 1) / 2];
+  double gacc[NB], d[Model::kK + 1];
+  const double f = lm_curve_eval_sums<Model, NPAD>(p, pid, tile, theta, acc, gacc, d, false);
+  lm_curve_eval_emit<NPAD>(acc, gacc, static_cast<int>(p.n), LmSinkGlobal{p.Hg + pid * kLmTri, p.gg + pid * kLmN});
+  if (threadIdx.x == 0) lm_publish_state(p, p.prob + pid, first, f);
 }
 
 // lm_iter_kernel for a curve model. LDS of the wave: the step's packed triangle | g, overlaid by the
@@ -935,6 +1097,54 @@ __global__ __launch_bounds__(64) void lm_curve_iter_kernel(LmParams p, int first
     __builtin_amdgcn_wave_barrier();
   }
   lm_curve_eval_wave<Model, NPAD>(p, first, pid, smem, smem + kUpd);
+}
+
+// lm_resident_kernel for a curve model, in lm_curve_iter_kernel's LDS. With one super-step (m <= 64) the
+// lane's K + 1 data are loaded once and stay in registers for the whole solve.
+template <typename Model, int NPAD, bool NT = false>
+__global__ __launch_bounds__(64) void lm_curve_resident_kernel(LmParams p, int first, uint32_t turns) {
+  constexpr int kUpd = lm_curve_upd_offset<NPAD>(), NB = NPAD / 16;
+  __shared__ __align__(16) double smem[kUpd + 64];
+  const uint64_t pid = blockIdx.x;
+  const int t = lm_fresh_lane(), n = static_cast<int>(p.n);
+  if (!first && p.prob[pid].done) return;
+  const LmStepShared sh{smem, smem + kLmTri, smem + kUpd};
+  const LmSinkGlobal glob{p.Hg + pid * kLmTri, p.gg + pid * kLmN};
+  v4d acc[NB * (NB + 1) / 2];
+  double gacc[NB], d[Model::kK + 1];
+#pragma unroll
+  for (int k = 0; k <= Model::kK; k++) d[k] = 0.0;
+  const bool keep = p.nstep == 1;
+  bool loaded = false;
+  sh.upd[t] = p.theta[pid * kLmN + t];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  LmRun run{};
+  bool fresh = first != 0, evaluate = fresh, done = false;
+  if (!first) {
+    run = lm_run_load(p.prob + pid);
+    lm_step_load<false>(p, pid, sh);
+  }
+  for (uint32_t k = 0;; k++) {  // as in lm_resident_kernel
+    if (evaluate) {
+      const int lane = lm_fresh_lane();
+      const double f =
+          lane_broadcast(lm_curve_eval_sums<Model, NPAD, NT>(p, pid, smem, sh.upd, acc, gacc, d, loaded), 0);
+      loaded = keep;
+      lm_curve_eval_emit<NPAD>(acc, gacc, n, LmSinkLds{sh.tri, sh.g});
+      if (k == turns) lm_curve_eval_emit<NPAD>(acc, gacc, n, glob);  // the launch ends here
+      run = fresh ? lm_run_first(p, f) : lm_run_next(p, run, f);
+      fresh = false;
+    }
+    if (k == turns) break;  // the launch is cut here
+    if ((done = lm_run_stops(p, run))) break;
+    const int lane = lm_fresh_lane();
+    const double th = sh.upd[lane];
+    lm_step_solve<false>(sh, n, run.lambda, false, lane);
+    lm_step_update(sh, n, th, lm_fresh_lane());
+    evaluate = true;
+  }
+  lm_resident_leave(p, pid, sh.upd, run, done);
 }
 
 // host layout t [problem][m][K], y [problem][m] -> [super-step][problem][K + 1][64], zeros past m

@@ -65,15 +65,19 @@ int rtc_build_de_batch(const nlsg_custom_objective *obj, int group, ResidentRtcK
 int rtc_build_pso_batch(const nlsg_custom_objective *obj, int group, int type, ResidentRtcKernels *out);
 struct LmRtcKernels : RtcModule {  // finite-difference model (default functors) around the user's objective
   hipFunction_t iter = nullptr;
+  hipFunction_t resident = nullptr;  // Gauss-Newton models of n <= 64: lm_resident_kernel / lm_curve_resident_kernel
 };
 // wide_chunks != 0: the evaluation kernel of the n > 64 path (a probe point of wide_chunks x 128
 // coordinates per wave) instead of the one-wave iteration kernel
 int rtc_build_lm(const nlsg_custom_objective *obj, int wide_chunks, bool reference_order, LmRtcKernels *out);
 // the Gauss-Newton evaluation kernel of n parameters (lm_iter_kernel to 64, the one-pass kernels to 128
 // and 256, the super-block kernel beyond) on the link `value_body` / `slope_body` describe; k->iter
+// (n <= 64: k->resident beside it)
 int rtc_build_lm_link(const nlsg_lm_link *link, uint64_t n, LmRtcKernels *out);
+// lm_resident_kernel<LmTanhLink> for a TanhRegression engine; k->resident only
+int rtc_build_lm_tanh_resident(LmRtcKernels *out);
 // the curve model's iteration kernel (lm_curve_iter_kernel) of n <= 64 parameters and curve->k data per
-// observation, around the residual-and-Jacobian body; k->iter
+// observation, around the residual-and-Jacobian body; k->iter, and lm_curve_resident_kernel as k->resident
 int rtc_build_lm_curve(const nlsg_lm_curve *curve, uint64_t n, LmRtcKernels *out);
 struct HybRtcKernels : RtcModule {
   hipFunction_t solve = nullptr;

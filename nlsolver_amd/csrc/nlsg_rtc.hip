@@ -2,6 +2,7 @@
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 
+#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <string>
@@ -421,6 +422,13 @@ int rtc_build_sann(const nlsg_custom_objective *obj, int chunks, bool vec, int g
                    true, out, {{name, &out->anneal}});
 }
 
+// NLSG_LM_RESIDENT_NT=1 (A/B switch, read when a module is built): the resident kernels re-read their data
+// with nontemporal loads, as the lock-step kernels stream theirs, instead of plain ones. Same bits.
+static const char *lm_resident_nt() {
+  const char *e = std::getenv("NLSG_LM_RESIDENT_NT");
+  return e && e[0] == '1' ? "true" : "false";
+}
+
 int rtc_build_lm(const nlsg_custom_objective *obj, int wide_chunks, bool reference_order, LmRtcKernels *out) {
   const std::string id = custom_id();
   const std::string name =
@@ -450,8 +458,20 @@ int rtc_build_lm_link(const nlsg_lm_link *link, uint64_t n, LmRtcKernels *out) {
   src += "\n  }\n};\n}  // namespace nlsg\n";
   const char *kernel = n <= 64 ? "lm_iter_kernel" : n <= 128 ? "lm_wide128x8_tanh_eval_kernel"
                      : n <= 256 ? "lm_wide256x8_tanh_eval_kernel" : "lm_wide_mfma_tanh_eval_kernel";
-  return rtc_build({NLSG_OK, src, "link"}, true, out,
-                   {{std::string("nlsg::") + kernel + "<nlsg::LmUserLink>", &out->iter}});
+  std::vector<RtcBind> binds = {{std::string("nlsg::") + kernel + "<nlsg::LmUserLink>", &out->iter}};
+  // (one wave per problem: the resident driver's kernel rides in the same module)
+  if (n <= 64)
+    binds.push_back({std::string("nlsg::lm_resident_kernel<nlsg::LmUserLink, ") + lm_resident_nt() + ">",
+                     &out->resident});
+  return rtc_build({NLSG_OK, src, "link"}, true, out, binds);
+}
+// The resident driver's kernel on the built-in link. The library's own set of kernels holds the lock-step
+// pair only, so a TanhRegression engine gets this one here, the first time the resident driver is chosen on
+// it; the code object is kept by its source, and every further engine loads it.
+int rtc_build_lm_tanh_resident(LmRtcKernels *out) {
+  return rtc_build({NLSG_OK, "#include \"nlsg_lm_kernels.h\"\n", "resident kernel"}, true, out,
+                   {{std::string("nlsg::lm_resident_kernel<nlsg::LmTanhLink, ") + lm_resident_nt() + ">",
+                     &out->resident}});
 }
 // lm_curve_iter_kernel on a model made of the body (nlsg_lm_kernels.h): K data per observation, the
 // padded column count chosen from n. The body sees th(j), t(k), y, n, r and J(j).
@@ -471,7 +491,10 @@ int rtc_build_lm_curve(const nlsg_lm_curve *curve, uint64_t n, LmRtcKernels *out
   src += "\n  }\n};\n}  // namespace nlsg\n";
   const int npad = n <= 16 ? 16 : n <= 32 ? 32 : 64;
   return rtc_build({NLSG_OK, src, "curve model"}, true, out,
-                   {{"nlsg::lm_curve_iter_kernel<nlsg::LmUserCurve, " + std::to_string(npad) + ">", &out->iter}});
+                   {{"nlsg::lm_curve_iter_kernel<nlsg::LmUserCurve, " + std::to_string(npad) + ">", &out->iter},
+                    {"nlsg::lm_curve_resident_kernel<nlsg::LmUserCurve, " + std::to_string(npad) + ", " +
+                         lm_resident_nt() + ">",
+                     &out->resident}});
 }
 
 }  // namespace nlsg

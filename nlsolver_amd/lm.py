@@ -16,7 +16,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import LMConfig, NlsgError, Status, check, lib, require  # noqa: F401
-from ._engine import LDS_BUDGET, CustomObjective, Engine, _rows_for_batch, pair_params, pd_of, timed_ms
+from ._engine import (LDS_BUDGET, CustomObjective, Engine, _rows_for_batch, check_driver, pair_params, pd_of,
+                      rtc_library_path, timed_ms)
 
 
 class TanhRegression:
@@ -180,8 +181,41 @@ class LMEngine(Engine):
 
     A CustomObjective with n_params > 0 (nlsg_lm_create_params): problem b minimises the objective under
     row b of set_params(rows) ([batch, n_params], read as p(k)) — one fit per series; rows are replaced
-    without recompiling. The row lives in the workgroup's LDS: fits() says whether a shape has room."""
+    without recompiling. The row lives in the workgroup's LDS: fits() says whether a shape has room.
+
+    solver=LM_CHOLESKY | LM_RESIDENT (NLSG_LM_RESIDENT; Gauss-Newton models, n <= 64): the whole loop of a solve in
+    one kernel, a 64-lane workgroup per problem, H, g and theta in LDS and the loop's scalars in registers,
+    at most ceil((max_iter + 1) / LM_RESIDENT_CUT) launches — theta, every status field and lambda are the
+    lock-step engine's bit for bit. set_solver(LM_CHOLESKY | LM_RESIDENT) switches an existing engine, the
+    plain value back; `.driver` says which one runs ("turns" / "resident"). fits_resident() says whether a shape is taken."""
     _destroy, _set_params = "nlsg_lm_destroy", "nlsg_lm_set_params"
+
+    @staticmethod
+    def has_resident():
+        """whether the loaded library has the resident mode (one older than the flag answers 0 to it)"""
+        try:
+            return int(require("nlsg_lm_lds_bytes")(2, _capi.LM_CHOLESKY | _capi.LM_RESIDENT)) != 0
+        except NlsgError:
+            return False
+
+    @staticmethod
+    def fits_resident(model_or_n, solver=_capi.LM_CHOLESKY):
+        """whether an engine with solver | LM_RESIDENT takes the model: a TanhRegression, LinkRegression or
+        CurveModel (or the parameter count of one) with 1 <= n <= 64, the Cholesky solver, and a library
+        that has the mode. An objective by name or a CustomObjective (the finite-difference model) never."""
+        if isinstance(model_or_n, (str, CustomObjective, bool)):
+            return False
+        if isinstance(model_or_n, (int, np.integer)):
+            n = int(model_or_n)
+        elif isinstance(model_or_n, CurveModel):
+            n = model_or_n.n
+        elif hasattr(model_or_n, "A"):
+            n = model_or_n.A.shape[2]
+        else:
+            return False
+        if solver != _capi.LM_CHOLESKY or not 1 <= n <= 64 or not LMEngine.has_resident():
+            return False
+        return int(require("nlsg_lm_lds_bytes")(n, _capi.LM_CHOLESKY | _capi.LM_RESIDENT)) != 0
 
     @staticmethod
     def lds_bytes(n, reference_order=False, n_params=0):
@@ -229,13 +263,26 @@ class LMEngine(Engine):
             create, set_data = require("nlsg_lm_create_curve"), require("nlsg_lm_set_curve_data")
             self._create_custom(create, cfg, _capi.LMCurveC(model.body.encode(), model.t.shape[2]))
             check(set_data(self._h, pd_of(model.t), pd_of(model.y)))
+        elif self.driver == "resident":  # a TanhRegression's resident kernel is compiled at run time
+            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
+            self._create(lib().nlsg_lm_create, cfg)
         else:
             self._create(lib().nlsg_lm_create, cfg)
         if not fd and not isinstance(model, CurveModel):
             check(lib().nlsg_lm_set_data(self._h, pd_of(model.A), pd_of(model.y)))
 
+    @property
+    def driver(self):
+        """"resident" or "turns": which driver runs the next solve (the flag in cfg.solver)"""
+        flagged = self.cfg.solver >= _capi.LM_RESIDENT and self.cfg.solver & _capi.LM_RESIDENT
+        return "resident" if flagged else "turns"
+
     def set_solver(self, solver):
-        """LM_CHOLESKY / LM_QR for the next solves; the model data stays on the device."""
+        """LM_CHOLESKY / LM_QR for the next solves, LM_CHOLESKY | LM_RESIDENT for the resident driver (the
+        plain value switches back); the model data stays on the device."""
+        flagged = solver >= _capi.LM_RESIDENT
+        if flagged:  # (the resident kernel of a TanhRegression engine is compiled here)
+            check(lib().nlsg_rtc_load(rtc_library_path().encode()))
         check(lib().nlsg_lm_set_solver(self._h, solver))
         self.cfg.solver = solver
 
@@ -296,7 +343,12 @@ class LevenbergMarquardt:
     per lane — the faster evaluation); everything else with LM_CHOLESKY.
 
     params: the run-time parameters of a CustomObjective with n_params > 0: one row (n_params,) shown
-    to every start, or (batch, n_params) with a 2-D x, a row per start."""
+    to every start, or (batch, n_params) with a 2-D x, a row per start.
+
+    with_driver("resident") (or .driver = "resident"): the solve runs in the resident kernel (LMEngine with
+    solver | LM_RESIDENT) whenever LMEngine.fits_resident holds — a Gauss-Newton model, n <= 64, the Cholesky solver, a library that has the
+    mode — and through the lock-step engine otherwise: the same x and status bit for bit either way.
+    `driver_used` says which one the last minimize() ran."""
 
     def __init__(self, f, lam=10.0, upward_mult=10.0, downward_mult=10.0, max_iter=100,
                  f_delta=1e-12, g=None, h=None, *, solver=None, device=0, params=None):
@@ -307,6 +359,24 @@ class LevenbergMarquardt:
         self.f = f
         self.args = dict(lam=lam, up=upward_mult, down=downward_mult, max_iter=max_iter,
                          f_delta=f_delta, solver=solver, device=device)
+
+    driver_used = None  # "turns" / "resident": what the last minimize() ran
+    _driver = "turns"
+
+    @property
+    def driver(self):
+        """"turns" (default) or "resident"; anything else is a ValueError"""
+        return self._driver
+
+    @driver.setter
+    def driver(self, driver):
+        check_driver(driver)
+        self._driver = driver
+
+    def with_driver(self, driver):
+        """sets .driver and returns the solver: LevenbergMarquardt(model).with_driver("resident").minimize(x)"""
+        self.driver = driver
+        return self
 
     def _engine(self, x):
         """x as (batch, n), the engine minimize() runs it on, and the parameter rows of that batch"""
@@ -321,10 +391,18 @@ class LevenbergMarquardt:
                 (isinstance(self.f, CustomObjective) and self.f.chain != 2)  # (given by its terms)
             args["solver"] = _capi.LM_CHOLESKY_REFERENCE_ORDER if ref else _capi.LM_CHOLESKY
         rows = _rows_for_batch(self.params, xb.shape[0])
+        # (the resident kernels are compiled at run time: a process that cannot load hiprtc stays with the turns,
+        # which need it for a TanhRegression not at all)
+        resident = self.driver == "resident" and LMEngine.fits_resident(self.f, args["solver"]) and \
+            lib().nlsg_rtc_load(rtc_library_path().encode()) == 0
+        if resident:
+            args["solver"] |= _capi.LM_RESIDENT
+        self._resident = resident
         return xb, LMEngine(self.f, **args, **shape), rows
 
     def minimize(self, x):
         xb, engine, rows = self._engine(x)
+        self.driver_used = "resident" if self._resident else "turns"
         with engine as eng:
             out, st, lam = eng.minimize(xb, params=rows)
         xb[...] = out
